@@ -6,16 +6,22 @@ build K(x, x) + diag(yerr^2) on the device, blocked fp64 Cholesky, log-det, forw
 r^T K^-1 r -> log-likelihood.  Inputs follow the reference's only benchmark
 (docs/tutorials/scaling.rst:56-59,67 / SURVEY.md 8d).
 
-    python bench.py --gpus N --steps K --warmup W [--n 65536] [--nb 512]
+    python bench.py --gpus N --steps K --warmup W [--n 65536] [--nb 512] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  ``--dump-outputs DIR``
+writes what the last timed step computed (DIR/log_likelihood.npy, DIR/log_determinant.npy, float64) so
+that two builds can be compared output for output on the same seeded inputs.  Everything else below
+(parity checks, CPU baselines, roofline and phase figures, the other configs and sizes) runs only with
+``--full``.
 
 N > 1 runs one rank per GPU (RCCL): the dense factorisation is sharded block-cyclically over the
 ranks (george_amd/distributed.py) -- same N, strong scaling.  Either the caller launches the ranks
 (``python -m torch.distributed.run --nproc-per-node N bench.py --gpus N``: WORLD_SIZE is set and must
 equal N) or plain ``python bench.py --gpus N`` re-launches itself under torch.distributed.run with N
-ranks; it never falls back to one GPU.  Rank 0 prints ONE JSON line; the N > 1 line carries its own
-parity block against tests/golden/large.json and the run exits non-zero above 1e-6.
+ranks; it never falls back to one GPU.  Rank 0 prints ONE JSON line; with --full the N > 1 line carries
+its own parity block against tests/golden/large.json and the run exits non-zero above 1e-6.
 
-At N = 1 the same line also carries (all timed in this run, on the GPU the driver leased):
+With --full the N = 1 line also carries (all timed in the same run, on the same GPU):
   parity            GPU vs the reference CPU path at the cpu_baseline sample size, and vs the committed
                     reference scalar at the headline size; the run FAILS if either is off by > 1e-6
   public_api        the same work through GP.compute / GP.log_likelihood on NumPy inputs (H2D included)
@@ -145,6 +151,7 @@ class DenseJob(object):
         N.check(N.lib.gh_chol_compute(self.h, self.dk.handle, self.x.data_ptr(), self.n, 1,
                                       self.yerr.data_ptr(), C.byref(logdet)))
         N.check(N.lib.gh_chol_dot_solve(self.h, self.y.data_ptr(), C.byref(q)))
+        self.log_determinant = logdet.value
         return -0.5 * (self.n * np.log(2 * np.pi) + logdet.value) - 0.5 * q.value    # gp.py:333-335,396
 
     def profile(self):
@@ -235,6 +242,7 @@ class HodlrJob(object):
         N.check(N.lib.gh_hodlr_compute(self.h, self.dk.handle, self.x.data_ptr(), self.n, 1,
                                        self.yerr.data_ptr(), C.byref(logdet)))
         N.check(N.lib.gh_hodlr_dot_solve(self.h, self.y.data_ptr(), C.byref(q)))
+        self.log_determinant = logdet.value
         return -0.5 * (self.n * np.log(2 * np.pi) + logdet.value) - 0.5 * q.value
 
     def ranks(self):
@@ -741,6 +749,8 @@ def hodlr_main(args, local_rank):
     n = args.n if args.n != 65536 else 262144
     job = HodlrJob(n, local_rank)
     elapsed, ll = run_timed(job, args.steps, args.warmup, lambda: None)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ll, job.log_determinant)
     ranks = job.ranks()
     out = {"metric": "gp_hodlr_compute_plus_log_likelihood_seconds", "value": elapsed / args.steps, "unit": "s",
            "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
@@ -749,7 +759,7 @@ def hodlr_main(args, local_rank):
                                   "compute()+log_likelihood()" % n, "N": n},
            "log_likelihood": ll, "max_rank": max(ranks) if ranks else 0, "n_internal_nodes": len(ranks)}
     job.close()
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         from oracle import hodlr_np, solver_np
         import george_amd.kernels as K
         nc = min(n, 32768)
@@ -762,6 +772,13 @@ def hodlr_main(args, local_rank):
                                "sample": "NumPy restatement of hodlr.h at N=%d (the reference's Eigen extension "
                                          "cannot be built here); loglike=%.10g" % (nc, llc)}
     emit(out)
+
+
+def dump_outputs(dirname, log_likelihood, log_determinant):
+    """--dump-outputs: what the caller of the timed path receives from its last step, as float64 .npy files"""
+    os.makedirs(dirname, exist_ok=True)
+    for name, v in (("log_likelihood", log_likelihood), ("log_determinant", log_determinant)):
+        np.save(os.path.join(dirname, name + ".npy"), np.array([v], dtype=np.float64))
 
 
 def emit(out, detail_path=None):
@@ -918,7 +935,7 @@ def main():
     ap.add_argument("--grid", default="", help="N > 1: process grid PrxPc (default: N x 1, whole tile rows per rank in snake order; "
                     "'square' = 1x2 / 2x2 / 2x4)")
     ap.add_argument("--detail", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"),
-                    help="where the FULL record goes (the printed line is its < 6 kB digest); '' = nowhere")
+                    help="where the FULL record of a --full run goes (the printed line is its < 6 kB digest); '' = nowhere")
     ap.add_argument("--abi-timeout", type=int, default=420,
                     help="N > 1: time limit in seconds for the second multi-GPU form (gh_mgpu_* behind the C ABI, one process) "
                          "that rank 0 runs in a child process after the ranks have left; 0 = skip")
@@ -937,7 +954,15 @@ def main():
     ap.add_argument("--tile-ops", default="hip", choices=["hip", "numpy"],
                     help="numpy: launcher self-test of the N > 1 path on a box without a GPU (tests/np_tile_ops.py; "
                          "the line says so in 'data' and is not a measurement)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement and check: parity against the reference, CPU baselines, "
+                         "roofline and phase figures, the other configs and sizes, the N > 1 link probe and other grid "
+                         "(--no-cpu / --no-extra still thin it out); without it only the headline steps run")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    extra = args.full and not args.no_extra
+    cpu = args.full and not args.no_cpu
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
@@ -1005,18 +1030,21 @@ def main():
         barrier = lambda: None
 
     links = None
-    if world > 1 and not args.no_extra:
+    if world > 1 and extra:
         import torch.distributed as dist
         try:
             links = link_probe(dist, "cpu" if selftest else "cuda", world, rank, args.n * job.nb * 8 // world)
         except Exception as e:                                    # (a backend without all_gather_into_tensor / batched p2p: say so)
             links = {"error": repr(e)[:200]}
     elapsed, ll = run_timed(job, args.steps, args.warmup, barrier)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, ll, job.chol.log_determinant if world > 1 else job.log_determinant)
     if world > 1:
         import torch.distributed as dist
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if selftest else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if world > 1 and args.full:
         # every rank must hold the same log-likelihood (replicated scalars)
         lls = torch.tensor([ll, -ll], dtype=torch.float64, device=t.device)
         dist.all_reduce(lls, op=dist.ReduceOp.MAX)
@@ -1029,7 +1057,7 @@ def main():
             tline = {"error": repr(e)}
         # configs[2] (C3: N=65536 Matern32, block-cyclic) on the same workspace: one warm-up + one timed step
         c3 = None
-        if not args.no_extra and args.kernel != "matern32" and (args.n == 65536 or selftest):
+        if extra and args.kernel != "matern32" and (args.n == 65536 or selftest):
             job.set_kernel("matern32")
             job.step()
             e3, ll3 = run_timed(job, 1, 0, barrier)
@@ -1040,7 +1068,7 @@ def main():
         # model, profiles/r04/scale_model.md), north_star words it 2-D block-cyclic -- one warm-up + one timed step of
         # 'square' (1x2 / 2x2 / 2x4), or of N x 1 when --grid asked for something else, so that ONE hardware run adjudicates
         other = None
-        if not args.no_extra and world in (2, 4, 8):
+        if extra and world in (2, 4, 8):
             og = "square" if not args.grid else ""
             try:
                 job.set_kernel(args.kernel)
@@ -1092,6 +1120,7 @@ def main():
             out["rccl_ranks_seen"] = rccl["ranks_seen"]
             out["config"]["grid"] = "%dx%d" % job.chol_grid()
             out["config"]["nb"] = job.nb
+        if world > 1 and args.full:
             parity = {"ranks_agree": {"spread": ll_spread, "rel": abs(ll_spread) / max(abs(ll), 1e-300)}}
             gold = golden_ll(args.n, KERNEL_NAMES[args.kernel])
             if gold is not None:
@@ -1142,7 +1171,7 @@ def main():
                     "frac": ach / PEAK_FP64_MFMA_TFLOPS, "traffic": None, "launches": calls,
                     "avg_launch_ms": ms / max(calls, 1), "algorithmic_flops_per_launch": fl / max(calls, 1),
                     "scope": "per GPU (rank 0)"}
-        if world == 1:
+        if world == 1 and args.full:
             p = job.profile()
             if p.n_trailing > 0 and p.ms_trailing > 0:
                 ach_syrk = p.trailing_flops / (p.ms_trailing * 1e-3) * 1e-12
@@ -1218,14 +1247,16 @@ def main():
                     "bound": "hbm", "achieved": bytes_alg / (p.ms_build * 1e-3) * 1e-9, "peak": PEAK_HBM_GBS, "unit": "GB/s",
                     "frac": bytes_alg / (p.ms_build * 1e-3) * 1e-9 / PEAK_HBM_GBS, "traffic": None,
                     "algorithmic_bytes": bytes_alg, "ms": p.ms_build}
+        if world == 1:
             job.close()
+        if world == 1 and args.full:
             parity = {}
             gold = golden_ll(args.n)
             if gold is not None:
                 parity["headline"] = {"n": args.n, "ll_gpu": ll, "ll_ref": gold[0], "rel": abs(ll - gold[0]) / abs(gold[0]),
                                       "ref": "tests/golden/large.json[%s]: reference C++ evaluator + LAPACK in the build "
                                              "container (oracle/gen_golden_large.py)" % gold[1]}
-            if not args.no_extra:
+            if extra:
                 out["public_api"] = public_api_report(args.n, local_rank)
                 out["value_public_api"] = {
                     "value": out["public_api"]["value_tflops"], "ms_per_step": out["public_api"]["seconds_per_step"] * 1e3,
@@ -1267,14 +1298,14 @@ def main():
                     out["config"]["also_curve"] = curve_report(local_rank)
                 except Exception as e:
                     out["config"]["also_curve_error"] = repr(e)
-            if not args.no_cpu:
+            if cpu:
                 out["cpu_baseline"] = cpu_baseline(args.cpu_n)
                 jp = DenseJob(args.cpu_n, args.nb, local_rank, profile=False)       # the GPU at the SAME N as the CPU sample
                 llp = jp.step()
                 jp.close()
                 llr = out["cpu_baseline"]["log_likelihood"]
                 parity["cpu_sample"] = {"n": args.cpu_n, "ll_gpu": llp, "ll_ref": llr, "rel": abs(llp - llr) / abs(llr)}
-                if args.cpu_n2 > 0 and not args.no_extra:
+                if args.cpu_n2 > 0 and extra:
                     try:
                         sp = cpu_baseline_second_point(args.cpu_n2, local_rank)
                         out["cpu_baseline"]["second_point"] = sp
@@ -1285,7 +1316,7 @@ def main():
                 out["parity"] = parity
                 out["parity"]["bound"] = 1e-6
                 out["parity"]["ok"] = all(v["rel"] <= 1e-6 for v in parity.values() if isinstance(v, dict))
-        if world > 1:
+        if world > 1 and args.full:
             out["timeline_rank0_ms"] = tline                     # panel / exchange / gather chain over the timed steps
     if world > 1:
         # the ranks leave (and give their GPUs back) BEFORE rank 0 runs the second multi-GPU form and prints the line
@@ -1297,10 +1328,10 @@ def main():
         job = None
         if not selftest:
             torch.cuda.empty_cache()
-            if args.abi_timeout > 0 and not args.share_gpu:
+            if args.full and args.abi_timeout > 0 and not args.share_gpu:
                 out["abi_form"] = abi_form_report(args, world)
     if rank == 0:
-        emit(out, args.detail or None)
+        emit(out, args.detail if args.full and args.detail else None)
         c5 = out.get("config", {}).get("also_C5", {})
         if c5 and (not c5.get("fused_not_slower_than_separate_calls", True) or "flop_model_error" in c5):
             sys.stderr.write("bench.py: C5 CHECK FAILED: fused objective slower than the separate calls, or a rate above "

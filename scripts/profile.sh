@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT="$R/gpurun_out/prof_$TAG"
 mkdir -p "$OUT"; rm -f "$OUT/bench_lines_under_rocprof.jsonl"
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $R/bench.py --no-cpu --no-extra"
+BENCH="python $R/bench.py --full --no-cpu --no-extra"
 # 1. kernel traces of the headline config (N = 65536) with and without look-ahead, and of configs[1]
 rocprofv3 --kernel-trace --stats -d "$OUT/trace64k" -o trace -- $BENCH --steps 2 --warmup 1 > "$OUT/trace64k.log" 2>&1
 rocprofv3 --kernel-trace --stats -d "$OUT/trace64k_nola" -o trace -- $BENCH --steps 2 --warmup 1 --no-lookahead > "$OUT/trace64k_nola.log" 2>&1

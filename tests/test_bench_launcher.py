@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -39,7 +40,7 @@ def _json_lines(text):
 def test_gpus_2_launches_two_ranks_and_prints_one_line(tmp_path):
     detail = str(tmp_path / "detail.json")
     r = _run(["--gpus", "2", "--backend", "gloo", "--tile-ops", "numpy", "--n", "600", "--nb", "128",
-              "--steps", "1", "--warmup", "0", "--no-cpu", "--detail", detail])
+              "--steps", "1", "--warmup", "0", "--no-cpu", "--full", "--detail", detail])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [d for d in _json_lines(r.stdout) if "metric" in d]
     assert len(lines) == 1
@@ -65,11 +66,34 @@ def test_gpus_2_launches_two_ranks_and_prints_one_line(tmp_path):
 
 def test_matern32_kernel_flag():
     r = _run(["--gpus", "2", "--backend", "gloo", "--tile-ops", "numpy", "--size", "500", "--nb", "128",
-              "--steps", "1", "--warmup", "0", "--no-cpu", "--kernel", "matern32"])
+              "--steps", "1", "--warmup", "0", "--no-cpu", "--full", "--kernel", "matern32"])
     assert r.returncode == 0, r.stderr[-2000:]
     d = [x for x in _json_lines(r.stdout) if "metric" in x][0]
     assert d["n_gpus"] == 2 and d["config"]["kernel"] == "Matern32" and d["parity"]["ok"]
     assert "C3_matern32" not in d.get("also", {})
+
+
+def test_plain_run_times_the_steps_and_dumps_outputs(tmp_path):
+    """without --full: the headline steps only (no parity, no secondary legs, no detail file); --dump-outputs writes what
+    the last timed step computed, and the same arguments give the same outputs"""
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ("out%d" % i)
+        r = _run(["--gpus", "2", "--backend", "gloo", "--tile-ops", "numpy", "--n", "400", "--nb", "128",
+                  "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = [x for x in _json_lines(r.stdout) if "metric" in x][0]
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["n_gpus"] == 2
+        assert line["metric"] == "gp_compute_plus_log_likelihood_effective_tflops" and line["unit"] == "TFLOP/s"
+        assert line["higher_is_better"] is True and line["dtype"] == "f64"
+        for k in ("parity", "also", "links", "detail", "timeline_rank0_ms"):
+            assert k not in line, k
+        ll = np.load(str(d / "log_likelihood.npy"))
+        ld = np.load(str(d / "log_determinant.npy"))
+        assert ll.dtype == np.float64 and ll.shape == (1,) and ld.dtype == np.float64 and ld.shape == (1,)
+        assert abs(ll[0] - line["log_likelihood"]) <= 1e-5 * abs(ll[0])     # the line rounds to 6 digits
+        dumps.append((ll[0], ld[0]))
+    assert dumps[0] == dumps[1]
 
 
 @pytest.mark.skipif(torch.cuda.is_available() and torch.cuda.device_count() >= 2, reason="box has the GPUs: would really launch")

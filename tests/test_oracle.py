@@ -1,6 +1,8 @@
 """Pin the oracle (CPU, no GPU): NumPy restatement vs the committed golden vectors produced by
 the real reference, vs the reference's published golden scalars, and -- where the compiled
-reference evaluator (oracle/_ref) or /root/reference is present -- vs the reference itself."""
+reference evaluator (oracle/_ref) or the reference package is present -- vs the reference itself."""
+import os
+
 import numpy as np
 import pytest
 
@@ -93,14 +95,27 @@ def test_mt19937_matches_std():
     assert [r(), r()] == [1608637542, 3421126067]     # std::mt19937 seeded with 42
 
 
-def test_flattener_accepts_reference_kernel_objects():
+@pytest.fixture(scope="module")
+def golden_ref_objects():
+    """what the reference's own kernel objects gave (oracle/gen_golden_refobjects.py)"""
+    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_objects.npz"))
+
+
+def test_flattener_accepts_reference_kernel_objects(golden_ref_objects):
     """Drop-in claim of INTEGRATION.md section 1: our spec flattener reads the reference's own
-    `george.kernels` objects (same attribute protocol as parser.h) into the same POD program."""
-    george = ref_loader.load_reference()
-    if george is None:
-        pytest.skip("/root/reference not present (GPU box)")
+    `george.kernels` objects (same attribute protocol as parser.h) into the same POD program.
+    Against the recorded programs of the reference's objects always; against the objects themselves
+    where the reference package is importable."""
     from george_amd import program
     ours = zoo.kernel_zoo(AK)
+    g = golden_ref_objects
+    for name, ka in ours:
+        assert bytes(program.flatten(ka)) == g[name + "/flat"].tobytes(), name
+        dk = program.DeviceKernel(ka)
+        assert [dk.ndim, dk.size] == list(g[name + "/ndim_size"]), name
+    george = ref_loader.load_reference()
+    if george is None:
+        return
     theirs = zoo.kernel_zoo(george.kernels)
     for (name, ka), (_, kr) in zip(ours, theirs):
         assert bytes(program.flatten(ka)) == bytes(program.flatten(kr)), name
@@ -112,10 +127,15 @@ def test_flattener_accepts_reference_kernel_objects():
     assert gp.solver_type is george_amd.BasicSolver
 
 
-def test_against_live_reference_when_available():
+def test_against_live_reference_when_available(golden_ref_objects):
+    """kernels_np against the reference's own get_value(): recorded values always, live where the package is importable"""
+    g = golden_ref_objects
+    for name, ka in zoo.kernel_zoo(AK)[::7]:
+        t1 = g[name + "/live_t1"]
+        np.testing.assert_allclose(kernels_np.value_symmetric(ka, t1), g[name + "/live_value"], rtol=RTOL, atol=ATOL)
     george = ref_loader.load_reference()
     if george is None:
-        pytest.skip("/root/reference not present (GPU box)")
+        return
     rng = np.random.RandomState(5)
     for name, k_ref in zoo.kernel_zoo(george.kernels)[::7]:
         t1 = rng.randn(11, k_ref.ndim)
