@@ -37,6 +37,8 @@
 #include <math.h>
 #include <string.h>
 #include <algorithm>
+#include <atomic>
+#include <memory>
 #include <thread>
 #include <vector>
 #include "gh_common.h"
@@ -830,19 +832,13 @@ __global__ __launch_bounds__(64 * AW_NODES) void hodlr_aca_wave_kernel(
   }
 }
 
-// 1 (default): the deep levels whose blocks have <= 256 rows and columns through hodlr_aca_wave_kernel; 0: every level through the
-// workgroup kernel (A/B and the same-bits test)
-static int g_hodlr_leaf_fused = 1;      // 128-row leaves of fast-form kernels: evaluated inside the factorisation kernel (0: a build launch first)
+static std::atomic<int> g_hodlr_leaf_fused{1};      // 128-row leaves of fast-form kernels: evaluated inside the factorisation kernel (0: a build launch first)
 extern "C" int gh_debug_set_hodlr_leaf_fused(int on) {
-  const int prev = g_hodlr_leaf_fused;
-  g_hodlr_leaf_fused = on ? 1 : 0;
-  return prev;
+  return g_hodlr_leaf_fused.exchange(on ? 1 : 0);
 }
-static int g_hodlr_coop_singles = 1;    // clusterable levels that end up with one workgroup per node ride at the end of the cooperative launch
+static std::atomic<int> g_hodlr_coop_singles{1};    // clusterable levels that end up with one workgroup per node ride at the end of the cooperative launch
 extern "C" int gh_debug_set_hodlr_coop_singles(int on) {
-  const int prev = g_hodlr_coop_singles;
-  g_hodlr_coop_singles = on ? 1 : 0;
-  return prev;
+  return g_hodlr_coop_singles.exchange(on ? 1 : 0);
 }
 // The clusters BELOW the first clustered level get 1 / this of the workgroups the even-load rule deals them (never fewer than two).
 // Even load per thread makes every cluster as fast as the root's -- but only the root's chain of ~20 ACA steps is the critical path
@@ -850,35 +846,27 @@ extern "C" int gh_debug_set_hodlr_coop_singles(int on) {
 // nothing else fits beside it) mostly waiting at cluster barriers.  Half as wide they take longer, still end before the root,
 // and the CUs go to the one-workgroup nodes and the leaves: C4 3.48 -> 3.40 ms, 1 048 576 17.9 -> 17.4, never slower
 // (profiles/r06/hodlr_coop_lower_ab.md; a quarter: 4.02 ms -- then they outlast the root).
-static int g_hodlr_coop_lower = 2;
+static std::atomic<int> g_hodlr_coop_lower{2};
 extern "C" int gh_debug_set_hodlr_coop_lower(int div) {
-  const int prev = g_hodlr_coop_lower;
-  g_hodlr_coop_lower = div < 1 ? 2 : div;
-  return prev;
+  return g_hodlr_coop_lower.exchange(div < 1 ? 2 : div);
 }
-static int g_hodlr_u_from_v = 1;        // the factorisation's leaf product reads the level-major V and writes U for the first time (no U from the compaction)
+static std::atomic<int> g_hodlr_u_from_v{1};        // the factorisation's leaf product reads the level-major V and writes U for the first time (no U from the compaction)
 extern "C" int gh_debug_set_hodlr_u_from_v(int on) {
-  const int prev = g_hodlr_u_from_v;
-  g_hodlr_u_from_v = on ? 1 : 0;
-  return prev;
+  return g_hodlr_u_from_v.exchange(on ? 1 : 0);
 }
-static int g_hodlr_lpt = 1;             // the one-workgroup ACA launch takes a level's nodes longest first (durations of the handle's previous compute())
+static std::atomic<int> g_hodlr_lpt{1};             // the one-workgroup ACA launch takes a level's nodes longest first (durations of the handle's previous compute())
 extern "C" int gh_debug_set_hodlr_lpt(int on) {
-  const int prev = g_hodlr_lpt;
-  g_hodlr_lpt = on ? 1 : 0;
-  return prev;
+  return g_hodlr_lpt.exchange(on ? 1 : 0);
 }
-static int g_hodlr_coop_wgs = 256;      // workgroups of the cooperative ACA launch (<= CUs: every cluster resident)
+static std::atomic<int> g_hodlr_coop_wgs{256};      // workgroups of the cooperative ACA launch (<= CUs: every cluster resident)
 extern "C" int gh_debug_set_hodlr_coop_wgs(int n) {
-  const int prev = g_hodlr_coop_wgs;
-  g_hodlr_coop_wgs = n < 32 ? 32 : (n > 256 ? 256 : n);
-  return prev;
+  return g_hodlr_coop_wgs.exchange(n < 32 ? 32 : (n > 256 ? 256 : n));
 }
-static int g_hodlr_wave_aca = 1;
+// 1 (default): the deep levels whose blocks have <= 256 rows and columns through hodlr_aca_wave_kernel; 0: every level through the
+// workgroup kernel (A/B and the same-bits test)
+static std::atomic<int> g_hodlr_wave_aca{1};
 extern "C" int gh_debug_set_hodlr_wave_aca(int on) {
-  const int prev = g_hodlr_wave_aca;
-  g_hodlr_wave_aca = on ? 1 : 0;
-  return prev;
+  return g_hodlr_wave_aca.exchange(on ? 1 : 0);
 }
 // (static + dynamic LDS of a launch with the mirrors is 67 KiB: above the 64 KiB a kernel gets without asking; per device)
 static int aca_lds_attr() {
@@ -2257,12 +2245,12 @@ __global__ __launch_bounds__(256) void hodlr_updred_kernel(const MMJob* __restri
       }
   }
 }
-static int launch_mm(gh_hodlr* h, const MMJob* jobs, int njobs, int max_m, const double* A, long a_rs, long a_cs,
+static int launch_mm(gh_hodlr* h, hipStream_t st, const MMJob* jobs, int njobs, int max_m, const double* A, long a_rs, long a_cs,
                      const double* B, long ldb, long b_col0, double* O, long ldo, long o_col0, int C, bool subtract, int mtiles = 1);
 static int launch_red(gh_hodlr* h, const MMJob* jobs, int njobs, int R, const double* V, const double* B, long ldb, long b_col0,
                       double* O, long ldo, long o_col0, int C) {
   if (njobs <= 0 || C <= 0 || R <= 0) return GH_OK;
-  if (R > 16 || C > 128) return launch_mm(h, jobs, njobs, R, V, 1, R, B, ldb, b_col0, O, ldo, o_col0, C, false, 1);
+  if (R > 16 || C > 128) return launch_mm(h, h->st, jobs, njobs, R, V, 1, R, B, ldb, b_col0, O, ldo, o_col0, C, false, 1);
   // (one instantiation per number of 16-column tiles: the LDS image is 128 x (16 CT + 1) doubles, and with 17-50 KB
   //  instead of 83 several workgroups share a CU at the shallow levels, whose U has few columns yet)
 #define GH_RED_LAUNCH(CT) hipLaunchKernelGGL(hodlr_red_kernel<CT>, dim3(njobs), dim3(256), 0, h->st, jobs, V, R, B, ldb, b_col0, O, ldo, o_col0, C)
@@ -2282,7 +2270,7 @@ static int launch_red(gh_hodlr* h, const MMJob* jobs, int njobs, int R, const do
 static int launch_upd(gh_hodlr* h, const MMJob* jobs, int njobs, int R, const double* A, long a_rs, const double* B, long ldb,
                       double* O, long ldo, int C) {
   if (njobs <= 0 || C <= 0 || R <= 0) return GH_OK;
-  if (R > 16 || C > 128 || HCH > 128) return launch_mm(h, jobs, njobs, HCH, A, a_rs, 1, B, ldb, 0, O, ldo, 0, C, true, HCH / 32);
+  if (R > 16 || C > 128 || HCH > 128) return launch_mm(h, h->st, jobs, njobs, HCH, A, a_rs, 1, B, ldb, 0, O, ldo, 0, C, true, HCH / 32);
 #define GH_UPD_LAUNCH(CT) hipLaunchKernelGGL(hodlr_upd_kernel<CT>, dim3(njobs), dim3(256), 0, h->st, jobs, A, a_rs, B, ldb, O, ldo, C)
   switch ((C + 15) / 16) {
     case 1: GH_UPD_LAUNCH(1); break;
@@ -2297,11 +2285,10 @@ static int launch_upd(gh_hodlr* h, const MMJob* jobs, int njobs, int R, const do
   return GH_OK;
 }
 
-static int hodlr_passes();
 // update of level `L` (columns [0, C) of U, C = L->off) + reduce of level `nx` over the same columns in one pass; false when
 // the pair cannot share a pass (the caller then launches the two kernels)
-static bool updred_possible(const HLevel* L, const HLevel* nx, int C, int cpass) {
-  return (hodlr_passes() & 2) && nx && !nx->top && !L->top && L->R <= 16 && nx->R <= 16 && C > 0 && C <= 128 && HCH == 128 &&
+static bool updred_possible(int passes, const HLevel* L, const HLevel* nx, int C, int cpass) {
+  return (passes & 2) && nx && !nx->top && !L->top && L->R <= 16 && nx->R <= 16 && C > 0 && C <= 128 && HCH == 128 &&
          nx->off + nx->R == C && C <= cpass && nx->chunk_geom == L->chunk_geom && !L->chunk_geom.empty();
 }
 static int launch_updred(gh_hodlr* h, const HLevel* L, const HLevel* nx, const double* A, long a_rs, const double* B, long ldb,
@@ -2324,14 +2311,14 @@ static int launch_updred(gh_hodlr* h, const HLevel* L, const HLevel* nx, const d
 
 // mtiles: 32-row tiles of a job handled by ONE workgroup (the update passes: 4, i.e. a whole 128-row
 // chunk -- 8192 workgroups of one tiny tile each spent their 50 us on being dispatched)
-static int launch_mm(gh_hodlr* h, const MMJob* jobs, int njobs, int max_m, const double* A, long a_rs, long a_cs,
+static int launch_mm(gh_hodlr* h, hipStream_t st, const MMJob* jobs, int njobs, int max_m, const double* A, long a_rs, long a_cs,
                      const double* B, long ldb, long b_col0, double* O, long ldo, long o_col0, int C, bool subtract, int mtiles) {
   if (njobs <= 0 || C <= 0 || max_m <= 0) return GH_OK;
   MMArgs a;
   a.mtiles = mtiles;
   a.jobs = jobs; a.A = A; a.a_rs = a_rs; a.a_cs = a_cs; a.B = B; a.ldb = ldb; a.b_col0 = b_col0;
   a.O = O; a.ldo = ldo; a.o_col0 = o_col0; a.C = C; a.subtract = subtract ? 1 : 0;
-  hipLaunchKernelGGL(hodlr_mm_kernel, dim3(njobs, ((max_m + 31) / 32 + mtiles - 1) / mtiles, (C + 63) / 64), dim3(256), 0, h->st, a);
+  hipLaunchKernelGGL(hodlr_mm_kernel, dim3(njobs, ((max_m + 31) / 32 + mtiles - 1) / mtiles, (C + 63) / 64), dim3(256), 0, st, a);
   GH_HIP(hipGetLastError());
   return GH_OK;
 }
@@ -2379,7 +2366,7 @@ static int apply_level(gh_hodlr* h, HLevel* L, double* X, long ldx, long xcol0, 
     hipLaunchKernelGGL(hodlr_sum_narrow_kernel, dim3(nn, 2 * R), dim3(256), 0, h->st, h->P.d(), (const int*)L->d_crange.p, R, Cp, C, h->Tsum.d());
     GH_HIP(hipGetLastError());
     if (L->top) GH_CHECK(h->sub.allreduce(h->sub.ctx, L->top_level, h->Tsum.d(), 2 * R, C, Cp, h->st));
-    GH_CHECK(launch_mm(h, (const MMJob*)L->d_smul_jobs.p, nn, 2 * R, L->sinv.d(), 2 * R, 1,
+    GH_CHECK(launch_mm(h, h->st, (const MMJob*)L->d_smul_jobs.p, nn, 2 * R, L->sinv.d(), 2 * R, 1,
                        h->Tsum.d(), Cp, 0, h->Tout.d(), Cp, 0, C, false));
     hipLaunchKernelGGL(hodlr_mv_update_kernel, dim3(L->nchunks), dim3(128), 0, h->st, uj, Ub, u_rs, h->Tout.d(), Cp, X, ldx, xcol0, C);
     GH_HIP(hipGetLastError());
@@ -2392,20 +2379,20 @@ static int apply_level(gh_hodlr* h, HLevel* L, double* X, long ldx, long xcol0, 
     const int cw = std::min(pw, C - cp);
     const long Cp = h->cpass;
     // reduce: P[chunk] = V_chunk^T X_chunk
-    GH_CHECK(launch_mm(h, (const MMJob*)L->d_red_jobs.p, L->nchunks, R, Vl, 1, R,
+    GH_CHECK(launch_mm(h, h->st, (const MMJob*)L->d_red_jobs.p, L->nchunks, R, Vl, 1, R,
                        X, ldx, xcol0 + cp, h->P.d(), Cp, 0, cw, false));
     hipLaunchKernelGGL(hodlr_sum_kernel, dim3(nn, 2 * R), dim3(64 * SUM_NS), 0, h->st, h->P.d(), (const int*)L->d_crange.p, R, Cp, cw, h->Tsum.d());
     GH_HIP(hipGetLastError());
     if (L->top) GH_CHECK(h->sub.allreduce(h->sub.ctx, L->top_level, h->Tsum.d(), 2 * R, cw, Cp, h->st));
     // core: Tout = S^-1 Tsum
-    GH_CHECK(launch_mm(h, (const MMJob*)L->d_smul_jobs.p, nn, 2 * R, L->sinv.d(), 2 * R, 1,
+    GH_CHECK(launch_mm(h, h->st, (const MMJob*)L->d_smul_jobs.p, nn, 2 * R, L->sinv.d(), 2 * R, 1,
                        h->Tsum.d(), Cp, 0, h->Tout.d(), Cp, 0, cw, false));
     // update: X_chunk -= U_chunk * Tout[half]
     if (U)
-      GH_CHECK(launch_mm(h, (const MMJob*)L->d_upd_jobs.p, L->nchunks, HCH, U + L->off, ldu, 1,
+      GH_CHECK(launch_mm(h, h->st, (const MMJob*)L->d_upd_jobs.p, L->nchunks, HCH, U + L->off, ldu, 1,
                          h->Tout.d(), Cp, 0, X, ldx, xcol0 + cp, cw, true, HCH / 32));
     else
-      GH_CHECK(launch_mm(h, (const MMJob*)L->d_updl_jobs.p, L->nchunks, HCH, h->UL.d() + (long)h->n * L->off, R, 1,
+      GH_CHECK(launch_mm(h, h->st, (const MMJob*)L->d_updl_jobs.p, L->nchunks, HCH, h->UL.d() + (long)h->n * L->off, R, 1,
                          h->Tout.d(), Cp, 0, X, ldx, xcol0 + cp, cw, true, HCH / 32));
   }
   return GH_OK;
@@ -2413,8 +2400,7 @@ static int apply_level(gh_hodlr* h, HLevel* L, double* X, long ldx, long xcol0, 
 // X rows of every leaf <- K_leaf^-1 X
 // red / red_done: the sweep's first call -- form the chunk products of level `red` over the same columns in the same pass when
 // its chunks are the leaves (then *red_done = true and the caller skips that level's reduce)
-static int hodlr_passes();
-static int apply_leaves(gh_hodlr* h, double* X, long ldx, long xcol0, int C, const HLevel* red = nullptr, bool* red_done = nullptr,
+static int apply_leaves(gh_hodlr* h, int passes, double* X, long ldx, long xcol0, int C, const HLevel* red = nullptr, bool* red_done = nullptr,
                         const LeafSrc* src = nullptr) {
   const LeafSrc ls = src ? *src : LeafSrc();         // (src: only on the 128-row-leaf path with ONE column pass -- leaf_src_possible())
   if (red_done) *red_done = false;
@@ -2427,7 +2413,7 @@ static int apply_leaves(gh_hodlr* h, double* X, long ldx, long xcol0, int C, con
   }
   if (h->leaf_pitch == 128 && h->max_leaf <= 128) {
     // one workgroup per leaf, in place; column passes of <= 128 (80 where that covers the rest: less LDS, fewer MFMAs)
-    bool fuse = (hodlr_passes() & 2) && red && red_done && C <= 128 && xcol0 == 0 && red->R > 0 && red->R <= 16 && !red->top &&
+    bool fuse = (passes & 2) && red && red_done && C <= 128 && xcol0 == 0 && red->R > 0 && red->R <= 16 && !red->top &&
                 red->off + red->R == C && C <= h->cpass && red->chunk_geom.size() == 2 * h->leaves.size();
     for (size_t q = 0; fuse && q < h->leaves.size(); ++q)
       fuse = red->chunk_geom[2 * q] == h->leaves[q].start && red->chunk_geom[2 * q + 1] == h->leaves[q].size;
@@ -2457,7 +2443,7 @@ static int apply_leaves(gh_hodlr* h, double* X, long ldx, long xcol0, int C, con
   }
   for (int cp = 0; cp < C; cp += h->cpass) {
     const int cw = std::min(h->cpass, C - cp);
-    GH_CHECK(launch_mm(h, (const MMJob*)h->d_leaf_jobs.p, (int)h->leaves.size(), h->max_leaf, h->leaf_inv.d(), h->leaf_pitch, 1,
+    GH_CHECK(launch_mm(h, h->st, (const MMJob*)h->d_leaf_jobs.p, (int)h->leaves.size(), h->max_leaf, h->leaf_inv.d(), h->leaf_pitch, 1,
                        X, ldx, xcol0 + cp, h->Y.d(), h->cpass, 0, cw, false));
     const long tot = h->n * cw;
     hipLaunchKernelGGL(hodlr_copyrows_kernel, dim3((unsigned)std::min<long>((tot + 255) / 256, 65535)), dim3(256), 0, h->st,
@@ -2469,23 +2455,15 @@ static int apply_leaves(gh_hodlr* h, double* X, long ldx, long xcol0, int C, con
 // full solve on X (n x C): leaves, then levels bottom-up (hodlr.h:107-114)
 // gh_debug_set_hodlr_passes (A/B in one process, tests): bit 0 = the narrow solve in shared passes (round 5), bit 1 = the
 // factorisation sweep's update of level l and reduce of the next level in one pass over U; default: both
-static int g_hodlr_passes = -1;
-static int hodlr_passes() {
-  if (g_hodlr_passes < 0) g_hodlr_passes = 3;
-  return g_hodlr_passes;
-}
+static std::atomic<int> g_hodlr_passes{3};
 // 1: leaves of 129 .. 256 rows through the pivoted Gauss-Jordan in place (the path every leaf of more than 256 rows takes)
 // instead of the 2 x 2 blocked Cholesky: validation arm, tests/test_gpu_hodlr.py
-static int g_hodlr_leaf_gj = 0;
+static std::atomic<int> g_hodlr_leaf_gj{0};
 extern "C" int gh_debug_set_hodlr_leaf_gj(int on) {
-  const int prev = g_hodlr_leaf_gj;
-  g_hodlr_leaf_gj = on ? 1 : 0;
-  return prev;
+  return g_hodlr_leaf_gj.exchange(on ? 1 : 0);
 }
 extern "C" int gh_debug_set_hodlr_passes(int mask) {
-  const int prev = hodlr_passes();
-  g_hodlr_passes = mask < 0 ? 3 : (mask & 3);
-  return prev;
+  return g_hodlr_passes.exchange(mask < 0 ? 3 : (mask & 3));
 }
 // the narrow solve: leaves (symmetric form), then per level "sum + core product" and ONE pass over the rows that applies this
 // level's update and forms the next level's chunk products (separate passes where the two levels' chunks differ)
@@ -2515,7 +2493,7 @@ static int solve_narrow(gh_hodlr* h, double* X, long ldx, int C) {
                          (const double*)L->sinv.d(), h->Tout.d());
     } else {
       hipLaunchKernelGGL(hodlr_sum_narrow_kernel, dim3(nn, 2 * L->R), dim3(256), 0, h->st, h->P.d(), (const int*)L->d_crange.p, L->R, Cp, C, h->Tsum.d());
-      GH_CHECK(launch_mm(h, (const MMJob*)L->d_smul_jobs.p, nn, 2 * L->R, L->sinv.d(), 2 * L->R, 1, h->Tsum.d(), Cp, 0, h->Tout.d(), Cp, 0, C, false));
+      GH_CHECK(launch_mm(h, h->st, (const MMJob*)L->d_smul_jobs.p, nn, 2 * L->R, L->sinv.d(), 2 * L->R, 1, h->Tsum.d(), Cp, 0, h->Tout.d(), Cp, 0, C, false));
     }
     HLevel* nx = i + 1 < Ls.size() ? Ls[i + 1] : nullptr;
     if (nx && nx->chunk_geom == L->chunk_geom) pass(L, nx);
@@ -2524,13 +2502,13 @@ static int solve_narrow(gh_hodlr* h, double* X, long ldx, int C) {
   GH_HIP(hipGetLastError());
   return GH_OK;
 }
-static int solve_all(gh_hodlr* h, double* X, long ldx, int C) {
-  if ((hodlr_passes() & 1) && C <= MV_C && h->max_leaf <= 256 && h->sub.depth == 0) {
+static int solve_all(gh_hodlr* h, int passes, double* X, long ldx, int C) {
+  if ((passes & 1) && C <= MV_C && h->max_leaf <= 256 && h->sub.depth == 0) {
     bool ok = true;
     for (auto* L : h->levels) ok = ok && !L->top && L->R <= 32 && (L->R == 0 || !L->chunk_geom.empty());
     if (ok) return solve_narrow(h, X, ldx, C);
   }
-  GH_CHECK(apply_leaves(h, X, ldx, 0, C));
+  GH_CHECK(apply_leaves(h, passes, X, ldx, 0, C));
   for (int l = (int)h->levels.size() - 1; l >= 0; --l)
     GH_CHECK(apply_level(h, h->levels[l], X, ldx, 0, C, nullptr, 0));
   return GH_OK;
@@ -2675,14 +2653,12 @@ __global__ __launch_bounds__(256) void hodlr_core_kernel(const double* __restric
     }
   }
 }
-static int g_hodlr_core_fused = 1;
+static std::atomic<int> g_hodlr_core_fused{1};
 extern "C" int gh_debug_set_hodlr_core_fused(int on) {
-  const int prev = g_hodlr_core_fused;
-  g_hodlr_core_fused = on ? 1 : 0;
-  return prev;
+  return g_hodlr_core_fused.exchange(on ? 1 : 0);
 }
 
-static int batched_inverse(gh_hodlr* h, double* base, const std::vector<long>& offs, const std::vector<int>& sizes,
+static int batched_inverse(gh_hodlr* h, hipStream_t st, double* base, const std::vector<long>& offs, const std::vector<int>& sizes,
                            double* d_logdet, GhBuf* const* tables = nullptr, bool tables_valid = false,
                            const double* tsum = nullptr, int tsum_R = 0) {
   const int nb = (int)sizes.size();
@@ -2695,28 +2671,28 @@ static int batched_inverse(gh_hodlr* h, double* base, const std::vector<long>& o
   GhBuf& d_sizes = tables ? *tables[1] : (GhBuf&)l_sizes;
   GhBuf& d_sc = tables ? *tables[2] : (GhBuf&)l_sc;
   if (!tables || !tables_valid) {
-    GH_CHECK(upload(d_offs, offs, h->st));
-    GH_CHECK(upload(d_sizes, sizes, h->st));
-    GH_CHECK(upload(d_sc, sc, h->st));
+    GH_CHECK(upload(d_offs, offs, st));
+    GH_CHECK(upload(d_sizes, sizes, st));
+    GH_CHECK(upload(d_sc, sc, st));
   }
   int nmax = 0;
   for (int v : sizes) nmax = std::max(nmax, v);
   if (nmax <= 32 && nb <= 64) {   // few cores (the top levels): a workgroup per matrix, columns over its four wavefronts
-    if (nmax <= 16) hipLaunchKernelGGL(gj_small4_kernel<16>, dim3(nb), dim3(256), 0, h->st, base, (const long*)d_offs.p, (const int*)d_sizes.p, nb, d_logdet, (int*)h->flags.p, tsum, (long)h->cpass, tsum_R);
-    else hipLaunchKernelGGL(gj_small4_kernel<32>, dim3(nb), dim3(256), 0, h->st, base, (const long*)d_offs.p, (const int*)d_sizes.p, nb, d_logdet, (int*)h->flags.p, tsum, (long)h->cpass, tsum_R);
+    if (nmax <= 16) hipLaunchKernelGGL(gj_small4_kernel<16>, dim3(nb), dim3(256), 0, st, base, (const long*)d_offs.p, (const int*)d_sizes.p, nb, d_logdet, (int*)h->flags.p, tsum, (long)h->cpass, tsum_R);
+    else hipLaunchKernelGGL(gj_small4_kernel<32>, dim3(nb), dim3(256), 0, st, base, (const long*)d_offs.p, (const int*)d_sizes.p, nb, d_logdet, (int*)h->flags.p, tsum, (long)h->cpass, tsum_R);
     GH_HIP(hipGetLastError());
     return GH_OK;
   }
   if (nmax <= 32) {                  // the Woodbury cores: one wavefront per matrix
     const dim3 grid((unsigned)((nb + 3) / 4));
-    if (nmax <= 8) hipLaunchKernelGGL(gj_small_kernel<8>, grid, dim3(256), 0, h->st, base, (const long*)d_offs.p, (const int*)d_sizes.p, nb, d_logdet, (int*)h->flags.p, tsum, (long)h->cpass, tsum_R);
-    else if (nmax <= 16) hipLaunchKernelGGL(gj_small_kernel<16>, grid, dim3(256), 0, h->st, base, (const long*)d_offs.p, (const int*)d_sizes.p, nb, d_logdet, (int*)h->flags.p, tsum, (long)h->cpass, tsum_R);
-    else hipLaunchKernelGGL(gj_small_kernel<32>, grid, dim3(256), 0, h->st, base, (const long*)d_offs.p, (const int*)d_sizes.p, nb, d_logdet, (int*)h->flags.p, tsum, (long)h->cpass, tsum_R);
+    if (nmax <= 8) hipLaunchKernelGGL(gj_small_kernel<8>, grid, dim3(256), 0, st, base, (const long*)d_offs.p, (const int*)d_sizes.p, nb, d_logdet, (int*)h->flags.p, tsum, (long)h->cpass, tsum_R);
+    else if (nmax <= 16) hipLaunchKernelGGL(gj_small_kernel<16>, grid, dim3(256), 0, st, base, (const long*)d_offs.p, (const int*)d_sizes.p, nb, d_logdet, (int*)h->flags.p, tsum, (long)h->cpass, tsum_R);
+    else hipLaunchKernelGGL(gj_small_kernel<32>, grid, dim3(256), 0, st, base, (const long*)d_offs.p, (const int*)d_sizes.p, nb, d_logdet, (int*)h->flags.p, tsum, (long)h->cpass, tsum_R);
     GH_HIP(hipGetLastError());
     return GH_OK;
   }
   if (tsum) {                                     // (cores too big for the wavefront kernel: build them first)
-    hipLaunchKernelGGL(hodlr_sbuild_kernel, dim3(nb), dim3(256), 0, h->st, tsum, (long)h->cpass, tsum_R, base);
+    hipLaunchKernelGGL(hodlr_sbuild_kernel, dim3(nb), dim3(256), 0, st, tsum, (long)h->cpass, tsum_R, base);
     GH_HIP(hipGetLastError());
   }
   GH_CHECK(d_sd.ensure(tot * sizeof(double)));
@@ -2731,41 +2707,75 @@ static int batched_inverse(gh_hodlr* h, double* base, const std::vector<long>& o
       attr_set = true;
     }
   }
-  hipLaunchKernelGGL(gj_inverse_kernel, dim3(nb), dim3(256), lds_bytes, h->st, base, (const long*)d_offs.p, (const int*)d_sizes.p,
+  hipLaunchKernelGGL(gj_inverse_kernel, dim3(nb), dim3(256), lds_bytes, st, base, (const long*)d_offs.p, (const int*)d_sizes.p,
                      d_sd.d(), (int*)d_si.p, (const long*)d_sc.p, d_logdet, (int*)h->flags.p, (int)(lds_bytes / sizeof(double)));
   GH_HIP(hipGetLastError());
   return GH_OK;
 }
 
-extern "C" int gh_hodlr_compute(gh_hodlr* h, gh_kernel* k, const double* x, int64_t n, int32_t ndim,
-                                const double* yerr, double* logdet_out) {
-  if (!h || !k || !x || !yerr || n <= 0) { gh_set_error("bad argument to compute"); return GH_ERR_BAD_ARG; }
-  if (ndim != k->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
-  if (n > 0x3fffffffL) { gh_set_error("HODLR: n too large"); return GH_ERR_BAD_ARG; }
-  GH_HIP(hipSetDevice(h->opts.device));
-  GH_CHECK(k->upload());
-  hipStream_t st = h->st;
+// ================================================================================ compute()
+// The HODLR switches as ONE compute() sees them, read once at its start (gh_hodlr_mgpu_compute runs compute() of several sub-tree
+// handles on threads of their own: a setter that reached one of them halfway would give it a mix of settings).
+struct HodlrSwitches { int leaf_fused, leaf_gj, coop_singles, coop_lower, coop_wgs, u_from_v, lpt, wave_aca, core_fused, passes; };
+struct AcaLevel { GhPooledBuf Tcm, idx, sync, part; int G = 1, rcap = 0; int flags[2] = {0, 0}; char* syncp = nullptr; bool sync_cleared = false;
+                  bool timed = false; };   // timed: its nodes wrote their durations behind the two flags (the one-workgroup launch)
+// ACA_MULTI bit 0: batched candidate search (one-workgroup nodes); bit 1: clusters draw the next row before the norms barrier
+static const int ACA_PSTRIDE = 8 + 2 * ACA_MAXR, ACA_FENCE = 0, ACA_MULTI = 3;   // (fence-free cluster barrier, 8 then 64 candidate rows per search pass: DESIGN.md section 4)
+
+// What the phases of one compute() share.  The destructor is its one join point: on any way out but the successful one it
+// synchronises every stream of the handle BEFORE the members below release their blocks into the process-wide cache, where
+// another handle -- a sibling sub-tree thread of gh_hodlr_mgpu_compute among them -- may pick one up while a side stream still
+// writes it.  A successful compute() has joined the side streams into h->st and synchronised that already.
+struct HodlrCall {
+  gh_hodlr* const h;
+  gh_kernel* const k;
+  const int64_t n;
+  const int32_t ndim;
+  const HodlrSwitches sw{g_hodlr_leaf_fused, g_hodlr_leaf_gj, g_hodlr_coop_singles, g_hodlr_coop_lower, g_hodlr_coop_wgs, g_hodlr_u_from_v,
+                         g_hodlr_lpt, g_hodlr_wave_aca, g_hodlr_core_fused, g_hodlr_passes};
+  int l0 = 0, nlev = 0, rcap0 = 0;
+  bool concurrent = false, user_cap = false;
+  std::vector<AcaLevel> al;
+  GhPooledBuf shared_Tcm;                              // serial mode: the scratch the levels take in turn
+  GhPooledBuf sync_all;                                // the levels' barrier counters / selections / flags: one buffer, ONE memset
+  std::vector<std::unique_ptr<GhPooledBuf>> levelB;   // serial mode: a level's factors parked in a compact buffer
+  GhPooledBuf linv, lstk, l22b, lwk;                   // the leaf stage's work blocks (129..256-row leaves)
+  size_t n_blocks = 0, ld_at = 0;                      // blocks whose log|det| goes to h->ld_all; the next free slot there
+  std::vector<size_t> top_ld;                          // where in ld_all the core of pseudo-level l put its log|det|
+  bool leaves_done = false, u_from_v = false, ok = false;
+  HodlrCall(gh_hodlr* h_, gh_kernel* k_, int64_t n_, int32_t ndim_) : h(h_), k(k_), n(n_), ndim(ndim_) {}
+  ~HodlrCall() { if (!ok) for (hipStream_t s : {h->st, h->st_b, h->st_c, h->st_d}) if (s) (void)hipStreamSynchronize(s); }
   // phase stamps on stderr (how the stalls of the split tree were found): a build-time aid, -DGH_HODLR_PHASE_MARKS
 #ifdef GH_HODLR_PHASE_MARKS
-  const auto dbg_t0 = std::chrono::steady_clock::now();
-  auto mark = [&](const char* what) {
-    fprintf(stderr, "[hodlr %p] %s at %.2f ms\n", (void*)h, what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - dbg_t0).count());
-  };
+  const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  void mark(const char* what) const {
+    fprintf(stderr, "[hodlr %p] %s at %.2f ms\n", (void*)h, what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  }
 #else
-  auto mark = [](const char*) {};
+  void mark(const char*) const {}
 #endif
-  h->computed = false;
-  h->n = n; h->ndim = ndim;
-  GH_CHECK(h->x.ensure((size_t)n * ndim * sizeof(double)));
-  GH_CHECK(h->yerr.ensure((size_t)n * sizeof(double)));
-  GH_CHECK(gh_to_device(h->x.d(), x, (size_t)n * ndim, st));
-  GH_CHECK(gh_to_device(h->yerr.d(), yerr, (size_t)n, st));
-  GH_CHECK(h->scal.ensure(64));
-  mark("inputs enqueued");
+};
 
-  // ---- tree (hodlr.h:47-64), breadth first; kept from the previous compute() when n and min_size are the same
+static int load_inputs(HodlrCall& c, const double* x, const double* yerr) {
+  gh_hodlr* const h = c.h;
+  GH_HIP(hipSetDevice(h->opts.device));
+  GH_CHECK(c.k->upload());
+  h->computed = false; h->n = c.n; h->ndim = c.ndim;
+  GH_CHECK(h->x.ensure((size_t)c.n * c.ndim * sizeof(double)));
+  GH_CHECK(h->yerr.ensure((size_t)c.n * sizeof(double)));
+  GH_CHECK(gh_to_device(h->x.d(), x, (size_t)c.n * c.ndim, h->st));
+  GH_CHECK(gh_to_device(h->yerr.d(), yerr, (size_t)c.n, h->st));
+  GH_CHECK(h->scal.ensure(64));
+  c.mark("inputs enqueued");
+  return GH_OK;
+}
+
+// ---- tree (hodlr.h:47-64), breadth first; kept from the previous compute() when n and min_size are the same
+static int build_tree(HodlrCall& c) {
+  gh_hodlr* const h = c.h;
+  const int64_t n = c.n;
   const int min_size = h->opts.min_size;
-  const int l0 = h->sub.depth;                   // levels [0, l0) are the pseudo-levels of a sub-tree handle (HSub)
+  const int l0 = c.l0 = h->sub.depth;            // levels [0, l0) are the pseudo-levels of a sub-tree handle (HSub)
   if (l0 > 0 && ((int)h->sub.half.size() != l0 || (int)h->sub.R.size() != l0 || (int)h->sub.T.size() != l0 || !h->sub.allreduce)) {
     gh_set_error("HODLR: incomplete sub-tree description"); return GH_ERR_BAD_ARG;
   }
@@ -2799,377 +2809,196 @@ extern "C" int gh_hodlr_compute(gh_hodlr* h, gh_kernel* k, const double* x, int6
   }
   h->max_leaf = 0;
   for (auto& lf : h->leaves) h->max_leaf = std::max(h->max_leaf, lf.size);
-
-  // ---- leaves: exact blocks -> explicit inverses + log-dets (hodlr.h:223-227, 87-89)
+  c.nlev = (int)h->levels.size();
+  c.top_ld.assign(l0, (size_t)-1);
   // log|det| of every factored block (leaves, then the cores level by level) is collected in ld_all
   // on the device and summed on the host after the ONE synchronisation that ends compute(); failure
   // flags likewise (flags[0]: singular Gauss-Jordan block, flags[2..3]: leaf Cholesky info).
-  size_t n_blocks = h->leaves.size();
-  for (auto* L : h->levels) n_blocks += L->node_ids.size();
-  GH_CHECK(h->ld_all.ensure(std::max<size_t>(n_blocks, 1) * sizeof(double)));
+  c.n_blocks = h->leaves.size();
+  for (auto* L : h->levels) c.n_blocks += L->node_ids.size();
+  GH_CHECK(h->ld_all.ensure(std::max<size_t>(c.n_blocks, 1) * sizeof(double)));
   GH_CHECK(h->flags.ensure(4 * sizeof(int)));
-  GH_HIP(hipMemsetAsync(h->ld_all.p, 0, std::max<size_t>(n_blocks, 1) * sizeof(double), st));
-  GH_HIP(hipMemsetAsync(h->flags.p, 0, 4 * sizeof(int), st));
-  size_t ld_at = 0;
-  // The leaf stage (build, batched Cholesky + inverse, K^-1 = L^-T L^-1: 1.4 ms at C4) depends on
-  // nothing the ACA produces, so it is issued on the second stream under the ACA of the top levels.
-  GhPooledBuf linv;                              // (lives until the final synchronisation: two streams touch it)
-  GhPooledBuf lstk, l22b, lwk;                   // (the 129..256-row leaf path's work blocks: as linv)
-  bool leaves_done = false;
-  auto leaf_stage = [&](hipStream_t st) -> int {
-    struct StreamSwap { gh_hodlr* h; hipStream_t keep; ~StreamSwap() { h->st = keep; } } swap_guard{h, h->st};
-    h->st = st;                                  // (launch_mm / batched_inverse issue on h->st)
-  if (h->max_leaf <= 128) {
-    // Leaves are symmetric positive definite and fit the dense solver's 128 x 128 diagonal-block
-    // kernel: build them identity-padded into 128 x 128 slots, factor + invert the factors as ONE
-    // batched launch of potf2_inv_mfma_kernel (79 us per block, a workgroup each), log-det from the
-    // factor's diagonal, K^-1 = L^-T L^-1 as one batched product.  (Gauss-Jordan with pivoting, the
-    // general path below, spends 7 ms on the 2048 leaves of C4; this one ~1.5 ms.)
-    const int nl = (int)h->leaves.size();
-    const size_t slot = (size_t)128 * 128;
-    GH_CHECK(h->leaf_inv.ensure(nl * slot * sizeof(double)));
-    long long* d_info = (long long*)((int*)h->flags.p + 2);
-    if (!h->leaf_tab_up) GH_CHECK(upload(h->d_leaves, h->leaves, st));
-    // K_leaf^-1 = L^-T L^-1 and log|K_leaf| in ONE launch per batch: gh_potf2.hip, potf2_kinv_kernel (round 6; it was the build + the
-    // batched factorisation + a log-det kernel + a batched transpose + a batched product: five launches, 2.3 GB through the L2s).
-    // Kernels of the a + b F(r^2) form are evaluated INSIDE that launch; the others keep the build launch in front of it.
-    static_assert(sizeof(LeafDesc) == 16, "potf2_kinv_kernel reads LeafDesc as {int start, size; long off}");
-    if (k->fast.ok && g_hodlr_leaf_fused) {
-      GH_CHECK(gh_launch_potf2_kinv_kernel_batched(h->leaf_inv.d(), 128, (int64_t)slot, h->ld_all.d() + ld_at, d_info, nl, k->fast,
-                                                   h->x.d(), h->yerr.d(), ndim, h->d_leaves.p, st));
-    } else {
-      hipLaunchKernelGGL(hodlr_leaf_build_kernel, dim3(nl, 8), dim3(256), 0, st, k->d_nodes, (int)k->nodes.size(), k->fast, ndim,
-                         h->x.d(), h->yerr.d(), (const LeafDesc*)h->d_leaves.p, h->leaf_inv.d(), 128);
-      GH_HIP(hipGetLastError());
-      GH_CHECK(gh_launch_potf2_kinv_batched(h->leaf_inv.d(), 128, (int64_t)slot, h->ld_all.d() + ld_at, d_info, nl, st));
-    }
-    ld_at += nl;
-    {
-      std::vector<MMJob> jobs(nl);
-      for (int i = 0; i < nl; ++i) jobs[i] = {(long)(i * slot), h->leaves[i].start, h->leaves[i].start, h->leaves[i].size, h->leaves[i].size};
-      if (!h->leaf_tab_up) {
-        GH_CHECK(upload(h->d_leaf_jobs, jobs, st));
-        h->leaf_tab_up = true;
-      }
-    }
-    h->leaf_pitch = 128;
-  } else if (h->max_leaf <= 256 && !g_hodlr_leaf_gj) {
-    // Leaves of 129 .. 256 rows -- the reference's tree stops splitting below 2 min_size, so with min_size = 100 most problem
-    // sizes have leaves of up to 199 rows (N = 50000: 256 leaves of 195 / 196) -- went through the pivoted Gauss-Jordan in place
-    // in HBM: 14 of the 17 ms of a step at N = 50000 (round 5 profile).  Same recipe as above on 256 x 256 identity-padded slots,
-    // as 2 x 2 blocks of 128 with the batched kernels there are:  L11 = chol(A11);  W = L21^T = L11^-1 A12;  A22 -= W^T W;
-    // L22 = chol(A22);  L^-1 = [[L11^-1, 0], [X, L22^-1]],  X = -L22^-1 L21 L11^-1;  K^-1 = L^-T L^-1 block by block
-    // (the full symmetric matrix is stored: the products read rows and, by symmetry, columns).
-    const int nl = (int)h->leaves.size();
-    const size_t slot = (size_t)256 * 256, blk = (size_t)128 * 128;
-    GH_CHECK(h->leaf_inv.ensure(nl * slot * sizeof(double)));
-    GH_CHECK(lstk.ensure(nl * 2 * blk * sizeof(double)));        // per leaf Z = [L11^-T | X'^T]  (128 x 256), X' = L22^-1 L21 L11^-1 = -X
-    GH_CHECK(l22b.ensure(nl * 2 * blk * sizeof(double)));        // L22^-1, L22^-T
-    GH_CHECK(lwk.ensure(nl * 2 * blk * sizeof(double)));         // L21, T^T
-    long long* d_info = (long long*)((int*)h->flags.p + 2);
-    if (!h->leaf_tab_up) GH_CHECK(upload(h->d_leaves, h->leaves, st));
-    hipLaunchKernelGGL(hodlr_leaf_build_kernel, dim3(nl, 16), dim3(256), 0, st, k->d_nodes, (int)k->nodes.size(), k->fast, ndim,
-                       h->x.d(), h->yerr.d(), (const LeafDesc*)h->d_leaves.p, h->leaf_inv.d(), 256);
-    GH_HIP(hipGetLastError());
-    double* const S = h->leaf_inv.d();
-    std::vector<MMJob> jobs(nl);
-    for (int i = 0; i < nl; ++i) jobs[i] = {(long)(i * slot), h->leaves[i].start, h->leaves[i].start, h->leaves[i].size, h->leaves[i].size};
-    if (!h->leaf_tab_up) {
-      GH_CHECK(upload(h->d_leaf_jobs, jobs, st));
-      h->leaf_tab_up = true;
-    }
-    // work blocks per leaf: Z = [L11^-T | X'^T] (128 x 256, k contiguous), L11^-1, L21 then T^T, L22^-1, L22^-T
-    GH_CHECK(linv.ensure(nl * blk * sizeof(double)));            // L11^-1 (row-major, from the factorisation kernel)
-    double* const Z = lstk.d();                                  // pitch 256
-    double* const W = lwk.d();                                   // block 0: L21, block 1: T^T   (pitch 128)
-    const long s2 = (long)slot, sZ = (long)(2 * blk), sW = (long)(2 * blk), sb = (long)blk;
-#define GH_BMM(ACC, C_, ldc_, sc_, A_, lda_, sa_, B_, ldb_, sb_, K_)                                                              \
-    hipLaunchKernelGGL(hodlr_bmm_nt_kernel<ACC>, dim3(nl), dim3(256), 0, st, C_, (long)(ldc_), (long)(sc_), (const double*)(A_), (long)(lda_), (long)(sa_), \
-                       (const double*)(B_), (long)(ldb_), (long)(sb_), (long)(K_))
-    GH_CHECK(gh_launch_potf2_batched(S, 256, (int64_t)slot, linv.d(), (int64_t)blk, d_info, nl, st));                             // L11 in place, L11^-1
-    hipLaunchKernelGGL(hodlr_transpose128_kernel, dim3(nl, 16), dim3(256), 0, st, (const double*)linv.d(), 128L, sb, Z, 256L, sZ);    // Z[:, 0:128] = L11^-T
-    GH_BMM(false, W, 128, sW, S + 128 * 256, 256, s2, linv.d(), 128, sb, 128);                                                     // L21 = A21 L11^-T
-    GH_BMM(true, S + 128 * 256 + 128, 256, s2, W, 128, sW, W, 128, sW, 128);                                                       // A22 -= L21 L21^T
-    GH_CHECK(gh_launch_potf2_batched(S + 128 * 256 + 128, 256, (int64_t)slot, l22b.d(), (int64_t)(2 * blk), d_info, nl, st));     // L22 in place, L22^-1
-    hipLaunchKernelGGL(hodlr_leaf_logdet256_kernel, dim3(nl), dim3(256), 0, st, (const double*)S, h->ld_all.d() + ld_at);
-    ld_at += nl;
-    hipLaunchKernelGGL(hodlr_transpose128_kernel, dim3(nl, 16), dim3(256), 0, st, (const double*)l22b.d(), 128L, sZ, l22b.d() + blk, 128L, sZ);   // L22^-T
-    GH_BMM(false, W + blk, 128, sW, Z, 256, sZ, W, 128, sW, 128);                                                                   // T^T = L11^-T L21^T   (T = L21 L11^-1)
-    GH_BMM(false, Z + 128, 256, sZ, W + blk, 128, sW, l22b.d(), 128, sZ, 128);                                                      // X'^T = T^T L22^-T    (X' = L22^-1 T = -X)
-    GH_HIP(hipMemsetAsync(S, 0, nl * slot * sizeof(double), st));                                                                  // (both factors are used up; K21, K12 are formed by subtraction)
-    GH_BMM(false, S, 256, s2, Z, 256, sZ, Z, 256, sZ, 256);                                                                         // K11 = L11^-T L11^-1 + X^T X
-    GH_BMM(false, S + 128 * 256 + 128, 256, s2, l22b.d() + blk, 128, sZ, l22b.d() + blk, 128, sZ, 128);                             // K22 = L22^-T L22^-1
-    GH_BMM(true, S + 128 * 256, 256, s2, l22b.d() + blk, 128, sZ, Z + 128, 256, sZ, 128);                                           // K21 = L22^-T X = -L22^-T X'
-    GH_BMM(true, S + 128, 256, s2, Z + 128, 256, sZ, l22b.d() + blk, 128, sZ, 128);                                                 // K12 = K21^T
-#undef GH_BMM
-    GH_HIP(hipGetLastError());
-    h->leaf_pitch = 256;
+  GH_HIP(hipMemsetAsync(h->ld_all.p, 0, std::max<size_t>(c.n_blocks, 1) * sizeof(double), h->st));
+  GH_HIP(hipMemsetAsync(h->flags.p, 0, 4 * sizeof(int), h->st));
+  c.mark("tree built");
+  return GH_OK;
+}
+
+// ---- leaves: exact blocks -> explicit inverses + log-dets (hodlr.h:223-227, 87-89), all on stream st.
+// The leaf stage (build, batched Cholesky + inverse, K^-1 = L^-T L^-1: 1.4 ms at C4) depends on nothing the ACA produces, so
+// it is issued on a side stream under the ACA of the top levels when the levels run concurrently.
+// The leaf job table: leaf i's inverse at i * slot, or at its own offset lf.off (slot 0).
+static std::vector<MMJob> leaf_jobs(const gh_hodlr* h, size_t slot) {
+  std::vector<MMJob> jobs;
+  for (const LeafDesc& lf : h->leaves) jobs.push_back({slot ? (long)(jobs.size() * slot) : lf.off, lf.start, lf.start, lf.size, lf.size});
+  return jobs;
+}
+// Leaves are symmetric positive definite and fit the dense solver's 128 x 128 diagonal-block
+// kernel: build them identity-padded into 128 x 128 slots, factor + invert the factors as ONE
+// batched launch of potf2_inv_mfma_kernel (79 us per block, a workgroup each), log-det from the
+// factor's diagonal, K^-1 = L^-T L^-1 as one batched product.  (Gauss-Jordan with pivoting, the
+// general path below, spends 7 ms on the 2048 leaves of C4; this one ~1.5 ms.)
+static int leaves_128(HodlrCall& c, hipStream_t st) {
+  gh_hodlr* const h = c.h;
+  const int nl = (int)h->leaves.size();
+  const size_t slot = (size_t)128 * 128;
+  GH_CHECK(h->leaf_inv.ensure(nl * slot * sizeof(double)));
+  long long* d_info = (long long*)((int*)h->flags.p + 2);
+  if (!h->leaf_tab_up) GH_CHECK(upload(h->d_leaves, h->leaves, st));
+  // K_leaf^-1 = L^-T L^-1 and log|K_leaf| in ONE launch per batch: gh_potf2.hip, potf2_kinv_kernel (round 6; it was the build + the
+  // batched factorisation + a log-det kernel + a batched transpose + a batched product: five launches, 2.3 GB through the L2s).
+  // Kernels of the a + b F(r^2) form are evaluated INSIDE that launch; the others keep the build launch in front of it.
+  static_assert(sizeof(LeafDesc) == 16, "potf2_kinv_kernel reads LeafDesc as {int start, size; long off}");
+  if (c.k->fast.ok && c.sw.leaf_fused) {
+    GH_CHECK(gh_launch_potf2_kinv_kernel_batched(h->leaf_inv.d(), 128, (int64_t)slot, h->ld_all.d() + c.ld_at, d_info, nl, c.k->fast,
+                                                 h->x.d(), h->yerr.d(), c.ndim, h->d_leaves.p, st));
   } else {
-  {
-    const int nl = (int)h->leaves.size();
-    const long tot = h->leaves.back().off + (long)h->leaves.back().size * h->leaves.back().size;
-    GH_CHECK(h->leaf_inv.ensure(tot * sizeof(double)));
-    GH_CHECK(upload(h->d_leaves, h->leaves, st));
-    hipLaunchKernelGGL(hodlr_leaf_build_kernel, dim3(nl, 8), dim3(256), 0, st, k->d_nodes, (int)k->nodes.size(), k->fast, ndim,
-                       h->x.d(), h->yerr.d(), (const LeafDesc*)h->d_leaves.p, h->leaf_inv.d(), 0);
+    hipLaunchKernelGGL(hodlr_leaf_build_kernel, dim3(nl, 8), dim3(256), 0, st, c.k->d_nodes, (int)c.k->nodes.size(), c.k->fast, c.ndim,
+                       h->x.d(), h->yerr.d(), (const LeafDesc*)h->d_leaves.p, h->leaf_inv.d(), 128);
     GH_HIP(hipGetLastError());
-    std::vector<long> offs(nl);
-    std::vector<int> sizes(nl);
-    std::vector<MMJob> jobs(nl);
+    GH_CHECK(gh_launch_potf2_kinv_batched(h->leaf_inv.d(), 128, (int64_t)slot, h->ld_all.d() + c.ld_at, d_info, nl, st));
+  }
+  c.ld_at += nl;
+  if (!h->leaf_tab_up) { GH_CHECK(upload(h->d_leaf_jobs, leaf_jobs(h, slot), st)); h->leaf_tab_up = true; }
+  h->leaf_pitch = 128;
+  return GH_OK;
+}
+// Leaves of 129 .. 256 rows -- the reference's tree stops splitting below 2 min_size, so with min_size = 100 most problem
+// sizes have leaves of up to 199 rows (N = 50000: 256 leaves of 195 / 196) -- went through the pivoted Gauss-Jordan in place
+// in HBM: 14 of the 17 ms of a step at N = 50000 (round 5 profile).  Same recipe as above on 256 x 256 identity-padded slots,
+// as 2 x 2 blocks of 128 with the batched kernels there are:  L11 = chol(A11);  W = L21^T = L11^-1 A12;  A22 -= W^T W;
+// L22 = chol(A22);  L^-1 = [[L11^-1, 0], [X, L22^-1]],  X = -L22^-1 L21 L11^-1;  K^-1 = L^-T L^-1 block by block
+// (the full symmetric matrix is stored: the products read rows and, by symmetry, columns).
+static int leaves_256(HodlrCall& c, hipStream_t st) {
+  gh_hodlr* const h = c.h;
+  const int nl = (int)h->leaves.size();
+  const size_t slot = (size_t)256 * 256, blk = (size_t)128 * 128;
+  GH_CHECK(h->leaf_inv.ensure(nl * slot * sizeof(double)));
+  GH_CHECK(c.lstk.ensure(nl * 2 * blk * sizeof(double)));        // per leaf Z = [L11^-T | X'^T]  (128 x 256), X' = L22^-1 L21 L11^-1 = -X
+  GH_CHECK(c.l22b.ensure(nl * 2 * blk * sizeof(double)));        // L22^-1, L22^-T
+  GH_CHECK(c.lwk.ensure(nl * 2 * blk * sizeof(double)));         // L21, T^T
+  long long* d_info = (long long*)((int*)h->flags.p + 2);
+  if (!h->leaf_tab_up) GH_CHECK(upload(h->d_leaves, h->leaves, st));
+  hipLaunchKernelGGL(hodlr_leaf_build_kernel, dim3(nl, 16), dim3(256), 0, st, c.k->d_nodes, (int)c.k->nodes.size(), c.k->fast, c.ndim,
+                     h->x.d(), h->yerr.d(), (const LeafDesc*)h->d_leaves.p, h->leaf_inv.d(), 256);
+  GH_HIP(hipGetLastError());
+  double* const S = h->leaf_inv.d();
+  if (!h->leaf_tab_up) { GH_CHECK(upload(h->d_leaf_jobs, leaf_jobs(h, slot), st)); h->leaf_tab_up = true; }
+  // work blocks per leaf: Z = [L11^-T | X'^T] (128 x 256, k contiguous), L11^-1, L21 then T^T, L22^-1, L22^-T
+  GH_CHECK(c.linv.ensure(nl * blk * sizeof(double)));          // L11^-1 (row-major, from the factorisation kernel)
+  double* const Z = c.lstk.d();                                // pitch 256
+  double* const W = c.lwk.d();                                 // block 0: L21, block 1: T^T   (pitch 128)
+  double* const L22 = c.l22b.d();
+  const long s2 = (long)slot, sZ = (long)(2 * blk), sW = (long)(2 * blk), sb = (long)blk;
+#define GH_BMM(ACC, C_, ldc_, sc_, A_, lda_, sa_, B_, ldb_, sb_, K_)                                                              \
+  hipLaunchKernelGGL(hodlr_bmm_nt_kernel<ACC>, dim3(nl), dim3(256), 0, st, C_, (long)(ldc_), (long)(sc_), (const double*)(A_), (long)(lda_), (long)(sa_), \
+                     (const double*)(B_), (long)(ldb_), (long)(sb_), (long)(K_))
+  GH_CHECK(gh_launch_potf2_batched(S, 256, (int64_t)slot, c.linv.d(), (int64_t)blk, d_info, nl, st));                            // L11 in place, L11^-1
+  hipLaunchKernelGGL(hodlr_transpose128_kernel, dim3(nl, 16), dim3(256), 0, st, (const double*)c.linv.d(), 128L, sb, Z, 256L, sZ); // Z[:, 0:128] = L11^-T
+  GH_BMM(false, W, 128, sW, S + 128 * 256, 256, s2, c.linv.d(), 128, sb, 128);                                                   // L21 = A21 L11^-T
+  GH_BMM(true, S + 128 * 256 + 128, 256, s2, W, 128, sW, W, 128, sW, 128);                                                       // A22 -= L21 L21^T
+  GH_CHECK(gh_launch_potf2_batched(S + 128 * 256 + 128, 256, (int64_t)slot, L22, (int64_t)(2 * blk), d_info, nl, st));          // L22 in place, L22^-1
+  hipLaunchKernelGGL(hodlr_leaf_logdet256_kernel, dim3(nl), dim3(256), 0, st, (const double*)S, h->ld_all.d() + c.ld_at);
+  c.ld_at += nl;
+  hipLaunchKernelGGL(hodlr_transpose128_kernel, dim3(nl, 16), dim3(256), 0, st, (const double*)L22, 128L, sZ, L22 + blk, 128L, sZ); // L22^-T
+  GH_BMM(false, W + blk, 128, sW, Z, 256, sZ, W, 128, sW, 128);                                                                   // T^T = L11^-T L21^T   (T = L21 L11^-1)
+  GH_BMM(false, Z + 128, 256, sZ, W + blk, 128, sW, L22, 128, sZ, 128);                                                           // X'^T = T^T L22^-T    (X' = L22^-1 T = -X)
+  GH_HIP(hipMemsetAsync(S, 0, nl * slot * sizeof(double), st));                                                                  // (both factors are used up; K21, K12 are formed by subtraction)
+  GH_BMM(false, S, 256, s2, Z, 256, sZ, Z, 256, sZ, 256);                                                                         // K11 = L11^-T L11^-1 + X^T X
+  GH_BMM(false, S + 128 * 256 + 128, 256, s2, L22 + blk, 128, sZ, L22 + blk, 128, sZ, 128);                                       // K22 = L22^-T L22^-1
+  GH_BMM(true, S + 128 * 256, 256, s2, L22 + blk, 128, sZ, Z + 128, 256, sZ, 128);                                                // K21 = L22^-T X = -L22^-T X'
+  GH_BMM(true, S + 128, 256, s2, Z + 128, 256, sZ, L22 + blk, 128, sZ, 128);                                                      // K12 = K21^T
+#undef GH_BMM
+  GH_HIP(hipGetLastError());
+  h->leaf_pitch = 256;
+  return GH_OK;
+}
+// Every other leaf set (leaves of more than 256 rows, and the leaf_gj validation arm): the pivoted Gauss-Jordan in place, each
+// inverse at pitch = its own size, then repacked to pitch max_leaf when the sizes differ (hodlr_mm_kernel takes one A pitch
+// per launch)
+static int leaves_gj(HodlrCall& c, hipStream_t st) {
+  gh_hodlr* const h = c.h;
+  const int nl = (int)h->leaves.size();
+  const long tot = h->leaves.back().off + (long)h->leaves.back().size * h->leaves.back().size;
+  GH_CHECK(h->leaf_inv.ensure(tot * sizeof(double)));
+  GH_CHECK(upload(h->d_leaves, h->leaves, st));
+  hipLaunchKernelGGL(hodlr_leaf_build_kernel, dim3(nl, 8), dim3(256), 0, st, c.k->d_nodes, (int)c.k->nodes.size(), c.k->fast, c.ndim,
+                     h->x.d(), h->yerr.d(), (const LeafDesc*)h->d_leaves.p, h->leaf_inv.d(), 0);
+  GH_HIP(hipGetLastError());
+  std::vector<long> offs(nl); std::vector<int> sizes(nl);
+  for (int i = 0; i < nl; ++i) { offs[i] = h->leaves[i].off; sizes[i] = h->leaves[i].size; }
+  GH_CHECK(upload(h->d_leaf_jobs, leaf_jobs(h, 0), st));
+  GH_CHECK(batched_inverse(h, st, h->leaf_inv.d(), offs, sizes, h->ld_all.d() + c.ld_at));
+  c.ld_at += nl;
+  bool uniform = true;
+  for (auto& lf : h->leaves) if (lf.size != h->max_leaf) uniform = false;
+  if (!uniform) {
+    const int ml = h->max_leaf;
+    GhBuf packed;
+    GH_CHECK(packed.ensure((size_t)nl * ml * ml * sizeof(double)));
+    GH_HIP(hipMemsetAsync(packed.p, 0, (size_t)nl * ml * ml * sizeof(double), st));
     for (int i = 0; i < nl; ++i) {
-      offs[i] = h->leaves[i].off; sizes[i] = h->leaves[i].size;
-      jobs[i] = {h->leaves[i].off, h->leaves[i].start, h->leaves[i].start, h->leaves[i].size, h->leaves[i].size};
+      const LeafDesc& lf = h->leaves[i];
+      GH_HIP(hipMemcpy2DAsync(packed.d() + (size_t)i * ml * ml, ml * sizeof(double), h->leaf_inv.d() + lf.off,
+                              lf.size * sizeof(double), lf.size * sizeof(double), lf.size, hipMemcpyDeviceToDevice, st));
     }
-    GH_CHECK(upload(h->d_leaf_jobs, jobs, st));
-    GH_CHECK(batched_inverse(h, h->leaf_inv.d(), offs, sizes, h->ld_all.d() + ld_at));
-    ld_at += nl;
+    GH_HIP(hipStreamSynchronize(st));
+    std::swap(h->leaf_inv.p, packed.p);
+    std::swap(h->leaf_inv.bytes, packed.bytes);
+    GH_CHECK(upload(h->d_leaf_jobs, leaf_jobs(h, (size_t)ml * ml), st));
   }
-  // leaf job rows use a per-job A stride = its own size: encode through a_rs = 0 -> handled below
-  // (hodlr_mm_kernel takes one a_rs per launch, so leaves are launched with a_rs = max_leaf after
-  //  re-packing: simpler -- store every leaf inverse with row pitch max_leaf)
-  // NOTE: leaf inverses were produced with pitch == size; repack to pitch max_leaf when sizes differ.
-  {
-    bool uniform = true;
-    for (auto& lf : h->leaves) if (lf.size != h->max_leaf) uniform = false;
-    if (!uniform) {
-      const int nl = (int)h->leaves.size(), ml = h->max_leaf;
-      GhBuf packed;
-      GH_CHECK(packed.ensure((size_t)nl * ml * ml * sizeof(double)));
-      GH_HIP(hipMemsetAsync(packed.p, 0, (size_t)nl * ml * ml * sizeof(double), st));
-      std::vector<MMJob> jobs(nl);
-      for (int i = 0; i < nl; ++i) {
-        const LeafDesc& lf = h->leaves[i];
-        GH_HIP(hipMemcpy2DAsync(packed.d() + (size_t)i * ml * ml, ml * sizeof(double), h->leaf_inv.d() + lf.off,
-                                lf.size * sizeof(double), lf.size * sizeof(double), lf.size, hipMemcpyDeviceToDevice, st));
-        jobs[i] = {(long)i * ml * ml, lf.start, lf.start, lf.size, lf.size};
-      }
-      GH_HIP(hipStreamSynchronize(st));
-      std::swap(h->leaf_inv.p, packed.p);
-      std::swap(h->leaf_inv.bytes, packed.bytes);
-      GH_CHECK(upload(h->d_leaf_jobs, jobs, st));
-    }
-  }
-    h->leaf_pitch = h->max_leaf;
-  }
+  h->leaf_pitch = h->max_leaf;
+  return GH_OK;
+}
+static int leaf_stage(HodlrCall& c, hipStream_t st) {
+  const int ml = c.h->max_leaf;
+  GH_CHECK(ml <= 128 ? leaves_128(c, st) : ml <= 256 && !c.sw.leaf_gj ? leaves_256(c, st) : leaves_gj(c, st));
+  c.leaves_done = true;
+  return GH_OK;
+}
 
-    leaves_done = true;
-    return GH_OK;
-  };
+// side stream `which` of the handle (1: st_b, 2: st_c -- its own or the process-wide ones; 3: st_d -- the process-wide chain
+// stream only) and its event, made on first use; one that cannot be had stays null
+static void ensure_side_stream(gh_hodlr* h, int which) {
+  hipStream_t& s = which == 1 ? h->st_b : which == 2 ? h->st_c : h->st_d;
+  hipEvent_t& e = which == 1 ? h->ev_b : which == 2 ? h->ev_c : h->ev_d;
+  if (s) return;
+  hipStream_t shq[4] = {nullptr, nullptr, nullptr, nullptr};
+  if (h->shared_streams) { if (gh_shared_streams(h->opts.device, shq)) s = shq[which == 1 ? 2 : which == 2 ? 3 : 1]; }
+  else if (which < 3 && hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) s = nullptr;
+  if (s && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) s = nullptr;
+  if (!s) (void)hipGetLastError();
+}
 
-  // ---- ACA of every level into column-major scratch, ranks back to the host
-  // Column capacity of the scratch: the caller's cap, else 256 to start with (doubled, up to RANK_CAP,
-  // for a level one of whose blocks is cut short by it -- that level is then redone).
-  // The levels are independent, so they are all ENQUEUED before the host looks at any result: the
-  // clustered levels (several workgroups per node, spin barriers: they must not share the chip with
-  // another spinning grid) one after the other on the solver's stream, the one-workgroup-per-node
-  // levels beside them on a second stream; one synchronisation instead of one per level (each cost
-  // a ~60 us bubble, and levels 8-10 of C4 -- 1.4 ms -- now run under levels 0-7).  Every level
-  // gets its own n x rcap scratch; if that is more than 12 GiB in total the levels share one and go
-  // one at a time.
-  const bool user_cap = h->opts.max_rank > 0;
-  const int rcap0 = user_cap ? h->opts.max_rank : std::min(256, RANK_CAP);
-  const int nlev = (int)h->levels.size();
-  const int aca_fence = 0, aca_multi = 3;   // bit 0: batched candidate search (one-workgroup nodes); bit 1: clusters draw the next row before the norms barrier         // (fence-free cluster barrier, 8 then 64 candidate rows per search pass: DESIGN.md section 4)
+// ---- ACA of every level into column-major scratch, ranks back to the host
+// Column capacity of the scratch: the caller's cap, else 256 to start with (doubled, up to RANK_CAP,
+// for a level one of whose blocks is cut short by it -- that level is then redone).
+// The levels are independent, so they are all ENQUEUED before the host looks at any result: the
+// clustered levels (several workgroups per node, spin barriers: they must not share the chip with
+// another spinning grid) one after the other on the solver's stream, the one-workgroup-per-node
+// levels beside them on a second stream; one synchronisation instead of one per level (each cost
+// a ~60 us bubble, and levels 8-10 of C4 -- 1.4 ms -- now run under levels 0-7).  Every level
+// gets its own n x rcap scratch; if that is more than 12 GiB in total the levels share one and go
+// one at a time.
+static int plan_aca(HodlrCall& c) {
+  gh_hodlr* const h = c.h;
+  const int nlev = c.nlev, l0 = c.l0;
+  c.user_cap = h->opts.max_rank > 0;
+  c.rcap0 = c.user_cap ? h->opts.max_rank : std::min(256, RANK_CAP);
   // (round 5: "more than 12 GiB" was a 64-GB-card habit; an MI355X has 288 GB.  Above 12 GiB the question is put to the device:
   //  all levels at once while their scratch fits in 40 % of what is free now -- N = 700000 went one level at a time, 34 ms)
-  bool concurrent = nlev - l0 > 1;
-  {
-    const double need = (double)n * rcap0 * sizeof(double) * (nlev - l0);
-    if (concurrent && need > 12.0 * (1u << 30)) {
-      size_t free_b = 0, tot_b = 0;
-      if (hipMemGetInfo(&free_b, &tot_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
-      // (blocks parked in the pool by the previous compute() of this handle count as used there and are what will be handed out again)
-      concurrent = need <= 0.4 * (double)free_b + (double)gh_pool_parked_bytes();
-    }
+  c.concurrent = nlev - l0 > 1;
+  const double need = (double)c.n * c.rcap0 * sizeof(double) * (nlev - l0);
+  if (c.concurrent && need > 12.0 * (1u << 30)) {
+    size_t free_b = 0, tot_b = 0;
+    if (hipMemGetInfo(&free_b, &tot_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
+    // (blocks parked in the pool by the previous compute() of this handle count as used there and are what will be handed out again)
+    c.concurrent = need <= 0.4 * (double)free_b + (double)gh_pool_parked_bytes();
   }
-  if (concurrent && !h->st_b) {
-    hipStream_t shq[4] = {nullptr, nullptr, nullptr, nullptr};
-    if (h->shared_streams && gh_shared_streams(h->opts.device, shq)) h->st_b = shq[2];
-    if ((!h->shared_streams && hipStreamCreateWithFlags(&h->st_b, hipStreamNonBlocking) != hipSuccess) ||
-        hipEventCreateWithFlags(&h->ev_b, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); h->st_b = nullptr; }
-  }
-  struct AcaLevel { GhPooledBuf Tcm, idx, sync, part; int G = 1, rcap = 0; int flags[2] = {0, 0}; char* syncp = nullptr; bool sync_cleared = false;
-                    bool timed = false; };   // timed: its nodes wrote their durations behind the two flags (the one-workgroup launch)
-  GhPooledBuf sync_all;                                  // the levels' barrier counters / selections / flags: one buffer, ONE memset
-  std::vector<AcaLevel> al(nlev);
-  GhPooledBuf shared_Tcm;
-  std::vector<GhBuf*> levelB(nlev, nullptr);
-  struct Cleanup { std::vector<GhBuf*>& v; ~Cleanup() { for (auto* b : v) delete b; } } cleanup{levelB};
-  const int pstride = 8 + 2 * ACA_MAXR;
-  // 0: level l goes through the workgroup kernel; 64 / 128 / 256: every block of the level has at most that many rows and
-  // columns and the level goes through hodlr_aca_wave_kernel
+  if (c.concurrent) { ensure_side_stream(h, 1); c.concurrent = h->st_b != nullptr; }   // (no second stream: one level at a time)
+  c.al.resize(nlev);
+  c.levelB.resize(nlev);
   if ((int)h->wave_bad.size() != nlev) h->wave_bad.assign(nlev, 0);
-  auto wave_mr = [&](int l) -> int {
-    if (!g_hodlr_wave_aca || h->wave_bad[l] || h->levels[l]->top || al[l].G != 1) return 0;
-    int mx = 0;
-    for (int id : h->levels[l]->node_ids) { const HNode& nd = h->nodes[id]; mx = std::max(mx, std::max(nd.half, nd.size - nd.half)); }
-    // (the interpreter's registers beside 128 of mirrors would spill: kernels off the a + b F(r^2) form stop at 128 x 128)
-    return mx <= 64 ? 64 : mx <= 128 ? 128 : (mx <= 256 && k->fast.ok) ? 256 : 0;
-  };
-  // buffers of level l for column capacity rc, counters cleared on stream sx
-  auto prepare_level = [&](int l, int rc, hipStream_t sx) -> int {
-    HLevel* L = h->levels[l];
-    AcaLevel& a = al[l];
-    const int nn = (int)L->node_ids.size();
-    a.rcap = rc;
-    GhBuf& T = (concurrent ? (GhBuf&)a.Tcm : (GhBuf&)shared_Tcm);
-    GH_CHECK(T.ensure((size_t)n * rc * sizeof(double)));
-    GH_CHECK(a.idx.ensure((size_t)n * sizeof(int)));
-    GH_CHECK(a.part.ensure((size_t)nn * a.G * pstride * sizeof(double)));
-    if (a.sync_cleared) {                                  // (its slice of sync_all was cleared with all the others)
-      a.sync_cleared = false;
-    } else {
-      GH_CHECK(a.sync.ensure((size_t)nn * (sizeof(unsigned) + 2 * sizeof(int)) + 2 * sizeof(int)));
-      a.syncp = (char*)a.sync.p;
-      GH_HIP(hipMemsetAsync(a.syncp, 0, (size_t)nn * (sizeof(unsigned) + 2 * sizeof(int)) + 2 * sizeof(int), sx));
-    }
-    return GH_OK;
-  };
-  // enqueue the ACA of level l with column capacity rc on stream sx (no synchronisation)
-  auto enqueue_level = [&](int l, int rc, hipStream_t sx) -> int {
-    HLevel* L = h->levels[l];
-    AcaLevel& a = al[l];
-    const int nn = (int)L->node_ids.size();
-    GH_CHECK(prepare_level(l, rc, sx));
-    GH_CHECK(aca_lds_attr());
-    GhBuf& T = (concurrent ? (GhBuf&)a.Tcm : (GhBuf&)shared_Tcm);
-    unsigned* d_bars = (unsigned*)a.syncp;
-    int* d_sel = (int*)(d_bars + nn);
-    int* d_fail = d_sel + nn;
-    if (const int mr = wave_mr(l)) {                       // blocks of <= 256 x 256: a wavefront per node
-#define GH_ACA_WAVE(F, EE)                                                                                        \
-      hipLaunchKernelGGL((hodlr_aca_wave_kernel<F, EE>), dim3((nn + AW_NODES - 1) / AW_NODES), dim3(64 * AW_NODES), 0, sx, \
-                         k->d_nodes, (int)k->nodes.size(), k->fast, ndim, h->x.d(), (const LvlNode*)L->d_nodes.p, nn, T.d(), (long)n, rc, \
-                         (int*)L->d_ranks.p, h->opts.tol, (unsigned long long)(unsigned)h->opts.seed, l, d_fail + 1)
-      if (k->fast.ok) { if (mr == 64) GH_ACA_WAVE(true, 1); else if (mr == 128) GH_ACA_WAVE(true, 2); else GH_ACA_WAVE(true, 4); }
-      else            { if (mr == 64) GH_ACA_WAVE(false, 1); else GH_ACA_WAVE(false, 2); }
-#undef GH_ACA_WAVE
-      GH_HIP(hipGetLastError());
-      return GH_OK;
-    }
-#define GH_ACA_LAUNCH(F, CLU)                                                                                          \
-    hipLaunchKernelGGL((hodlr_aca_kernel<F, CLU>), dim3(nn * a.G), dim3(ACA_THREADS), a.G == 1 ? ACA_DYN_BYTES : 0, sx, k->d_nodes, (int)k->nodes.size(),  \
-                       k->fast, ndim, h->x.d(), (const LvlNode*)L->d_nodes.p, T.d(), (long)n, rc, (int*)a.idx.p,     \
-                       (int*)L->d_ranks.p, h->opts.tol, (unsigned long long)(unsigned)h->opts.seed, l,               \
-                       a.G, d_bars, a.part.d(), pstride, d_sel, d_fail, aca_multi, aca_fence, d_fail + 1,            \
-                       (const AcaSeg*)nullptr, 0, a.G == 1 ? ACA_CAPD : 0)
-    if (a.G == 1) { if (k->fast.ok) GH_ACA_LAUNCH(true, false); else GH_ACA_LAUNCH(false, false); }
-    else          { if (k->fast.ok) GH_ACA_LAUNCH(true, true); else GH_ACA_LAUNCH(false, true); }
-#undef GH_ACA_LAUNCH
-    GH_HIP(hipGetLastError());
-    return GH_OK;
-  };
-  // all clustered levels `cl` as ONE launch of at most 256 workgroups (al[l].G already balanced)
-  auto enqueue_fused = [&](const std::vector<int>& cl, int rc, hipStream_t sx, GhBuf& segbuf, int threads = ACA_THREADS) -> int {
-    std::vector<AcaSeg> segs;
-    int wg = 0;
-    bool ones_only = true;                                 // (one-workgroup nodes only: the launch carries the LDS mirrors)
-    for (int l : cl) ones_only = ones_only && al[l].G == 1;
-    GH_CHECK(aca_lds_attr());
-    for (int l : cl) {
-      HLevel* L = h->levels[l];
-      AcaLevel& a = al[l];
-      const int nn = (int)L->node_ids.size();
-      GH_CHECK(prepare_level(l, rc, sx));
-      unsigned* d_bars = (unsigned*)a.syncp;
-      int* d_sel = (int*)(d_bars + nn);
-      int* d_fail = d_sel + nn;
-      int* d_dur = nullptr;
-      const int* d_order = nullptr;
-      if (ones_only && g_hodlr_lpt) {
-        // The nodes of a level differ in cost by 4x (C4, level 8: 205 us on average, ~800 us for the few whose search runs dry
-        // first), and a long one dispatched late is the end of phase 1: every node reports how long it took, and the next
-        // compute() of the handle launches the level longest first.  Inside an optimiser loop the costs hardly move.
-        d_dur = d_fail + 2;
-        a.timed = true;
-        if ((int)L->aca_dur.size() == nn) {
-          std::vector<int> ord(nn);
-          for (int q = 0; q < nn; ++q) ord[q] = q;
-          std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return L->aca_dur[x] > L->aca_dur[y]; });
-          GH_CHECK(upload(L->d_order, ord, sx));
-          d_order = (const int*)L->d_order.p;
-        }
-      }
-      segs.push_back({(const LvlNode*)L->d_nodes.p, a.Tcm.d(), (int*)a.idx.p, (int*)L->d_ranks.p, d_bars, a.part.d(), d_sel,
-                      d_fail, d_fail + 1, l, a.G, wg, nn * a.G, d_dur, d_order});
-      wg += nn * a.G;
-    }
-    GH_CHECK(upload(segbuf, segs, sx));
-#define GH_ACA_LAUNCH(F, CLU)                                                                                          \
-    hipLaunchKernelGGL((hodlr_aca_kernel<F, CLU>), dim3(wg), dim3(threads), ones_only ? ACA_DYN_BYTES : 0, sx, k->d_nodes, (int)k->nodes.size(),    \
-                       k->fast, ndim, h->x.d(), (const LvlNode*)nullptr, (double*)nullptr, (long)n, rc, (int*)nullptr, \
-                       (int*)nullptr, h->opts.tol, (unsigned long long)(unsigned)h->opts.seed, 0,                     \
-                       1, (unsigned*)nullptr, (double*)nullptr, pstride, (int*)nullptr, (int*)nullptr, aca_multi, aca_fence, \
-                       (int*)nullptr, (const AcaSeg*)segbuf.p, (int)segs.size(), ones_only ? ACA_CAPD : 0)
-    if (ones_only) { if (k->fast.ok) GH_ACA_LAUNCH(true, false); else GH_ACA_LAUNCH(false, false); }
-    else           { if (k->fast.ok) GH_ACA_LAUNCH(true, true); else GH_ACA_LAUNCH(false, true); }
-#undef GH_ACA_LAUNCH
-    GH_HIP(hipGetLastError());
-    return GH_OK;
-  };
-  // flags and ranks of level l back to the host (a device-to-host copy into pageable memory holds the
-  // host until the stream gets there, so these are issued only after EVERY level has been enqueued)
-  auto fetch_level = [&](int l, hipStream_t sx) -> int {
-    HLevel* L = h->levels[l];
-    AcaLevel& a = al[l];
-    const int nn = (int)L->node_ids.size();
-    int* d_fail = (int*)((unsigned*)a.syncp + nn) + nn;
-    L->ranks.resize(nn);
-    GH_HIP(hipMemcpyAsync(a.flags, d_fail, 2 * sizeof(int), hipMemcpyDeviceToHost, sx));
-    GH_HIP(hipMemcpyAsync(L->ranks.data(), L->d_ranks.p, nn * sizeof(int), hipMemcpyDeviceToHost, sx));
-    return GH_OK;
-  };
-  // after a synchronisation: validate level l, redo it with more columns while a block is cut short
-  auto settle_level = [&](int l) -> int {
-    AcaLevel& a = al[l];
-    for (;;) {
-      if (a.flags[0]) { gh_set_error("HODLR: cluster barrier of the ACA kernel timed out at level %d", l); return GH_ERR_HIP; }
-      if (!a.flags[1]) return GH_OK;
-      if (a.flags[1] >= 2) {
-        // a block of this level asked the wavefront-per-node kernel for more than AW_RW_OF(E) columns: the level again, with the
-        // workgroup kernel (same draws, same results), and the handle remembers it for its next compute()
-        h->wave_bad[l] = 1;
-        GH_CHECK(enqueue_level(l, a.rcap, st));
-        GH_CHECK(fetch_level(l, st));
-        GH_HIP(hipStreamSynchronize(st));
-        continue;
-      }
-      // hodlr.h:147 lets the rank grow to min(rows, cols); a cut-short block would be a silently wrong answer
-      if (user_cap || a.rcap >= RANK_CAP) {
-        gh_set_error("HODLR: an off-diagonal block of level %d needs a rank above %d to reach tol = %g (%s); "
-                     "the factorisation is not usable", l, a.rcap, h->opts.tol,
-                     user_cap ? "opts.max_rank" : "the solver's ceiling: loosen tol, raise min_size or use the dense solver");
-        return user_cap ? GH_ERR_BAD_ARG : GH_ERR_RANK;
-      }
-      GH_CHECK(enqueue_level(l, std::min(2 * a.rcap, RANK_CAP), st));
-      GH_CHECK(fetch_level(l, st));
-      GH_HIP(hipStreamSynchronize(st));
-    }
-  };
-  auto rank_of_level = [&](int l) {
-    HLevel* L = h->levels[l];
-    if (L->top) L->ranks.assign(1, h->sub.R[l]);         // (given: the ACA of the ancestor ran elsewhere)
-    L->R = 0;
-    for (int r : L->ranks) L->R = std::max(L->R, r);
-    L->off = h->Rtot;
-    h->Rtot += L->R;
-    h->maxR = std::max(h->maxR, L->R);
-  };
-  // serial mode only (one scratch shared by the levels): park the level's factors in a compact buffer
-  auto compact_level = [&](int l) -> int {
-    HLevel* L = h->levels[l];
-    const int nn = (int)L->node_ids.size();
-    rank_of_level(l);
-    if (L->R > 0) {
-      levelB[l] = new GhPooledBuf();
-      GH_CHECK(levelB[l]->ensure((size_t)n * L->R * sizeof(double)));
-      GH_HIP(hipMemsetAsync(levelB[l]->p, 0, (size_t)n * L->R * sizeof(double), st));
-      hipLaunchKernelGGL(hodlr_compact_kernel, dim3(nn, std::max(8, std::min(512, 2048 / nn))), dim3(256), 0, st, shared_Tcm.d(), (long)n, (const LvlNode*)L->d_nodes.p,
-                         (const int*)L->d_ranks.p, L->R, levelB[l]->d(), (long)L->R, 0L, (double*)nullptr, 0L, 0L);
-      GH_HIP(hipGetLastError());
-    }
-    return GH_OK;
-  };
   h->Rtot = 0; h->maxR = 0; h->max_chunks = 0;
   for (int l = 0; l < nlev; ++l) {
     HLevel* L = h->levels[l];
@@ -3177,286 +3006,515 @@ extern "C" int gh_hodlr_compute(gh_hodlr* h, gh_kernel* k, const double* x, int6
     std::vector<LvlNode> ln(nn);
     const int seed_off = (l >= l0 && l - l0 < (int)h->sub.seed_off.size()) ? h->sub.seed_off[l - l0] : 0;
     for (int q = 0; q < nn; ++q) { const HNode& nd = h->nodes[L->node_ids[q]]; ln[q] = {nd.start, nd.half, nd.size, seed_off}; }
-    if (!L->nodes_up) { GH_CHECK(upload(L->d_nodes, ln, st)); L->nodes_up = true; }
+    if (!L->nodes_up) { GH_CHECK(upload(L->d_nodes, ln, h->st)); L->nodes_up = true; }
     GH_CHECK(L->d_ranks.ensure(nn * sizeof(int)));
     if (L->top) {                                        // no ACA here: its "rank" is the level's, the staged factors are zero-padded to it
-      GH_HIP(hipMemcpyAsync(L->d_ranks.p, &h->sub.R[l], sizeof(int), hipMemcpyHostToDevice, st));
-      al[l].G = 1;
+      GH_HIP(hipMemcpyAsync(L->d_ranks.p, &h->sub.R[l], sizeof(int), hipMemcpyHostToDevice, h->st));
+      c.al[l].G = 1;
       continue;
     }
     // cluster size: as many workgroups per node as keep the whole grid resident (nodes * G <= 256)
     // and leave every thread `ept` columns (measured at C4 with a switch that went in round 4: 2 -> 12.5 ms,
     // 4 -> 13.1, 8 -> 14.1, 16 -> 16.0: the step is bound by per-thread memory latency, not by the
     // barriers, so more and smaller workgroups win)
-    int G = 1;
-    {
-      const int ept = 2;
-      int min_half = INT32_MAX;
-      for (int q = 0; q < nn; ++q) min_half = std::min(min_half, ln[q].half);
-      while (G * 2 * nn <= 256 && (long)(G * 2) * ACA_THREADS * ept <= min_half) G *= 2;
-    }
-    al[l].G = G;
+    const int ept = 2;
+    int G = 1, min_half = INT32_MAX;
+    for (int q = 0; q < nn; ++q) min_half = std::min(min_half, ln[q].half);
+    while (G * 2 * nn <= 256 && (long)(G * 2) * ACA_THREADS * ept <= min_half) G *= 2;
+    c.al[l].G = G;
   }
-  if (concurrent && h->st_b) {
-    {
-      // (a memset per level in front of every launch: thirteen ~7 us fill kernels, 100 us before the one-workgroup levels started)
-      size_t off = 0;
-      std::vector<size_t> at(nlev, 0);
-      for (int l = l0; l < nlev; ++l) {
-        if (h->levels[l]->top) continue;
-        at[l] = off;
-        off += (size_t)gh_round_up((int64_t)(h->levels[l]->node_ids.size() * (sizeof(unsigned) + 2 * sizeof(int)) + 2 * sizeof(int)), 256);   // bars | sel | fail, trunc | dur
+  return GH_OK;
+}
+
+// 0: level l goes through the workgroup kernel; 64 / 128 / 256: every block of the level has at most that many rows and
+// columns and the level goes through hodlr_aca_wave_kernel
+static int wave_mr(const HodlrCall& c, int l) {
+  const gh_hodlr* h = c.h;
+  if (!c.sw.wave_aca || h->wave_bad[l] || h->levels[l]->top || c.al[l].G != 1) return 0;
+  int mx = 0;
+  for (int id : h->levels[l]->node_ids) { const HNode& nd = h->nodes[id]; mx = std::max(mx, std::max(nd.half, nd.size - nd.half)); }
+  // (the interpreter's registers beside 128 of mirrors would spill: kernels off the a + b F(r^2) form stop at 128 x 128)
+  return mx <= 64 ? 64 : mx <= 128 ? 128 : (mx <= 256 && c.k->fast.ok) ? 256 : 0;
+}
+static GhBuf& aca_scratch(HodlrCall& c, int l) { return c.concurrent ? (GhBuf&)c.al[l].Tcm : (GhBuf&)c.shared_Tcm; }
+// buffers of level l for column capacity rc, counters cleared on stream sx
+static int prepare_level(HodlrCall& c, int l, int rc, hipStream_t sx) {
+  AcaLevel& a = c.al[l];
+  const int nn = (int)c.h->levels[l]->node_ids.size();
+  a.rcap = rc;
+  GH_CHECK(aca_scratch(c, l).ensure((size_t)c.n * rc * sizeof(double)));
+  GH_CHECK(a.idx.ensure((size_t)c.n * sizeof(int)));
+  GH_CHECK(a.part.ensure((size_t)nn * a.G * ACA_PSTRIDE * sizeof(double)));
+  if (a.sync_cleared) {                                  // (its slice of sync_all was cleared with all the others)
+    a.sync_cleared = false;
+  } else {
+    GH_CHECK(a.sync.ensure((size_t)nn * (sizeof(unsigned) + 2 * sizeof(int)) + 2 * sizeof(int)));
+    a.syncp = (char*)a.sync.p;
+    GH_HIP(hipMemsetAsync(a.syncp, 0, (size_t)nn * (sizeof(unsigned) + 2 * sizeof(int)) + 2 * sizeof(int), sx));
+  }
+  return GH_OK;
+}
+// enqueue the ACA of level l with column capacity rc on stream sx (no synchronisation)
+static int enqueue_level(HodlrCall& c, int l, int rc, hipStream_t sx) {
+  gh_hodlr* const h = c.h;
+  gh_kernel* const k = c.k;
+  HLevel* L = h->levels[l];
+  AcaLevel& a = c.al[l];
+  const int nn = (int)L->node_ids.size();
+  GH_CHECK(prepare_level(c, l, rc, sx));
+  GH_CHECK(aca_lds_attr());
+  GhBuf& T = aca_scratch(c, l);
+  unsigned* d_bars = (unsigned*)a.syncp;
+  int* d_sel = (int*)(d_bars + nn);
+  int* d_fail = d_sel + nn;
+  if (const int mr = wave_mr(c, l)) {                    // blocks of <= 256 x 256: a wavefront per node
+#define GH_ACA_WAVE(F, EE)                                                                                        \
+    hipLaunchKernelGGL((hodlr_aca_wave_kernel<F, EE>), dim3((nn + AW_NODES - 1) / AW_NODES), dim3(64 * AW_NODES), 0, sx, \
+                       k->d_nodes, (int)k->nodes.size(), k->fast, c.ndim, h->x.d(), (const LvlNode*)L->d_nodes.p, nn, T.d(), (long)c.n, rc, \
+                       (int*)L->d_ranks.p, h->opts.tol, (unsigned long long)(unsigned)h->opts.seed, l, d_fail + 1)
+    if (k->fast.ok) { if (mr == 64) GH_ACA_WAVE(true, 1); else if (mr == 128) GH_ACA_WAVE(true, 2); else GH_ACA_WAVE(true, 4); }
+    else            { if (mr == 64) GH_ACA_WAVE(false, 1); else GH_ACA_WAVE(false, 2); }
+#undef GH_ACA_WAVE
+    GH_HIP(hipGetLastError());
+    return GH_OK;
+  }
+#define GH_ACA_LAUNCH(F, CLU)                                                                                          \
+  hipLaunchKernelGGL((hodlr_aca_kernel<F, CLU>), dim3(nn * a.G), dim3(ACA_THREADS), a.G == 1 ? ACA_DYN_BYTES : 0, sx, k->d_nodes, (int)k->nodes.size(),  \
+                     k->fast, c.ndim, h->x.d(), (const LvlNode*)L->d_nodes.p, T.d(), (long)c.n, rc, (int*)a.idx.p,             \
+                     (int*)L->d_ranks.p, h->opts.tol, (unsigned long long)(unsigned)h->opts.seed, l,               \
+                     a.G, d_bars, a.part.d(), ACA_PSTRIDE, d_sel, d_fail, ACA_MULTI, ACA_FENCE, d_fail + 1,        \
+                     (const AcaSeg*)nullptr, 0, a.G == 1 ? ACA_CAPD : 0)
+  if (a.G == 1) { if (k->fast.ok) GH_ACA_LAUNCH(true, false); else GH_ACA_LAUNCH(false, false); }
+  else          { if (k->fast.ok) GH_ACA_LAUNCH(true, true); else GH_ACA_LAUNCH(false, true); }
+#undef GH_ACA_LAUNCH
+  GH_HIP(hipGetLastError());
+  return GH_OK;
+}
+// all levels `cl` as ONE launch of segments (the clustered ones: at most 256 workgroups, al[l].G already balanced)
+static int enqueue_fused(HodlrCall& c, const std::vector<int>& cl, int rc, hipStream_t sx, GhBuf& segbuf) {
+  gh_hodlr* const h = c.h;
+  gh_kernel* const k = c.k;
+  std::vector<AcaSeg> segs;
+  int wg = 0;
+  bool ones_only = true;                                 // (one-workgroup nodes only: the launch carries the LDS mirrors)
+  for (int l : cl) ones_only = ones_only && c.al[l].G == 1;
+  GH_CHECK(aca_lds_attr());
+  for (int l : cl) {
+    HLevel* L = h->levels[l];
+    AcaLevel& a = c.al[l];
+    const int nn = (int)L->node_ids.size();
+    GH_CHECK(prepare_level(c, l, rc, sx));
+    unsigned* d_bars = (unsigned*)a.syncp;
+    int* d_sel = (int*)(d_bars + nn);
+    int* d_fail = d_sel + nn;
+    int* d_dur = nullptr;
+    const int* d_order = nullptr;
+    if (ones_only && c.sw.lpt) {
+      // The nodes of a level differ in cost by 4x (C4, level 8: 205 us on average, ~800 us for the few whose search runs dry
+      // first), and a long one dispatched late is the end of phase 1: every node reports how long it took, and the next
+      // compute() of the handle launches the level longest first.  Inside an optimiser loop the costs hardly move.
+      d_dur = d_fail + 2;
+      a.timed = true;
+      if ((int)L->aca_dur.size() == nn) {
+        std::vector<int> ord(nn);
+        for (int q = 0; q < nn; ++q) ord[q] = q;
+        std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return L->aca_dur[x] > L->aca_dur[y]; });
+        GH_CHECK(upload(L->d_order, ord, sx));
+        d_order = (const int*)L->d_order.p;
       }
-      GH_CHECK(sync_all.ensure(std::max<size_t>(off, 256)));
-      GH_HIP(hipMemsetAsync(sync_all.p, 0, std::max<size_t>(off, 256), st));
-      for (int l = l0; l < nlev; ++l) if (!h->levels[l]->top) { al[l].syncp = (char*)sync_all.p + at[l]; al[l].sync_cleared = true; }
     }
-    GH_HIP(hipEventRecord(h->ev_b, st));                   // x and the node tables are uploaded
-    GH_HIP(hipStreamWaitEvent(h->st_b, h->ev_b, 0));
-    // Clustered levels: one launch, the 256 workgroup slots dealt so that the per-thread load is as even
-    // as it gets (start from <= 32 workgroups per level, then keep doubling the cluster of the level
-    // whose threads carry most columns).
-    std::vector<int> cl;
-    for (int l = l0; l < nlev; ++l) if (al[l].G > 1) cl.push_back(l);
-    if (cl.size() >= 2) {
-      std::vector<int> gmax(nlev, 1), half(nlev, 1);
-      int total = 0;
-      for (int l : cl) {
-        const int nn = (int)h->levels[l]->node_ids.size();
-        gmax[l] = al[l].G;
-        int mh = INT32_MAX;
-        for (int id : h->levels[l]->node_ids) mh = std::min(mh, h->nodes[id].half);
-        half[l] = mh;
-        int G = 1;
-        while (G * 2 <= gmax[l] && nn * G * 2 <= g_hodlr_coop_wgs / 8) G *= 2;
-        al[l].G = G;
-        // (round 6: a clusterable level left with one workgroup per node -- level 5 of C4: 32 blocks of 4096 x 4096, 0.54 ms per
-        //  node -- stays in the cooperative launch as one-workgroup segments at its end while the launch still fits the chip: in
-        //  the one-workgroup launch its nodes found no SIMD with room beside a cooperative workgroup before ~0.5 ms and were the
-        //  tail of phase 1, profiles/r06/hodlr_phase1_registers.md)
-        if (G > 1 || (g_hodlr_coop_singles && nn <= g_hodlr_coop_wgs / 8)) total += nn * G;       // (reserved: the doubling below stays inside the budget)
-      }
-      for (;;) {
-        int best = -1;
-        double load = 0.0;
-        for (int l : cl) {
-          const int nn = (int)h->levels[l]->node_ids.size();
-          if (al[l].G < 2 || al[l].G * 2 > gmax[l] || total + nn * al[l].G > g_hodlr_coop_wgs) continue;
-          const double ld = (double)half[l] / al[l].G;
-          if (ld > load) { load = ld; best = l; }
-        }
-        if (best < 0) break;
-        total += (int)h->levels[best]->node_ids.size() * al[best].G;
-        al[best].G *= 2;
-      }
-      // (the clusters below the root at 1 / g_hodlr_coop_lower of that width: see there)
-      for (size_t q = 1; q < cl.size(); ++q) { int& G = al[cl[q]].G; int d = g_hodlr_coop_lower; while (d > 1 && G >= 4) { G /= 2; d /= 2; } }
-      std::vector<int> fused, single;
-      {
-        int used = 0;
-        for (int l : cl) if (al[l].G > 1) used += (int)h->levels[l]->node_ids.size() * al[l].G;
-        for (int l : cl) {
-          const int nn = (int)h->levels[l]->node_ids.size();
-          if (al[l].G > 1) fused.push_back(l);
-          // (G = 1 segments.  With the clusters below the root at half width there is room for a second such level -- C4: level 6,
-          //  64 blocks of 2048 x 2048, which start at 0 instead of waiting ~0.24 ms for a CU: 3.40 -> 3.31 ms)
-          else if (g_hodlr_coop_singles && nn <= g_hodlr_coop_wgs / 4 && used + nn <= g_hodlr_coop_wgs) { fused.push_back(l); used += nn; }
-          else single.push_back(l);
-        }
-      }
-      if (h->aca_fused_ev[0] == nullptr) { GH_HIP(hipEventCreate(&h->aca_fused_ev[0])); GH_HIP(hipEventCreate(&h->aca_fused_ev[1])); }
-      GH_HIP(hipEventRecord(h->aca_fused_ev[0], st));
-      GH_CHECK(enqueue_fused(fused, rcap0, st, h->d_aca_segs));
-      GH_HIP(hipEventRecord(h->aca_fused_ev[1], st));
-      h->aca_timed = true;
-      // The one-workgroup-per-node levels and the leaf stage are independent of the fused launch and of
-      // each other, but HIP multiplexes streams onto 4 hardware queues (3 seen by this library: more
-      // streams than that just share a queue and serialise -- measured: a "fourth stream" ran its kernels
-      // behind the fused launch).  So: three queues -- the solver's stream (fused launch first) and two
-      // side streams -- and the items are dealt longest-first onto the least loaded queue, with the
-      // durations MEASURED in the previous compute() of this handle (HIP events; a default guess the
-      // first time): ranks, and with them the cost profile, hardly move inside an optimiser loop.
-      if (!h->st_c) {
-        hipStream_t shq[4] = {nullptr, nullptr, nullptr, nullptr};
-        if (h->shared_streams && gh_shared_streams(h->opts.device, shq)) h->st_c = shq[3];
-        if ((!h->shared_streams && hipStreamCreateWithFlags(&h->st_c, hipStreamNonBlocking) != hipSuccess) ||
-            hipEventCreateWithFlags(&h->ev_c, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); h->st_c = nullptr; }
-      }
-      if (!h->st_d && h->shared_streams && h->st_c) {
-        hipStream_t shq[4] = {nullptr, nullptr, nullptr, nullptr};
-        if (gh_shared_streams(h->opts.device, shq) && shq[1] && hipEventCreateWithFlags(&h->ev_d, hipEventDisableTiming) == hipSuccess) h->st_d = shq[1];
-        else (void)hipGetLastError();
-      }
-      std::vector<int> ones = single;
-      for (int l = l0; l < nlev; ++l) if (gmax[l] == 1) ones.push_back(l);
-      // The one-workgroup-per-node levels as ONE launch too (segments in order of decreasing block size: the long
-      // workgroups are dispatched first): launched one per queue they were balanced by hand over three queues with last
-      // compute()'s durations, and the queue that drew the two slowest levels ended 0.4 ms after the others.  One grid
-      // leaves the balancing to the dispatcher: C4 5.36 -> 5.24 ms.  (EVERY level in one grid, clustered segments first, was
-      // no better: 5.30.)
-      // the deep levels that take the wavefront-per-node kernel: launches of their own, first, on the fourth queue (the
-      // process-wide chain stream: high priority) where there is one
-      bool wave_on_d = false;
-      {
-        std::vector<int> keep;
-        hipStream_t sw = h->st_d ? h->st_d : h->st_b;
-        for (int l : ones) {
-          if (!wave_mr(l)) { keep.push_back(l); continue; }
-          if (sw == h->st_d && !wave_on_d) { GH_HIP(hipStreamWaitEvent(h->st_d, h->ev_b, 0)); wave_on_d = true; }
-          GH_CHECK(enqueue_level(l, rcap0, sw));
-        }
-        ones.swap(keep);
-        if (wave_on_d) { GH_HIP(hipEventRecord(h->ev_d, h->st_d)); GH_HIP(hipStreamWaitEvent(st, h->ev_d, 0)); }
-      }
-      if (ones.size() >= 2 && h->st_c) {
-        std::sort(ones.begin(), ones.end());
+    segs.push_back({(const LvlNode*)L->d_nodes.p, a.Tcm.d(), (int*)a.idx.p, (int*)L->d_ranks.p, d_bars, a.part.d(), d_sel,
+                    d_fail, d_fail + 1, l, a.G, wg, nn * a.G, d_dur, d_order});
+    wg += nn * a.G;
+  }
+  GH_CHECK(upload(segbuf, segs, sx));
+#define GH_ACA_LAUNCH(F, CLU)                                                                                          \
+  hipLaunchKernelGGL((hodlr_aca_kernel<F, CLU>), dim3(wg), dim3(ACA_THREADS), ones_only ? ACA_DYN_BYTES : 0, sx, k->d_nodes, (int)k->nodes.size(), \
+                     k->fast, c.ndim, h->x.d(), (const LvlNode*)nullptr, (double*)nullptr, (long)c.n, rc, (int*)nullptr, \
+                     (int*)nullptr, h->opts.tol, (unsigned long long)(unsigned)h->opts.seed, 0,                     \
+                     1, (unsigned*)nullptr, (double*)nullptr, ACA_PSTRIDE, (int*)nullptr, (int*)nullptr, ACA_MULTI, ACA_FENCE, \
+                     (int*)nullptr, (const AcaSeg*)segbuf.p, (int)segs.size(), ones_only ? ACA_CAPD : 0)
+  if (ones_only) { if (k->fast.ok) GH_ACA_LAUNCH(true, false); else GH_ACA_LAUNCH(false, false); }
+  else           { if (k->fast.ok) GH_ACA_LAUNCH(true, true); else GH_ACA_LAUNCH(false, true); }
+#undef GH_ACA_LAUNCH
+  GH_HIP(hipGetLastError());
+  return GH_OK;
+}
+// flags and ranks of level l back to the host (a device-to-host copy into pageable memory holds the
+// host until the stream gets there, so these are issued only after EVERY level has been enqueued)
+static int fetch_level(HodlrCall& c, int l, hipStream_t sx) {
+  HLevel* L = c.h->levels[l];
+  AcaLevel& a = c.al[l];
+  const int nn = (int)L->node_ids.size();
+  int* d_fail = (int*)((unsigned*)a.syncp + nn) + nn;
+  L->ranks.resize(nn);
+  GH_HIP(hipMemcpyAsync(a.flags, d_fail, 2 * sizeof(int), hipMemcpyDeviceToHost, sx));
+  GH_HIP(hipMemcpyAsync(L->ranks.data(), L->d_ranks.p, nn * sizeof(int), hipMemcpyDeviceToHost, sx));
+  return GH_OK;
+}
+// after a synchronisation: validate level l, redo it with more columns while a block is cut short
+static int settle_level(HodlrCall& c, int l) {
+  gh_hodlr* const h = c.h;
+  AcaLevel& a = c.al[l];
+  for (;;) {
+    if (a.flags[0]) { gh_set_error("HODLR: cluster barrier of the ACA kernel timed out at level %d", l); return GH_ERR_HIP; }
+    if (!a.flags[1]) return GH_OK;
+    if (a.flags[1] >= 2) {
+      // a block of this level asked the wavefront-per-node kernel for more than AW_RW_OF(E) columns: the level again, with the
+      // workgroup kernel (same draws, same results), and the handle remembers it for its next compute()
+      h->wave_bad[l] = 1;
+      GH_CHECK(enqueue_level(c, l, a.rcap, h->st));
+      GH_CHECK(fetch_level(c, l, h->st));
+      GH_HIP(hipStreamSynchronize(h->st));
+      continue;
+    }
+    // hodlr.h:147 lets the rank grow to min(rows, cols); a cut-short block would be a silently wrong answer
+    if (c.user_cap || a.rcap >= RANK_CAP) {
+      gh_set_error("HODLR: an off-diagonal block of level %d needs a rank above %d to reach tol = %g (%s); "
+                   "the factorisation is not usable", l, a.rcap, h->opts.tol,
+                   c.user_cap ? "opts.max_rank" : "the solver's ceiling: loosen tol, raise min_size or use the dense solver");
+      return c.user_cap ? GH_ERR_BAD_ARG : GH_ERR_RANK;
+    }
+    GH_CHECK(enqueue_level(c, l, std::min(2 * a.rcap, RANK_CAP), h->st));
+    GH_CHECK(fetch_level(c, l, h->st));
+    GH_HIP(hipStreamSynchronize(h->st));
+  }
+}
+static void rank_of_level(gh_hodlr* h, int l) {
+  HLevel* L = h->levels[l];
+  if (L->top) L->ranks.assign(1, h->sub.R[l]);         // (given: the ACA of the ancestor ran elsewhere)
+  L->R = 0;
+  for (int r : L->ranks) L->R = std::max(L->R, r);
+  L->off = h->Rtot;
+  h->Rtot += L->R;
+  h->maxR = std::max(h->maxR, L->R);
+}
+// serial mode only (one scratch shared by the levels): park the level's factors in a compact buffer
+static int compact_level(HodlrCall& c, int l) {
+  HLevel* L = c.h->levels[l];
+  const int nn = (int)L->node_ids.size();
+  const int64_t n = c.n;
+  rank_of_level(c.h, l);
+  if (L->R > 0) {
+    c.levelB[l] = std::make_unique<GhPooledBuf>();
+    GH_CHECK(c.levelB[l]->ensure((size_t)n * L->R * sizeof(double)));
+    GH_HIP(hipMemsetAsync(c.levelB[l]->p, 0, (size_t)n * L->R * sizeof(double), c.h->st));
+    hipLaunchKernelGGL(hodlr_compact_kernel, dim3(nn, std::max(8, std::min(512, 2048 / nn))), dim3(256), 0, c.h->st, c.shared_Tcm.d(), (long)n, (const LvlNode*)L->d_nodes.p,
+                       (const int*)L->d_ranks.p, L->R, c.levelB[l]->d(), (long)L->R, 0L, (double*)nullptr, 0L, 0L);
+    GH_HIP(hipGetLastError());
+  }
+  return GH_OK;
+}
+// the levels one at a time through ONE shared scratch (when the levels' scratch would not fit side by side)
+static int run_aca_serial(HodlrCall& c) {
+  for (int l = 0; l < c.l0; ++l) rank_of_level(c.h, l);
+  c.mark("serial ACA starts");
+  for (int l = c.l0; l < c.nlev; ++l) {
+    GH_CHECK(enqueue_level(c, l, c.rcap0, c.h->st));
+    c.mark("  level enqueued");
+    GH_CHECK(fetch_level(c, l, c.h->st));
+    GH_HIP(hipStreamSynchronize(c.h->st));
+    c.mark("  level synchronised");
+    GH_CHECK(settle_level(c, l));
+    GH_CHECK(compact_level(c, l));
+  }
+  return GH_OK;
+}
+
+// The cooperative launch's budget: the 256 workgroup slots dealt over the clustered levels `cl` so that the per-thread load is as
+// even as it gets (start from <= 32 workgroups per level, then keep doubling the cluster of the level whose threads carry most
+// columns).  gmax[l]: level l's cluster size before (1: not clustered); fused: the levels of the cooperative launch; single: the
+// clusterable levels left to the one-workgroup launch.
+static void coop_budget(HodlrCall& c, const std::vector<int>& cl, std::vector<int>& gmax, std::vector<int>& fused, std::vector<int>& single) {
+  const gh_hodlr* h = c.h;
+  std::vector<AcaLevel>& al = c.al;
+  const int wgs = c.sw.coop_wgs;
+  std::vector<int> half(c.nlev, 1);
+  gmax.assign(c.nlev, 1);
+  int total = 0;
+  for (int l : cl) {
+    const int nn = (int)h->levels[l]->node_ids.size();
+    gmax[l] = al[l].G;
+    int mh = INT32_MAX;
+    for (int id : h->levels[l]->node_ids) mh = std::min(mh, h->nodes[id].half);
+    half[l] = mh;
+    int G = 1;
+    while (G * 2 <= gmax[l] && nn * G * 2 <= wgs / 8) G *= 2;
+    al[l].G = G;
+    // (round 6: a clusterable level left with one workgroup per node -- level 5 of C4: 32 blocks of 4096 x 4096, 0.54 ms per
+    //  node -- stays in the cooperative launch as one-workgroup segments at its end while the launch still fits the chip: in
+    //  the one-workgroup launch its nodes found no SIMD with room beside a cooperative workgroup before ~0.5 ms and were the
+    //  tail of phase 1, profiles/r06/hodlr_phase1_registers.md)
+    if (G > 1 || (c.sw.coop_singles && nn <= wgs / 8)) total += nn * G;       // (reserved: the doubling below stays inside the budget)
+  }
+  for (;;) {
+    int best = -1;
+    double load = 0.0;
+    for (int l : cl) {
+      const int nn = (int)h->levels[l]->node_ids.size();
+      if (al[l].G < 2 || al[l].G * 2 > gmax[l] || total + nn * al[l].G > wgs) continue;
+      const double ld = (double)half[l] / al[l].G;
+      if (ld > load) { load = ld; best = l; }
+    }
+    if (best < 0) break;
+    total += (int)h->levels[best]->node_ids.size() * al[best].G;
+    al[best].G *= 2;
+  }
+  // (the clusters below the root at 1 / coop_lower of that width: see gh_debug_set_hodlr_coop_lower)
+  for (size_t q = 1; q < cl.size(); ++q) { int& G = al[cl[q]].G; int d = c.sw.coop_lower; while (d > 1 && G >= 4) { G /= 2; d /= 2; } }
+  int used = 0;
+  for (int l : cl) if (al[l].G > 1) used += (int)h->levels[l]->node_ids.size() * al[l].G;
+  for (int l : cl) {
+    const int nn = (int)h->levels[l]->node_ids.size();
+    if (al[l].G > 1) fused.push_back(l);
+    // (G = 1 segments.  With the clusters below the root at half width there is room for a second such level -- C4: level 6,
+    //  64 blocks of 2048 x 2048, which start at 0 instead of waiting ~0.24 ms for a CU: 3.40 -> 3.31 ms)
+    else if (c.sw.coop_singles && nn <= wgs / 4 && used + nn <= wgs) { fused.push_back(l); used += nn; }
+    else single.push_back(l);
+  }
+}
+// record the next timing event of the side items on sx
+static int stamp(gh_hodlr* h, hipStream_t sx) {
+  if (h->aca_ev_used == h->aca_ev.size()) { hipEvent_t e; GH_HIP(hipEventCreate(&e)); h->aca_ev.push_back(e); }
+  GH_HIP(hipEventRecord(h->aca_ev[h->aca_ev_used++], sx));
+  return GH_OK;
+}
+// two or more clustered levels: the cooperative launch on the solver's stream, everything else of phase 1 beside it
+static int enqueue_coop(HodlrCall& c, const std::vector<int>& cl) {
+  gh_hodlr* const h = c.h;
+  const hipStream_t st = h->st;
+  const int nlev = c.nlev;
+  std::vector<int> gmax, fused, single;
+  coop_budget(c, cl, gmax, fused, single);
+  if (h->aca_fused_ev[0] == nullptr) { GH_HIP(hipEventCreate(&h->aca_fused_ev[0])); GH_HIP(hipEventCreate(&h->aca_fused_ev[1])); }
+  GH_HIP(hipEventRecord(h->aca_fused_ev[0], st));
+  GH_CHECK(enqueue_fused(c, fused, c.rcap0, st, h->d_aca_segs));
+  GH_HIP(hipEventRecord(h->aca_fused_ev[1], st));
+  h->aca_timed = true;
+  // The one-workgroup-per-node levels and the leaf stage are independent of the fused launch and of
+  // each other, but HIP multiplexes streams onto 4 hardware queues (3 seen by this library: more
+  // streams than that just share a queue and serialise -- measured: a "fourth stream" ran its kernels
+  // behind the fused launch).  So: three queues -- the solver's stream (fused launch first) and two
+  // side streams -- and the items are dealt longest-first onto the least loaded queue, with the
+  // durations MEASURED in the previous compute() of this handle (HIP events; a default guess the
+  // first time): ranks, and with them the cost profile, hardly move inside an optimiser loop.
+  ensure_side_stream(h, 2);
+  if (h->st_c) ensure_side_stream(h, 3);
+  std::vector<int> ones = single;
+  for (int l = c.l0; l < nlev; ++l) if (gmax[l] == 1) ones.push_back(l);
+  // The one-workgroup-per-node levels as ONE launch too (segments in order of decreasing block size: the long
+  // workgroups are dispatched first): launched one per queue they were balanced by hand over three queues with last
+  // compute()'s durations, and the queue that drew the two slowest levels ended 0.4 ms after the others.  One grid
+  // leaves the balancing to the dispatcher: C4 5.36 -> 5.24 ms.  (EVERY level in one grid, clustered segments first, was
+  // no better: 5.30.)
+  // the deep levels that take the wavefront-per-node kernel: launches of their own, first, on the fourth queue (the
+  // process-wide chain stream: high priority) where there is one
+  bool wave_on_d = false;
+  std::vector<int> keep;
+  const hipStream_t sw = h->st_d ? h->st_d : h->st_b;
+  for (int l : ones) {
+    if (!wave_mr(c, l)) { keep.push_back(l); continue; }
+    if (sw == h->st_d && !wave_on_d) { GH_HIP(hipStreamWaitEvent(h->st_d, h->ev_b, 0)); wave_on_d = true; }
+    GH_CHECK(enqueue_level(c, l, c.rcap0, sw));
+  }
+  ones.swap(keep);
+  if (wave_on_d) { GH_HIP(hipEventRecord(h->ev_d, h->st_d)); GH_HIP(hipStreamWaitEvent(st, h->ev_d, 0)); }
+  if (ones.size() >= 2 && h->st_c) {
+    std::sort(ones.begin(), ones.end());
 #ifdef ACA_ONES_DEEPEST_FIRST
-        std::reverse(ones.begin(), ones.end());
+    std::reverse(ones.begin(), ones.end());
 #endif
 #ifdef ACA_ONES_LAST_FIRST
-        std::rotate(ones.begin(), ones.end() - 1, ones.end());       // deepest level first, then by decreasing block size
+    std::rotate(ones.begin(), ones.end() - 1, ones.end());       // deepest level first, then by decreasing block size
 #endif
-        GH_HIP(hipStreamWaitEvent(h->st_c, h->ev_b, 0));
-        if (h->st_d) GH_HIP(hipStreamWaitEvent(h->st_d, h->ev_b, 0));
-        // (round 5, measured and left out -- HISTORY.md: the leaf chain first and this launch behind it: +1.5 %; the levels with
-        //  blocks of <= 256 rows as a launch of their own with 256 / 128 / 64 threads per workgroup: 0 / +2.4 / +8 %.  The three
-        //  pieces of this phase are bound by what they ask of the chip together, not by their order or their shapes.)
-        GH_CHECK(enqueue_fused(ones, rcap0, h->st_b, h->d_aca_segs1));
-        GH_CHECK(leaf_stage(h->st_c));
-        GH_HIP(hipEventRecord(h->ev_c, h->st_c));
-        GH_HIP(hipStreamWaitEvent(st, h->ev_c, 0));
-        h->aca_timed = false;
-        ones.clear();
-      }
-      struct Item { int level; double cost; };             // level -1: the leaf stage
-      std::vector<Item> items;
-      const bool have = (int)h->aca_ms.size() == nlev + 2;     // [0..nlev): levels, [nlev]: fused launch, [nlev+1]: leaf stage
-      for (int l : ones) items.push_back({l, have && h->aca_ms[l] > 0 ? h->aca_ms[l] : 1.0});
-      if (!leaves_done) items.push_back({-1, have && h->aca_ms[nlev + 1] > 0 ? h->aca_ms[nlev + 1] : 1.2});
-      std::sort(items.begin(), items.end(), [](const Item& x, const Item& y) { return x.cost > y.cost; });
-      hipStream_t qs[4] = {st, h->st_b, h->st_c ? h->st_c : h->st_b, h->st_d ? h->st_d : h->st_b};
-      double load[4] = {have && h->aca_ms[nlev] > 0 ? h->aca_ms[nlev] : 1.5, 0.0, h->st_c ? 0.0 : 1e30, h->st_d ? 0.0 : 1e30};
-      if (h->st_c) GH_HIP(hipStreamWaitEvent(h->st_c, h->ev_b, 0));
-      if (h->st_d) GH_HIP(hipStreamWaitEvent(h->st_d, h->ev_b, 0));
-      h->aca_ev_used = 0;
-      auto stamp = [&](hipStream_t sx) -> int {               // record the next timing event on sx
-        if (h->aca_ev_used == h->aca_ev.size()) {
-          hipEvent_t e;
-          GH_HIP(hipEventCreate(&e));
-          h->aca_ev.push_back(e);
-        }
-        GH_HIP(hipEventRecord(h->aca_ev[h->aca_ev_used++], sx));
-        return GH_OK;
-      };
-      h->aca_items.clear();
-      // (the fused launch was enqueued above, between two stamps on st)
-      for (const Item& it : items) {
-        int q = 0;
-        for (int w = 1; w < 4; ++w) if (load[w] < load[q]) q = w;
-        load[q] += it.cost;
-        GH_CHECK(stamp(qs[q]));
-        if (it.level >= 0) GH_CHECK(enqueue_level(it.level, rcap0, qs[q])); else GH_CHECK(leaf_stage(qs[q]));
-        GH_CHECK(stamp(qs[q]));
-        h->aca_items.push_back(it.level);
-      }
-      if (h->st_c) { GH_HIP(hipEventRecord(h->ev_c, h->st_c)); GH_HIP(hipStreamWaitEvent(st, h->ev_c, 0)); }
-      if (h->st_d) { GH_HIP(hipEventRecord(h->ev_d, h->st_d)); GH_HIP(hipStreamWaitEvent(st, h->ev_d, 0)); }
-    } else {
-      for (int l = l0; l < nlev; ++l) GH_CHECK(enqueue_level(l, rcap0, al[l].G > 1 ? st : h->st_b));
-      GH_CHECK(leaf_stage(h->st_b));
-    }
-    GH_HIP(hipEventRecord(h->ev_b, h->st_b));
-    GH_HIP(hipStreamWaitEvent(st, h->ev_b, 0));
-    {
-      // one gather launch + one copy into pinned memory for the ranks and the two failure flags of every level
-      std::vector<GatherItem> items;
-      int tot = 0;
-      for (int l = l0; l < nlev; ++l) {
-        HLevel* L = h->levels[l];
-        const int nn = (int)L->node_ids.size();
-        items.push_back({(const int*)L->d_ranks.p, nn, tot}); tot += nn;
-        items.push_back({(const int*)((unsigned*)al[l].syncp + nn) + nn, 2 + (al[l].timed ? nn : 0), tot}); tot += 2 + (al[l].timed ? nn : 0);
-      }
-      // (pinned host memory, read by the kernel in place: the item table needs no copy of its own)
-      const size_t need = (size_t)tot + 4 + items.size() * (sizeof(GatherItem) / sizeof(int));
-      if (need > h->h_gather_cap) {
-        if (h->h_gather) (void)hipHostFree(h->h_gather);
-        h->h_gather = nullptr; h->h_gather_cap = 0;
-        GH_HIP(hipHostMalloc((void**)&h->h_gather, need * 2 * sizeof(int), hipHostMallocDefault));
-        h->h_gather_cap = need * 2;
-      }
-      GatherItem* const h_items = (GatherItem*)(h->h_gather + ((tot + 3) / 4) * 4);       // (16-byte aligned, behind the results)
-      memcpy(h_items, items.data(), items.size() * sizeof(GatherItem));
-      GH_CHECK(h->d_gather.ensure((size_t)tot * sizeof(int)));
-      hipLaunchKernelGGL(hodlr_gather_kernel, dim3((unsigned)items.size()), dim3(256), 0, st, (const GatherItem*)h_items, (int*)h->d_gather.p);
-      GH_HIP(hipGetLastError());
-      GH_HIP(hipMemcpyAsync(h->h_gather, h->d_gather.p, (size_t)tot * sizeof(int), hipMemcpyDeviceToHost, st));
-      GH_HIP(hipStreamSynchronize(st));
-      int at = 0;
-      for (int l = l0; l < nlev; ++l) {
-        HLevel* L = h->levels[l];
-        const int nn = (int)L->node_ids.size();
-        L->ranks.assign(h->h_gather + at, h->h_gather + at + nn); at += nn;
-        al[l].flags[0] = h->h_gather[at]; al[l].flags[1] = h->h_gather[at + 1]; at += 2;
-        if (al[l].timed) { L->aca_dur.assign(h->h_gather + at, h->h_gather + at + nn); at += nn; }
-      }
-    }
-    if (h->aca_timed) {                                 // durations for the next compute()'s schedule
-      h->aca_ms.assign(nlev + 2, 0.0);
-      float ms = 0;
-      if (hipEventElapsedTime(&ms, h->aca_fused_ev[0], h->aca_fused_ev[1]) == hipSuccess) h->aca_ms[nlev] = ms;
-      for (size_t q = 0; q < h->aca_items.size() && 2 * q + 1 < h->aca_ev_used; ++q) {
-        if (hipEventElapsedTime(&ms, h->aca_ev[2 * q], h->aca_ev[2 * q + 1]) != hipSuccess) { (void)hipGetLastError(); continue; }
-        const int lv = h->aca_items[q];
-        h->aca_ms[lv >= 0 ? lv : nlev + 1] = ms;
-      }
-      h->aca_timed = false;
-    }
-#ifdef GH_ACA_TIMES
-    {
-      static int calls = 0;
-      if (++calls == 3)
-        for (int l = l0; l < nlev; ++l) {
-          if (al[l].G != 1) { fprintf(stderr, "[aca] level %d: G = %d\n", l, al[l].G); continue; }
-          const int nn = (int)h->levels[l]->node_ids.size();
-          std::vector<double> hp((size_t)nn * pstride);
-          (void)hipMemcpy(hp.data(), al[l].part.p, hp.size() * sizeof(double), hipMemcpyDeviceToHost);
-          double mx = 0, sum = 0, t0min = 1e300, t1max = 0, ps = 0, rem = 0;
-          int who = 0;
-          for (int q = 0; q < nn; ++q) {
-            const double* e = hp.data() + (size_t)q * pstride;
-            sum += e[0]; ps += e[3]; rem += e[2];
-            if (e[0] > mx) { mx = e[0]; who = q; }
-            t0min = std::min(t0min, e[4]); t1max = std::max(t1max, e[4] + e[0]);
-          }
-          const double* w = hp.data() + (size_t)who * pstride;
-          fprintf(stderr, "[aca] level %2d: %4d nodes  per-node us mean %8.1f max %8.1f (node %d: rank %d, rows left %d, passes %d)  mean passes %.1f "
-                  "mean rows left %.1f  first start %.1f .. last end %.1f us (100 MHz clock)\n", l, nn, sum / nn * 0.01, mx * 0.01, who, (int)w[1], (int)w[2], (int)w[3],
-                  ps / nn, rem / nn, t0min * 0.01, t1max * 0.01);
-        }
-    }
-#endif
-    for (int l = 0; l < nlev; ++l) { if (l >= l0) GH_CHECK(settle_level(l)); rank_of_level(l); }
-  } else {
-    for (int l = 0; l < l0; ++l) rank_of_level(l);
-    mark("serial ACA starts");
-    for (int l = l0; l < nlev; ++l) {
-      GH_CHECK(enqueue_level(l, rcap0, st));
-      mark("  level enqueued");
-      GH_CHECK(fetch_level(l, st));
-      GH_HIP(hipStreamSynchronize(st));
-      mark("  level synchronised");
-      GH_CHECK(settle_level(l));
-      GH_CHECK(compact_level(l));
-    }
+    GH_HIP(hipStreamWaitEvent(h->st_c, h->ev_b, 0));
+    if (h->st_d) GH_HIP(hipStreamWaitEvent(h->st_d, h->ev_b, 0));
+    // (round 5, measured and left out -- HISTORY.md: the leaf chain first and this launch behind it: +1.5 %; the levels with
+    //  blocks of <= 256 rows as a launch of their own with 256 / 128 / 64 threads per workgroup: 0 / +2.4 / +8 %.  The three
+    //  pieces of this phase are bound by what they ask of the chip together, not by their order or their shapes.)
+    GH_CHECK(enqueue_fused(c, ones, c.rcap0, h->st_b, h->d_aca_segs1));
+    GH_CHECK(leaf_stage(c, h->st_c));
+    GH_HIP(hipEventRecord(h->ev_c, h->st_c));
+    GH_HIP(hipStreamWaitEvent(st, h->ev_c, 0));
+    h->aca_timed = false;
+    ones.clear();
   }
-  GhPooledBuf& Tcm = shared_Tcm;
-  GhPooledBuf idx;
-  Tcm.release();
-  idx.release();
-  mark("ACA done, ranks known");
+  struct Item { int level; double cost; };             // level -1: the leaf stage
+  std::vector<Item> items;
+  const bool have = (int)h->aca_ms.size() == nlev + 2;     // [0..nlev): levels, [nlev]: fused launch, [nlev+1]: leaf stage
+  for (int l : ones) items.push_back({l, have && h->aca_ms[l] > 0 ? h->aca_ms[l] : 1.0});
+  if (!c.leaves_done) items.push_back({-1, have && h->aca_ms[nlev + 1] > 0 ? h->aca_ms[nlev + 1] : 1.2});
+  std::sort(items.begin(), items.end(), [](const Item& x, const Item& y) { return x.cost > y.cost; });
+  hipStream_t qs[4] = {st, h->st_b, h->st_c ? h->st_c : h->st_b, h->st_d ? h->st_d : h->st_b};
+  double load[4] = {have && h->aca_ms[nlev] > 0 ? h->aca_ms[nlev] : 1.5, 0.0, h->st_c ? 0.0 : 1e30, h->st_d ? 0.0 : 1e30};
+  if (h->st_c) GH_HIP(hipStreamWaitEvent(h->st_c, h->ev_b, 0));
+  if (h->st_d) GH_HIP(hipStreamWaitEvent(h->st_d, h->ev_b, 0));
+  h->aca_ev_used = 0;
+  h->aca_items.clear();
+  // (the fused launch was enqueued above, between two stamps on st)
+  for (const Item& it : items) {
+    int q = 0;
+    for (int w = 1; w < 4; ++w) if (load[w] < load[q]) q = w;
+    load[q] += it.cost;
+    GH_CHECK(stamp(h, qs[q]));
+    if (it.level >= 0) GH_CHECK(enqueue_level(c, it.level, c.rcap0, qs[q])); else GH_CHECK(leaf_stage(c, qs[q]));
+    GH_CHECK(stamp(h, qs[q]));
+    h->aca_items.push_back(it.level);
+  }
+  if (h->st_c) { GH_HIP(hipEventRecord(h->ev_c, h->st_c)); GH_HIP(hipStreamWaitEvent(st, h->ev_c, 0)); }
+  if (h->st_d) { GH_HIP(hipEventRecord(h->ev_d, h->st_d)); GH_HIP(hipStreamWaitEvent(st, h->ev_d, 0)); }
+  return GH_OK;
+}
+#ifdef GH_ACA_TIMES
+// per-level node durations of the one-workgroup launches (from the ACA kernel's partials), once, at the third compute()
+static void print_aca_times(HodlrCall& c) {
+  static int calls = 0;                           // (the third compute(): the durations of the handle's previous one are in use)
+  if (++calls != 3) return;
+  for (int l = c.l0; l < c.nlev; ++l) {
+    if (c.al[l].G != 1) { fprintf(stderr, "[aca] level %d: G = %d\n", l, c.al[l].G); continue; }
+    const int nn = (int)c.h->levels[l]->node_ids.size();
+    std::vector<double> hp((size_t)nn * ACA_PSTRIDE);
+    (void)hipMemcpy(hp.data(), c.al[l].part.p, hp.size() * sizeof(double), hipMemcpyDeviceToHost);
+    double mx = 0, sum = 0, t0min = 1e300, t1max = 0, ps = 0, rem = 0;
+    int who = 0;
+    for (int q = 0; q < nn; ++q) {
+      const double* e = hp.data() + (size_t)q * ACA_PSTRIDE;
+      sum += e[0]; ps += e[3]; rem += e[2];
+      if (e[0] > mx) { mx = e[0]; who = q; }
+      t0min = std::min(t0min, e[4]); t1max = std::max(t1max, e[4] + e[0]);
+    }
+    const double* w = hp.data() + (size_t)who * ACA_PSTRIDE;
+    fprintf(stderr, "[aca] level %2d: %4d nodes  per-node us mean %8.1f max %8.1f (node %d: rank %d, rows left %d, passes %d)  mean passes %.1f "
+            "mean rows left %.1f  first start %.1f .. last end %.1f us (100 MHz clock)\n", l, nn, sum / nn * 0.01, mx * 0.01, who, (int)w[1], (int)w[2], (int)w[3],
+            ps / nn, rem / nn, t0min * 0.01, t1max * 0.01);
+  }
+}
+#endif
+// every level at once: all of phase 1 enqueued, then ONE synchronisation for the ranks and flags of every level
+static int run_aca_concurrent(HodlrCall& c) {
+  gh_hodlr* const h = c.h;
+  const hipStream_t st = h->st;
+  const int nlev = c.nlev, l0 = c.l0;
+  std::vector<AcaLevel>& al = c.al;
+  // (a memset per level in front of every launch: thirteen ~7 us fill kernels, 100 us before the one-workgroup levels started)
+  size_t off = 0;
+  std::vector<size_t> slice(nlev, 0);
+  for (int l = l0; l < nlev; ++l) {
+    if (h->levels[l]->top) continue;
+    slice[l] = off;
+    off += (size_t)gh_round_up((int64_t)(h->levels[l]->node_ids.size() * (sizeof(unsigned) + 2 * sizeof(int)) + 2 * sizeof(int)), 256);   // bars | sel | fail, trunc | dur
+  }
+  GH_CHECK(c.sync_all.ensure(std::max<size_t>(off, 256)));
+  GH_HIP(hipMemsetAsync(c.sync_all.p, 0, std::max<size_t>(off, 256), st));
+  for (int l = l0; l < nlev; ++l) if (!h->levels[l]->top) { al[l].syncp = (char*)c.sync_all.p + slice[l]; al[l].sync_cleared = true; }
+  GH_HIP(hipEventRecord(h->ev_b, st));                   // x and the node tables are uploaded
+  GH_HIP(hipStreamWaitEvent(h->st_b, h->ev_b, 0));
+  std::vector<int> cl;
+  for (int l = l0; l < nlev; ++l) if (al[l].G > 1) cl.push_back(l);
+  if (cl.size() >= 2) {
+    GH_CHECK(enqueue_coop(c, cl));
+  } else {
+    for (int l = l0; l < nlev; ++l) GH_CHECK(enqueue_level(c, l, c.rcap0, al[l].G > 1 ? st : h->st_b));
+    GH_CHECK(leaf_stage(c, h->st_b));
+  }
+  GH_HIP(hipEventRecord(h->ev_b, h->st_b));
+  GH_HIP(hipStreamWaitEvent(st, h->ev_b, 0));
+  // one gather launch + one copy into pinned memory for the ranks and the two failure flags of every level
+  std::vector<GatherItem> items;
+  int tot = 0;
+  for (int l = l0; l < nlev; ++l) {
+    HLevel* L = h->levels[l];
+    const int nn = (int)L->node_ids.size();
+    items.push_back({(const int*)L->d_ranks.p, nn, tot}); tot += nn;
+    items.push_back({(const int*)((unsigned*)al[l].syncp + nn) + nn, 2 + (al[l].timed ? nn : 0), tot}); tot += 2 + (al[l].timed ? nn : 0);
+  }
+  // (pinned host memory, read by the kernel in place: the item table needs no copy of its own)
+  const size_t need = (size_t)tot + 4 + items.size() * (sizeof(GatherItem) / sizeof(int));
+  if (need > h->h_gather_cap) {
+    if (h->h_gather) (void)hipHostFree(h->h_gather);
+    h->h_gather = nullptr; h->h_gather_cap = 0;
+    GH_HIP(hipHostMalloc((void**)&h->h_gather, need * 2 * sizeof(int), hipHostMallocDefault));
+    h->h_gather_cap = need * 2;
+  }
+  GatherItem* const h_items = (GatherItem*)(h->h_gather + ((tot + 3) / 4) * 4);       // (16-byte aligned, behind the results)
+  memcpy(h_items, items.data(), items.size() * sizeof(GatherItem));
+  GH_CHECK(h->d_gather.ensure((size_t)tot * sizeof(int)));
+  hipLaunchKernelGGL(hodlr_gather_kernel, dim3((unsigned)items.size()), dim3(256), 0, st, (const GatherItem*)h_items, (int*)h->d_gather.p);
+  GH_HIP(hipGetLastError());
+  GH_HIP(hipMemcpyAsync(h->h_gather, h->d_gather.p, (size_t)tot * sizeof(int), hipMemcpyDeviceToHost, st));
+  GH_HIP(hipStreamSynchronize(st));
+  int at = 0;
+  for (int l = l0; l < nlev; ++l) {
+    HLevel* L = h->levels[l];
+    const int nn = (int)L->node_ids.size();
+    L->ranks.assign(h->h_gather + at, h->h_gather + at + nn); at += nn;
+    al[l].flags[0] = h->h_gather[at]; al[l].flags[1] = h->h_gather[at + 1]; at += 2;
+    if (al[l].timed) { L->aca_dur.assign(h->h_gather + at, h->h_gather + at + nn); at += nn; }
+  }
+  if (h->aca_timed) {                                 // durations for the next compute()'s schedule
+    h->aca_ms.assign(nlev + 2, 0.0);
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, h->aca_fused_ev[0], h->aca_fused_ev[1]) == hipSuccess) h->aca_ms[nlev] = ms;
+    for (size_t q = 0; q < h->aca_items.size() && 2 * q + 1 < h->aca_ev_used; ++q) {
+      if (hipEventElapsedTime(&ms, h->aca_ev[2 * q], h->aca_ev[2 * q + 1]) != hipSuccess) { (void)hipGetLastError(); continue; }
+      const int lv = h->aca_items[q];
+      h->aca_ms[lv >= 0 ? lv : nlev + 1] = ms;
+    }
+    h->aca_timed = false;
+  }
+#ifdef GH_ACA_TIMES
+  print_aca_times(c);
+#endif
+  for (int l = 0; l < nlev; ++l) { if (l >= l0) GH_CHECK(settle_level(c, l)); rank_of_level(c.h, l); }
+  return GH_OK;
+}
 
-  // ---- UA / VA (n x Rtot) and the per-level chunk / job tables
+// chunk / job tables of level L (cached: they depend on the tree and on (R, off, Rtot) only)
+static int level_tables(gh_hodlr* h, HLevel* L, long Rtot) {
+  const int R = L->R, nn = (int)L->node_ids.size();
+  if (L->tab_R == R && L->tab_off == L->off && L->tab_Rtot == Rtot) { h->max_chunks = std::max(h->max_chunks, L->nchunks); return GH_OK; }
+  std::vector<Chunk> chunks;
+  std::vector<int> crange(nn * 4);
+  std::vector<MMJob> red, upd, updl, smul(nn);
+  for (int q = 0; q < nn; ++q) {
+    const HNode& nd = h->nodes[L->node_ids[q]];
+    for (int half = 0; half < 2; ++half) {
+      const int r0 = half == 0 ? nd.start : nd.start + nd.half;
+      const int cnt = half == 0 ? nd.half : nd.size - nd.half;
+      crange[(q * 2 + half) * 2] = (int)chunks.size();
+      for (int s = 0; s < cnt; s += HCH) {
+        const int nr = std::min(HCH, cnt - s);
+        const int ch = (int)chunks.size();
+        chunks.push_back({q, half, r0 + s, nr});
+        red.push_back({(long)(r0 + s) * R, r0 + s, ch * R, R, nr});                    // A = V_l rows (level-major block, transposed access)
+        upd.push_back({(long)(r0 + s) * Rtot, q * 2 * R + (half == 0 ? 0 : R), r0 + s, nr, R});
+        updl.push_back({(long)(r0 + s) * R, q * 2 * R + (half == 0 ? 0 : R), r0 + s, nr, R});      // same against UL
+      }
+      crange[(q * 2 + half) * 2 + 1] = (int)chunks.size();
+    }
+    smul[q] = {(long)q * 4 * R * R, q * 2 * R, q * 2 * R, 2 * R, 2 * R};
+  }
+  L->nchunks = (int)chunks.size();
+  L->chunk_geom.clear();
+  for (const Chunk& ch : chunks) { L->chunk_geom.push_back(ch.row0); L->chunk_geom.push_back(ch.nrows); }
+  h->max_chunks = std::max(h->max_chunks, L->nchunks);
+  GH_CHECK(upload(L->d_chunks, chunks, h->st));
+  GH_CHECK(upload(L->d_crange, crange, h->st));
+  GH_CHECK(upload(L->d_red_jobs, red, h->st));
+  GH_CHECK(upload(L->d_upd_jobs, upd, h->st));
+  GH_CHECK(upload(L->d_updl_jobs, updl, h->st));
+  GH_CHECK(upload(L->d_smul_jobs, smul, h->st));
+  L->tab_R = R; L->tab_off = L->off; L->tab_Rtot = Rtot;
+  return GH_OK;
+}
+// ---- UA / VA (n x Rtot) from the ACA scratch, the per-level chunk / job tables, the work arrays of the sweep
+static int assemble_factors(HodlrCall& c) {
+  gh_hodlr* const h = c.h;
+  const hipStream_t st = h->st;
+  const int64_t n = c.n;
+  const int nlev = c.nlev, l0 = c.l0;
+  c.shared_Tcm.release();
+  c.mark("ACA done, ranks known");
   const long Rtot = std::max(h->Rtot, 1);
   GH_CHECK(h->UA.ensure((size_t)n * Rtot * sizeof(double)));
   GH_CHECK(h->VA.ensure((size_t)n * Rtot * sizeof(double)));
@@ -3465,11 +3523,11 @@ extern "C" int gh_hodlr_compute(gh_hodlr* h, gh_kernel* k, const double* x, int6
   bool complete = true;
   for (int l = l0; l < nlev; ++l) if (h->levels[l]->node_ids.size() != ((size_t)1 << (l - l0))) complete = false;   // (a pseudo-level covers every local row)
   bool fused_compact = nlev <= 24;                     // (CompactSegs)
-  for (int l = 0; l < nlev; ++l) if (levelB[l]) fused_compact = false;
+  for (int l = 0; l < nlev; ++l) if (c.levelB[l]) fused_compact = false;
   // (round 6) the compaction writes the level-major copy only and the leaf product -- the first thing that touches U -- reads that and
   // writes the row-major U itself, where that product is ONE pass of the 128-row-leaf kernel over all columns (LeafSrc)
-  const bool u_from_v = g_hodlr_u_from_v && fused_compact && complete && l0 == 0 && nlev <= 24 && h->leaf_pitch == 128 && h->max_leaf <= 128 &&
-                        h->Rtot > MV_C && h->Rtot <= 128;
+  c.u_from_v = c.sw.u_from_v && fused_compact && complete && l0 == 0 && nlev <= 24 && h->leaf_pitch == 128 && h->max_leaf <= 128 &&
+               h->Rtot > MV_C && h->Rtot <= 128;
   if (!(complete && fused_compact)) {
     GH_HIP(hipMemsetAsync(h->UA.p, 0, (size_t)n * Rtot * sizeof(double), st));
     GH_HIP(hipMemsetAsync(h->VA.p, 0, (size_t)n * Rtot * sizeof(double), st));
@@ -3481,7 +3539,7 @@ extern "C" int gh_hodlr_compute(gh_hodlr* h, gh_kernel* k, const double* x, int6
       HLevel* L = h->levels[l];
       if (L->R == 0) continue;
       const int nn = (int)L->node_ids.size(), ny = std::max(8, std::min(512, 2048 / nn));
-      segs.push_back({L->top ? h->sub.T[l] : al[l].Tcm.d(), (const LvlNode*)L->d_nodes.p, (const int*)L->d_ranks.p, L->R, ny, (long)L->off, (long)n * L->off,
+      segs.push_back({L->top ? h->sub.T[l] : c.al[l].Tcm.d(), (const LvlNode*)L->d_nodes.p, (const int*)L->d_ranks.p, L->R, ny, (long)L->off, (long)n * L->off,
                       (long)L->R, b0, nn * ny});
       b0 += nn * ny;
     }
@@ -3490,7 +3548,7 @@ extern "C" int gh_hodlr_compute(gh_hodlr* h, gh_kernel* k, const double* x, int6
       cs.n = (int)segs.size();
       for (int q = 0; q < cs.n; ++q) cs.s[q] = segs[q];
       hipLaunchKernelGGL(hodlr_compact_all_kernel, dim3((unsigned)b0), dim3(256), 0, st, cs,
-                         (long)n, u_from_v ? (double*)nullptr : h->UA.d(), (long)Rtot, h->VA.d());
+                         (long)n, c.u_from_v ? (double*)nullptr : h->UA.d(), (long)Rtot, h->VA.d());
       GH_HIP(hipGetLastError());
     }
   }
@@ -3498,109 +3556,92 @@ extern "C" int gh_hodlr_compute(gh_hodlr* h, gh_kernel* k, const double* x, int6
     HLevel* L = h->levels[l];
     if (L->R == 0) continue;
     const int R = L->R, nn = (int)L->node_ids.size();
-    if (fused_compact) {
-      // (done above, all levels in one launch)
-    } else if (levelB[l]) {
+    if (c.levelB[l]) {
       // (serial mode) scatter the compact level buffer into column block [off, off+R) of UA and VA
-      GH_HIP(hipMemcpy2DAsync(h->UA.d() + L->off, Rtot * sizeof(double), levelB[l]->p, R * sizeof(double), R * sizeof(double), n, hipMemcpyDeviceToDevice, st));
-      GH_HIP(hipMemcpyAsync(h->VA.d() + (long)n * L->off, levelB[l]->p, (size_t)n * R * sizeof(double), hipMemcpyDeviceToDevice, st));
-    } else {
+      GH_HIP(hipMemcpy2DAsync(h->UA.d() + L->off, Rtot * sizeof(double), c.levelB[l]->p, R * sizeof(double), R * sizeof(double), n, hipMemcpyDeviceToDevice, st));
+      GH_HIP(hipMemcpyAsync(h->VA.d() + (long)n * L->off, c.levelB[l]->p, (size_t)n * R * sizeof(double), hipMemcpyDeviceToDevice, st));
+    } else if (!fused_compact) {                         // (else done above, all levels in one launch)
       // every rank is known by now: the level's scratch goes straight into its column block (22 strided
       // device copies per compute() before)
-      hipLaunchKernelGGL(hodlr_compact_kernel, dim3(nn, std::max(8, std::min(512, 2048 / nn))), dim3(256), 0, st, L->top ? h->sub.T[l] : al[l].Tcm.d(), (long)n, (const LvlNode*)L->d_nodes.p,
+      hipLaunchKernelGGL(hodlr_compact_kernel, dim3(nn, std::max(8, std::min(512, 2048 / nn))), dim3(256), 0, st, L->top ? h->sub.T[l] : c.al[l].Tcm.d(), (long)n, (const LvlNode*)L->d_nodes.p,
                          (const int*)L->d_ranks.p, R, h->UA.d(), (long)Rtot, (long)L->off, h->VA.d(), (long)R, (long)n * L->off);
       GH_HIP(hipGetLastError());
     }
     GH_CHECK(L->sinv.ensure((size_t)nn * 4 * R * R * sizeof(double)));
-    if (L->tab_R == R && L->tab_off == L->off && L->tab_Rtot == Rtot) { h->max_chunks = std::max(h->max_chunks, L->nchunks); continue; }
-    std::vector<Chunk> chunks;
-    std::vector<int> crange(nn * 4);
-    std::vector<MMJob> red, upd, updl, smul(nn);
-    for (int q = 0; q < nn; ++q) {
-      const HNode& nd = h->nodes[L->node_ids[q]];
-      for (int half = 0; half < 2; ++half) {
-        const int r0 = half == 0 ? nd.start : nd.start + nd.half;
-        const int cnt = half == 0 ? nd.half : nd.size - nd.half;
-        crange[(q * 2 + half) * 2] = (int)chunks.size();
-        for (int s = 0; s < cnt; s += HCH) {
-          const int nr = std::min(HCH, cnt - s);
-          const int ch = (int)chunks.size();
-          chunks.push_back({q, half, r0 + s, nr});
-          red.push_back({(long)(r0 + s) * R, r0 + s, ch * R, R, nr});                    // A = V_l rows (level-major block, transposed access)
-          upd.push_back({(long)(r0 + s) * Rtot, q * 2 * R + (half == 0 ? 0 : R), r0 + s, nr, R});
-          updl.push_back({(long)(r0 + s) * R, q * 2 * R + (half == 0 ? 0 : R), r0 + s, nr, R});      // same against UL
-        }
-        crange[(q * 2 + half) * 2 + 1] = (int)chunks.size();
-      }
-      smul[q] = {(long)q * 4 * R * R, q * 2 * R, q * 2 * R, 2 * R, 2 * R};
-    }
-    L->nchunks = (int)chunks.size();
-    L->chunk_geom.clear();
-    for (const Chunk& c : chunks) { L->chunk_geom.push_back(c.row0); L->chunk_geom.push_back(c.nrows); }
-    h->max_chunks = std::max(h->max_chunks, L->nchunks);
-    GH_CHECK(upload(L->d_chunks, chunks, st));
-    GH_CHECK(upload(L->d_crange, crange, st));
-    GH_CHECK(upload(L->d_red_jobs, red, st));
-    GH_CHECK(upload(L->d_upd_jobs, upd, st));
-    GH_CHECK(upload(L->d_updl_jobs, updl, st));
-    GH_CHECK(upload(L->d_smul_jobs, smul, st));
-    L->tab_R = R; L->tab_off = L->off; L->tab_Rtot = Rtot;
+    GH_CHECK(level_tables(h, L, Rtot));
   }
-  mark("tables enqueued");
+  c.mark("tables enqueued");
   // The ACA scratch (n x 256 doubles per level: 6 GB at C4, 12 GB for a 524288-row sub-tree) goes back to the block
   // cache NOW, not when compute() returns, in a SPLIT tree: the next sub-tree of this device starts while this one waits
   // for the others in its top levels, and found the cache empty -- tens of GB of hipMalloc / hipFree per compute(),
   // stalls of 1.4-2.8 s at N = 2M over four sub-trees on one GPU.  That takes a host synchronisation (another handle may pick the
   // blocks up on a stream of its own), 20 us in the middle of a 3.4-ms step: a handle that owns its whole tree keeps the scratch
-  // until the end of compute() instead -- the guard below synchronises before the buffers' destructors run on any path out.
-  struct SyncBeforeRelease { hipStream_t st; ~SyncBeforeRelease() { (void)hipStreamSynchronize(st); } } sync_before_release{st};
+  // until the end of compute() instead (HodlrCall).
   if (l0 > 0) {
     GH_HIP(hipStreamSynchronize(st));
-    mark("U, V assembled");
-    for (auto& a : al) { a.Tcm.release(); a.idx.release(); a.sync.release(); a.part.release(); }
-    sync_all.release();
-    for (auto*& b : levelB) { delete b; b = nullptr; }
+    c.mark("U, V assembled");
+    for (auto& a : c.al) { a.Tcm.release(); a.idx.release(); a.sync.release(); a.part.release(); }
+    c.sync_all.release();
+    for (auto& b : c.levelB) b.reset();
   }
-  {
-    size_t maxnodes = 1;
-    for (auto* L : h->levels) maxnodes = std::max(maxnodes, L->node_ids.size() * (size_t)std::max(L->R, 1));
-    h->cpass = std::max(CPASS, (h->maxR + 63) / 64 * 64);       // the core build handles a level's R columns in ONE pass
-    GH_CHECK(h->P.ensure((size_t)std::max(h->max_chunks, 1) * std::max(h->maxR, 1) * h->cpass * sizeof(double)));
-    GH_CHECK(h->Tsum.ensure(maxnodes * 2 * h->cpass * sizeof(double)));
-    GH_CHECK(h->Tout.ensure(maxnodes * 2 * h->cpass * sizeof(double)));
-    GH_CHECK(h->Y.ensure((size_t)n * h->cpass * sizeof(double)));
+  size_t maxnodes = 1;
+  for (auto* L : h->levels) maxnodes = std::max(maxnodes, L->node_ids.size() * (size_t)std::max(L->R, 1));
+  h->cpass = std::max(CPASS, (h->maxR + 63) / 64 * 64);       // the core build handles a level's R columns in ONE pass
+  GH_CHECK(h->P.ensure((size_t)std::max(h->max_chunks, 1) * std::max(h->maxR, 1) * h->cpass * sizeof(double)));
+  GH_CHECK(h->Tsum.ensure(maxnodes * 2 * h->cpass * sizeof(double)));
+  GH_CHECK(h->Tout.ensure(maxnodes * 2 * h->cpass * sizeof(double)));
+  GH_CHECK(h->Y.ensure((size_t)n * h->cpass * sizeof(double)));
+  return GH_OK;
+}
+
+// ---- factorisation sweep (hodlr.h:75-103, level-batched): leaves into every U, then levels bottom-up
+// Level l's core product is in Tout: U[:, 0:off) of the shallower levels -= U_l Tout.  Where the next shallower level with R > 0
+// can share that pass over U, it forms that level's chunk products as well (hodlr_updred_kernel) and *red_ready says so.
+static int update_shallower(HodlrCall& c, int l, bool* red_ready) {
+  gh_hodlr* const h = c.h;
+  const HLevel* L = h->levels[l];
+  const long Rtot = std::max(h->Rtot, 1);
+  const HLevel* nx = nullptr;
+  for (int q = l - 1; q >= 0 && !nx; --q) if (h->levels[q]->R > 0) nx = h->levels[q];
+  if (updred_possible(c.sw.passes, L, nx, L->off, h->cpass)) {
+    GH_CHECK(launch_updred(h, L, nx, h->UA.d() + L->off, Rtot, h->Tout.d(), h->cpass, h->UA.d(), Rtot, L->off,
+                           h->VA.d() + (long)c.n * nx->off, h->P.d(), h->cpass));
+    *red_ready = true;
+    return GH_OK;
   }
-
-  // ---- leaves (enqueued above, beside the ACA, when the levels run concurrently)
-  if (!leaves_done) GH_CHECK(leaf_stage(st));
-  mark("work arrays, leaf stage enqueued");
-
-  // ---- factorisation sweep (hodlr.h:75-103, level-batched): leaves into every U, then levels bottom-up
+  return launch_upd(h, (const MMJob*)L->d_upd_jobs.p, L->nchunks, L->R, h->UA.d() + L->off, Rtot, h->Tout.d(), h->cpass, h->UA.d(), Rtot, L->off);
+}
+static int factor_sweep(HodlrCall& c) {
+  gh_hodlr* const h = c.h;
+  const hipStream_t st = h->st;
+  const int64_t n = c.n;
+  const int nlev = c.nlev, l0 = c.l0;
+  const long Rtot = std::max(h->Rtot, 1);
   bool red_ready = false;                            // the chunk products of the next level to be processed are in P already
   if (h->Rtot > 0) {
     const HLevel* deepest = nullptr;
     for (int q = nlev - 1; q >= 0 && !deepest; --q) if (h->levels[q]->R > 0) deepest = h->levels[q];
     LeafSrc ls;
-    if (u_from_v) {
+    if (c.u_from_v) {
       ls.VA = h->VA.d(); ls.nlev = nlev;
       for (int q = 0; q < nlev; ++q) { ls.off[q] = h->levels[q]->off; ls.R[q] = h->levels[q]->R; ls.offv[q] = (long)n * h->levels[q]->off; }
     }
-    GH_CHECK(apply_leaves(h, h->UA.d(), Rtot, 0, h->Rtot, deepest, &red_ready, u_from_v ? &ls : nullptr));
+    GH_CHECK(apply_leaves(h, c.sw.passes, h->UA.d(), Rtot, 0, h->Rtot, deepest, &red_ready, c.u_from_v ? &ls : nullptr));
   }
-  std::vector<size_t> top_ld(l0, (size_t)-1);        // where in ld_all the core of pseudo-level l put its log|det|
   bool local_done = (l0 == 0);
   for (int l = nlev - 1; l >= 0; --l) {
     HLevel* L = h->levels[l];
     if (l < l0 && !local_done) {
       // everything below needs the other devices: tell the owner of the split that this one has finished on its own
-      mark("local sweep enqueued");
+      c.mark("local sweep enqueued");
       GH_HIP(hipStreamSynchronize(st));
-      mark("local sweep done");
+      c.mark("local sweep done");
       local_done = true;
       if (h->sub.local_done) GH_CHECK(h->sub.local_done(h->sub.ctx));
     }
     if (L->R == 0) continue;
     const int R = L->R, nn = (int)L->node_ids.size();
+    GhBuf* const tabs[3] = {&L->d_gj_offs, &L->d_gj_sizes, &L->d_gj_sc};
     if (L->top) {
       // The ancestor's core: V^T U over its own columns, each device the rows it holds, completed over the devices below
       // the ancestor; every one of them then inverts the same 2R x 2R matrix and updates its own rows of the shallower U's.
@@ -3609,13 +3650,10 @@ extern "C" int gh_hodlr_compute(gh_hodlr* h, gh_kernel* k, const double* x, int6
       hipLaunchKernelGGL(hodlr_sum_kernel, dim3(nn, 2 * R), dim3(64 * SUM_NS), 0, st, h->P.d(), (const int*)L->d_crange.p, R, (long)h->cpass, R, h->Tsum.d());
       GH_HIP(hipGetLastError());
       GH_CHECK(h->sub.allreduce(h->sub.ctx, l, h->Tsum.d(), 2 * R, R, (long)h->cpass, st));
-      const std::vector<long> offs1(1, 0L);
-      const std::vector<int> sizes1(1, 2 * R);
-      GhBuf* const tabs[3] = {&L->d_gj_offs, &L->d_gj_sizes, &L->d_gj_sc};
-      GH_CHECK(batched_inverse(h, L->sinv.d(), offs1, sizes1, h->ld_all.d() + ld_at, tabs, L->gj_R == R, h->Tsum.d(), R));
+      GH_CHECK(batched_inverse(h, st, L->sinv.d(), {0L}, {2 * R}, h->ld_all.d() + c.ld_at, tabs, L->gj_R == R, h->Tsum.d(), R));
       L->gj_R = R;
-      top_ld[l] = ld_at;
-      ld_at += 1;
+      c.top_ld[l] = c.ld_at;
+      c.ld_at += 1;
       GH_CHECK(apply_level(h, L, h->UA.d(), Rtot, 0, L->off, h->UA.d(), Rtot));
       continue;
     }
@@ -3626,38 +3664,27 @@ extern "C" int gh_hodlr_compute(gh_hodlr* h, gh_kernel* k, const double* x, int6
     const int Call = L->off + R;
     const bool merged = Call <= h->cpass;
     // (round 6) levels of many small nodes: sum + core inverse + core product in one launch (hodlr_core_kernel)
-    const bool core_fused = g_hodlr_core_fused && merged && L->off > 0 && nn >= 32 && 2 * R <= 32 && Call <= 128 &&
+    const bool core_fused = c.sw.core_fused && merged && L->off > 0 && nn >= 32 && 2 * R <= 32 && Call <= 128 &&
                             L->nchunks <= 128 * nn;      // (a workgroup adds up ITS node's chunk partials: few chunks per node)
-    if (core_fused) {
-      if (!red_ready)
-        GH_CHECK(launch_red(h, (const MMJob*)L->d_red_jobs.p, L->nchunks, R, h->VA.d() + (long)n * L->off,
-                            h->UA.d(), Rtot, 0, h->P.d(), h->cpass, 0, Call));
-      red_ready = false;
-#define GH_CORE_LAUNCH(NM) hipLaunchKernelGGL(hodlr_core_kernel<NM>, dim3(nn), dim3(256), 0, st, h->P.d(), (const int*)L->d_crange.p, R, (long)h->cpass, Call, \
-                                              L->off, L->off, L->sinv.d(), h->ld_all.d() + ld_at, (int*)h->flags.p, h->Tout.d())
-      if (2 * R <= 8) GH_CORE_LAUNCH(8); else if (2 * R <= 16) GH_CORE_LAUNCH(16); else GH_CORE_LAUNCH(32);
-#undef GH_CORE_LAUNCH
-      GH_HIP(hipGetLastError());
-      L->gj_R = -1;                                    // (the separate launch's tables were not refreshed)
-      ld_at += nn;
-      const HLevel* nx = nullptr;
-      for (int q = l - 1; q >= 0 && !nx; --q) if (h->levels[q]->R > 0) nx = h->levels[q];
-      if (updred_possible(L, nx, L->off, h->cpass)) {
-        GH_CHECK(launch_updred(h, L, nx, h->UA.d() + L->off, Rtot, h->Tout.d(), h->cpass, h->UA.d(), Rtot, L->off,
-                               h->VA.d() + (long)n * nx->off, h->P.d(), h->cpass));
-        red_ready = true;
-      } else {
-        GH_CHECK(launch_upd(h, (const MMJob*)L->d_upd_jobs.p, L->nchunks, R, h->UA.d() + L->off, Rtot,
-                            h->Tout.d(), h->cpass, h->UA.d(), Rtot, L->off));
-      }
-      continue;
-    }
     if (merged) {
       // (red_ready: the deeper level's update pass has already formed this level's chunk products -- hodlr_updred_kernel)
       if (!red_ready)
         GH_CHECK(launch_red(h, (const MMJob*)L->d_red_jobs.p, L->nchunks, R, h->VA.d() + (long)n * L->off,
                             h->UA.d(), Rtot, 0, h->P.d(), h->cpass, 0, Call));
       red_ready = false;
+    }
+    if (core_fused) {
+#define GH_CORE_LAUNCH(NM) hipLaunchKernelGGL(hodlr_core_kernel<NM>, dim3(nn), dim3(256), 0, st, h->P.d(), (const int*)L->d_crange.p, R, (long)h->cpass, Call, \
+                                            L->off, L->off, L->sinv.d(), h->ld_all.d() + c.ld_at, (int*)h->flags.p, h->Tout.d())
+      if (2 * R <= 8) GH_CORE_LAUNCH(8); else if (2 * R <= 16) GH_CORE_LAUNCH(16); else GH_CORE_LAUNCH(32);
+#undef GH_CORE_LAUNCH
+      GH_HIP(hipGetLastError());
+      L->gj_R = -1;                                    // (the separate launch's tables were not refreshed)
+      c.ld_at += nn;
+      GH_CHECK(update_shallower(c, l, &red_ready));
+      continue;
+    }
+    if (merged) {
       hipLaunchKernelGGL(hodlr_sum_kernel, dim3(nn, 2 * R), dim3(64 * SUM_NS), 0, st, h->P.d(), (const int*)L->d_crange.p, R, (long)h->cpass, Call, h->Tsum.d());
       GH_HIP(hipGetLastError());
     } else {
@@ -3668,29 +3695,16 @@ extern "C" int gh_hodlr_compute(gh_hodlr* h, gh_kernel* k, const double* x, int6
     }
     const double* const core_src = h->Tsum.d() + (merged ? L->off : 0);      // V_l^T U[:, own columns]: the core is built from it inside the inverse
     std::vector<long> offs(nn);
-    std::vector<int> sizes(nn, 2 * R);
     for (int q = 0; q < nn; ++q) offs[q] = (long)q * 4 * R * R;
-    {
-      GhBuf* const tabs[3] = {&L->d_gj_offs, &L->d_gj_sizes, &L->d_gj_sc};
-      GH_CHECK(batched_inverse(h, L->sinv.d(), offs, sizes, h->ld_all.d() + ld_at, tabs, L->gj_R == R, core_src, R));
-      L->gj_R = R;
-    }
-    ld_at += nn;
+    GH_CHECK(batched_inverse(h, st, L->sinv.d(), offs, std::vector<int>(nn, 2 * R), h->ld_all.d() + c.ld_at, tabs, L->gj_R == R, core_src, R));
+    L->gj_R = R;
+    c.ld_at += nn;
     // apply this level's inverse to the U's of all shallower levels: columns [0, off)
     if (merged && L->off > 0) {
       // (Tsum already holds V_l^T U[:, 0:off]: core product and update only)
-      GH_CHECK(launch_mm(h, (const MMJob*)L->d_smul_jobs.p, nn, 2 * R, L->sinv.d(), 2 * R, 1,
+      GH_CHECK(launch_mm(h, st, (const MMJob*)L->d_smul_jobs.p, nn, 2 * R, L->sinv.d(), 2 * R, 1,
                          h->Tsum.d(), h->cpass, 0, h->Tout.d(), h->cpass, 0, L->off, false));
-      const HLevel* nx = nullptr;
-      for (int q = l - 1; q >= 0 && !nx; --q) if (h->levels[q]->R > 0) nx = h->levels[q];
-      if (updred_possible(L, nx, L->off, h->cpass)) {
-        GH_CHECK(launch_updred(h, L, nx, h->UA.d() + L->off, Rtot, h->Tout.d(), h->cpass, h->UA.d(), Rtot, L->off,
-                               h->VA.d() + (long)n * nx->off, h->P.d(), h->cpass));
-        red_ready = true;
-      } else {
-        GH_CHECK(launch_upd(h, (const MMJob*)L->d_upd_jobs.p, L->nchunks, R, h->UA.d() + L->off, Rtot,
-                            h->Tout.d(), h->cpass, h->UA.d(), Rtot, L->off));
-      }
+      GH_CHECK(update_shallower(c, l, &red_ready));
     } else {
       GH_CHECK(apply_level(h, L, h->UA.d(), Rtot, 0, L->off, h->UA.d(), Rtot));
     }
@@ -3698,9 +3712,15 @@ extern "C" int gh_hodlr_compute(gh_hodlr* h, gh_kernel* k, const double* x, int6
   // (the level-major copy of the final U that the WIDE solves multiply from is made when one of them asks for it -- ensure_ul;
   //  the narrow solve of a log-likelihood reads the row-major U: 90 us of every C4 step for a copy nothing read)
   h->ul_valid = false;
-  // (into PINNED host memory: a copy to pageable memory is staged and waited for inside the call -- two of them were ~45 us
-  //  between the last kernel and the return)
-  const size_t nld = std::max<size_t>(n_blocks, 1);
+  c.mark("sweep enqueued");
+  return GH_OK;
+}
+
+// ---- every log|det| and the failure flags back in ONE copy, into PINNED host memory (a copy to pageable memory is staged
+// and waited for inside the call -- two of them were ~45 us between the last kernel and the return); the sum in a fixed order
+static int finish(HodlrCall& c, double* logdet_out) {
+  gh_hodlr* const h = c.h;
+  const size_t nld = std::max<size_t>(c.n_blocks, 1);
   if (h->pin_doubles < nld + 2) {
     if (h->pin) (void)hipHostFree(h->pin);
     h->pin = nullptr; h->pin_doubles = 0;
@@ -3709,9 +3729,9 @@ extern "C" int gh_hodlr_compute(gh_hodlr* h, gh_kernel* k, const double* x, int6
   }
   double* const ld_host = h->pin;
   int fl[4] = {0, 0, 0, 0};
-  GH_HIP(hipMemcpyAsync(ld_host, h->ld_all.p, nld * sizeof(double), hipMemcpyDeviceToHost, st));
-  GH_HIP(hipMemcpyAsync(ld_host + nld, h->flags.p, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
-  GH_HIP(hipStreamSynchronize(st));
+  GH_HIP(hipMemcpyAsync(ld_host, h->ld_all.p, nld * sizeof(double), hipMemcpyDeviceToHost, h->st));
+  GH_HIP(hipMemcpyAsync(ld_host + nld, h->flags.p, 4 * sizeof(int), hipMemcpyDeviceToHost, h->st));
+  GH_HIP(hipStreamSynchronize(h->st));
   memcpy(fl, ld_host + nld, 4 * sizeof(int));
   long long leaf_info = 0;
   memcpy(&leaf_info, fl + 2, sizeof(long long));
@@ -3719,13 +3739,33 @@ extern "C" int gh_hodlr_compute(gh_hodlr* h, gh_kernel* k, const double* x, int6
   if (fl[0] != 0) { gh_set_error("HODLR: singular block encountered (matrix %d of its batch)", fl[0] - 1); return GH_ERR_NOT_PD; }
   // (a sub-tree handle reports the blocks it owns alone; the ancestors' cores, the same on every device below them,
   //  are handed to the owner of the split separately)
-  h->sub.ld_top.assign(l0, 0.0);
-  for (int l = 0; l < l0; ++l) if (top_ld[l] != (size_t)-1) { h->sub.ld_top[l] = ld_host[top_ld[l]]; ld_host[top_ld[l]] = 0.0; }
+  h->sub.ld_top.assign(c.l0, 0.0);
+  for (int l = 0; l < c.l0; ++l) if (c.top_ld[l] != (size_t)-1) { h->sub.ld_top[l] = ld_host[c.top_ld[l]]; ld_host[c.top_ld[l]] = 0.0; }
   double logdet = 0.0;
-  for (size_t i = 0; i < ld_at; ++i) logdet += ld_host[i];          // leaves first, then the cores bottom-up: fixed order
+  for (size_t i = 0; i < c.ld_at; ++i) logdet += ld_host[i];        // leaves first, then the cores bottom-up: fixed order
   h->logdet = logdet;
   h->computed = true;
   if (logdet_out) *logdet_out = logdet;
+  return GH_OK;
+}
+
+extern "C" int gh_hodlr_compute(gh_hodlr* h, gh_kernel* k, const double* x, int64_t n, int32_t ndim,
+                                const double* yerr, double* logdet_out) {
+  if (!h || !k || !x || !yerr || n <= 0) { gh_set_error("bad argument to compute"); return GH_ERR_BAD_ARG; }
+  if (ndim != k->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
+  if (n > 0x3fffffffL) { gh_set_error("HODLR: n too large"); return GH_ERR_BAD_ARG; }
+  HodlrCall c(h, k, n, ndim);
+  GH_CHECK(load_inputs(c, x, yerr));
+  GH_CHECK(build_tree(c));
+  GH_CHECK(plan_aca(c));
+  GH_CHECK(c.concurrent ? run_aca_concurrent(c) : run_aca_serial(c));
+  GH_CHECK(assemble_factors(c));
+  // ---- leaves (enqueued beside the ACA when the levels run concurrently)
+  if (!c.leaves_done) GH_CHECK(leaf_stage(c, h->st));
+  c.mark("work arrays, leaf stage enqueued");
+  GH_CHECK(factor_sweep(c));
+  GH_CHECK(finish(c, logdet_out));
+  c.ok = true;                                     // (finish() has synchronised h->st, which waits for every side stream)
   return GH_OK;
 }
 
@@ -3742,7 +3782,7 @@ extern "C" int gh_hodlr_solve(gh_hodlr* h, const double* b, int64_t nrhs, double
   const size_t tot = (size_t)h->n * nrhs;
   GH_CHECK(h->rhs.ensure(tot * sizeof(double)));
   GH_CHECK(gh_to_device(h->rhs.d(), b, tot, h->st));
-  GH_CHECK(solve_all(h, h->rhs.d(), nrhs, (int)nrhs));
+  GH_CHECK(solve_all(h, g_hodlr_passes, h->rhs.d(), nrhs, (int)nrhs));
   return gh_from_device(out, h->rhs.d(), tot, h->st);
 }
 extern "C" int gh_hodlr_dot_solve(gh_hodlr* h, const double* y, double* out) {
@@ -3753,7 +3793,7 @@ extern "C" int gh_hodlr_dot_solve(gh_hodlr* h, const double* y, double* out) {
   GH_CHECK(gh_to_device(h->rhs.d(), y, (size_t)h->n, h->st));
   const double* yd = y;                              // (a device-resident y is read where it is)
   if (!gh_is_device_ptr(y)) { GH_CHECK(gh_to_device(h->work.d(), y, (size_t)h->n, h->st)); yd = h->work.d(); }
-  GH_CHECK(solve_all(h, h->rhs.d(), 1, 1));
+  GH_CHECK(solve_all(h, g_hodlr_passes, h->rhs.d(), 1, 1));
   GH_CHECK(h->dotp.ensure(256 * sizeof(double)));
   hipLaunchKernelGGL(hodlr_dot_kernel, dim3(256), dim3(256), 0, h->st, yd, h->rhs.d(), (long)h->n, h->dotp.d());
   hipLaunchKernelGGL(hodlr_dot_kernel, dim3(1), dim3(256), 0, h->st, h->dotp.d(), (const double*)nullptr, 256L, h->scal.d());
@@ -3772,7 +3812,7 @@ extern "C" int gh_hodlr_get_inverse(gh_hodlr* h, double* out) {
   GH_HIP(hipMemsetAsync(h->rhs.p, 0, (size_t)n * n * sizeof(double), h->st));
   hipLaunchKernelGGL(hodlr_eye_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, h->rhs.d(), n);
   GH_HIP(hipGetLastError());
-  GH_CHECK(solve_all(h, h->rhs.d(), n, (int)n));
+  GH_CHECK(solve_all(h, g_hodlr_passes, h->rhs.d(), n, (int)n));
   return gh_from_device(out, h->rhs.d(), (size_t)n * n, h->st);
 }
 extern "C" int gh_hodlr_ranks(const gh_hodlr* h, int32_t* ranks_out, int32_t max_out, int32_t* n_out) {

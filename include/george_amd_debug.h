@@ -34,6 +34,9 @@ int gh_debug_set_build_on_chain(int on);
  * trailing matrix behind them has more than 25 600 columns and 1024 after; 0: 1024 throughout; n > 1: the bound is n columns.
  * Returns the previous setting.  Same bits whatever the widths (the update adds the same k in the same order). */
 int gh_debug_set_adaptive_panels(int on);
+/* The gh_debug_set_hodlr_* switches below take effect at the next gh_hodlr_compute(): every compute() reads all of them once, at
+ * its start, and a compute() running on another thread keeps the settings it started with.  (The passes mask is read the same way
+ * by every solve.) */
 /* HODLR passes that serve two levels at once (round 5): bit 0 = the narrow solve (update of level l + chunk products of the
  * next level in one pass over the rows, "sum + core product" in one launch, symmetric leaf product), bit 1 = the factorisation
  * sweep's update of level l + reduce of the next level in one pass over U; -1: the default (both); returns the previous mask.
