@@ -1,0 +1,307 @@
+// gh_batch.hip -- B log-likelihoods of one kernel STRUCTURE at B parameter vectors in one device call
+// (gh_chol_objective_batch: GP.log_likelihood_batch, the hook for emcee's `vectorize=True`).
+//
+// At the sizes samplers run (N of a few hundred to a few thousand) one factorisation fills a few percent of the chip: it is a
+// serial chain of 128-column steps, and a sampler step used to run B such chains one after the other.  Here every launch of
+// ONE chain carries all B members: the launch count is that of one problem and each launch does B times the work.
+//
+// Bordered storage.  Member b owns an (np + 128) x (np + 128) row-major block, np = N rounded up to 128.  The top-left
+// np x np holds K_b with identity padding (as the one-problem build pads), row np holds r_b^T (zero-padded), the rest of the
+// border tile row is zero.  The right-looking factorisation over the first np / 128 tile columns then leaves
+// z_b = L_b^-1 r_b in border row np and -r_b^T K_b^-1 r_b at [np][np]: there is no separate triangular solve.  Per step j,
+// three launches over all members:
+//   potf2 : tile (j, j) -> L_jj and L_jj^-1 (gh_potf2::potf2_body; info per member);
+//   TRSM  : tiles (i, j), i > j, border tile included:  P <- P L_jj^-T      (gh_tile128_nt_sp<false>);
+//   SYRK  : lower tiles (i, l), j < l <= i, border row included:  C -= P_i P_l^T, K = 128   (gh_tile128_nt_sp<true>).
+// A member whose info is set returns from every later kernel at once.
+//
+// Bits.  The one-problem factorisation (gh_chol.hip) applies the same updates to every tile in the same k order, only in
+// longer K (panel widths, rows-below TRSM): every k-major x k-major kernel shares one k assignment (gh_gemm_tile.h) and a
+// tile's accumulators start from -C and are written back as -acc, both exact, so cutting K at 128 changes no bits.  The
+// elements are formed by the same evaluator calls in the same argument order as kmat_generic_tile, and the log-determinant
+// is summed in launch_logdet's slice order: L_b and logdet[b] equal gh_chol_compute's bit for bit.  quad[b] is summed tile by
+// tile instead of by the chained forward solve and matches to rounding.
+#include <math.h>
+#include <string.h>
+#include <algorithm>
+#include <vector>
+#include "gh_common.h"
+#include "gh_gemm_tile.h"
+#include "gh_potf2_body.h"
+
+#define T 128
+
+struct GhBatchBufs {
+  GhBuf A;                     // B bordered blocks
+  GhBuf dinv;                  // B x (np / 128) inverses of the 128 x 128 diagonal blocks
+  GhBuf in;                    // [member nodes | member fast forms | x | yerr | r] (the last three when they come from the host)
+  GhBuf out;                   // [logdet (B) | quad (B) | info (B)]
+  std::vector<char> stage;     // host image of `in`: ONE host-to-device copy per call
+  std::vector<double> back;    // host image of `out`: ONE device-to-host copy per call
+};
+GhBatchBufs* gh_batch_new() { return new GhBatchBufs(); }
+size_t gh_batch_bytes(const GhBatchBufs* b) {
+  if (!b) return 0;
+  size_t tot = 0;
+  for (const GhBuf* x : {&b->A, &b->dinv, &b->in, &b->out}) tot += x->p ? x->bytes : 0;
+  return tot;
+}
+void gh_batch_free(GhBatchBufs* b) { delete b; }
+
+// lower-triangular enumeration t -> (ti, tj), tj <= ti (as gh_kmat.hip's tri_index)
+__device__ __forceinline__ void batch_tri_index(long t, int& ti, int& tj) {
+  long i = (long)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+  while (i * (i + 1) / 2 > t) --i;
+  while ((i + 1) * (i + 2) / 2 <= t) ++i;
+  ti = (int)i;
+  tj = (int)(t - i * (i + 1) / 2);
+}
+// wave-uniform: has member b failed at an earlier step?
+__device__ __forceinline__ bool member_failed(const long long* info, int b) {
+  return __builtin_amdgcn_readfirstlane((int)(info[b] != 0)) != 0;
+}
+
+// ---------------------------------------------------------------------------------------------------- build
+struct BatchBuild {
+  const GhNode* nodes; int n_nodes; int ndim;    // member b's program: nodes + b * n_nodes
+  const GhFast* fast;                            // (B) when every member has the a + b F(r^2) form
+  const double* x; long n;                       // (n, ndim), shared
+  const double* yerr; const double* r;           // (B, n)
+  double* A; long ld, np, stride;                // member b's block: A + b * stride, row pitch ld = np + 128
+  long long* info;                               // (B): cleared here
+  long tiles;                                    // 128-tiles per member: the lower triangle of the (np / 128 + 1)^2 tile grid
+};
+// blockIdx.x = member * 4 * tiles + 4 * tile + quadrant: one 64 x 64 quarter of a lower 128-tile, as kmat_tile_of builds them
+template <bool FAST>
+__global__ __launch_bounds__(256) void batch_build_kernel(BatchBuild a) {
+  const long q4 = (long)blockIdx.x;
+  const int b = (int)(q4 / (4 * a.tiles));
+  const long t = (q4 / 4) % a.tiles;
+  const int quad = (int)(q4 & 3);
+  int TI, TJ;
+  batch_tri_index(t, TI, TJ);
+  if (t == 0 && quad == 0 && threadIdx.x == 0) a.info[b] = 0;
+  const long r0 = (long)TI * T + (quad >> 1) * 64, c0 = (long)TJ * T + (quad & 1) * 64;
+  const GhNode* prog = a.nodes + (long)b * a.n_nodes;
+  const double* yerr = a.yerr + (long)b * a.n;
+  const double* res = a.r + (long)b * a.n;
+  double* Ab = a.A + (long)b * a.stride;
+  const int nd = a.ndim;
+  const int lc = (threadIdx.x & 31) * 2, lr = threadIdx.x >> 5;
+  for (int pass = 0; pass < 8; ++pass) {
+    const long r = r0 + lr + pass * 8, c = c0 + lc;
+    double v[2];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const long cc = c + e;
+      double val;
+      if (r < a.n && cc < a.n) {
+        const double* p1 = a.x + r * nd;
+        const double* p2 = a.x + cc * nd;
+        // k(x_min, x_max), the argument order of kmat_generic_tile's symmetric build
+        const bool swap = r > cc;
+        val = FAST ? gh_fast_value(a.fast[b], swap ? p2 : p1, swap ? p1 : p2)
+                   : gh_eval_value(prog, a.n_nodes, swap ? p2 : p1, swap ? p1 : p2);
+        if (r == cc) { const double e2 = yerr[r]; val += e2 * e2; }
+      } else if (r < a.np) {
+        val = (r == cc) ? 1.0 : 0.0;             // identity padding
+      } else if (r == a.np) {
+        val = cc < a.n ? res[cc] : 0.0;          // the border row: r_b^T
+      } else {
+        val = 0.0;
+      }
+      v[e] = val;
+    }
+    *reinterpret_cast<double2*>(Ab + r * a.ld + c) = make_double2(v[0], v[1]);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------- step j
+// potf2 of every member's diagonal tile j (the 75-KB LDS body of potf2_inv_mfma_kernel: two workgroups per CU)
+__global__ __launch_bounds__(256, 2) void batch_potf2_kernel(double* A, long ld, long stride, double* dinv, long dstride,
+                                                             long long* info, int j) {
+  const int b = blockIdx.x;
+  if (member_failed(info, b)) return;
+  __shared__ double s[GH_POTF2_S_DOUBLES];
+  __shared__ double dscr[GH_POTF2_D_DOUBLES];
+  __shared__ int fail_at;
+  const long j0 = (long)j * T;
+  (void)gh_potf2::potf2_body(A + (long)b * stride + j0 * ld + j0, ld, dinv + (long)b * dstride + (long)j * T * T, info + b,
+                             (long long)j0, s, dscr, &fail_at);
+}
+// tile (j + 1 + t, j) <- tile L_jj^-T for t < m (m - 1 tiles below the diagonal and the border tile); blockIdx.x = member * m + t
+__global__ __launch_bounds__(256, 2) void batch_trsm_kernel(double* A, long ld, long stride, const double* dinv, long dstride,
+                                                            const long long* info, int j, int m) {
+  const int b = blockIdx.x / m;
+  const long i = j + 1 + (long)(blockIdx.x % m);
+  if (member_failed(info, b)) return;
+  __shared__ __attribute__((aligned(1024))) double sm[4 * BM * BK];
+  double* P = A + (long)b * stride + i * T * ld + (long)j * T;
+  gh_tile128_nt_sp<false>(sm, P, ld, P, ld, dinv + (long)b * dstride + (long)j * T * T, T, T);
+}
+// tile (i, l) -= P_i P_l^T, j < l <= i (border row included), K = 128; blockIdx.x = member * m (m + 1) / 2 + pair
+__global__ __launch_bounds__(256, 2) void batch_syrk_kernel(double* A, long ld, long stride, const long long* info, int j, long pairs) {
+  const int b = (int)(blockIdx.x / pairs);
+  if (member_failed(info, b)) return;
+  __shared__ __attribute__((aligned(1024))) double sm[4 * BM * BK];
+  int ti, tl;
+  batch_tri_index((long)(blockIdx.x % pairs), ti, tl);
+  const long i = j + 1 + ti, l = j + 1 + tl;
+  double* Ab = A + (long)b * stride;
+  gh_tile128_nt_sp<true>(sm, Ab + i * T * ld + l * T, ld, Ab + i * T * ld + (long)j * T, ld, Ab + l * T * ld + (long)j * T, ld, T);
+}
+
+// ---------------------------------------------------------------------------------------------------- reductions
+// (wave_sum / block_sum_256 of gh_chol.hip, the same operations in the same order)
+__device__ __forceinline__ double batch_wave_sum(double v) {
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;
+}
+__device__ __forceinline__ double batch_block_sum_256(double v, double* sh) {
+  v = batch_wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+// logdet[b] = 2 sum_i log L_b[i][i] over the np diagonal entries in launch_logdet's order (gh_chol.hip: g contiguous slices,
+// each summed by 256 lanes and a block reduction, the slices added in index order); quad[b] = -A_b[np][np].  Failed members: NaN.
+__global__ __launch_bounds__(256) void batch_reduce_kernel(const double* A, long ld, long stride, long np, const long long* info,
+                                                           double* logdet, double* quad) {
+  __shared__ double sh[4];
+  const int b = blockIdx.x;
+  const double* Ab = A + (long)b * stride;
+  if (member_failed(info, b)) {
+    if (threadIdx.x == 0) logdet[b] = quad[b] = __longlong_as_double(0x7FF8000000000000LL);
+    return;
+  }
+  const long g = (np + 2047) / 2048 < 64 ? (np + 2047) / 2048 : 64;
+  double tot = 0.0;
+  if (g <= 1) {
+    double v = 0.0;
+    for (long i = threadIdx.x; i < np; i += 256) v += log(Ab[i * ld + i]);
+    tot = batch_block_sum_256(v, sh);
+  } else {
+    const long per = (np + g - 1) / g;
+    for (long s = 0; s < g; ++s) {
+      const long lo = s * per, hi = lo + per < np ? lo + per : np;
+      double v = 0.0;
+      for (long i = lo + threadIdx.x; i < hi; i += 256) v += log(Ab[i * ld + i]);
+      tot += batch_block_sum_256(v, sh);
+    }
+  }
+  if (threadIdx.x == 0) {
+    logdet[b] = 2.0 * tot;
+    quad[b] = -Ab[np * ld + np];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------- host
+static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+extern "C" int gh_chol_objective_batch(gh_chol* s, gh_kernel* k, const double* params, int32_t nbatch,
+                                       const double* x, int64_t n, int32_t ndim, const double* yerr, const double* r,
+                                       double* logdet, double* quad, int64_t* info) {
+  if (!s || !k || nbatch < 0 || n <= 0 || !x || !yerr || !r || !logdet || !quad || !info || (k->size > 0 && !params)) {
+    gh_set_error("bad argument to objective_batch");
+    return GH_ERR_BAD_ARG;
+  }
+  if (ndim != k->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
+  if (nbatch == 0) return GH_OK;
+  hipStream_t st = nullptr;
+  GhBatchBufs* bb = nullptr;
+  GH_CHECK(gh_chol_batch_begin(s, &st, &bb));
+  const long B = nbatch, np = gh_round_up(n, T), nt = np / T, ld = np + T;
+  const long stride = ld * ld, dstride = nt * T * T;
+  const long tiles = (nt + 1) * (nt + 2) / 2;
+  if (B * tiles * 4 > 0x7fffffffL) { gh_set_error("objective_batch: batch too large for one call"); return GH_ERR_BAD_ARG; }
+  const int nn = (int)k->nodes.size();
+
+  // ---- member programs: k's structure with each row's parameters (gh_node_set_params: the bits of gh_kernel_create)
+  std::vector<double> prow;
+  const double* P = params;
+  if (k->size > 0 && gh_is_device_ptr(params)) {
+    prow.resize((size_t)B * k->size);
+    GH_HIP(hipMemcpy(prow.data(), params, prow.size() * sizeof(double), hipMemcpyDeviceToHost));
+    P = prow.data();
+  }
+  const bool x_dev = gh_is_device_ptr(x), e_dev = gh_is_device_ptr(yerr), r_dev = gh_is_device_ptr(r);
+  const size_t o_nodes = 0, o_fast = align256((size_t)B * nn * sizeof(GhNode));
+  const size_t o_x = o_fast + align256((size_t)B * sizeof(GhFast));
+  const size_t o_e = o_x + (x_dev ? 0 : align256((size_t)n * ndim * sizeof(double)));
+  const size_t o_r = o_e + (e_dev ? 0 : align256((size_t)B * n * sizeof(double)));
+  const size_t in_bytes = o_r + (r_dev ? 0 : align256((size_t)B * n * sizeof(double)));
+  bb->stage.resize(in_bytes);
+  char* h = bb->stage.data();
+  GhNode* hn = (GhNode*)(h + o_nodes);
+  GhFast* hf = (GhFast*)(h + o_fast);
+  bool fast = true;
+  for (long b = 0; b < B; ++b) {
+    GhNode* nodes = hn + b * nn;
+    memcpy(nodes, k->nodes.data(), (size_t)nn * sizeof(GhNode));
+    const double* row = P + b * k->size;
+    for (int i = 0; i < nn; ++i)
+      if (nodes[i].op == GH_OP_LEAF) gh_node_set_params(nodes[i], row + nodes[i].poff, row + nodes[i].poff + nodes[i].npar);
+    gh_fast_form(nodes, nn, hf + b);
+    fast = fast && hf[b].ok;                     // (structural: the same for every member)
+  }
+  if (!x_dev) memcpy(h + o_x, x, (size_t)n * ndim * sizeof(double));
+  if (!e_dev) memcpy(h + o_e, yerr, (size_t)B * n * sizeof(double));
+  if (!r_dev) memcpy(h + o_r, r, (size_t)B * n * sizeof(double));
+
+  // ---- buffers (grown once, re-used by every later call of the same or a smaller size)
+  GH_CHECK(bb->in.ensure(in_bytes));
+  GH_CHECK(bb->A.ensure((size_t)B * stride * sizeof(double)));
+  GH_CHECK(bb->dinv.ensure((size_t)B * dstride * sizeof(double)));
+  GH_CHECK(bb->out.ensure((size_t)3 * B * sizeof(double)));
+  char* d = (char*)bb->in.p;
+  GH_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, st));
+  double* A = bb->A.d();
+  double* dinv = bb->dinv.d();
+  double* d_logdet = bb->out.d();
+  double* d_quad = d_logdet + B;
+  long long* d_info = (long long*)(d_logdet + 2 * B);
+
+  // ---- build
+  BatchBuild a;
+  a.nodes = (const GhNode*)(d + o_nodes); a.n_nodes = nn; a.ndim = ndim;
+  a.fast = fast ? (const GhFast*)(d + o_fast) : nullptr;
+  a.x = x_dev ? x : (const double*)(d + o_x); a.n = n;
+  a.yerr = e_dev ? yerr : (const double*)(d + o_e);
+  a.r = r_dev ? r : (const double*)(d + o_r);
+  a.A = A; a.ld = ld; a.np = np; a.stride = stride; a.info = d_info; a.tiles = tiles;
+  const dim3 gb((unsigned)(B * tiles * 4)), blk(256);
+  if (fast) hipLaunchKernelGGL(batch_build_kernel<true>, gb, blk, 0, st, a);
+  else      hipLaunchKernelGGL(batch_build_kernel<false>, gb, blk, 0, st, a);
+  GH_HIP(hipGetLastError());
+
+  // ---- factorisation: three launches per 128-column step, each over every member
+  for (long j = 0; j < nt; ++j) {
+    hipLaunchKernelGGL(batch_potf2_kernel, dim3((unsigned)B), blk, 0, st, A, ld, stride, dinv, dstride, d_info, (int)j);
+    const long m = nt - j;                       // tiles j + 1 .. nt (the border tile is tile nt)
+    hipLaunchKernelGGL(batch_trsm_kernel, dim3((unsigned)(B * m)), blk, 0, st, A, ld, stride, (const double*)dinv, dstride,
+                       (const long long*)d_info, (int)j, (int)m);
+    const long pairs = m * (m + 1) / 2;
+    hipLaunchKernelGGL(batch_syrk_kernel, dim3((unsigned)(B * pairs)), blk, 0, st, A, ld, stride, (const long long*)d_info,
+                       (int)j, pairs);
+    GH_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(batch_reduce_kernel, dim3((unsigned)B), blk, 0, st, (const double*)A, ld, stride, np,
+                     (const long long*)d_info, d_logdet, d_quad);
+  GH_HIP(hipGetLastError());
+
+  // ---- results: one copy back, one synchronisation
+  bb->back.resize((size_t)3 * B);
+  GH_HIP(hipMemcpyAsync(bb->back.data(), d_logdet, (size_t)3 * B * sizeof(double), hipMemcpyDeviceToHost, st));
+  GH_HIP(hipStreamSynchronize(st));
+  const double* hb = bb->back.data();
+  auto put = [](void* dst, const void* src, size_t bytes) -> int {
+    if (gh_is_device_ptr(dst)) GH_HIP(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
+    else memcpy(dst, src, bytes);
+    return GH_OK;
+  };
+  GH_CHECK(put(logdet, hb, (size_t)B * sizeof(double)));
+  GH_CHECK(put(quad, hb + B, (size_t)B * sizeof(double)));
+  GH_CHECK(put(info, hb + 2 * B, (size_t)B * sizeof(int64_t)));
+  return GH_OK;
+}

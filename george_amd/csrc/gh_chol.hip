@@ -552,6 +552,7 @@ struct gh_chol {
   GhBuf A, dinv, x, yerr, v0, v1, v2, scal, rhs, work, work2, scratch, chain;
   long long* d_info = nullptr;           // = (long long*)(scal + 2): the failure word lives beside the scalars (set in compute_enqueue)
   bool build_on_chain = false;           // this compute(): inputs + kernel-matrix build were enqueued on the chain stream (st2)
+  GhBatchBufs* batch = nullptr;          // gh_chol_objective_batch's buffers (gh_batch.hip), grown once and re-used
   gh_chol_profile prof;
   std::vector<EvPair> ev_pool;
   size_t ev_used = 0;
@@ -582,6 +583,7 @@ struct gh_chol {
 
     if (st2 && !shared_streams) (void)hipStreamDestroy(st2);
     if (st && !shared_streams) (void)hipStreamDestroy(st);
+    gh_batch_free(batch);
   }
 };
 
@@ -791,7 +793,16 @@ extern "C" int64_t gh_chol_device_bytes(const gh_chol* s) {
   size_t tot = 0;
   for (const GhBuf* b : {&s->A, &s->dinv, &s->x, &s->yerr, &s->v0, &s->v1, &s->v2, &s->scal, &s->rhs, &s->work, &s->work2,
                          &s->scratch, &s->chain}) tot += b->p ? b->bytes : 0;
-  return (int64_t)tot;
+  return (int64_t)(tot + gh_batch_bytes(s->batch));
+}
+int gh_chol_batch_begin(gh_chol* s, hipStream_t* st, GhBatchBufs** bufs) {
+  GH_CHECK(set_device(s));
+  s->computed = false;
+  s->info = 0;
+  if (!s->batch) s->batch = gh_batch_new();
+  *st = s->st;
+  *bufs = s->batch;
+  return GH_OK;
 }
 extern "C" int gh_chol_get_update_intervals(const gh_chol* s, double* out, int32_t max_launches, int32_t* n_out) {
   if (!s || !n_out || (max_launches > 0 && !out)) { gh_set_error("null argument"); return GH_ERR_BAD_ARG; }
@@ -1787,6 +1798,8 @@ extern "C" void gh_chol_release_buffers(gh_chol* s) {
   if (s->st) (void)hipStreamSynchronize(s->st);
   s->computed = false;
   for (GhBuf* b : {&s->A, &s->dinv, &s->x, &s->yerr, &s->v0, &s->v1, &s->v2, &s->rhs, &s->work, &s->work2, &s->scratch, &s->chain}) b->release();
+  gh_batch_free(s->batch);
+  s->batch = nullptr;
 }
 extern "C" void gh_chol_trim(gh_chol* s) {
   // frees the transient N x N / N x M work buffers of predict / grad / get_inverse, keeps the factor
@@ -1794,4 +1807,6 @@ extern "C" void gh_chol_trim(gh_chol* s) {
   (void)hipSetDevice(s->opts.device);
   if (s->st) (void)hipStreamSynchronize(s->st);
   for (GhBuf* b : {&s->rhs, &s->work, &s->work2, &s->scratch}) b->release();
+  gh_batch_free(s->batch);
+  s->batch = nullptr;
 }

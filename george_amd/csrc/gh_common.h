@@ -97,6 +97,19 @@ struct gh_kernel {
   int upload();                // ensure d_nodes valid on the current device
 };
 
+// raw parameters -> a leaf node's p / m / q (gh_kmat.hip; d.ktype, npar, mtype, nmet set), and the a + b F(r^2) form of a
+// program (f->ok == 0 when it has none, or when GEORGE_AMD_NO_FAST_KERNEL is set)
+void gh_node_set_params(GhNode& d, const double* params, const double* metric);
+void gh_fast_form(const GhNode* nodes, int n_nodes, GhFast* f);
+
+// the buffers of gh_chol_objective_batch (gh_batch.hip), owned by a gh_chol handle
+struct GhBatchBufs;
+GhBatchBufs* gh_batch_new();
+size_t gh_batch_bytes(const GhBatchBufs* b);
+void gh_batch_free(GhBatchBufs* b);
+// gh_batch.hip's view of a handle: sets its device, marks it not computed, returns its main stream and its batch buffers
+int gh_chol_batch_begin(gh_chol* s, hipStream_t* st, GhBatchBufs** bufs);
+
 // ----------------------------------------------------------------- launchers
 // (all device pointers; sizes need not be tile multiples unless noted)
 // out[r*ldo + c] = k(x1[r], x2[c]) for r < n1, c < n2; rows/cols up to (rows_p, cols_p) are

@@ -200,13 +200,14 @@ static bool is_stationary(int kt) {
 
 // Reduce the postfix program to  a + b * F(r2)  with one unblocked stationary leaf F over an
 // isotropic / axis-aligned metric, if it has that shape (constants fold: Constant = naxes * c).
-static void detect_fast_form(gh_kernel* k) {
-  memset(&k->fast, 0, sizeof(k->fast));
+// (also the batched objective's, gh_batch.hip: one call per member on that member's nodes)
+void gh_fast_form(const GhNode* nodes, int n_nodes, GhFast* out) {
+  memset(out, 0, sizeof(*out));
   if (getenv("GEORGE_AMD_NO_FAST_KERNEL")) return;
   struct Aff { bool ok; double a, b; int leaf; };
   std::vector<Aff> st;
-  for (size_t i = 0; i < k->nodes.size(); ++i) {
-    const GhNode& nd = k->nodes[i];
+  for (int i = 0; i < n_nodes; ++i) {
+    const GhNode& nd = nodes[i];
     if (nd.op == GH_OP_LEAF) {
       if (nd.ktype == GH_K_CONSTANT) st.push_back({true, nd.naxes * nd.q[0], 0.0, -1});
       else if (nd.mtype >= 0 && nd.mtype <= 1 && !nd.blocked) st.push_back({true, 0.0, 1.0, (int)i});
@@ -231,14 +232,39 @@ static void detect_fast_form(gh_kernel* k) {
   // only the shapes whose rounding the interpreter reproduces exactly: a single scaling and/or
   // a single offset (two leaves of the same kernel summed would fold b = b1 + b2 differently)
   int nstat = 0;
-  for (const GhNode& nd : k->nodes) if (nd.op == GH_OP_LEAF && nd.mtype >= 0) ++nstat;
+  for (int i = 0; i < n_nodes; ++i) if (nodes[i].op == GH_OP_LEAF && nodes[i].mtype >= 0) ++nstat;
   if (nstat != 1) return;
-  const GhNode& lf = k->nodes[st[0].leaf];
-  GhFast& f = k->fast;
+  const GhNode& lf = nodes[st[0].leaf];
+  GhFast& f = *out;
   f.ktype = lf.ktype; f.mtype = lf.mtype; f.naxes = lf.naxes;
   for (int i = 0; i < lf.naxes; ++i) { f.axes[i] = lf.axes[i]; f.m[i] = lf.m[lf.mtype == 0 ? 0 : i]; }
   f.a = st[0].a; f.b = st[0].b; f.q0 = lf.q[0];
   f.ok = 1;
+}
+
+// Raw parameters -> the leaf's device fields: p, the metric m (after its exp(-v) transform) and the reparameterisations q.
+// d.ktype, d.npar, d.mtype and d.nmet must be set.  (gh_kernel_create, and gh_batch.hip for every member of a batch: a member's
+// nodes are bit for bit those of a kernel created with the same vector.)
+void gh_node_set_params(GhNode& d, const double* params, const double* metric) {
+  for (int p = 0; p < d.npar; ++p) d.p[p] = params[p];
+  if (d.mtype == 2) {
+    // GeneralMetric::set_parameter, metrics.h:171-181: diagonal slots (0,2,5,9,..) hold exp(-v)
+    for (int j = 0; j < d.nmet; ++j) d.m[j] = metric[j];
+    for (int j = 0, step = 2; j < d.nmet; j += step, ++step) d.m[j] = exp(-metric[j]);
+  } else if (d.mtype >= 0) {
+    for (int j = 0; j < d.nmet; ++j) d.m[j] = exp(-metric[j]);     // metrics.h:46-49
+  }
+  // reparameterisations (kernels/*.yml `reparams`)
+  switch (d.ktype) {
+    case GH_K_RATQUAD:    d.q[0] = exp(d.p[0]); break;                 // alpha
+    case GH_K_CONSTANT:   d.q[0] = exp(d.p[0]); break;                 // constant
+    case GH_K_COSINE:     d.q[0] = 2 * M_PI * exp(-d.p[0]); break;     // factor
+    case GH_K_EXPSINE2:   d.q[0] = M_PI * exp(-d.p[1]); break;         // factor
+    case GH_K_LOCALGAUSS: d.q[0] = 0.5 * exp(-d.p[1]); break;          // inv_2w
+    case GH_K_LINEAR:     d.q[0] = exp(-d.p[0]); break;                // inv_gamma2
+    case GH_K_POLYNOMIAL: d.q[0] = exp(d.p[0]); break;                 // sigma2
+    default: break;
+  }
 }
 
 extern "C" int gh_kernel_create(const gh_knode* in, int n_nodes, gh_kernel** out) {
@@ -268,36 +294,18 @@ extern "C" int gh_kernel_create(const gh_knode* in, int n_nodes, gh_kernel** out
         if (s.axes[a] < 0 || s.axes[a] >= s.ndim) { delete k; gh_set_error("invalid axis"); return GH_ERR_BAD_ARG; }
         d.axes[a] = s.axes[a];
       }
-      for (int p = 0; p < d.npar; ++p) d.p[p] = s.params[p];
       d.cst = s.constant;
       if (is_stationary(kt)) {
         d.mtype = s.metric_type;
         int want = d.mtype == 0 ? 1 : d.mtype == 1 ? s.naxes : d.mtype == 2 ? s.naxes * (s.naxes + 1) / 2 : -1;
         if (want < 0 || s.n_metric != want) { delete k; gh_set_error("unrecognized metric"); return GH_ERR_BAD_ARG; }
         d.nmet = want;
-        if (d.mtype == 2) {
-          // GeneralMetric::set_parameter, metrics.h:171-181: diagonal slots (0,2,5,9,..) hold exp(-v)
-          for (int j = 0; j < want; ++j) d.m[j] = s.metric[j];
-          for (int j = 0, step = 2; j < want; j += step, ++step) d.m[j] = exp(-s.metric[j]);
-        } else {
-          for (int j = 0; j < want; ++j) d.m[j] = exp(-s.metric[j]);     // metrics.h:46-49
-        }
         d.blocked = s.blocked ? 1 : 0;
         for (int a = 0; a < s.naxes; ++a) { d.lo[a] = s.min_block[a]; d.hi[a] = s.max_block[a]; }
       } else {
         d.mtype = -1;
       }
-      // reparameterisations (kernels/*.yml `reparams`)
-      switch (kt) {
-        case GH_K_RATQUAD:    d.q[0] = exp(d.p[0]); break;                 // alpha
-        case GH_K_CONSTANT:   d.q[0] = exp(d.p[0]); break;                 // constant
-        case GH_K_COSINE:     d.q[0] = 2 * M_PI * exp(-d.p[0]); break;     // factor
-        case GH_K_EXPSINE2:   d.q[0] = M_PI * exp(-d.p[1]); break;         // factor
-        case GH_K_LOCALGAUSS: d.q[0] = 0.5 * exp(-d.p[1]); break;          // inv_2w
-        case GH_K_LINEAR:     d.q[0] = exp(-d.p[0]); break;                // inv_gamma2
-        case GH_K_POLYNOMIAL: d.q[0] = exp(d.p[0]); break;                 // sigma2
-        default: break;
-      }
+      gh_node_set_params(d, s.params, s.metric);
       d.poff = poff; d.psize = d.npar + d.nmet; d.psize1 = 0;
       poff += d.psize;
       st.push_back({d.poff, d.psize, d.ndim});
@@ -317,7 +325,7 @@ extern "C" int gh_kernel_create(const gh_knode* in, int n_nodes, gh_kernel** out
   k->ndim = st[0].ndim;
   k->size = st[0].psize;
   if (k->size > GH_MAX_GRAD) { delete k; gh_set_error("too many kernel parameters (max %d)", GH_MAX_GRAD); return GH_ERR_BAD_ARG; }
-  detect_fast_form(k);
+  gh_fast_form(k->nodes.data(), (int)k->nodes.size(), &k->fast);
   *out = k;
   return GH_OK;
 }

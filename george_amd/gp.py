@@ -354,6 +354,108 @@ class GP(ModelSet):
         self._obj_cache = (np.array(vector, dtype=np.float64), np.array(y, dtype=np.float64), g)
         return -g
 
+    # -- ensembles (emcee ``vectorize=True``) ------------------------------------------------------
+    def log_likelihood_batch(self, vectors, y, quiet=True):
+        """``log_likelihood(y, quiet)`` at each row of ``vectors`` (shape ``(B, len(gp))``, ``get_parameter_vector()``
+        order), as an array of shape ``(B,)``.  Uses the ``x`` and ``yerr`` of the last ``compute``.  With the HIP
+        :class:`BasicSolver` and ``N <= BasicSolver.BATCH_MAX_N`` the B members are factorised together, every launch of
+        one factorisation carrying all of them (gh_chol_objective_batch); otherwise -- larger N, other solvers -- the rows
+        go through ``set_parameter_vector`` + ``log_likelihood`` one by one, with the same results.  A failed member is
+        ``-inf`` with ``quiet=True``; with ``quiet=False`` the first one raises ``np.linalg.LinAlgError`` naming it.  The
+        GP's parameter vector, ``computed`` flag and factorisation are what they were before the call."""
+        if not (hasattr(self, "_x") and hasattr(self, "_yerr2")):
+            raise RuntimeError("you must call 'compute' first")
+        vectors = np.asarray(vectors, dtype=np.float64)
+        if vectors.ndim != 2 or vectors.shape[1] != len(self):
+            raise ValueError("vectors must have shape (B, {0})".format(len(self)))
+        y = np.asarray(self._check_dimensions(y), dtype=np.float64)
+        B = len(vectors)
+        if B == 0:
+            return np.empty(0)
+        if self.solver_type is BasicSolver and len(self._x) <= BasicSolver.BATCH_MAX_N:
+            return self._log_likelihood_batch_device(vectors, y, quiet)
+        return self._log_likelihood_batch_loop(vectors, y, quiet)
+
+    def _batch_inputs(self, vectors, y, quiet):
+        """Per-member (full kernel parameter rows (B, kernel.full_size), sigma (B, N), r (B, N), ok (B,)) for rows in
+        ``get_parameter_vector()`` order: exactly what ``set_parameter_vector(v)`` followed by ``compute`` / ``_residual``
+        forms, without touching the GP's state.  Constant mean and white-noise models are mapped column-wise; any other
+        model goes through its own ``set_parameter_vector`` / ``get_value`` per member (and is restored)."""
+        B, n = len(vectors), len(self._x)
+        blocks, at = {}, 0
+        for name in ("mean", "white_noise", "kernel"):
+            m = self.models[name]
+            full = np.tile(m.get_parameter_vector(include_frozen=True), (B, 1))
+            k = int(m.unfrozen_mask.sum())
+            full[:, m.unfrozen_mask] = vectors[:, at:at + k]
+            blocks[name] = full
+            at += k
+        xarg = self._model_arg(self._x)
+
+        def values(name):
+            m = self.models[name]
+            rows = blocks[name]
+            if type(m) is ConstantModel:
+                return rows[:, :1] + np.zeros((B, n))                 # ConstantModel.get_value, row by row
+            saved, was_dirty = m.get_parameter_vector(include_frozen=True), m.dirty
+            out = np.empty((B, n))
+            try:
+                for b in range(B):
+                    m.set_parameter_vector(rows[b], include_frozen=True)
+                    out[b] = m.get_value(xarg).flatten()
+            finally:
+                m.set_parameter_vector(saved, include_frozen=True)
+                m.dirty = was_dirty
+            return out
+
+        mu = values("mean")
+        ok = np.all(np.isfinite(mu), axis=1)                           # (_call_mean raises where this is False)
+        if not quiet and not ok.all():
+            b = int(np.argmin(ok))
+            raise ValueError("member {0}: mean function returned NaN or Inf for parameters:\n{1}".format(b, blocks["mean"][b]))
+        with np.errstate(invalid="ignore", over="ignore"):
+            sigma = np.sqrt(self._yerr2[None, :] + np.exp(values("white_noise")))
+        r = np.ascontiguousarray(y[None, :] - mu)
+        return blocks["kernel"], sigma, r, ok
+
+    def _log_likelihood_batch_device(self, vectors, y, quiet):
+        kp, sigma, r, ok = self._batch_inputs(vectors, y, quiet)
+        solver = BasicSolver(self.kernel, **(self.solver_kwargs))      # (its own pooled handle: self.solver is untouched)
+        logdet, quad, info = solver.objective_batch(kp, self._x, sigma, r)
+        if not quiet:
+            bad = np.flatnonzero(info != 0)
+            if len(bad):
+                b = int(bad[0])
+                raise np.linalg.LinAlgError("member {0}: {1}-th leading minor of the array is not positive definite".format(
+                    b, int(info[b])))
+        with np.errstate(invalid="ignore"):
+            const = -0.5 * (len(self._x) * np.log(2 * np.pi) + logdet)
+            ll = const - 0.5 * quad
+        ll[~(ok & (info == 0) & np.isfinite(ll))] = -np.inf
+        return ll
+
+    def _log_likelihood_batch_loop(self, vectors, y, quiet):
+        saved = dict(vector=self.get_parameter_vector(include_frozen=True), solver=self.solver,
+                     computed=self._computed, dirty=[m.dirty for m in self.models.values()],
+                     const=getattr(self, "_const", None), alpha=self._alpha, y=self._y,
+                     obj_cache=getattr(self, "_obj_cache", None))
+        out = np.empty(len(vectors))
+        try:
+            for b, v in enumerate(vectors):
+                self.set_parameter_vector(v)
+                try:
+                    out[b] = self.log_likelihood(y, quiet=quiet)
+                except np.linalg.LinAlgError as e:
+                    raise np.linalg.LinAlgError("member {0}: {1}".format(b, e))
+        finally:
+            ModelSet.set_parameter_vector(self, saved["vector"], include_frozen=True)
+            for m, d in zip(self.models.values(), saved["dirty"]):
+                m.dirty = d
+            self.solver, self._computed = saved["solver"], saved["computed"]
+            self._const, self._alpha, self._y = saved["const"], saved["alpha"], saved["y"]
+            self._obj_cache = saved["obj_cache"]
+        return out
+
     def predict(self, y, t, return_cov=True, return_var=False, cache=True, kernel=None):
         """Conditional mean and (co)variance at ``t``  (gp.py:482-545)."""
         self.recompute()

@@ -90,37 +90,63 @@ class BasicSolver(object):
     def _pooled_bytes():
         return sum(int(N.lib.gh_chol_device_bytes(h)) for free in BasicSolver._POOL.values() for h in free)
 
-    def __del__(self):
-        h = getattr(self, "_handle", None)
-        if h is not None and h.value:
-            try:
-                free = BasicSolver._POOL.setdefault(self._pool_key(), [])
-                room = BasicSolver._POOL_MAX_BYTES - BasicSolver._pooled_bytes()
-                if len(free) < BasicSolver._POOL_MAX and int(N.lib.gh_chol_device_bytes(h)) <= room:
-                    free.append(h)                     # as it is: the next iterate re-uses the work arrays too
-                elif len(free) < BasicSolver._POOL_MAX:
-                    N.lib.gh_chol_trim(h)              # keep the factor-sized buffers, drop the work arrays
-                    if int(N.lib.gh_chol_device_bytes(h)) <= room:
-                        free.append(h)
-                    else:
-                        N.lib.gh_chol_destroy(h)
-                else:
-                    N.lib.gh_chol_destroy(h)
-            except Exception:
-                pass
-            self._handle = None
+    # the batched objective's handle (objective_batch): pooled under a key of its own, so that the factor of a GP's solver
+    # handle and the bordered batch buffers never share (or evict) one another
+    def _batch_pool_key(self):
+        return self._pool_key() + (("batch", True),)
 
-    def _retry_without_parked_memory(self, call):
+    def _ensure_batch_handle(self):
+        if getattr(self, "_bhandle", None) is None:
+            free = BasicSolver._POOL.get(self._batch_pool_key())
+            if free:
+                self._bhandle = free.pop()
+            else:
+                o = N.gh_chol_opts()
+                o.device, o.nb = self._opts["device"], self._opts["nb"]
+                o.profile, o.lookahead = int(self._opts["profile"]), int(self._opts["lookahead"])
+                h = N._vp()
+                N.check(N.lib.gh_chol_create(C.byref(o), C.byref(h)))
+                self._bhandle = h
+        return self._bhandle
+
+    @staticmethod
+    def _park(h, key):
+        free = BasicSolver._POOL.setdefault(key, [])
+        room = BasicSolver._POOL_MAX_BYTES - BasicSolver._pooled_bytes()
+        if len(free) < BasicSolver._POOL_MAX and int(N.lib.gh_chol_device_bytes(h)) <= room:
+            free.append(h)                     # as it is: the next iterate re-uses the work arrays too
+        elif len(free) < BasicSolver._POOL_MAX:
+            N.lib.gh_chol_trim(h)              # keep the factor-sized buffers, drop the work arrays
+            if int(N.lib.gh_chol_device_bytes(h)) <= room:
+                free.append(h)
+            else:
+                N.lib.gh_chol_destroy(h)
+        else:
+            N.lib.gh_chol_destroy(h)
+
+    def __del__(self):
+        for attr, key in (("_handle", self._pool_key), ("_bhandle", self._batch_pool_key)):
+            h = getattr(self, attr, None)
+            if h is not None and h.value:
+                try:
+                    BasicSolver._park(h, key())
+                except Exception:
+                    pass
+                setattr(self, attr, None)
+
+    def _retry_without_parked_memory(self, call, ensure=None):
         """Run ``call(handle)``; on MemoryError give back what dead solvers left parked on the device -- the handle pool
         (up to _POOL_MAX_BYTES, work arrays included) and the native block cache (up to 48 GB) -- and try ONCE more: a
-        new pool key, a multi-GPU handle or the application's own allocations must not fail because of memory nobody uses."""
+        new pool key, a multi-GPU handle or the application's own allocations must not fail because of memory nobody uses.
+        (``ensure``: where the handle comes from; the solver's own by default.)"""
+        ensure = ensure or self._ensure_handle
         try:
-            return call(self._ensure_handle())
+            return call(ensure())
         except MemoryError:
             type(self).release_pool()
             BasicSolver.release_pool()
             N.lib.gh_release_caches(int(self._opts["device"]))
-            return call(self._ensure_handle())
+            return call(ensure())
 
     @classmethod
     def release_pool(cls):
@@ -139,6 +165,7 @@ class BasicSolver(object):
     def __getstate__(self):
         state = self.__dict__.copy()
         state["_handle"] = None
+        state.pop("_bhandle", None)
         state["_dk"] = None
         state.pop("_factor_state", None)
         keep = self._computed and self._handle is not None and (
@@ -222,6 +249,46 @@ class BasicSolver(object):
         self.log_determinant = logdet.value
         self.computed = True
         return logdet.value, quad.value, (g[:self._dk.size] if g is not None else None), alpha, diagA
+
+    # -- many parameter vectors at once (GP.log_likelihood_batch: emcee's ``vectorize=True``)
+    # One chunk's bordered blocks, (Np + 128)^2 doubles per member, stay under this many bytes of device memory.
+    BATCH_MAX_BYTES = 8 << 30
+    # Largest N routed to the batched path by GP.log_likelihood_batch: above it one problem fills a third of the chip.
+    BATCH_MAX_N = 8192
+
+    def objective_batch(self, params, x, sigma, r):
+        """B independent log-likelihood pieces over one set of points (gh_chol_objective_batch): member b has the
+        kernel's structure with the FULL parameter vector ``params[b]`` (frozen entries included), standard deviations
+        ``sigma[b]`` (white noise included) and residual ``r[b]``.  Returns ``(logdet (B,), quad (B,), info (B,))``;
+        ``info[b] != 0`` (the 1-based failing pivot) marks a member that is not positive definite -- its logdet / quad
+        are NaN.  Runs on a pooled handle of its own: this solver's factor, if any, is untouched."""
+        x = N.as_f64(x)
+        if x.ndim != 2:
+            raise ValueError("x must be (nsamples, ndim)")
+        n = len(x)
+        params = N.as_f64(params)
+        B = params.shape[0] if params.ndim == 2 else -1
+        dk = DeviceKernel(self.kernel)
+        if B < 0 or params.shape[1] != dk.size:
+            raise ValueError("params must be (B, {0})".format(dk.size))
+        sigma = N.as_f64(np.broadcast_to(sigma, (B, n)))
+        r = N.as_f64(r)
+        if r.shape != (B, n):
+            raise ValueError("dimension mismatch")
+        if x.shape[1] != dk.ndim:
+            raise RuntimeError("dimension mismatch")
+        logdet, quad, info = np.empty(B), np.empty(B), np.zeros(B, dtype=np.int64)
+        if B == 0:
+            return logdet, quad, info
+        np_ = -(-n // 128) * 128
+        per = ((np_ + 128) ** 2 + np_ * 128) * 8
+        chunk = int(max(1, min(B, BasicSolver.BATCH_MAX_BYTES // per)))
+        for b0 in range(0, B, chunk):
+            b1 = min(B, b0 + chunk)
+            self._retry_without_parked_memory(lambda hh: N.check(N.lib.gh_chol_objective_batch(
+                hh, dk.handle, N.ptr(params[b0:b1]), b1 - b0, N.ptr(x), n, x.shape[1], N.ptr(sigma[b0:b1]), N.ptr(r[b0:b1]),
+                N.ptr(logdet[b0:]), N.ptr(quad[b0:]), N.ptr(info[b0:]))), ensure=self._ensure_batch_handle)
+        return logdet, quad, info
 
     def _need(self):
         if self._computed and self._handle is None and getattr(self, "_factor_state", None) is not None:

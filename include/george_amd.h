@@ -186,6 +186,17 @@ int  gh_chol_objective(gh_chol* s, gh_kernel* k, const double* x, int64_t n, int
                        const double* yerr, const double* r /* n: y - mean */, const uint32_t* which,
                        double* logdet, double* quad, double* grad /* size or NULL */,
                        double* alpha /* n or NULL */, double* diagA /* n or NULL */);
+/* B independent problems that share the points x (n, ndim) and the kernel's STRUCTURE, each with its own parameters, error bars
+ * and residual (B rounds of compute gp.py:303-337 + log_likelihood :369-397, one device call):
+ *   K_b = k(params_b)(x, x) + diag(yerr_b^2);  logdet[b] = log|K_b|;  quad[b] = r_b^T K_b^-1 r_b;
+ *   info[b] = 0, or the 1-based index of the failing pivot of K_b (the gh_chol_info of the one-problem call).
+ * params: (B, gh_kernel_size(k)) row-major, each row a FULL parameter vector of k (frozen entries included, k's order);
+ * k supplies the structure only.  yerr, r: (B, n) row-major.  A member that is not positive definite does not fail the call:
+ * GH_OK is returned whenever every member was evaluated, and failures are reported in info (logdet / quad of such a member
+ * are NaN).  Any pointer may be host or device memory.  The handle is left NOT computed. */
+int  gh_chol_objective_batch(gh_chol* s, gh_kernel* k, const double* params, int32_t nbatch,
+                             const double* x, int64_t n, int32_t ndim, const double* yerr, const double* r,
+                             double* logdet, double* quad, int64_t* info);
 /* Checkpointing of the device factor (the reference's BasicSolver pickles COMPUTED,
  * tests/test_pickle.py:21-36, because its factor is a NumPy array, basic.py:68): the lower
  * triangle of L packed by rows (gh_chol_factor_size() = n (n + 1) / 2 doubles) and the inverses of
@@ -197,8 +208,8 @@ int  gh_chol_export_factor(gh_chol* s, double* packed_lower, double* dinv_out);
 int  gh_chol_import_factor(gh_chol* s, int64_t n, int32_t ndim, const double* x,
                            const double* packed_lower, const double* dinv_in, double logdet);
 /* memory management of a long-lived handle: trim() frees the transient work buffers of predict /
- * grad / get_inverse (up to 3 x 8 N^2 bytes) and keeps the factor; release_buffers() frees
- * everything but the handle (streams, events) -- the next compute() re-allocates. */
+ * grad / get_inverse (up to 3 x 8 N^2 bytes) and the buffers of objective_batch, and keeps the factor;
+ * release_buffers() frees everything but the handle (streams, events) -- the next compute() re-allocates. */
 void gh_chol_trim(gh_chol* s);
 void gh_chol_release_buffers(gh_chol* s);
 /* profile counters of the last compute(): see george_amd/csrc/gh_chol.hip */
