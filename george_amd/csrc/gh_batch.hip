@@ -36,6 +36,8 @@ struct GhBatchBufs {
   GhBuf dinv;                  // B x (np / 128) inverses of the 128 x 128 diagonal blocks
   GhBuf in;                    // [member nodes | member fast forms | x | yerr | r] (the last three when they come from the host)
   GhBuf out;                   // [logdet (B) | quad (B) | info (B)]
+  GhBuf O;                     // predict: B x (mt + 1 + K** tiles) 128 x 128 output tiles of the Schur complement
+  GhBuf res;                   // predict: [mu (B, m) | var (B, m) or cov (B, m, m)] in the caller's layout
   std::vector<char> stage;     // host image of `in`: ONE host-to-device copy per call
   std::vector<double> back;    // host image of `out`: ONE device-to-host copy per call
 };
@@ -43,7 +45,7 @@ GhBatchBufs* gh_batch_new() { return new GhBatchBufs(); }
 size_t gh_batch_bytes(const GhBatchBufs* b) {
   if (!b) return 0;
   size_t tot = 0;
-  for (const GhBuf* x : {&b->A, &b->dinv, &b->in, &b->out}) tot += x->p ? x->bytes : 0;
+  for (const GhBuf* x : {&b->A, &b->dinv, &b->in, &b->out, &b->O, &b->res}) tot += x->p ? x->bytes : 0;
   return tot;
 }
 void gh_batch_free(GhBatchBufs* b) { delete b; }
@@ -116,6 +118,89 @@ __global__ __launch_bounds__(256) void batch_build_kernel(BatchBuild a) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------------- predict: build
+struct BatchPBuild {
+  const GhNode* nodes; int n_nodes; int ndim;    // member b's program: nodes + b * n_nodes
+  const GhFast* fast;                            // (B) when every member has the a + b F(r^2) form
+  const double* x; long n;                       // (n, ndim), shared
+  const double* xs; long m;                      // (m, ndim), shared
+  const double* yerr; const double* r;           // (B, n)
+  double* A; long np, stride;                    // member b's panel: A + b * stride, (np + 128 + mp) rows of pitch np
+  double* O; long ostride; int mt, kss;          // member b's output tiles: O + b * ostride; kss: K** tiles 0 none, 1 diagonal, 2 lower
+  long long* info;                               // (B): cleared here
+  long ktiles, ptiles, tiles;                    // per member: K's lower tiles, + the panel tiles below K, + the output tiles
+};
+// blockIdx.x = member * 4 * tiles + 4 * tile + quadrant (64 x 64 quarters, as batch_build_kernel).  Tiles, in order: K's lower
+// triangle (batch_build_kernel's elements), the (1 + mt) x nt panel tiles below it (residual tile, then test rows), the mt + 1
+// residual-column output tiles (zero), the K** output tiles.
+template <bool FAST>
+__global__ __launch_bounds__(256) void batch_pbuild_kernel(BatchPBuild a) {
+  const long q4 = (long)blockIdx.x;
+  const int b = (int)(q4 / (4 * a.tiles));
+  const long t = (q4 / 4) % a.tiles;
+  const int quad = (int)(q4 & 3);
+  if (t == 0 && quad == 0 && threadIdx.x == 0) a.info[b] = 0;
+  const long nt = a.np / T;
+  const GhNode* prog = a.nodes + (long)b * a.n_nodes;
+  const int nd = a.ndim;
+  auto kval = [&](const double* p1, const double* p2) -> double {
+    return FAST ? gh_fast_value(a.fast[b], p1, p2) : gh_eval_value(prog, a.n_nodes, p1, p2);
+  };
+  int kind;                                      // 0 K, 1 panel below K, 2 residual-column output, 3 K**
+  long TI, TJ, u = 0;
+  if (t < a.ktiles) {
+    int ti, tj;
+    batch_tri_index(t, ti, tj);
+    kind = 0; TI = ti; TJ = tj;
+  } else if (t < a.ktiles + a.ptiles) {
+    const long v = t - a.ktiles;
+    kind = 1; TI = nt + v / nt; TJ = v % nt;
+  } else if (t < a.ktiles + a.ptiles + a.mt + 1) {
+    kind = 2; u = t - a.ktiles - a.ptiles; TI = TJ = 0;
+  } else {
+    const long v = t - a.ktiles - a.ptiles - a.mt - 1;
+    kind = 3; u = a.mt + 1 + v;
+    if (a.kss == 1) { TI = TJ = v; } else { int ti, tj; batch_tri_index(v, ti, tj); TI = ti; TJ = tj; }
+  }
+  const long r0 = TI * T + (quad >> 1) * 64, c0 = TJ * T + (quad & 1) * 64;
+  const double* yerr = a.yerr + (long)b * a.n;
+  const double* res = a.r + (long)b * a.n;
+  double* dst;
+  long ld;
+  if (kind <= 1) { dst = a.A + (long)b * a.stride + r0 * a.np + c0; ld = a.np; }
+  else { dst = a.O + (long)b * a.ostride + u * T * T + (quad >> 1) * 64 * T + (quad & 1) * 64; ld = T; }
+  const int lc = (threadIdx.x & 31) * 2, lr = threadIdx.x >> 5;
+  for (int pass = 0; pass < 8; ++pass) {
+    const long r = r0 + lr + pass * 8, c = c0 + lc;
+    double v[2];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const long cc = c + e;
+      double val = 0.0;
+      if (kind == 0) {
+        if (r < a.n && cc < a.n) {
+          const double* p1 = a.x + r * nd;
+          const double* p2 = a.x + cc * nd;
+          const bool swap = r > cc;              // k(x_min, x_max), as batch_build_kernel
+          val = kval(swap ? p2 : p1, swap ? p1 : p2);
+          if (r == cc) { const double e2 = yerr[r]; val += e2 * e2; }
+        } else {
+          val = (r == cc) ? 1.0 : 0.0;           // identity padding
+        }
+      } else if (kind == 1) {
+        const long c_s = r - a.np - T;           // test row index
+        if (r == a.np) val = cc < a.n ? res[cc] : 0.0;
+        else if (c_s >= 0 && c_s < a.m && cc < a.n) val = kval(a.x + cc * nd, a.xs + c_s * nd);   // k(x_i, xs_c)
+      } else if (kind == 3 && r < a.m && cc < a.m) {
+        const bool swap = r > cc;                // the one-problem symmetric build: k(xs_min, xs_max), no noise
+        val = kval(a.xs + (swap ? cc : r) * nd, a.xs + (swap ? r : cc) * nd);
+      }
+      v[e] = val;
+    }
+    *reinterpret_cast<double2*>(dst + (long)(lr + pass * 8) * ld + lc) = make_double2(v[0], v[1]);
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------- step j
 // potf2 of every member's diagonal tile j (the 75-KB LDS body of potf2_inv_mfma_kernel: two workgroups per CU)
 __global__ __launch_bounds__(256, 2) void batch_potf2_kernel(double* A, long ld, long stride, double* dinv, long dstride,
@@ -151,6 +236,50 @@ __global__ __launch_bounds__(256, 2) void batch_syrk_kernel(double* A, long ld, 
   gh_tile128_nt_sp<true>(sm, Ab + i * T * ld + l * T, ld, Ab + i * T * ld + (long)j * T, ld, Ab + l * T * ld + (long)j * T, ld, T);
 }
 
+// predict: tile (i, l) -= P_i P_l^T for j < l < nt and l <= i < rt -- K's trailing triangle, then the rectangle of the panel rows
+// below K (residual and test tiles); the border columns wait for batch_schur_kernel.  K = 128; blockIdx.x = member * pairs + pair.
+__global__ __launch_bounds__(256, 2) void batch_trap_kernel(double* A, long ld, long stride, const long long* info, int j, int nt,
+                                                            long pairs) {
+  const int b = (int)(blockIdx.x / pairs);
+  if (member_failed(info, b)) return;
+  __shared__ __attribute__((aligned(1024))) double sm[4 * BM * BK];
+  const long p = (long)(blockIdx.x % pairs), w = nt - j - 1, tri = w * (w + 1) / 2;
+  long i, l;
+  if (p < tri) {
+    int ti, tl;
+    batch_tri_index(p, ti, tl);
+    i = j + 1 + ti; l = j + 1 + tl;
+  } else {
+    i = nt + (p - tri) / w; l = j + 1 + (p - tri) % w;
+  }
+  double* Ab = A + (long)b * stride;
+  gh_tile128_nt_sp<true>(sm, Ab + i * T * ld + l * T, ld, Ab + i * T * ld + (long)j * T, ld, Ab + l * T * ld + (long)j * T, ld, T);
+}
+// predict, after the chain: output tile u of member b, C -= P_a P_b^T with K = np.  u <= mt: panel row tile nt + u against the
+// residual tile nt (u = 0: -z^T z at [0][0]; u > 0: -V^T z in column 0); u > mt: test tiles (c, d) of K** - V^T V (kss 1:
+// the diagonal tiles, kss 2: the lower ones).  blockIdx.x = member * q + u.
+// (ldo, the output tiles' pitch, is 128 but a kernel argument: as a constant it lets the compiler fold and keep addresses live
+// until the K = np loop spills)
+__global__ __launch_bounds__(256, 2) void batch_schur_kernel(const double* A, long ld, long stride, double* O, long ostride,
+                                                             long ldo, const long long* info, int nt, int mt, int kss, long q) {
+  const int b = (int)(blockIdx.x / q);
+  if (member_failed(info, b)) return;
+  __shared__ __attribute__((aligned(1024))) double sm[4 * BM * BK];
+  const long u = (long)(blockIdx.x % q);
+  long ia, ib;
+  if (u <= mt) {
+    ia = nt + u; ib = nt;
+  } else if (kss == 1) {
+    ia = ib = nt + u - mt;
+  } else {
+    int ti, tl;
+    batch_tri_index(u - mt - 1, ti, tl);
+    ia = nt + 1 + ti; ib = nt + 1 + tl;
+  }
+  const double* Ab = A + (long)b * stride;
+  gh_tile128_nt_sp<true>(sm, O + (long)b * ostride + u * T * T, ldo, Ab + ia * T * ld, ld, Ab + ib * T * ld, ld, ld);
+}
+
 // ---------------------------------------------------------------------------------------------------- reductions
 // (wave_sum / block_sum_256 of gh_chol.hip, the same operations in the same order)
 __device__ __forceinline__ double batch_wave_sum(double v) {
@@ -166,8 +295,9 @@ __device__ __forceinline__ double batch_block_sum_256(double v, double* sh) {
 }
 // logdet[b] = 2 sum_i log L_b[i][i] over the np diagonal entries in launch_logdet's order (gh_chol.hip: g contiguous slices,
 // each summed by 256 lanes and a block reduction, the slices added in index order); quad[b] = -A_b[np][np].  Failed members: NaN.
-__global__ __launch_bounds__(256) void batch_reduce_kernel(const double* A, long ld, long stride, long np, const long long* info,
-                                                           double* logdet, double* quad) {
+// (qsrc + b * qstride: where -quad[b] is, A_b[np][np] for the objective, O_b[0][0] for predict)
+__global__ __launch_bounds__(256) void batch_reduce_kernel(const double* A, long ld, long stride, long np, const double* qsrc,
+                                                           long qstride, const long long* info, double* logdet, double* quad) {
   __shared__ double sh[4];
   const int b = blockIdx.x;
   const double* Ab = A + (long)b * stride;
@@ -192,32 +322,54 @@ __global__ __launch_bounds__(256) void batch_reduce_kernel(const double* A, long
   }
   if (threadIdx.x == 0) {
     logdet[b] = 2.0 * tot;
-    quad[b] = -Ab[np * ld + np];
+    quad[b] = -qsrc[(long)b * qstride];
+  }
+}
+
+// predict: the caller's layout.  Element e of member b's [mu (m) | var (m) or cov (m x m)]; blockIdx.x = member * blocks + block.
+// cov[c][d] and cov[d][c] read the same lower element: exactly symmetric.  Failed members: NaN.
+__global__ __launch_bounds__(256) void batch_pfinal_kernel(const double* O, long ostride, const long long* info, long m, int mt,
+                                                           int kss, long per, long blocks, double* mu, double* var, double* cov) {
+  const long b = (long)blockIdx.x / blocks;
+  const long e = ((long)blockIdx.x % blocks) * 256 + threadIdx.x;
+  if (e >= per) return;
+  const bool bad = info[b] != 0;
+  const double* Ob = O + b * ostride;
+  const double nan = __longlong_as_double(0x7FF8000000000000LL);
+  if (e < m) {
+    mu[b * m + e] = bad ? nan : -Ob[(1 + e / T) * T * T + (e % T) * T];
+  } else if (kss == 1) {
+    const long c = e - m;
+    var[b * m + c] = bad ? nan : Ob[(mt + 1 + c / T) * T * T + (c % T) * (T + 1)];
+  } else {
+    const long c = (e - m) / m, d = (e - m) % m;
+    const long lo = c > d ? c : d, hi = c > d ? d : c, ti = lo / T, tj = hi / T;
+    cov[b * m * m + c * m + d] = bad ? nan : Ob[(mt + 1 + ti * (ti + 1) / 2 + tj) * T * T + (lo % T) * T + hi % T];
   }
 }
 
 // ---------------------------------------------------------------------------------------------------- host
 static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
-extern "C" int gh_chol_objective_batch(gh_chol* s, gh_kernel* k, const double* params, int32_t nbatch,
-                                       const double* x, int64_t n, int32_t ndim, const double* yerr, const double* r,
-                                       double* logdet, double* quad, int64_t* info) {
-  if (!s || !k || nbatch < 0 || n <= 0 || !x || !yerr || !r || !logdet || !quad || !info || (k->size > 0 && !params)) {
-    gh_set_error("bad argument to objective_batch");
-    return GH_ERR_BAD_ARG;
-  }
-  if (ndim != k->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
-  if (nbatch == 0) return GH_OK;
-  hipStream_t st = nullptr;
-  GhBatchBufs* bb = nullptr;
-  GH_CHECK(gh_chol_batch_begin(s, &st, &bb));
-  const long B = nbatch, np = gh_round_up(n, T), nt = np / T, ld = np + T;
-  const long stride = ld * ld, dstride = nt * T * T;
-  const long tiles = (nt + 1) * (nt + 2) / 2;
-  if (B * tiles * 4 > 0x7fffffffL) { gh_set_error("objective_batch: batch too large for one call"); return GH_ERR_BAD_ARG; }
-  const int nn = (int)k->nodes.size();
+// host results -> the caller's pointer, host or device
+static int batch_put(void* dst, const void* src, size_t bytes) {
+  if (gh_is_device_ptr(dst)) GH_HIP(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
+  else memcpy(dst, src, bytes);
+  return GH_OK;
+}
 
-  // ---- member programs: k's structure with each row's parameters (gh_node_set_params: the bits of gh_kernel_create)
+// Device views of a call's inputs, staged by batch_stage.
+struct BatchInputs {
+  const GhNode* nodes;                           // (B, k->nodes.size()): member programs
+  const GhFast* fast;                            // (B) fast forms, or nullptr when the structure has none
+  const double* x; const double* yerr; const double* r; const double* xs;
+};
+// The host side both entry points share: member programs (k's structure with each row's parameters, gh_node_set_params: the bits
+// of gh_kernel_create), their fast forms, and whichever of x, yerr, r and xs (m rows; none when m == 0) live on the host -- ONE
+// host-to-device copy into bb->in, enqueued on st.
+static int batch_stage(gh_kernel* k, GhBatchBufs* bb, hipStream_t st, const double* params, long B, const double* x, long n,
+                       int ndim, const double* yerr, const double* r, const double* xs, long m, BatchInputs* out) {
+  const int nn = (int)k->nodes.size();
   std::vector<double> prow;
   const double* P = params;
   if (k->size > 0 && gh_is_device_ptr(params)) {
@@ -226,11 +378,13 @@ extern "C" int gh_chol_objective_batch(gh_chol* s, gh_kernel* k, const double* p
     P = prow.data();
   }
   const bool x_dev = gh_is_device_ptr(x), e_dev = gh_is_device_ptr(yerr), r_dev = gh_is_device_ptr(r);
+  const bool s_dev = m == 0 || gh_is_device_ptr(xs);
   const size_t o_nodes = 0, o_fast = align256((size_t)B * nn * sizeof(GhNode));
   const size_t o_x = o_fast + align256((size_t)B * sizeof(GhFast));
   const size_t o_e = o_x + (x_dev ? 0 : align256((size_t)n * ndim * sizeof(double)));
   const size_t o_r = o_e + (e_dev ? 0 : align256((size_t)B * n * sizeof(double)));
-  const size_t in_bytes = o_r + (r_dev ? 0 : align256((size_t)B * n * sizeof(double)));
+  const size_t o_s = o_r + (r_dev ? 0 : align256((size_t)B * n * sizeof(double)));
+  const size_t in_bytes = o_s + (s_dev ? 0 : align256((size_t)m * ndim * sizeof(double)));
   bb->stage.resize(in_bytes);
   char* h = bb->stage.data();
   GhNode* hn = (GhNode*)(h + o_nodes);
@@ -248,14 +402,41 @@ extern "C" int gh_chol_objective_batch(gh_chol* s, gh_kernel* k, const double* p
   if (!x_dev) memcpy(h + o_x, x, (size_t)n * ndim * sizeof(double));
   if (!e_dev) memcpy(h + o_e, yerr, (size_t)B * n * sizeof(double));
   if (!r_dev) memcpy(h + o_r, r, (size_t)B * n * sizeof(double));
-
-  // ---- buffers (grown once, re-used by every later call of the same or a smaller size)
+  if (!s_dev) memcpy(h + o_s, xs, (size_t)m * ndim * sizeof(double));
+  // (grown once, re-used by every later call of the same or a smaller size)
   GH_CHECK(bb->in.ensure(in_bytes));
+  char* d = (char*)bb->in.p;
+  GH_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, st));
+  out->nodes = (const GhNode*)(d + o_nodes);
+  out->fast = fast ? (const GhFast*)(d + o_fast) : nullptr;
+  out->x = x_dev ? x : (const double*)(d + o_x);
+  out->yerr = e_dev ? yerr : (const double*)(d + o_e);
+  out->r = r_dev ? r : (const double*)(d + o_r);
+  out->xs = s_dev ? xs : (const double*)(d + o_s);
+  return GH_OK;
+}
+
+extern "C" int gh_chol_objective_batch(gh_chol* s, gh_kernel* k, const double* params, int32_t nbatch,
+                                       const double* x, int64_t n, int32_t ndim, const double* yerr, const double* r,
+                                       double* logdet, double* quad, int64_t* info) {
+  if (!s || !k || nbatch < 0 || n <= 0 || !x || !yerr || !r || !logdet || !quad || !info || (k->size > 0 && !params)) {
+    gh_set_error("bad argument to objective_batch");
+    return GH_ERR_BAD_ARG;
+  }
+  if (ndim != k->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
+  if (nbatch == 0) return GH_OK;
+  hipStream_t st = nullptr;
+  GhBatchBufs* bb = nullptr;
+  GH_CHECK(gh_chol_batch_begin(s, &st, &bb));
+  const long B = nbatch, np = gh_round_up(n, T), nt = np / T, ld = np + T;
+  const long stride = ld * ld, dstride = nt * T * T;
+  const long tiles = (nt + 1) * (nt + 2) / 2;
+  if (B * tiles * 4 > 0x7fffffffL) { gh_set_error("objective_batch: batch too large for one call"); return GH_ERR_BAD_ARG; }
+  BatchInputs in;
+  GH_CHECK(batch_stage(k, bb, st, params, B, x, n, ndim, yerr, r, nullptr, 0, &in));
   GH_CHECK(bb->A.ensure((size_t)B * stride * sizeof(double)));
   GH_CHECK(bb->dinv.ensure((size_t)B * dstride * sizeof(double)));
   GH_CHECK(bb->out.ensure((size_t)3 * B * sizeof(double)));
-  char* d = (char*)bb->in.p;
-  GH_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, st));
   double* A = bb->A.d();
   double* dinv = bb->dinv.d();
   double* d_logdet = bb->out.d();
@@ -264,14 +445,14 @@ extern "C" int gh_chol_objective_batch(gh_chol* s, gh_kernel* k, const double* p
 
   // ---- build
   BatchBuild a;
-  a.nodes = (const GhNode*)(d + o_nodes); a.n_nodes = nn; a.ndim = ndim;
-  a.fast = fast ? (const GhFast*)(d + o_fast) : nullptr;
-  a.x = x_dev ? x : (const double*)(d + o_x); a.n = n;
-  a.yerr = e_dev ? yerr : (const double*)(d + o_e);
-  a.r = r_dev ? r : (const double*)(d + o_r);
+  a.nodes = in.nodes; a.n_nodes = (int)k->nodes.size(); a.ndim = ndim;
+  a.fast = in.fast;
+  a.x = in.x; a.n = n;
+  a.yerr = in.yerr;
+  a.r = in.r;
   a.A = A; a.ld = ld; a.np = np; a.stride = stride; a.info = d_info; a.tiles = tiles;
   const dim3 gb((unsigned)(B * tiles * 4)), blk(256);
-  if (fast) hipLaunchKernelGGL(batch_build_kernel<true>, gb, blk, 0, st, a);
+  if (a.fast) hipLaunchKernelGGL(batch_build_kernel<true>, gb, blk, 0, st, a);
   else      hipLaunchKernelGGL(batch_build_kernel<false>, gb, blk, 0, st, a);
   GH_HIP(hipGetLastError());
 
@@ -287,7 +468,7 @@ extern "C" int gh_chol_objective_batch(gh_chol* s, gh_kernel* k, const double* p
     GH_HIP(hipGetLastError());
   }
   hipLaunchKernelGGL(batch_reduce_kernel, dim3((unsigned)B), blk, 0, st, (const double*)A, ld, stride, np,
-                     (const long long*)d_info, d_logdet, d_quad);
+                     (const double*)A + np * ld + np, stride, (const long long*)d_info, d_logdet, d_quad);
   GH_HIP(hipGetLastError());
 
   // ---- results: one copy back, one synchronisation
@@ -295,13 +476,103 @@ extern "C" int gh_chol_objective_batch(gh_chol* s, gh_kernel* k, const double* p
   GH_HIP(hipMemcpyAsync(bb->back.data(), d_logdet, (size_t)3 * B * sizeof(double), hipMemcpyDeviceToHost, st));
   GH_HIP(hipStreamSynchronize(st));
   const double* hb = bb->back.data();
-  auto put = [](void* dst, const void* src, size_t bytes) -> int {
-    if (gh_is_device_ptr(dst)) GH_HIP(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
-    else memcpy(dst, src, bytes);
-    return GH_OK;
-  };
-  GH_CHECK(put(logdet, hb, (size_t)B * sizeof(double)));
-  GH_CHECK(put(quad, hb + B, (size_t)B * sizeof(double)));
-  GH_CHECK(put(info, hb + 2 * B, (size_t)B * sizeof(int64_t)));
+  GH_CHECK(batch_put(logdet, hb, (size_t)B * sizeof(double)));
+  GH_CHECK(batch_put(quad, hb + B, (size_t)B * sizeof(double)));
+  GH_CHECK(batch_put(info, hb + 2 * B, (size_t)B * sizeof(int64_t)));
+  return GH_OK;
+}
+
+
+extern "C" int gh_chol_predict_batch(gh_chol* s, gh_kernel* k, const double* params, int32_t nbatch,
+                                     const double* x, int64_t n, int32_t ndim, const double* yerr, const double* r,
+                                     const double* xs, int64_t m, double* mu, double* var, double* cov,
+                                     double* logdet, double* quad, int64_t* info) {
+  if (!s || !k || nbatch < 0 || n <= 0 || m < 0 || !x || !yerr || !r || (m > 0 && (!xs || !mu)) || !info || (var && cov) ||
+      (k->size > 0 && !params)) {
+    gh_set_error("bad argument to predict_batch");
+    return GH_ERR_BAD_ARG;
+  }
+  if (ndim != k->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
+  if (nbatch == 0) return GH_OK;
+  hipStream_t st = nullptr;
+  GhBatchBufs* bb = nullptr;
+  GH_CHECK(gh_chol_batch_begin(s, &st, &bb));
+  const long B = nbatch, np = gh_round_up(n, T), nt = np / T, mp = gh_round_up(m, T), mt = mp / T;
+  const int kss = cov ? 2 : var ? 1 : 0;
+  const long ld = np, rt = nt + 1 + mt, stride = rt * T * ld, dstride = nt * T * T;
+  const long q = mt + 1 + (kss == 2 ? mt * (mt + 1) / 2 : kss == 1 ? mt : 0);     // output tiles per member
+  const long ostride = q * T * T;
+  const long ktiles = nt * (nt + 1) / 2, ptiles = (1 + mt) * nt, tiles = ktiles + ptiles + q;
+  const long per = m + (kss == 2 ? m * m : kss == 1 ? m : 0), fblocks = (per + 255) / 256;
+  if (B * tiles * 4 > 0x7fffffffL || B * fblocks > 0x7fffffffL) {
+    gh_set_error("predict_batch: batch too large for one call");
+    return GH_ERR_BAD_ARG;
+  }
+  BatchInputs in;
+  GH_CHECK(batch_stage(k, bb, st, params, B, x, n, ndim, yerr, r, xs, m, &in));
+  GH_CHECK(bb->A.ensure((size_t)B * stride * sizeof(double)));
+  GH_CHECK(bb->dinv.ensure((size_t)B * dstride * sizeof(double)));
+  GH_CHECK(bb->out.ensure((size_t)3 * B * sizeof(double)));
+  GH_CHECK(bb->O.ensure((size_t)B * ostride * sizeof(double)));
+  if (per > 0) GH_CHECK(bb->res.ensure((size_t)B * per * sizeof(double)));
+  double* A = bb->A.d();
+  double* dinv = bb->dinv.d();
+  double* O = bb->O.d();
+  double* d_logdet = bb->out.d();
+  double* d_quad = d_logdet + B;
+  long long* d_info = (long long*)(d_logdet + 2 * B);
+  double* d_mu = per > 0 ? bb->res.d() : nullptr;
+  double* d_second = per > 0 ? d_mu + B * m : nullptr;            // var (B, m) or cov (B, m, m)
+
+  // ---- build: K, the residual and test rows below it, the output tiles
+  BatchPBuild a;
+  a.nodes = in.nodes; a.n_nodes = (int)k->nodes.size(); a.ndim = ndim;
+  a.fast = in.fast;
+  a.x = in.x; a.n = n; a.xs = in.xs; a.m = m;
+  a.yerr = in.yerr; a.r = in.r;
+  a.A = A; a.np = np; a.stride = stride;
+  a.O = O; a.ostride = ostride; a.mt = (int)mt; a.kss = kss;
+  a.info = d_info; a.ktiles = ktiles; a.ptiles = ptiles; a.tiles = tiles;
+  const dim3 gb((unsigned)(B * tiles * 4)), blk(256);
+  if (a.fast) hipLaunchKernelGGL(batch_pbuild_kernel<true>, gb, blk, 0, st, a);
+  else        hipLaunchKernelGGL(batch_pbuild_kernel<false>, gb, blk, 0, st, a);
+  GH_HIP(hipGetLastError());
+
+  // ---- factorisation of K, every panel row below it carried along: three launches per step, each over every member
+  for (long j = 0; j < nt; ++j) {
+    hipLaunchKernelGGL(batch_potf2_kernel, dim3((unsigned)B), blk, 0, st, A, ld, stride, dinv, dstride, d_info, (int)j);
+    const long below = rt - j - 1;               // K's tiles below (j, j), the residual tile, the test tiles
+    hipLaunchKernelGGL(batch_trsm_kernel, dim3((unsigned)(B * below)), blk, 0, st, A, ld, stride, (const double*)dinv, dstride,
+                       (const long long*)d_info, (int)j, (int)below);
+    const long w = nt - j - 1;                   // trailing tile columns of K
+    if (w > 0) {
+      const long pairs = w * (w + 1) / 2 + (1 + mt) * w;
+      hipLaunchKernelGGL(batch_trap_kernel, dim3((unsigned)(B * pairs)), blk, 0, st, A, ld, stride, (const long long*)d_info,
+                         (int)j, (int)nt, pairs);
+    }
+    GH_HIP(hipGetLastError());
+  }
+  // ---- the border: one launch of K = np tile products, then logdet and the caller's layout
+  hipLaunchKernelGGL(batch_schur_kernel, dim3((unsigned)(B * q)), blk, 0, st, (const double*)A, ld, stride, O, ostride, (long)T,
+                     (const long long*)d_info, (int)nt, (int)mt, kss, q);
+  hipLaunchKernelGGL(batch_reduce_kernel, dim3((unsigned)B), blk, 0, st, (const double*)A, ld, stride, np, (const double*)O,
+                     ostride, (const long long*)d_info, d_logdet, d_quad);
+  if (per > 0)
+    hipLaunchKernelGGL(batch_pfinal_kernel, dim3((unsigned)(B * fblocks)), blk, 0, st, (const double*)O, ostride,
+                       (const long long*)d_info, (long)m, (int)mt, kss, per, fblocks, d_mu, d_second, d_second);
+  GH_HIP(hipGetLastError());
+
+  // ---- results: straight into the caller's arrays, one synchronisation
+  auto kind = [](const void* p) { return gh_is_device_ptr(p) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost; };
+  double* second = kss == 2 ? cov : var;
+  if (m > 0) GH_HIP(hipMemcpyAsync(mu, d_mu, (size_t)B * m * sizeof(double), kind(mu), st));
+  if (kss) GH_HIP(hipMemcpyAsync(second, d_second, (size_t)B * (per - m) * sizeof(double), kind(second), st));
+  bb->back.resize((size_t)3 * B);
+  GH_HIP(hipMemcpyAsync(bb->back.data(), d_logdet, (size_t)3 * B * sizeof(double), hipMemcpyDeviceToHost, st));
+  GH_HIP(hipStreamSynchronize(st));
+  const double* hb = bb->back.data();
+  if (logdet) GH_CHECK(batch_put(logdet, hb, (size_t)B * sizeof(double)));
+  if (quad) GH_CHECK(batch_put(quad, hb + B, (size_t)B * sizeof(double)));
+  GH_CHECK(batch_put(info, hb + 2 * B, (size_t)B * sizeof(int64_t)));
   return GH_OK;
 }

@@ -13,6 +13,7 @@ the import.  Differences are behind the API:
   any other duck-typed solver takes the generic NumPy path below, formula for
   formula as the reference.
 """
+import contextlib
 import warnings
 
 import numpy as np
@@ -376,11 +377,13 @@ class GP(ModelSet):
             return self._log_likelihood_batch_device(vectors, y, quiet)
         return self._log_likelihood_batch_loop(vectors, y, quiet)
 
-    def _batch_inputs(self, vectors, y, quiet):
+    def _batch_inputs(self, vectors, y, quiet, t=None):
         """Per-member (full kernel parameter rows (B, kernel.full_size), sigma (B, N), r (B, N), ok (B,)) for rows in
         ``get_parameter_vector()`` order: exactly what ``set_parameter_vector(v)`` followed by ``compute`` / ``_residual``
         forms, without touching the GP's state.  Constant mean and white-noise models are mapped column-wise; any other
-        model goes through its own ``set_parameter_vector`` / ``get_value`` per member (and is restored)."""
+        model goes through its own ``set_parameter_vector`` / ``get_value`` per member (and is restored).  With test
+        points ``t`` ((M, ndim), parsed) the tuple has a fifth entry, the mean model at ``t`` (B, M), and ``ok`` also
+        requires that one to be finite."""
         B, n = len(vectors), len(self._x)
         blocks, at = {}, 0
         for name in ("mean", "white_noise", "kernel"):
@@ -390,33 +393,41 @@ class GP(ModelSet):
             full[:, m.unfrozen_mask] = vectors[:, at:at + k]
             blocks[name] = full
             at += k
-        xarg = self._model_arg(self._x)
 
-        def values(name):
+        def values(name, arg):
             m = self.models[name]
             rows = blocks[name]
             if type(m) is ConstantModel:
-                return rows[:, :1] + np.zeros((B, n))                 # ConstantModel.get_value, row by row
+                return rows[:, :1] + np.zeros((B, len(arg)))          # ConstantModel.get_value, row by row
             saved, was_dirty = m.get_parameter_vector(include_frozen=True), m.dirty
-            out = np.empty((B, n))
+            out = np.empty((B, len(arg)))
             try:
                 for b in range(B):
                     m.set_parameter_vector(rows[b], include_frozen=True)
-                    out[b] = m.get_value(xarg).flatten()
+                    out[b] = m.get_value(arg).flatten()
             finally:
                 m.set_parameter_vector(saved, include_frozen=True)
                 m.dirty = was_dirty
             return out
 
-        mu = values("mean")
-        ok = np.all(np.isfinite(mu), axis=1)                           # (_call_mean raises where this is False)
-        if not quiet and not ok.all():
-            b = int(np.argmin(ok))
-            raise ValueError("member {0}: mean function returned NaN or Inf for parameters:\n{1}".format(b, blocks["mean"][b]))
+        def check(mu, where):
+            ok = np.all(np.isfinite(mu), axis=1)                       # (_call_mean raises where this is False)
+            if not quiet and not ok.all():
+                b = int(np.argmin(ok))
+                raise ValueError("member {0}: mean function returned NaN or Inf{1} for parameters:\n{2}".format(
+                    b, where, blocks["mean"][b]))
+            return ok
+
+        mu = values("mean", self._model_arg(self._x))
+        ok = check(mu, "")
         with np.errstate(invalid="ignore", over="ignore"):
-            sigma = np.sqrt(self._yerr2[None, :] + np.exp(values("white_noise")))
+            sigma = np.sqrt(self._yerr2[None, :] + np.exp(values("white_noise", self._model_arg(self._x))))
         r = np.ascontiguousarray(y[None, :] - mu)
-        return blocks["kernel"], sigma, r, ok
+        if t is None:
+            return blocks["kernel"], sigma, r, ok
+        mu_t = values("mean", self._model_arg(t))
+        ok = ok & check(mu_t, " at the test points")
+        return blocks["kernel"], sigma, r, ok, mu_t
 
     def _log_likelihood_batch_device(self, vectors, y, quiet):
         kp, sigma, r, ok = self._batch_inputs(vectors, y, quiet)
@@ -434,19 +445,17 @@ class GP(ModelSet):
         ll[~(ok & (info == 0) & np.isfinite(ll))] = -np.inf
         return ll
 
-    def _log_likelihood_batch_loop(self, vectors, y, quiet):
+    @contextlib.contextmanager
+    def _state_kept(self):
+        """Restores, on exit, what a per-member loop of ``set_parameter_vector`` + ``compute`` changes: the parameter
+        vector, the models' dirty flags, the solver and its factor, the ``computed`` flag, the alpha cache and the
+        objective cache."""
         saved = dict(vector=self.get_parameter_vector(include_frozen=True), solver=self.solver,
                      computed=self._computed, dirty=[m.dirty for m in self.models.values()],
                      const=getattr(self, "_const", None), alpha=self._alpha, y=self._y,
                      obj_cache=getattr(self, "_obj_cache", None))
-        out = np.empty(len(vectors))
         try:
-            for b, v in enumerate(vectors):
-                self.set_parameter_vector(v)
-                try:
-                    out[b] = self.log_likelihood(y, quiet=quiet)
-                except np.linalg.LinAlgError as e:
-                    raise np.linalg.LinAlgError("member {0}: {1}".format(b, e))
+            yield
         finally:
             ModelSet.set_parameter_vector(self, saved["vector"], include_frozen=True)
             for m, d in zip(self.models.values(), saved["dirty"]):
@@ -454,6 +463,103 @@ class GP(ModelSet):
             self.solver, self._computed = saved["solver"], saved["computed"]
             self._const, self._alpha, self._y = saved["const"], saved["alpha"], saved["y"]
             self._obj_cache = saved["obj_cache"]
+
+    def _log_likelihood_batch_loop(self, vectors, y, quiet):
+        out = np.empty(len(vectors))
+        with self._state_kept():
+            for b, v in enumerate(vectors):
+                self.set_parameter_vector(v)
+                try:
+                    out[b] = self.log_likelihood(y, quiet=quiet)
+                except np.linalg.LinAlgError as e:
+                    raise np.linalg.LinAlgError("member {0}: {1}".format(b, e))
+        return out
+
+    def predict_batch(self, vectors, y, t, return_cov=True, return_var=False, quiet=False):
+        """``predict(y, t, return_cov, return_var)`` at each row of ``vectors`` (shape ``(B, len(gp))``,
+        ``get_parameter_vector()`` order), stacked: ``mu`` (B, M), and ``var`` (B, M) or ``cov`` (B, M, M) as ``predict``
+        returns them (``return_var`` wins).  Row b includes member b's mean model at ``t``.  Uses the ``x`` and ``yerr``
+        of the last ``compute``.  With the HIP :class:`BasicSolver`, ``N <= BasicSolver.BATCH_MAX_N`` and one member's
+        device buffers within ``BasicSolver.BATCH_MAX_BYTES`` the B members are factorised and predicted together
+        (gh_chol_predict_batch); otherwise the rows go through ``set_parameter_vector`` + ``predict`` one by one, with the
+        same results.  A member whose matrix is not positive definite, or whose mean model is not finite at ``x`` or
+        ``t``, raises (``np.linalg.LinAlgError`` / ``ValueError`` naming it) unless ``quiet``, which gives it NaN rows.
+        The GP's parameter vector, ``computed`` flag, factorisation and caches are what they were before the call."""
+        if not (hasattr(self, "_x") and hasattr(self, "_yerr2")):
+            raise RuntimeError("you must call 'compute' first")
+        vectors = np.asarray(vectors, dtype=np.float64)
+        if vectors.ndim != 2 or vectors.shape[1] != len(self):
+            raise ValueError("vectors must have shape (B, {0})".format(len(self)))
+        y = np.asarray(self._check_dimensions(y), dtype=np.float64)
+        xs = np.ascontiguousarray(self.parse_samples(t), dtype=np.float64)
+        want_var = bool(return_var)
+        want_cov = bool(return_cov) and not want_var
+        n, m = len(self._x), len(xs)
+        if (self.solver_type is BasicSolver and n <= BasicSolver.BATCH_MAX_N
+                and BasicSolver.predict_batch_bytes(n, m, want_var, want_cov) <= BasicSolver.BATCH_MAX_BYTES):
+            mu, var, cov = self._predict_batch_device(vectors, y, xs, want_var, want_cov, quiet)
+        else:
+            mu, var, cov = self._predict_batch_loop(vectors, y, xs, want_var, want_cov, quiet)
+        if want_var:
+            return mu, var
+        if want_cov:
+            return mu, cov
+        return mu
+
+    def _predict_batch_device(self, vectors, y, xs, want_var, want_cov, quiet):
+        B, m = len(vectors), len(xs)
+        if B == 0:
+            return np.empty((0, m)), np.empty((0, m)) if want_var else None, np.empty((0, m, m)) if want_cov else None
+        kp, sigma, r, ok, mean_t = self._batch_inputs(vectors, y, quiet, t=xs)
+        solver = BasicSolver(self.kernel, **(self.solver_kwargs))      # (its own pooled handle: self.solver is untouched)
+        mu, var, cov, info = solver.predict_batch(kp, self._x, sigma, r, xs, return_var=want_var, return_cov=want_cov)
+        if not quiet:
+            bad = np.flatnonzero(info != 0)
+            if len(bad):
+                b = int(bad[0])
+                raise np.linalg.LinAlgError("member {0}: {1}-th leading minor of the array is not positive definite".format(
+                    b, int(info[b])))
+        mu += mean_t
+        failed = ~(ok & (info == 0))
+        for a in (mu, var, cov):
+            if a is not None:
+                a[failed] = np.nan
+        return mu, var, cov
+
+    def _predict_batch_loop(self, vectors, y, xs, want_var, want_cov, quiet):
+        B, m = len(vectors), len(xs)
+        mu = np.full((B, m), np.nan)
+        var = np.full((B, m), np.nan) if want_var else None
+        cov = np.full((B, m, m), np.nan) if want_cov else None
+        with self._state_kept():
+            for b, v in enumerate(vectors):
+                self.set_parameter_vector(v)
+                try:
+                    out = self.predict(y, xs, return_cov=want_cov, return_var=want_var)
+                except ValueError as e:                                # (np.linalg.LinAlgError is one)
+                    if quiet:
+                        continue
+                    raise type(e)("member {0}: {1}".format(b, e))
+                if want_var:
+                    mu[b], var[b] = out
+                elif want_cov:
+                    mu[b], cov[b] = out
+                else:
+                    mu[b] = out
+        return mu, var, cov
+
+    def sample_conditional_batch(self, vectors, y, t, size=1, quiet=False):
+        """``sample_conditional(y, t, size)`` at each row of ``vectors``: ``predict_batch(..., return_cov=True)`` and then,
+        for b = 0, 1, ... in order, ``multivariate_gaussian_samples(cov_b, size, mean=mu_b)`` -- the random stream is
+        consumed as the loop of ``set_parameter_vector`` + ``sample_conditional`` consumes it.  The draws are made on the
+        host (SVD, as the reference).  Returns (B, M) for ``size == 1``, else (B, size, M).  A member that failed under
+        ``quiet=True`` has NaN draws and consumes no random numbers."""
+        mu, cov = self.predict_batch(vectors, y, t, return_cov=True, quiet=quiet)
+        B, m = mu.shape
+        out = np.full((B, m) if size == 1 else (B, size, m), np.nan)
+        for b in range(B):
+            if np.all(np.isfinite(mu[b])):
+                out[b] = multivariate_gaussian_samples(cov[b], size, mean=mu[b])
         return out
 
     def predict(self, y, t, return_cov=True, return_var=False, cache=True, kernel=None):

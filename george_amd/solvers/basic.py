@@ -290,6 +290,53 @@ class BasicSolver(object):
                 N.ptr(logdet[b0:]), N.ptr(quad[b0:]), N.ptr(info[b0:]))), ensure=self._ensure_batch_handle)
         return logdet, quad, info
 
+    def predict_batch(self, params, x, sigma, r, xs, return_var=False, return_cov=False):
+        """B posterior predictions over one set of points (gh_chol_predict_batch): member b is objective_batch's member b,
+        predicted at ``xs``.  Returns ``(mu (B, M), var (B, M) or None, cov (B, M, M) or None, info (B,))``; ``mu`` has no
+        mean model (as :meth:`predict`), ``return_var`` wins over ``return_cov``, and a member with ``info[b] != 0`` has NaN
+        rows.  Runs on objective_batch's pooled handle, in chunks under BATCH_MAX_BYTES."""
+        x, xs = N.as_f64(x), N.as_f64(xs)
+        if x.ndim != 2 or xs.ndim != 2:
+            raise ValueError("x and xs must be (nsamples, ndim)")
+        n, m = len(x), len(xs)
+        params = N.as_f64(params)
+        B = params.shape[0] if params.ndim == 2 else -1
+        dk = DeviceKernel(self.kernel)
+        if B < 0 or params.shape[1] != dk.size:
+            raise ValueError("params must be (B, {0})".format(dk.size))
+        sigma = N.as_f64(np.broadcast_to(sigma, (B, n)))
+        r = N.as_f64(r)
+        if r.shape != (B, n):
+            raise ValueError("dimension mismatch")
+        if x.shape[1] != dk.ndim or xs.shape[1] != dk.ndim:
+            raise RuntimeError("dimension mismatch")
+        want_var = bool(return_var)
+        want_cov = bool(return_cov) and not want_var
+        mu = np.empty((B, m))
+        var = np.empty((B, m)) if want_var else None
+        cov = np.empty((B, m, m)) if want_cov else None
+        info = np.zeros(B, dtype=np.int64)
+        if B == 0:
+            return mu, var, cov, info
+        chunk = int(max(1, min(B, BasicSolver.BATCH_MAX_BYTES // self.predict_batch_bytes(n, m, want_var, want_cov))))
+        for b0 in range(0, B, chunk):
+            b1 = min(B, b0 + chunk)
+            self._retry_without_parked_memory(lambda hh: N.check(N.lib.gh_chol_predict_batch(
+                hh, dk.handle, N.ptr(params[b0:b1]), b1 - b0, N.ptr(x), n, x.shape[1], N.ptr(sigma[b0:b1]), N.ptr(r[b0:b1]),
+                N.ptr(xs), m, N.ptr(mu[b0:]), N.ptr(var[b0:]) if want_var else None,
+                N.ptr(cov[b0:]) if want_cov else None, None, None, N.ptr(info[b0:]))), ensure=self._ensure_batch_handle)
+        return mu, var, cov, info
+
+    @staticmethod
+    def predict_batch_bytes(n, m, return_var=False, return_cov=False):
+        """Device bytes of one member of predict_batch: its panel (Np + 128 + Mp rows of Np), the inverses of its diagonal
+        blocks, its 128 x 128 output tiles (Mp / 128 + 1, plus the K** tiles) and its results in the caller's layout."""
+        np_, mp = -(-n // 128) * 128, -(-m // 128) * 128
+        mt = mp // 128
+        kss = mt * (mt + 1) // 2 if return_cov and not return_var else mt if return_var else 0
+        res = m + (m if return_var else m * m if return_cov else 0)
+        return ((np_ + 128 + mp) * np_ + np_ * 128 + (mt + 1 + kss) * 128 * 128 + res) * 8
+
     def _need(self):
         if self._computed and self._handle is None and getattr(self, "_factor_state", None) is not None:
             self._restore()

@@ -197,6 +197,18 @@ int  gh_chol_objective(gh_chol* s, gh_kernel* k, const double* x, int64_t n, int
 int  gh_chol_objective_batch(gh_chol* s, gh_kernel* k, const double* params, int32_t nbatch,
                              const double* x, int64_t n, int32_t ndim, const double* yerr, const double* r,
                              double* logdet, double* quad, int64_t* info);
+/* B posterior predictions of one kernel STRUCTURE at B parameter vectors (B rounds of compute gp.py:303-337 + predict
+ * :482-545, one device call).  params, x, yerr, r, info: as gh_chol_objective_batch.  xs: (m, ndim).
+ *   mu[b]  (m)    = K_b(xs, x) K_b^-1 r_b                          (no mean model: the caller adds it, as for gh_chol_predict)
+ *   var[b] (m)    = diag K_b(xs, xs) - diag K_b(xs, x) K_b^-1 K_b(x, xs)     or NULL
+ *   cov[b] (m, m) = K_b(xs, xs) - K_b(xs, x) K_b^-1 K_b(x, xs)               or NULL   (not both var and cov)
+ *   logdet[b], quad[b]: as gh_chol_objective_batch, or NULL.
+ * A failed member's rows are NaN; GH_OK whenever every member was evaluated.  Any pointer may be host or device memory.
+ * The handle is left NOT computed. */
+int  gh_chol_predict_batch(gh_chol* s, gh_kernel* k, const double* params, int32_t nbatch,
+                           const double* x, int64_t n, int32_t ndim, const double* yerr, const double* r,
+                           const double* xs, int64_t m, double* mu, double* var, double* cov,
+                           double* logdet, double* quad, int64_t* info);
 /* Checkpointing of the device factor (the reference's BasicSolver pickles COMPUTED,
  * tests/test_pickle.py:21-36, because its factor is a NumPy array, basic.py:68): the lower
  * triangle of L packed by rows (gh_chol_factor_size() = n (n + 1) / 2 doubles) and the inverses of
@@ -208,7 +220,7 @@ int  gh_chol_export_factor(gh_chol* s, double* packed_lower, double* dinv_out);
 int  gh_chol_import_factor(gh_chol* s, int64_t n, int32_t ndim, const double* x,
                            const double* packed_lower, const double* dinv_in, double logdet);
 /* memory management of a long-lived handle: trim() frees the transient work buffers of predict /
- * grad / get_inverse (up to 3 x 8 N^2 bytes) and the buffers of objective_batch, and keeps the factor;
+ * grad / get_inverse (up to 3 x 8 N^2 bytes) and the buffers of objective_batch / predict_batch, and keeps the factor;
  * release_buffers() frees everything but the handle (streams, events) -- the next compute() re-allocates. */
 void gh_chol_trim(gh_chol* s);
 void gh_chol_release_buffers(gh_chol* s);
