@@ -150,6 +150,8 @@ SIGNATURES = {
     "gh_chol_objective_batch": (C.c_int, [_vp, _vp, _dp, _i32, _dp, _i64, _i32, _dp, _dp, _dp, _dp, _dp]),
     "gh_chol_predict_batch": (C.c_int, [_vp, _vp, _dp, _i32, _dp, _i64, _i32, _dp, _dp, _dp, _i64, _dp, _dp, _dp, _dp, _dp,
                                         _dp]),
+    "gh_chol_objective_grad_batch": (C.c_int, [_vp, _vp, _dp, _i32, _dp, _i64, _i32, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                               _dp, _dp]),
     "gh_chol_factor_size": (_i64, [_vp]),
     "gh_chol_dinv_size": (_i64, [_vp]),
     "gh_chol_export_factor": (C.c_int, [_vp, _dp, _dp]),

@@ -1,5 +1,6 @@
 // gh_batch.hip -- B log-likelihoods of one kernel STRUCTURE at B parameter vectors in one device call
-// (gh_chol_objective_batch: GP.log_likelihood_batch, the hook for emcee's `vectorize=True`).
+// (gh_chol_objective_batch: GP.log_likelihood_batch, the hook for emcee's `vectorize=True`), with B predictions
+// (gh_chol_predict_batch) and B likelihood gradients (gh_chol_objective_grad_batch) built on the same chain.
 //
 // At the sizes samplers run (N of a few hundred to a few thousand) one factorisation fills a few percent of the chip: it is a
 // serial chain of 128-column steps, and a sampler step used to run B such chains one after the other.  Here every launch of
@@ -36,8 +37,9 @@ struct GhBatchBufs {
   GhBuf dinv;                  // B x (np / 128) inverses of the 128 x 128 diagonal blocks
   GhBuf in;                    // [member nodes | member fast forms | x | yerr | r] (the last three when they come from the host)
   GhBuf out;                   // [logdet (B) | quad (B) | info (B)]
-  GhBuf O;                     // predict: B x (mt + 1 + K** tiles) 128 x 128 output tiles of the Schur complement
-  GhBuf res;                   // predict: [mu (B, m) | var (B, m) or cov (B, m, m)] in the caller's layout
+  GhBuf O;                     // predict: B x (mt + 1 + K** tiles) 128 x 128 output tiles of the Schur complement; grad: -z^T z, -alpha, -K^-1
+  GhBuf res;                   // predict: [mu (B, m) | var (B, m) or cov (B, m, m)]; grad: [grad (B, P) | alpha (B, n) | diagA (B, n)]
+  GhBuf part;                  // grad: [which (P) | partial rows of the reduction (B, 64-tiles, P)]
   std::vector<char> stage;     // host image of `in`: ONE host-to-device copy per call
   std::vector<double> back;    // host image of `out`: ONE device-to-host copy per call
 };
@@ -45,7 +47,7 @@ GhBatchBufs* gh_batch_new() { return new GhBatchBufs(); }
 size_t gh_batch_bytes(const GhBatchBufs* b) {
   if (!b) return 0;
   size_t tot = 0;
-  for (const GhBuf* x : {&b->A, &b->dinv, &b->in, &b->out, &b->O, &b->res}) tot += x->p ? x->bytes : 0;
+  for (const GhBuf* x : {&b->A, &b->dinv, &b->in, &b->out, &b->O, &b->res, &b->part}) tot += x->p ? x->bytes : 0;
   return tot;
 }
 void gh_batch_free(GhBatchBufs* b) { delete b; }
@@ -133,7 +135,8 @@ struct BatchPBuild {
 // blockIdx.x = member * 4 * tiles + 4 * tile + quadrant (64 x 64 quarters, as batch_build_kernel).  Tiles, in order: K's lower
 // triangle (batch_build_kernel's elements), the (1 + mt) x nt panel tiles below it (residual tile, then test rows), the mt + 1
 // residual-column output tiles (zero), the K** output tiles.
-template <bool FAST>
+// EYE (gh_chol_objective_grad_batch): the m = np test rows are the identity and the K** tiles zero.
+template <bool FAST, bool EYE = false>
 __global__ __launch_bounds__(256) void batch_pbuild_kernel(BatchPBuild a) {
   const long q4 = (long)blockIdx.x;
   const int b = (int)(q4 / (4 * a.tiles));
@@ -190,8 +193,9 @@ __global__ __launch_bounds__(256) void batch_pbuild_kernel(BatchPBuild a) {
       } else if (kind == 1) {
         const long c_s = r - a.np - T;           // test row index
         if (r == a.np) val = cc < a.n ? res[cc] : 0.0;
+        else if (EYE) val = (c_s == cc) ? 1.0 : 0.0;
         else if (c_s >= 0 && c_s < a.m && cc < a.n) val = kval(a.x + cc * nd, a.xs + c_s * nd);   // k(x_i, xs_c)
-      } else if (kind == 3 && r < a.m && cc < a.m) {
+      } else if (kind == 3 && !EYE && r < a.m && cc < a.m) {
         const bool swap = r > cc;                // the one-problem symmetric build: k(xs_min, xs_max), no noise
         val = kval(a.xs + (swap ? cc : r) * nd, a.xs + (swap ? r : cc) * nd);
       }
@@ -346,6 +350,138 @@ __global__ __launch_bounds__(256) void batch_pfinal_kernel(const double* O, long
     const long lo = c > d ? c : d, hi = c > d ? d : c, ti = lo / T, tj = hi / T;
     cov[b * m * m + c * m + d] = bad ? nan : Ob[(mt + 1 + ti * (ti + 1) / 2 + tj) * T * T + (lo % T) * T + hi % T];
   }
+}
+
+// ---------------------------------------------------------------------------------------------------- gradient
+// grad, after the chain: output tile u of member b, C -= P_a P_b^T from k-tile k0 on.  The np identity rows below the residual
+// tile have become W = L^-T, upper triangular: W's row tile c is zero left of k-tile c, and those k are skipped (the products
+// there are exact zeros).  u = 0: the residual tile against itself, K = np: -z^T z at [0][0]; 0 < u <= nt: W's row tile u - 1
+// against the residual tile: -alpha in column 0; u > nt: lower tile (c, d) of -W W^T = -K^-1, from k-tile c on.
+// blockIdx.x = member * q + u.  (ldo: as batch_schur_kernel)
+__global__ __launch_bounds__(256, 2) void batch_gschur_kernel(const double* A, long ld, long stride, double* O, long ostride,
+                                                              long ldo, const long long* info, int nt, long q) {
+  const int b = (int)(blockIdx.x / q);
+  if (member_failed(info, b)) return;
+  __shared__ __attribute__((aligned(1024))) double sm[4 * BM * BK];
+  const long u = (long)(blockIdx.x % q);
+  long ia, ib, k0;
+  if (u <= nt) {
+    ia = nt + u; ib = nt; k0 = u > 0 ? (u - 1) * T : 0;
+  } else {
+    int ti, tl;
+    batch_tri_index(u - nt - 1, ti, tl);
+    ia = nt + 1 + ti; ib = nt + 1 + tl; k0 = (long)ti * T;
+  }
+  const double* Ab = A + (long)b * stride;
+  gh_tile128_nt_sp<true>(sm, O + (long)b * ostride + u * T * T, ldo, Ab + ia * T * ld + k0, ld, Ab + ib * T * ld + k0, ld,
+                         ld - k0);
+}
+
+// The batched form of gh_kmat.hip's kgrad_reduce_kernel: one 64 x 64 tile of member b's lower triangle per workgroup, member b's
+// program, alpha and K^-1 read from its output tiles (negated: exact), the same per-element weights (1/2 on the diagonal) and
+// the same wave / cross-wave reduction; one partial row per (member, tile).  The diagonal writes alpha[b] and diagA[b]; a failed
+// member gets NaN rows there.  blockIdx.x = member * nblk + tile.
+#define GT 64
+struct BatchGrad {
+  const GhNode* nodes; int n_nodes; int ndim; int P;   // member b's program: nodes + b * n_nodes
+  const uint32_t* which;                               // (P), shared by every member
+  const double* x; long n;                             // (n, ndim), shared
+  const double* O; long ostride; long nt;              // member b's output tiles (batch_gschur_kernel): O + b * ostride
+  const long long* info;
+  double* partial;                                     // (B, nblk, P)
+  double* alpha; double* diagA;                        // (B, n)
+  long nblk;                                           // 64-tiles of the lower triangle per member
+};
+template <int PMAX>
+__global__ __launch_bounds__(256, PMAX <= 16 ? 4 : 1) void batch_kgrad_kernel(BatchGrad a) {
+  __shared__ double xr[GT * GH_MAX_NDIM];
+  __shared__ double xc[GT * GH_MAX_NDIM];
+  __shared__ double ar[GT], ac[GT];
+  __shared__ double red[4][PMAX];
+  const int b = (int)(blockIdx.x / a.nblk);
+  const long t = (long)(blockIdx.x % a.nblk);
+  int ti, tj;
+  batch_tri_index(t, ti, tj);
+  const long r0 = (long)ti * GT, c0 = (long)tj * GT, n = a.n;
+  const int nd = a.ndim, P = a.P;
+  if (member_failed(a.info, b)) {
+    if (ti == tj && threadIdx.x < GT && r0 + threadIdx.x < n) {
+      const double nan = __longlong_as_double(0x7FF8000000000000LL);
+      a.alpha[b * n + r0 + threadIdx.x] = nan;
+      a.diagA[b * n + r0 + threadIdx.x] = nan;
+    }
+    return;
+  }
+  const double* Ob = a.O + (long)b * a.ostride;
+  for (int e = threadIdx.x; e < GT * nd; e += 256) {
+    const long r = r0 + e / nd;
+    xr[e] = (r < n) ? a.x[r * nd + (e % nd)] : 0.0;
+    const long c = c0 + e / nd;
+    xc[e] = (c < n) ? a.x[c * nd + (e % nd)] : 0.0;
+  }
+  if (threadIdx.x < GT) {                        // alpha_i = -O[tile 1 + i / 128][i % 128][0]
+    const long r = r0 + threadIdx.x, c = c0 + threadIdx.x;
+    ar[threadIdx.x] = (r < n) ? -Ob[(1 + r / T) * T * T + (r % T) * T] : 0.0;
+    ac[threadIdx.x] = (c < n) ? -Ob[(1 + c / T) * T * T + (c % T) * T] : 0.0;
+  }
+  __syncthreads();
+  const long TI = r0 / T, TJ = c0 / T;           // the 128-tile of -K^-1 that holds this 64-tile
+  const double* kt = Ob + (a.nt + 1 + TI * (TI + 1) / 2 + TJ) * T * T + (r0 % T) * T + (c0 % T);
+  const GhNode* prog = a.nodes + (long)b * a.n_nodes;
+  double acc[PMAX];
+#pragma unroll
+  for (int p = 0; p < PMAX; ++p) acc[p] = 0.0;
+  const int lc = threadIdx.x & 63;
+  const int lr = threadIdx.x >> 6;
+#pragma unroll 1
+  for (int pass = 0; pass < GT / 4; ++pass) {
+    const int rr = lr + pass * 4;
+    const long r = r0 + rr, c = c0 + lc;
+    if (r < n && c <= r) {
+      double g[PMAX];
+      // ordered arguments (x_min, x_max) = (x_c, x_r) since c <= r, as kgrad_reduce_kernel
+      gh_eval_grad(prog, a.n_nodes, &xc[lc * nd], &xr[rr * nd], g);
+      const double kin = -kt[rr * T + lc];
+      const double aij = ar[rr] * ac[lc] - kin;
+      const double w = (r == c) ? 0.5 * aij : aij;
+      if (r == c) { a.diagA[b * n + r] = aij; a.alpha[b * n + r] = ar[rr]; }
+#pragma unroll
+      for (int p = 0; p < PMAX; ++p) if (p < P) acc[p] += w * g[p];
+    }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int p = 0; p < PMAX; ++p) {
+    double v = acc[p];
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    if (lane == 0) red[wave][p] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < PMAX && threadIdx.x < P) {
+    const int p = threadIdx.x;
+    a.partial[((long)b * a.nblk + t) * P + p] = a.which[p] ? (red[0][p] + red[1][p]) + (red[2][p] + red[3][p]) : 0.0;
+  }
+}
+// grad[b][p]: the partial rows of member b summed by one workgroup in a fixed-order tree (kgrad_final_kernel's), so a member's
+// result depends on nothing but its own rows.  Failed members: NaN.  blockIdx.x = member * P + p.
+__global__ __launch_bounds__(256) void batch_kgrad_final_kernel(const double* partial, long nblk, int P, const long long* info,
+                                                                double* grad) {
+  __shared__ double s[256];
+  const int b = blockIdx.x / P, p = blockIdx.x % P;
+  if (member_failed(info, b)) {
+    if (threadIdx.x == 0) grad[(long)b * P + p] = __longlong_as_double(0x7FF8000000000000LL);
+    return;
+  }
+  const double* pb = partial + (long)b * nblk * P;
+  double v = 0.0;
+  for (long t = threadIdx.x; t < nblk; t += 256) v += pb[t * P + p];
+  s[threadIdx.x] = v;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if ((int)threadIdx.x < off) s[threadIdx.x] += s[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) grad[(long)b * P + p] = s[0];
 }
 
 // ---------------------------------------------------------------------------------------------------- host
@@ -573,6 +709,123 @@ extern "C" int gh_chol_predict_batch(gh_chol* s, gh_kernel* k, const double* par
   const double* hb = bb->back.data();
   if (logdet) GH_CHECK(batch_put(logdet, hb, (size_t)B * sizeof(double)));
   if (quad) GH_CHECK(batch_put(quad, hb + B, (size_t)B * sizeof(double)));
+  GH_CHECK(batch_put(info, hb + 2 * B, (size_t)B * sizeof(int64_t)));
+  return GH_OK;
+}
+
+
+// B rounds of objective + gradient (gh_chol_objective with a gradient, gh_chol.hip): predict_batch's panel with the np rows of
+// the identity in place of the test rows.  The chain turns them into W = L^-T, upper triangular, so at step j only the identity
+// row tiles 0 .. j are carried (the TRSM covers tiles j + 1 .. nt + 1 + j, the trapezoid rows nt .. nt + 1 + j); one Schur
+// launch from each tile's first non-zero k-tile on leaves -z^T z, -alpha and the lower tiles of -K^-1 (batch_gschur_kernel);
+// then logdet / quad (batch_reduce_kernel, as predict_batch) and the gradient reduction over all members.
+extern "C" int gh_chol_objective_grad_batch(gh_chol* s, gh_kernel* k, const double* params, int32_t nbatch,
+                                            const double* x, int64_t n, int32_t ndim, const double* yerr, const double* r,
+                                            const uint32_t* which, double* logdet, double* quad, double* grad,
+                                            double* alpha, double* diagA, int64_t* info) {
+  if (!s || !k || nbatch < 0 || n <= 0 || !x || !yerr || !r || !which || !logdet || !quad || !grad || !info ||
+      (k->size > 0 && !params)) {
+    gh_set_error("bad argument to objective_grad_batch");
+    return GH_ERR_BAD_ARG;
+  }
+  if (k->size > GH_MAX_GRAD) { gh_set_error("too many kernel parameters (max %d)", GH_MAX_GRAD); return GH_ERR_BAD_ARG; }
+  if (ndim != k->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
+  if (nbatch == 0) return GH_OK;
+  const long B = nbatch, np = gh_round_up(n, T), nt = np / T;
+  const long ld = np, rt = 2 * nt + 1, stride = rt * T * ld, dstride = nt * T * T;
+  const long q = nt + 1 + nt * (nt + 1) / 2, ostride = q * T * T;            // output tiles per member
+  const long ktiles = nt * (nt + 1) / 2, ptiles = (1 + nt) * nt, tiles = ktiles + ptiles + q;
+  const int P = k->size;
+  const long gm = (n + GT - 1) / GT, nblk = gm * (gm + 1) / 2;
+  if (B * tiles * 4 > 0x7fffffffL || B * nblk > 0x7fffffffL) {
+    gh_set_error("objective_grad_batch: batch too large for one call");
+    return GH_ERR_BAD_ARG;
+  }
+  hipStream_t st = nullptr;
+  GhBatchBufs* bb = nullptr;
+  GH_CHECK(gh_chol_batch_begin(s, &st, &bb));
+  BatchInputs in;
+  GH_CHECK(batch_stage(k, bb, st, params, B, x, n, ndim, yerr, r, nullptr, 0, &in));
+  const size_t which_bytes = align256(sizeof(uint32_t) * (P > 0 ? P : 1));
+  GH_CHECK(bb->A.ensure((size_t)B * stride * sizeof(double)));
+  GH_CHECK(bb->dinv.ensure((size_t)B * dstride * sizeof(double)));
+  GH_CHECK(bb->out.ensure((size_t)3 * B * sizeof(double)));
+  GH_CHECK(bb->O.ensure((size_t)B * ostride * sizeof(double)));
+  GH_CHECK(bb->res.ensure((size_t)B * (P + 2 * n) * sizeof(double)));
+  GH_CHECK(bb->part.ensure(which_bytes + (size_t)B * nblk * (P > 0 ? P : 1) * sizeof(double)));
+  double* A = bb->A.d();
+  double* dinv = bb->dinv.d();
+  double* O = bb->O.d();
+  double* d_logdet = bb->out.d();
+  double* d_quad = d_logdet + B;
+  long long* d_info = (long long*)(d_logdet + 2 * B);
+  double* d_grad = bb->res.d();
+  double* d_alpha = d_grad + B * P;
+  double* d_diagA = d_alpha + B * n;
+  uint32_t* d_which = (uint32_t*)bb->part.p;
+  double* partial = (double*)((char*)bb->part.p + which_bytes);
+  if (P > 0)
+    GH_HIP(hipMemcpyAsync(d_which, which, sizeof(uint32_t) * P,
+                          gh_is_device_ptr(which) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+
+  // ---- build: K, the residual tile and the identity rows below it, the output tiles (zero)
+  BatchPBuild a;
+  a.nodes = in.nodes; a.n_nodes = (int)k->nodes.size(); a.ndim = ndim;
+  a.fast = in.fast;
+  a.x = in.x; a.n = n; a.xs = nullptr; a.m = np;
+  a.yerr = in.yerr; a.r = in.r;
+  a.A = A; a.np = np; a.stride = stride;
+  a.O = O; a.ostride = ostride; a.mt = (int)nt; a.kss = 2;
+  a.info = d_info; a.ktiles = ktiles; a.ptiles = ptiles; a.tiles = tiles;
+  const dim3 gb((unsigned)(B * tiles * 4)), blk(256);
+  if (a.fast) hipLaunchKernelGGL((batch_pbuild_kernel<true, true>), gb, blk, 0, st, a);
+  else        hipLaunchKernelGGL((batch_pbuild_kernel<false, true>), gb, blk, 0, st, a);
+  GH_HIP(hipGetLastError());
+
+  // ---- factorisation of K; the residual tile and the identity row tiles that are non-zero in column j carried along
+  for (long j = 0; j < nt; ++j) {
+    hipLaunchKernelGGL(batch_potf2_kernel, dim3((unsigned)B), blk, 0, st, A, ld, stride, dinv, dstride, d_info, (int)j);
+    const long below = nt + 1;                   // K's tiles below (j, j), the residual tile, identity row tiles 0 .. j
+    hipLaunchKernelGGL(batch_trsm_kernel, dim3((unsigned)(B * below)), blk, 0, st, A, ld, stride, (const double*)dinv, dstride,
+                       (const long long*)d_info, (int)j, (int)below);
+    const long w = nt - j - 1;                   // trailing tile columns of K
+    if (w > 0) {
+      const long pairs = w * (w + 1) / 2 + (j + 2) * w;      // rows nt (residual) .. nt + 1 + j (identity tile j)
+      hipLaunchKernelGGL(batch_trap_kernel, dim3((unsigned)(B * pairs)), blk, 0, st, A, ld, stride, (const long long*)d_info,
+                         (int)j, (int)nt, pairs);
+    }
+    GH_HIP(hipGetLastError());
+  }
+  // ---- -z^T z, -alpha and -K^-1 in one launch; logdet and quad; the gradient reduction
+  hipLaunchKernelGGL(batch_gschur_kernel, dim3((unsigned)(B * q)), blk, 0, st, (const double*)A, ld, stride, O, ostride, (long)T,
+                     (const long long*)d_info, (int)nt, q);
+  hipLaunchKernelGGL(batch_reduce_kernel, dim3((unsigned)B), blk, 0, st, (const double*)A, ld, stride, np, (const double*)O,
+                     ostride, (const long long*)d_info, d_logdet, d_quad);
+  BatchGrad g;
+  g.nodes = in.nodes; g.n_nodes = (int)k->nodes.size(); g.ndim = ndim; g.P = P;
+  g.which = d_which; g.x = in.x; g.n = n;
+  g.O = O; g.ostride = ostride; g.nt = nt;
+  g.info = d_info; g.partial = partial; g.alpha = d_alpha; g.diagA = d_diagA; g.nblk = nblk;
+  const dim3 gg((unsigned)(B * nblk));
+  if (P <= 4)       hipLaunchKernelGGL(batch_kgrad_kernel<4>, gg, blk, 0, st, g);
+  else if (P <= 16) hipLaunchKernelGGL(batch_kgrad_kernel<16>, gg, blk, 0, st, g);
+  else              hipLaunchKernelGGL(batch_kgrad_kernel<GH_MAX_GRAD>, gg, blk, 0, st, g);
+  if (P > 0)
+    hipLaunchKernelGGL(batch_kgrad_final_kernel, dim3((unsigned)(B * P)), blk, 0, st, (const double*)partial, nblk, P,
+                       (const long long*)d_info, d_grad);
+  GH_HIP(hipGetLastError());
+
+  // ---- results: straight into the caller's arrays, one synchronisation
+  auto kind = [](const void* p) { return gh_is_device_ptr(p) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost; };
+  if (P > 0) GH_HIP(hipMemcpyAsync(grad, d_grad, (size_t)B * P * sizeof(double), kind(grad), st));
+  if (alpha) GH_HIP(hipMemcpyAsync(alpha, d_alpha, (size_t)B * n * sizeof(double), kind(alpha), st));
+  if (diagA) GH_HIP(hipMemcpyAsync(diagA, d_diagA, (size_t)B * n * sizeof(double), kind(diagA), st));
+  bb->back.resize((size_t)3 * B);
+  GH_HIP(hipMemcpyAsync(bb->back.data(), d_logdet, (size_t)3 * B * sizeof(double), hipMemcpyDeviceToHost, st));
+  GH_HIP(hipStreamSynchronize(st));
+  const double* hb = bb->back.data();
+  GH_CHECK(batch_put(logdet, hb, (size_t)B * sizeof(double)));
+  GH_CHECK(batch_put(quad, hb + B, (size_t)B * sizeof(double)));
   GH_CHECK(batch_put(info, hb + 2 * B, (size_t)B * sizeof(int64_t)));
   return GH_OK;
 }

@@ -377,6 +377,51 @@ class GP(ModelSet):
             return self._log_likelihood_batch_device(vectors, y, quiet)
         return self._log_likelihood_batch_loop(vectors, y, quiet)
 
+    def _batch_blocks(self, vectors):
+        """{model name: its FULL parameter rows (B, full size)} for rows in ``get_parameter_vector()`` order."""
+        blocks, at = {}, 0
+        for name in ("mean", "white_noise", "kernel"):
+            m = self.models[name]
+            full = np.tile(m.get_parameter_vector(include_frozen=True), (len(vectors), 1))
+            k = int(m.unfrozen_mask.sum())
+            full[:, m.unfrozen_mask] = vectors[:, at:at + k]
+            blocks[name] = full
+            at += k
+        return blocks
+
+    def _batch_values(self, name, rows, arg):
+        """(B, len(arg)): model ``name``'s ``get_value(arg)`` at each of its full parameter rows.  A ConstantModel is mapped
+        column-wise; any other model is set row by row and restored."""
+        m = self.models[name]
+        B = len(rows)
+        if type(m) is ConstantModel:
+            return rows[:, :1] + np.zeros((B, len(arg)))              # ConstantModel.get_value, row by row
+        out = np.empty((B, len(arg)))
+        for b, v in enumerate(self._per_member(m, rows, lambda: m.get_value(arg))):
+            out[b] = v.flatten()
+        return out
+
+    def _batch_gradients(self, name, rows, arg):
+        """[model ``name``'s ``get_gradient(arg)`` at row b for b in range(B)].  A ConstantModel's gradient does not depend on
+        its value: it is evaluated once."""
+        m = self.models[name]
+        if type(m) is ConstantModel:
+            return [m.get_gradient(arg)] * len(rows)
+        return self._per_member(m, rows, lambda: m.get_gradient(arg))
+
+    @staticmethod
+    def _per_member(m, rows, fn):
+        saved, was_dirty = m.get_parameter_vector(include_frozen=True), m.dirty
+        out = []
+        try:
+            for row in rows:
+                m.set_parameter_vector(row, include_frozen=True)
+                out.append(fn())
+        finally:
+            m.set_parameter_vector(saved, include_frozen=True)
+            m.dirty = was_dirty
+        return out
+
     def _batch_inputs(self, vectors, y, quiet, t=None):
         """Per-member (full kernel parameter rows (B, kernel.full_size), sigma (B, N), r (B, N), ok (B,)) for rows in
         ``get_parameter_vector()`` order: exactly what ``set_parameter_vector(v)`` followed by ``compute`` / ``_residual``
@@ -385,30 +430,10 @@ class GP(ModelSet):
         points ``t`` ((M, ndim), parsed) the tuple has a fifth entry, the mean model at ``t`` (B, M), and ``ok`` also
         requires that one to be finite."""
         B, n = len(vectors), len(self._x)
-        blocks, at = {}, 0
-        for name in ("mean", "white_noise", "kernel"):
-            m = self.models[name]
-            full = np.tile(m.get_parameter_vector(include_frozen=True), (B, 1))
-            k = int(m.unfrozen_mask.sum())
-            full[:, m.unfrozen_mask] = vectors[:, at:at + k]
-            blocks[name] = full
-            at += k
+        blocks = self._batch_blocks(vectors)
 
         def values(name, arg):
-            m = self.models[name]
-            rows = blocks[name]
-            if type(m) is ConstantModel:
-                return rows[:, :1] + np.zeros((B, len(arg)))          # ConstantModel.get_value, row by row
-            saved, was_dirty = m.get_parameter_vector(include_frozen=True), m.dirty
-            out = np.empty((B, len(arg)))
-            try:
-                for b in range(B):
-                    m.set_parameter_vector(rows[b], include_frozen=True)
-                    out[b] = m.get_value(arg).flatten()
-            finally:
-                m.set_parameter_vector(saved, include_frozen=True)
-                m.dirty = was_dirty
-            return out
+            return self._batch_values(name, blocks[name], arg)
 
         def check(mu, where):
             ok = np.all(np.isfinite(mu), axis=1)                       # (_call_mean raises where this is False)
@@ -561,6 +586,133 @@ class GP(ModelSet):
             if np.all(np.isfinite(mu[b])):
                 out[b] = multivariate_gaussian_samples(cov[b], size, mean=mu[b])
         return out
+
+    # -- many gradients at once (multi-start fits, per-iteration re-fits, gradient-based ensembles) -----------------------
+    def grad_log_likelihood_batch(self, vectors, y, quiet=True):
+        """``grad_log_likelihood(y, quiet)`` at each row of ``vectors`` (shape ``(B, len(gp))``, ``get_parameter_vector()``
+        order), as an array of shape ``(B, len(gp))`` ordered mean | white_noise | kernel.  Uses the ``x`` and ``yerr`` of
+        the last ``compute``.  With the HIP :class:`BasicSolver`, ``N <= BasicSolver.BATCH_MAX_N`` and one member's device
+        buffers within ``BasicSolver.BATCH_MAX_BYTES`` the B members are factorised, inverted and reduced together
+        (gh_chol_objective_grad_batch); otherwise the rows go through ``set_parameter_vector`` + ``grad_log_likelihood``
+        one by one, with the same results.  A member whose matrix is not positive definite, or whose mean is not finite,
+        has a zero gradient with ``quiet=True``; with ``quiet=False`` the first one raises (``np.linalg.LinAlgError`` /
+        ``ValueError`` naming it).  The GP's parameter vector, ``computed`` flag, factorisation and caches are what they
+        were before the call."""
+        vectors, y = self._grad_batch_args(vectors, y)
+        if len(vectors) == 0:
+            return np.empty((0, len(self)))
+        if self._grad_batch_on_device():
+            return self._grad_batch_device(vectors, y, quiet)[1]
+        out = np.empty((len(vectors), len(self)))
+        with self._state_kept():
+            for b, v in enumerate(vectors):
+                self.set_parameter_vector(v)
+                try:
+                    out[b] = self.grad_log_likelihood(y, quiet=quiet)
+                except ValueError as e:                                # (np.linalg.LinAlgError is one)
+                    raise type(e)("member {0}: {1}".format(b, e))
+        return out
+
+    def nll_and_grad_batch(self, vectors, y, quiet=True):
+        """``nll_and_grad(v, y, quiet)`` at each row ``v`` of ``vectors``: ``(nll (B,), grad (B, len(gp)))``.  A row
+        outside the prior gives ``(inf, 0)`` and is not evaluated; a failed member gives ``(inf, 0)`` with ``quiet=True``.
+        Routing, errors and the GP's state as :meth:`grad_log_likelihood_batch`."""
+        vectors, y = self._grad_batch_args(vectors, y)
+        B = len(vectors)
+        nll, grad = np.full(B, np.inf), np.zeros((B, len(self)))
+        if B == 0:
+            return nll, grad
+        idx = np.flatnonzero(self._batch_in_prior(vectors))
+        if not len(idx):
+            return nll, grad
+        if self._grad_batch_on_device():
+            ll, g = self._grad_batch_device(vectors[idx], y, quiet, index=idx)
+            nll[idx], grad[idx] = -ll, -g
+            return nll, grad
+        with self._state_kept():
+            for b in idx:
+                try:
+                    nll[b], grad[b] = self.nll_and_grad(vectors[b], y, quiet=quiet)
+                except ValueError as e:
+                    raise type(e)("member {0}: {1}".format(b, e))
+        return nll, grad
+
+    def _grad_batch_args(self, vectors, y):
+        if not (hasattr(self, "_x") and hasattr(self, "_yerr2")):
+            raise RuntimeError("you must call 'compute' first")
+        vectors = np.asarray(vectors, dtype=np.float64)
+        if vectors.ndim != 2 or vectors.shape[1] != len(self):
+            raise ValueError("vectors must have shape (B, {0})".format(len(self)))
+        return vectors, np.asarray(self._check_dimensions(y), dtype=np.float64)
+
+    def _grad_batch_on_device(self):
+        n = len(self._x)
+        return (self.solver_type is BasicSolver and n <= BasicSolver.BATCH_MAX_N
+                and BasicSolver.grad_batch_bytes(n) <= BasicSolver.BATCH_MAX_BYTES)
+
+    def _batch_in_prior(self, vectors):
+        """(B,) bool: is ``log_prior()`` finite at each row (evaluated on the GP's own models, then restored)?"""
+        inside = np.empty(len(vectors), dtype=bool)
+        with self._state_kept():
+            for b, v in enumerate(vectors):
+                ModelSet.set_parameter_vector(self, v)
+                inside[b] = np.isfinite(self.log_prior())
+        return inside
+
+    def _grad_batch_device(self, vectors, y, quiet, index=None):
+        """(log-likelihood (B,), gradient (B, len(gp))) of every row from one batched device call; failed members are
+        (-inf, 0) or, with ``quiet=False``, the first one in row order raises (named by ``index[b]`` when given)."""
+        kp, sigma, r, ok = self._batch_inputs(vectors, y, True)
+        solver = BasicSolver(self.kernel, **(self.solver_kwargs))      # (its own pooled handle: self.solver is untouched)
+        which = self.kernel.unfrozen_mask.astype(np.uint32)
+        logdet, quad, kg, alpha, diagA, info = solver.objective_grad_batch(kp, self._x, sigma, r, which)
+        with np.errstate(invalid="ignore", over="ignore"):
+            grad, ok_g = self._assemble_grad_batch(vectors, alpha, diagA, kg)
+            ll = -0.5 * (len(self._x) * np.log(2 * np.pi) + logdet) - 0.5 * quad
+        bad = ~ok | (info != 0) | ~ok_g
+        if not quiet and bad.any():
+            b = int(np.argmax(bad))
+            name = b if index is None else int(index[b])
+            if not ok[b]:
+                raise ValueError("member {0}: mean function returned NaN or Inf for parameters:\n{1}".format(
+                    name, self._batch_blocks(vectors[b:b + 1])["mean"][0]))
+            if info[b] != 0:
+                raise np.linalg.LinAlgError("member {0}: {1}-th leading minor of the array is not positive definite".format(
+                    name, int(info[b])))
+            raise ValueError("member {0}: mean gradient function returned NaN or Inf for parameters:\n{1}".format(
+                name, self._batch_blocks(vectors[b:b + 1])["mean"][0]))
+        ll[bad | ~np.isfinite(ll)] = -np.inf
+        grad[bad] = 0.0
+        return ll, grad
+
+    def _assemble_grad_batch(self, vectors, alpha, diagA, kgrad):
+        """Row b is ``set_parameter_vector(vectors[b])`` + ``_assemble_grad(alpha[b], diagA[b], kgrad[b][kernel mask])``,
+        bit for bit, without touching the GP's state: the gradient counterpart of :meth:`_batch_inputs`.  ``alpha``,
+        ``diagA``: (B, N); ``kgrad``: (B, kernel.full_size).  Returns ``(grad (B, len(gp)), ok (B,))``; ``ok[b]`` is False
+        (and the row zero) where the mean gradient is not finite, where ``_assemble_grad`` raises or, quiet, returns zeros."""
+        B = len(vectors)
+        blocks = self._batch_blocks(vectors)
+        arg = self._model_arg(self._x)
+        n_m, n_wn, n_k = len(self.mean), len(self.white_noise), len(self.kernel)
+        grad = np.empty((B, len(self)))
+        ok = np.ones(B, dtype=bool)
+        at = 0
+        if n_m:
+            for b, mg in enumerate(self._batch_gradients("mean", blocks["mean"], arg)):
+                if np.any(np.isnan(mg)) or np.any(np.isinf(mg)):
+                    ok[b] = False
+                else:
+                    grad[b, at:at + n_m] = np.dot(mg, alpha[b])
+            at += n_m
+        if n_wn:
+            wn = self._batch_values("white_noise", blocks["white_noise"], arg)
+            for b, wng in enumerate(self._batch_gradients("white_noise", blocks["white_noise"], arg)):
+                grad[b, at:at + n_wn] = 0.5 * np.sum((np.exp(wn[b]) * diagA[b])[None, :] * wng, axis=1)
+            at += n_wn
+        if n_k:
+            grad[:, at:at + n_k] = np.asarray(kgrad)[:, self.kernel.unfrozen_mask]
+        grad[~ok] = 0.0
+        return grad, ok
 
     def predict(self, y, t, return_cov=True, return_var=False, cache=True, kernel=None):
         """Conditional mean and (co)variance at ``t``  (gp.py:482-545)."""

@@ -337,6 +337,57 @@ class BasicSolver(object):
         res = m + (m if return_var else m * m if return_cov else 0)
         return ((np_ + 128 + mp) * np_ + np_ * 128 + (mt + 1 + kss) * 128 * 128 + res) * 8
 
+    def objective_grad_batch(self, params, x, sigma, r, which=None):
+        """B log-likelihood pieces and kernel gradients over one set of points (gh_chol_objective_grad_batch): member b is
+        objective_batch's member b.  ``which``: the kernel's parameter mask (all by default), shared by the members.
+        Returns ``(logdet (B,), quad (B,), grad (B, kernel.full_size), alpha (B, N), diagA (B, N), info (B,))`` with
+        ``grad[b] = 1/2 sum_ij A_ij dK_ij/dtheta`` (masked entries 0), ``alpha[b] = K_b^-1 r_b`` and ``diagA[b] =
+        diag(alpha alpha^T - K_b^-1)``; a member with ``info[b] != 0`` has NaN rows.  Runs on objective_batch's pooled
+        handle, in chunks under BATCH_MAX_BYTES."""
+        x = N.as_f64(x)
+        if x.ndim != 2:
+            raise ValueError("x must be (nsamples, ndim)")
+        n = len(x)
+        params = N.as_f64(params)
+        B = params.shape[0] if params.ndim == 2 else -1
+        dk = DeviceKernel(self.kernel)
+        if B < 0 or params.shape[1] != dk.size:
+            raise ValueError("params must be (B, {0})".format(dk.size))
+        sigma = N.as_f64(np.broadcast_to(sigma, (B, n)))
+        r = N.as_f64(r)
+        if r.shape != (B, n):
+            raise ValueError("dimension mismatch")
+        if x.shape[1] != dk.ndim:
+            raise RuntimeError("dimension mismatch")
+        wh = np.ones(max(dk.size, 1), dtype=np.uint32)
+        if which is not None:
+            which = np.asarray(which)
+            if which.shape != (dk.size,):
+                raise ValueError("which must have shape ({0},)".format(dk.size))
+            wh[:dk.size] = which != 0
+        logdet, quad, info = np.empty(B), np.empty(B), np.zeros(B, dtype=np.int64)
+        grad, alpha, diagA = np.zeros((B, max(dk.size, 1))), np.empty((B, n)), np.empty((B, n))
+        if B > 0:
+            chunk = int(max(1, min(B, BasicSolver.BATCH_MAX_BYTES // self.grad_batch_bytes(n))))
+            for b0 in range(0, B, chunk):
+                b1 = min(B, b0 + chunk)
+                self._retry_without_parked_memory(lambda hh: N.check(N.lib.gh_chol_objective_grad_batch(
+                    hh, dk.handle, N.ptr(params[b0:b1]), b1 - b0, N.ptr(x), n, x.shape[1], N.ptr(sigma[b0:b1]),
+                    N.ptr(r[b0:b1]), N.ptr(wh), N.ptr(logdet[b0:]), N.ptr(quad[b0:]), N.ptr(grad[b0:]), N.ptr(alpha[b0:]),
+                    N.ptr(diagA[b0:]), N.ptr(info[b0:]))), ensure=self._ensure_batch_handle)
+        return logdet, quad, grad[:, :dk.size], alpha, diagA, info
+
+    @staticmethod
+    def grad_batch_bytes(n):
+        """Device bytes of one member of objective_grad_batch: its panel (2 Np + 128 rows of Np: K, the residual tile, the
+        identity rows that become L^-T), the inverses of its diagonal blocks, its 128 x 128 output tiles (Np / 128 + 1 for
+        -z^T z and -alpha, the lower tiles of -K^-1), its results (grad, alpha, diagA) and the partial rows of the gradient
+        reduction, both counted at the largest parameter count (64)."""
+        np_ = -(-n // 128) * 128
+        nt, gm = np_ // 128, -(-n // 64)
+        q = nt + 1 + nt * (nt + 1) // 2
+        return ((2 * np_ + 128) * np_ + np_ * 128 + q * 128 * 128 + 64 + 2 * n + gm * (gm + 1) // 2 * 64) * 8
+
     def _need(self):
         if self._computed and self._handle is None and getattr(self, "_factor_state", None) is not None:
             self._restore()

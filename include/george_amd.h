@@ -209,6 +209,18 @@ int  gh_chol_predict_batch(gh_chol* s, gh_kernel* k, const double* params, int32
                            const double* x, int64_t n, int32_t ndim, const double* yerr, const double* r,
                            const double* xs, int64_t m, double* mu, double* var, double* cov,
                            double* logdet, double* quad, int64_t* info);
+/* B rounds of compute gp.py:303-337 + log_likelihood :369-397 + the kernel part of grad_log_likelihood :429-466, one device
+ * call.  params, x, yerr, r, info: as gh_chol_objective_batch.  which: (gh_kernel_size(k)) mask shared by all members.
+ *   logdet[b], quad[b]      as gh_chol_objective_batch (logdet bit-identical to it)
+ *   grad[b] (P)             1/2 sum_ij A_ij dK_ij/dtheta_p, A = alpha alpha^T - K_b^-1; masked entries exactly 0
+ *   alpha[b] (n)            K_b^-1 r_b                                     (or NULL)
+ *   diagA[b] (n)            diag(A)                                        (or NULL)
+ * A failed member has info[b] != 0 and NaN in every output row; GH_OK whenever every member was evaluated.  Any pointer
+ * may be host or device memory.  The handle is left NOT computed. */
+int  gh_chol_objective_grad_batch(gh_chol* s, gh_kernel* k, const double* params, int32_t nbatch,
+                                  const double* x, int64_t n, int32_t ndim, const double* yerr, const double* r,
+                                  const uint32_t* which, double* logdet, double* quad, double* grad,
+                                  double* alpha, double* diagA, int64_t* info);
 /* Checkpointing of the device factor (the reference's BasicSolver pickles COMPUTED,
  * tests/test_pickle.py:21-36, because its factor is a NumPy array, basic.py:68): the lower
  * triangle of L packed by rows (gh_chol_factor_size() = n (n + 1) / 2 doubles) and the inverses of
@@ -220,7 +232,7 @@ int  gh_chol_export_factor(gh_chol* s, double* packed_lower, double* dinv_out);
 int  gh_chol_import_factor(gh_chol* s, int64_t n, int32_t ndim, const double* x,
                            const double* packed_lower, const double* dinv_in, double logdet);
 /* memory management of a long-lived handle: trim() frees the transient work buffers of predict /
- * grad / get_inverse (up to 3 x 8 N^2 bytes) and the buffers of objective_batch / predict_batch, and keeps the factor;
+ * grad / get_inverse (up to 3 x 8 N^2 bytes) and the buffers of objective_batch / predict_batch / objective_grad_batch, and keeps the factor;
  * release_buffers() frees everything but the handle (streams, events) -- the next compute() re-allocates. */
 void gh_chol_trim(gh_chol* s);
 void gh_chol_release_buffers(gh_chol* s);
