@@ -6,15 +6,23 @@
 // serial chain of 128-column steps, and a sampler step used to run B such chains one after the other.  Here every launch of
 // ONE chain carries all B members: the launch count is that of one problem and each launch does B times the work.
 //
-// Bordered storage.  Member b owns an (np + 128) x (np + 128) row-major block, np = N rounded up to 128.  The top-left
-// np x np holds K_b with identity padding (as the one-problem build pads), row np holds r_b^T (zero-padded), the rest of the
-// border tile row is zero.  The right-looking factorisation over the first np / 128 tile columns then leaves
-// z_b = L_b^-1 r_b in border row np and -r_b^T K_b^-1 r_b at [np][np]: there is no separate triangular solve.  Per step j,
-// three launches over all members:
+// One layout.  Member b owns a row-major panel of rt tile rows (128 rows each) of pitch ld; np = N rounded up to 128,
+// nt = np / 128.  The top nt tile rows hold K_b with identity padding (as the one-problem build pads); tile row nt is the
+// residual tile, r_b^T (zero-padded) in its first row; the tile rows below it are carried rows: the test rows of a prediction,
+// the rows of the identity for a gradient, none for the plain objective.  Besides the panel the member has q 128 x 128 output
+// tiles.  The right-looking factorisation over K's nt tile columns leaves z_b = L_b^-1 r_b in row np and the carried rows
+// times L_b^-T below it: there is no separate triangular solve.  Per step j, three launches over all members (batch_chain):
 //   potf2 : tile (j, j) -> L_jj and L_jj^-1 (gh_potf2::potf2_body; info per member);
-//   TRSM  : tiles (i, j), i > j, border tile included:  P <- P L_jj^-T      (gh_tile128_nt_sp<false>);
-//   SYRK  : lower tiles (i, l), j < l <= i, border row included:  C -= P_i P_l^T, K = 128   (gh_tile128_nt_sp<true>).
-// A member whose info is set returns from every later kernel at once.
+//   TRSM  : tiles (i, j), i > j, of K, the residual tile and the carried rows:  P <- P L_jj^-T   (gh_tile128_nt_sp<false>);
+//   update: tiles (i, l), j < l < ld / 128, l <= i:  C -= P_i P_l^T, K = 128   (gh_tile128_nt_sp<true>, batch_trap_kernel).
+// A member whose info is set returns from every later kernel at once.  The three entry points are three shapes of it:
+//   objective: ld = np + 128, rt = nt + 1, nothing carried.  The panel is a bordered square; its one output tile is the corner
+//              tile at [np][np], INSIDE the panel, so the update's triangle takes it in and the chain itself leaves
+//              -r_b^T K_b^-1 r_b at [np][np].  (The border column tiles above the corner are never written or read.)
+//   predict  : ld = np, rt = nt + 1 + mt, the mt test tile rows carried at every step.  One Schur launch after the chain
+//              (batch_schur_kernel, K = np) forms the output tiles -z^T z, -V^T z and K** - V^T V.
+//   gradient : ld = np, rt = 2 nt + 1, identity rows: at step j only identity row tiles 0 .. j are non-zero and carried; the
+//              Schur launch skips each tile's leading zero k-tiles.
 //
 // Bits.  The one-problem factorisation (gh_chol.hip) applies the same updates to every tile in the same k order, only in
 // longer K (panel widths, rows-below TRSM): every k-major x k-major kernel shares one k assignment (gh_gemm_tile.h) and a
@@ -27,13 +35,14 @@
 #include <algorithm>
 #include <vector>
 #include "gh_common.h"
+#include "gh_device_util.h"
 #include "gh_gemm_tile.h"
 #include "gh_potf2_body.h"
 
 #define T 128
 
 struct GhBatchBufs {
-  GhBuf A;                     // B bordered blocks
+  GhBuf A;                     // B panels
   GhBuf dinv;                  // B x (np / 128) inverses of the 128 x 128 diagonal blocks
   GhBuf in;                    // [member nodes | member fast forms | x | yerr | r] (the last three when they come from the host)
   GhBuf out;                   // [logdet (B) | quad (B) | info (B)]
@@ -52,97 +61,77 @@ size_t gh_batch_bytes(const GhBatchBufs* b) {
 }
 void gh_batch_free(GhBatchBufs* b) { delete b; }
 
-// lower-triangular enumeration t -> (ti, tj), tj <= ti (as gh_kmat.hip's tri_index)
-__device__ __forceinline__ void batch_tri_index(long t, int& ti, int& tj) {
-  long i = (long)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-  while (i * (i + 1) / 2 > t) --i;
-  while ((i + 1) * (i + 2) / 2 <= t) ++i;
-  ti = (int)i;
-  tj = (int)(t - i * (i + 1) / 2);
-}
 // wave-uniform: has member b failed at an earlier step?
 __device__ __forceinline__ bool member_failed(const long long* info, int b) {
   return __builtin_amdgcn_readfirstlane((int)(info[b] != 0)) != 0;
 }
 
 // ---------------------------------------------------------------------------------------------------- build
-struct BatchBuild {
-  const GhNode* nodes; int n_nodes; int ndim;    // member b's program: nodes + b * n_nodes
-  const GhFast* fast;                            // (B) when every member has the a + b F(r^2) form
-  const double* x; long n;                       // (n, ndim), shared
-  const double* yerr; const double* r;           // (B, n)
-  double* A; long ld, np, stride;                // member b's block: A + b * stride, row pitch ld = np + 128
-  long long* info;                               // (B): cleared here
-  long tiles;                                    // 128-tiles per member: the lower triangle of the (np / 128 + 1)^2 tile grid
-};
-// blockIdx.x = member * 4 * tiles + 4 * tile + quadrant: one 64 x 64 quarter of a lower 128-tile, as kmat_tile_of builds them
-template <bool FAST>
-__global__ __launch_bounds__(256) void batch_build_kernel(BatchBuild a) {
-  const long q4 = (long)blockIdx.x;
-  const int b = (int)(q4 / (4 * a.tiles));
-  const long t = (q4 / 4) % a.tiles;
-  const int quad = (int)(q4 & 3);
-  int TI, TJ;
-  batch_tri_index(t, TI, TJ);
-  if (t == 0 && quad == 0 && threadIdx.x == 0) a.info[b] = 0;
-  const long r0 = (long)TI * T + (quad >> 1) * 64, c0 = (long)TJ * T + (quad & 1) * 64;
-  const GhNode* prog = a.nodes + (long)b * a.n_nodes;
-  const double* yerr = a.yerr + (long)b * a.n;
-  const double* res = a.r + (long)b * a.n;
-  double* Ab = a.A + (long)b * a.stride;
-  const int nd = a.ndim;
-  const int lc = (threadIdx.x & 31) * 2, lr = threadIdx.x >> 5;
-  for (int pass = 0; pass < 8; ++pass) {
-    const long r = r0 + lr + pass * 8, c = c0 + lc;
-    double v[2];
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const long cc = c + e;
-      double val;
-      if (r < a.n && cc < a.n) {
-        const double* p1 = a.x + r * nd;
-        const double* p2 = a.x + cc * nd;
-        // k(x_min, x_max), the argument order of kmat_generic_tile's symmetric build
-        const bool swap = r > cc;
-        val = FAST ? gh_fast_value(a.fast[b], swap ? p2 : p1, swap ? p1 : p2)
-                   : gh_eval_value(prog, a.n_nodes, swap ? p2 : p1, swap ? p1 : p2);
-        if (r == cc) { const double e2 = yerr[r]; val += e2 * e2; }
-      } else if (r < a.np) {
-        val = (r == cc) ? 1.0 : 0.0;             // identity padding
-      } else if (r == a.np) {
-        val = cc < a.n ? res[cc] : 0.0;          // the border row: r_b^T
-      } else {
-        val = 0.0;
-      }
-      v[e] = val;
-    }
-    *reinterpret_cast<double2*>(Ab + r * a.ld + c) = make_double2(v[0], v[1]);
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------- predict: build
 struct BatchPBuild {
   const GhNode* nodes; int n_nodes; int ndim;    // member b's program: nodes + b * n_nodes
   const GhFast* fast;                            // (B) when every member has the a + b F(r^2) form
   const double* x; long n;                       // (n, ndim), shared
   const double* xs; long m;                      // (m, ndim), shared
   const double* yerr; const double* r;           // (B, n)
-  double* A; long np, stride;                    // member b's panel: A + b * stride, (np + 128 + mp) rows of pitch np
-  double* O; long ostride; int mt, kss;          // member b's output tiles: O + b * ostride; kss: K** tiles 0 none, 1 diagonal, 2 lower
+  double* A; long ld, np, stride;                // member b's panel: A + b * stride, (np + 128 + mp) rows of pitch ld
+  double* O; long ostride;                       // member b's output tile u (not in the panel): O + b * ostride + u * 128 * 128
+  int mt, kss;                                   // carried tile rows; K** tiles: 0 none, 1 diagonal, 2 lower
   long long* info;                               // (B): cleared here
   long ktiles, ptiles, tiles;                    // per member: K's lower tiles, + the panel tiles below K, + the output tiles
 };
-// blockIdx.x = member * 4 * tiles + 4 * tile + quadrant (64 x 64 quarters, as batch_build_kernel).  Tiles, in order: K's lower
-// triangle (batch_build_kernel's elements), the (1 + mt) x nt panel tiles below it (residual tile, then test rows), the mt + 1
+// blockIdx.x = member * 4 * tiles + 4 * tile + quadrant: one 64 x 64 quarter of a 128-tile, as kmat_tile_of builds them.  Tiles,
+// in order: K's lower triangle, the (1 + mt) x nt panel tiles below it (residual tile, then carried rows), the mt + 1
 // residual-column output tiles (zero), the K** output tiles.
-// EYE (gh_chol_objective_grad_batch): the m = np test rows are the identity and the K** tiles zero.
-template <bool FAST, bool EYE = false>
+// ROWS, what is carried below the residual tile: 1 the test rows k(x_i, xs_c), with K** output tiles; 2 the rows of the identity
+// (gh_chol_objective_grad_batch; the K** tiles zero); 0 nothing, and the one output tile is the panel's corner tile (the
+// objective's bordered square): every tile is then a panel tile, the lower triangle of the (nt + 1)^2 tile grid in tri_index order.
+template <bool FAST, int ROWS>
 __global__ __launch_bounds__(256) void batch_pbuild_kernel(BatchPBuild a) {
   const long q4 = (long)blockIdx.x;
   const int b = (int)(q4 / (4 * a.tiles));
   const long t = (q4 / 4) % a.tiles;
   const int quad = (int)(q4 & 3);
   if (t == 0 && quad == 0 && threadIdx.x == 0) a.info[b] = 0;
+  if constexpr (ROWS == 0) {
+    // the bordered square on its own: measured 3 % faster with the 17-node walker than the general body below compiled for
+    // "nothing carried" (profiles/batch/refactor_ab.md), so the objective keeps the build it always had
+    int TI, TJ;
+    tri_index(t, TI, TJ);
+    const long r0 = (long)TI * T + (quad >> 1) * 64, c0 = (long)TJ * T + (quad & 1) * 64;
+    const GhNode* prog = a.nodes + (long)b * a.n_nodes;
+    const double* yerr = a.yerr + (long)b * a.n;
+    const double* res = a.r + (long)b * a.n;
+    double* Ab = a.A + (long)b * a.stride;
+    const int nd = a.ndim;
+    const int lc = (threadIdx.x & 31) * 2, lr = threadIdx.x >> 5;
+    for (int pass = 0; pass < 8; ++pass) {
+      const long r = r0 + lr + pass * 8, c = c0 + lc;
+      double v[2];
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const long cc = c + e;
+        double val;
+        if (r < a.n && cc < a.n) {
+          const double* p1 = a.x + r * nd;
+          const double* p2 = a.x + cc * nd;
+          // k(x_min, x_max), the argument order of kmat_generic_tile's symmetric build
+          const bool swap = r > cc;
+          val = FAST ? gh_fast_value(a.fast[b], swap ? p2 : p1, swap ? p1 : p2)
+                     : gh_eval_value(prog, a.n_nodes, swap ? p2 : p1, swap ? p1 : p2);
+          if (r == cc) { const double e2 = yerr[r]; val += e2 * e2; }
+        } else if (r < a.np) {
+          val = (r == cc) ? 1.0 : 0.0;             // identity padding
+        } else if (r == a.np) {
+          val = cc < a.n ? res[cc] : 0.0;          // the border row: r_b^T
+        } else {
+          val = 0.0;
+        }
+        v[e] = val;
+      }
+      *reinterpret_cast<double2*>(Ab + r * a.ld + c) = make_double2(v[0], v[1]);
+    }
+    return;
+  }
   const long nt = a.np / T;
   const GhNode* prog = a.nodes + (long)b * a.n_nodes;
   const int nd = a.ndim;
@@ -153,7 +142,7 @@ __global__ __launch_bounds__(256) void batch_pbuild_kernel(BatchPBuild a) {
   long TI, TJ, u = 0;
   if (t < a.ktiles) {
     int ti, tj;
-    batch_tri_index(t, ti, tj);
+    tri_index(t, ti, tj);
     kind = 0; TI = ti; TJ = tj;
   } else if (t < a.ktiles + a.ptiles) {
     const long v = t - a.ktiles;
@@ -163,14 +152,14 @@ __global__ __launch_bounds__(256) void batch_pbuild_kernel(BatchPBuild a) {
   } else {
     const long v = t - a.ktiles - a.ptiles - a.mt - 1;
     kind = 3; u = a.mt + 1 + v;
-    if (a.kss == 1) { TI = TJ = v; } else { int ti, tj; batch_tri_index(v, ti, tj); TI = ti; TJ = tj; }
+    if (a.kss == 1) { TI = TJ = v; } else { int ti, tj; tri_index(v, ti, tj); TI = ti; TJ = tj; }
   }
   const long r0 = TI * T + (quad >> 1) * 64, c0 = TJ * T + (quad & 1) * 64;
   const double* yerr = a.yerr + (long)b * a.n;
   const double* res = a.r + (long)b * a.n;
   double* dst;
   long ld;
-  if (kind <= 1) { dst = a.A + (long)b * a.stride + r0 * a.np + c0; ld = a.np; }
+  if (kind <= 1) { dst = a.A + (long)b * a.stride + r0 * a.ld + c0; ld = a.ld; }
   else { dst = a.O + (long)b * a.ostride + u * T * T + (quad >> 1) * 64 * T + (quad & 1) * 64; ld = T; }
   const int lc = (threadIdx.x & 31) * 2, lr = threadIdx.x >> 5;
   for (int pass = 0; pass < 8; ++pass) {
@@ -184,7 +173,7 @@ __global__ __launch_bounds__(256) void batch_pbuild_kernel(BatchPBuild a) {
         if (r < a.n && cc < a.n) {
           const double* p1 = a.x + r * nd;
           const double* p2 = a.x + cc * nd;
-          const bool swap = r > cc;              // k(x_min, x_max), as batch_build_kernel
+          const bool swap = r > cc;              // k(x_min, x_max), as above
           val = kval(swap ? p2 : p1, swap ? p1 : p2);
           if (r == cc) { const double e2 = yerr[r]; val += e2 * e2; }
         } else {
@@ -193,9 +182,9 @@ __global__ __launch_bounds__(256) void batch_pbuild_kernel(BatchPBuild a) {
       } else if (kind == 1) {
         const long c_s = r - a.np - T;           // test row index
         if (r == a.np) val = cc < a.n ? res[cc] : 0.0;
-        else if (EYE) val = (c_s == cc) ? 1.0 : 0.0;
+        else if (ROWS == 2) val = (c_s == cc) ? 1.0 : 0.0;
         else if (c_s >= 0 && c_s < a.m && cc < a.n) val = kval(a.x + cc * nd, a.xs + c_s * nd);   // k(x_i, xs_c)
-      } else if (kind == 3 && !EYE && r < a.m && cc < a.m) {
+      } else if (kind == 3 && ROWS == 1 && r < a.m && cc < a.m) {
         const bool swap = r > cc;                // the one-problem symmetric build: k(xs_min, xs_max), no noise
         val = kval(a.xs + (swap ? cc : r) * nd, a.xs + (swap ? r : cc) * nd);
       }
@@ -218,7 +207,7 @@ __global__ __launch_bounds__(256, 2) void batch_potf2_kernel(double* A, long ld,
   (void)gh_potf2::potf2_body(A + (long)b * stride + j0 * ld + j0, ld, dinv + (long)b * dstride + (long)j * T * T, info + b,
                              (long long)j0, s, dscr, &fail_at);
 }
-// tile (j + 1 + t, j) <- tile L_jj^-T for t < m (m - 1 tiles below the diagonal and the border tile); blockIdx.x = member * m + t
+// tile (j + 1 + t, j) <- tile L_jj^-T for t < m (K's tiles below the diagonal, the residual tile, carried tiles); blockIdx.x = member * m + t
 __global__ __launch_bounds__(256, 2) void batch_trsm_kernel(double* A, long ld, long stride, const double* dinv, long dstride,
                                                             const long long* info, int j, int m) {
   const int b = blockIdx.x / m;
@@ -228,75 +217,61 @@ __global__ __launch_bounds__(256, 2) void batch_trsm_kernel(double* A, long ld, 
   double* P = A + (long)b * stride + i * T * ld + (long)j * T;
   gh_tile128_nt_sp<false>(sm, P, ld, P, ld, dinv + (long)b * dstride + (long)j * T * T, T, T);
 }
-// tile (i, l) -= P_i P_l^T, j < l <= i (border row included), K = 128; blockIdx.x = member * m (m + 1) / 2 + pair
-__global__ __launch_bounds__(256, 2) void batch_syrk_kernel(double* A, long ld, long stride, const long long* info, int j, long pairs) {
-  const int b = (int)(blockIdx.x / pairs);
-  if (member_failed(info, b)) return;
-  __shared__ __attribute__((aligned(1024))) double sm[4 * BM * BK];
-  int ti, tl;
-  batch_tri_index((long)(blockIdx.x % pairs), ti, tl);
-  const long i = j + 1 + ti, l = j + 1 + tl;
-  double* Ab = A + (long)b * stride;
-  gh_tile128_nt_sp<true>(sm, Ab + i * T * ld + l * T, ld, Ab + i * T * ld + (long)j * T, ld, Ab + l * T * ld + (long)j * T, ld, T);
-}
-
-// predict: tile (i, l) -= P_i P_l^T for j < l < nt and l <= i < rt -- K's trailing triangle, then the rectangle of the panel rows
-// below K (residual and test tiles); the border columns wait for batch_schur_kernel.  K = 128; blockIdx.x = member * pairs + pair.
-__global__ __launch_bounds__(256, 2) void batch_trap_kernel(double* A, long ld, long stride, const long long* info, int j, int nt,
+// tile (i, l) -= P_i P_l^T for j < l < tc and l <= i: the trailing triangle over tile columns j + 1 .. tc - 1, then the rectangle
+// of the tile rows from tc on (as many as `pairs` covers).  tc = nt: K's triangle, then the residual and carried tiles below K
+// (their border columns wait for batch_schur_kernel); tc = nt + 1 (the objective): the residual tile row and the corner tile are
+// in the triangle and there is no rectangle.  K = 128; blockIdx.x = member * pairs + pair.
+__global__ __launch_bounds__(256, 2) void batch_trap_kernel(double* A, long ld, long stride, const long long* info, int j, int tc,
                                                             long pairs) {
   const int b = (int)(blockIdx.x / pairs);
   if (member_failed(info, b)) return;
   __shared__ __attribute__((aligned(1024))) double sm[4 * BM * BK];
-  const long p = (long)(blockIdx.x % pairs), w = nt - j - 1, tri = w * (w + 1) / 2;
+  const long p = (long)(blockIdx.x % pairs), w = tc - j - 1, tri = w * (w + 1) / 2;
   long i, l;
   if (p < tri) {
     int ti, tl;
-    batch_tri_index(p, ti, tl);
+    tri_index(p, ti, tl);
     i = j + 1 + ti; l = j + 1 + tl;
   } else {
-    i = nt + (p - tri) / w; l = j + 1 + (p - tri) % w;
+    i = tc + (p - tri) / w; l = j + 1 + (p - tri) % w;
   }
   double* Ab = A + (long)b * stride;
   gh_tile128_nt_sp<true>(sm, Ab + i * T * ld + l * T, ld, Ab + i * T * ld + (long)j * T, ld, Ab + l * T * ld + (long)j * T, ld, T);
 }
-// predict, after the chain: output tile u of member b, C -= P_a P_b^T with K = np.  u <= mt: panel row tile nt + u against the
-// residual tile nt (u = 0: -z^T z at [0][0]; u > 0: -V^T z in column 0); u > mt: test tiles (c, d) of K** - V^T V (kss 1:
-// the diagonal tiles, kss 2: the lower ones).  blockIdx.x = member * q + u.
+// After the chain: output tile u of member b, C -= P_a P_b^T with K = np.  u <= mt: panel row tile nt + u against the residual
+// tile nt (u = 0: -z^T z at [0][0]; u > 0: -V^T z in column 0); u > mt: carried tiles (c, d) of K** - V^T V (kss 1: the
+// diagonal tiles, kss 2: the lower ones).  blockIdx.x = member * q + u.
+// KSKIP (the gradient; mt = nt, kss = 2, K** = 0): the carried rows, the identity's, have become W = L^-T, upper triangular:
+// W's row tile c is zero left of k-tile c, and each product starts at its first non-zero k-tile (the products skipped are exact
+// zeros).  u = 0: K = np as ever; 0 < u <= nt: W's row tile u - 1 against the residual tile: -alpha in column 0; u > nt: lower
+// tile (c, d) of -W W^T = -K^-1, from k-tile c on.
 // (ldo, the output tiles' pitch, is 128 but a kernel argument: as a constant it lets the compiler fold and keep addresses live
 // until the K = np loop spills)
+template <bool KSKIP>
 __global__ __launch_bounds__(256, 2) void batch_schur_kernel(const double* A, long ld, long stride, double* O, long ostride,
                                                              long ldo, const long long* info, int nt, int mt, int kss, long q) {
   const int b = (int)(blockIdx.x / q);
   if (member_failed(info, b)) return;
   __shared__ __attribute__((aligned(1024))) double sm[4 * BM * BK];
   const long u = (long)(blockIdx.x % q);
-  long ia, ib;
+  long ia, ib, k0 = 0;
   if (u <= mt) {
     ia = nt + u; ib = nt;
-  } else if (kss == 1) {
+    if (KSKIP && u > 0) k0 = (u - 1) * T;
+  } else if (!KSKIP && kss == 1) {
     ia = ib = nt + u - mt;
   } else {
     int ti, tl;
-    batch_tri_index(u - mt - 1, ti, tl);
+    tri_index(u - mt - 1, ti, tl);
     ia = nt + 1 + ti; ib = nt + 1 + tl;
+    if (KSKIP) k0 = (long)ti * T;
   }
   const double* Ab = A + (long)b * stride;
-  gh_tile128_nt_sp<true>(sm, O + (long)b * ostride + u * T * T, ldo, Ab + ia * T * ld, ld, Ab + ib * T * ld, ld, ld);
+  gh_tile128_nt_sp<true>(sm, O + (long)b * ostride + u * T * T, ldo, Ab + ia * T * ld + k0, ld, Ab + ib * T * ld + k0, ld,
+                         ld - k0);
 }
 
 // ---------------------------------------------------------------------------------------------------- reductions
-// (wave_sum / block_sum_256 of gh_chol.hip, the same operations in the same order)
-__device__ __forceinline__ double batch_wave_sum(double v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ double batch_block_sum_256(double v, double* sh) {
-  v = batch_wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
 // logdet[b] = 2 sum_i log L_b[i][i] over the np diagonal entries in launch_logdet's order (gh_chol.hip: g contiguous slices,
 // each summed by 256 lanes and a block reduction, the slices added in index order); quad[b] = -A_b[np][np].  Failed members: NaN.
 // (qsrc + b * qstride: where -quad[b] is, A_b[np][np] for the objective, O_b[0][0] for predict)
@@ -314,14 +289,14 @@ __global__ __launch_bounds__(256) void batch_reduce_kernel(const double* A, long
   if (g <= 1) {
     double v = 0.0;
     for (long i = threadIdx.x; i < np; i += 256) v += log(Ab[i * ld + i]);
-    tot = batch_block_sum_256(v, sh);
+    tot = block_sum_256(v, sh);
   } else {
     const long per = (np + g - 1) / g;
     for (long s = 0; s < g; ++s) {
       const long lo = s * per, hi = lo + per < np ? lo + per : np;
       double v = 0.0;
       for (long i = lo + threadIdx.x; i < hi; i += 256) v += log(Ab[i * ld + i]);
-      tot += batch_block_sum_256(v, sh);
+      tot += block_sum_256(v, sh);
     }
   }
   if (threadIdx.x == 0) {
@@ -353,30 +328,6 @@ __global__ __launch_bounds__(256) void batch_pfinal_kernel(const double* O, long
 }
 
 // ---------------------------------------------------------------------------------------------------- gradient
-// grad, after the chain: output tile u of member b, C -= P_a P_b^T from k-tile k0 on.  The np identity rows below the residual
-// tile have become W = L^-T, upper triangular: W's row tile c is zero left of k-tile c, and those k are skipped (the products
-// there are exact zeros).  u = 0: the residual tile against itself, K = np: -z^T z at [0][0]; 0 < u <= nt: W's row tile u - 1
-// against the residual tile: -alpha in column 0; u > nt: lower tile (c, d) of -W W^T = -K^-1, from k-tile c on.
-// blockIdx.x = member * q + u.  (ldo: as batch_schur_kernel)
-__global__ __launch_bounds__(256, 2) void batch_gschur_kernel(const double* A, long ld, long stride, double* O, long ostride,
-                                                              long ldo, const long long* info, int nt, long q) {
-  const int b = (int)(blockIdx.x / q);
-  if (member_failed(info, b)) return;
-  __shared__ __attribute__((aligned(1024))) double sm[4 * BM * BK];
-  const long u = (long)(blockIdx.x % q);
-  long ia, ib, k0;
-  if (u <= nt) {
-    ia = nt + u; ib = nt; k0 = u > 0 ? (u - 1) * T : 0;
-  } else {
-    int ti, tl;
-    batch_tri_index(u - nt - 1, ti, tl);
-    ia = nt + 1 + ti; ib = nt + 1 + tl; k0 = (long)ti * T;
-  }
-  const double* Ab = A + (long)b * stride;
-  gh_tile128_nt_sp<true>(sm, O + (long)b * ostride + u * T * T, ldo, Ab + ia * T * ld + k0, ld, Ab + ib * T * ld + k0, ld,
-                         ld - k0);
-}
-
 // The batched form of gh_kmat.hip's kgrad_reduce_kernel: one 64 x 64 tile of member b's lower triangle per workgroup, member b's
 // program, alpha and K^-1 read from its output tiles (negated: exact), the same per-element weights (1/2 on the diagonal) and
 // the same wave / cross-wave reduction; one partial row per (member, tile).  The diagonal writes alpha[b] and diagA[b]; a failed
@@ -386,7 +337,7 @@ struct BatchGrad {
   const GhNode* nodes; int n_nodes; int ndim; int P;   // member b's program: nodes + b * n_nodes
   const uint32_t* which;                               // (P), shared by every member
   const double* x; long n;                             // (n, ndim), shared
-  const double* O; long ostride; long nt;              // member b's output tiles (batch_gschur_kernel): O + b * ostride
+  const double* O; long ostride; long nt;              // member b's output tiles (batch_schur_kernel<true>): O + b * ostride
   const long long* info;
   double* partial;                                     // (B, nblk, P)
   double* alpha; double* diagA;                        // (B, n)
@@ -401,7 +352,7 @@ __global__ __launch_bounds__(256, PMAX <= 16 ? 4 : 1) void batch_kgrad_kernel(Ba
   const int b = (int)(blockIdx.x / a.nblk);
   const long t = (long)(blockIdx.x % a.nblk);
   int ti, tj;
-  batch_tri_index(t, ti, tj);
+  tri_index(t, ti, tj);
   const long r0 = (long)ti * GT, c0 = (long)tj * GT, n = a.n;
   const int nd = a.ndim, P = a.P;
   if (member_failed(a.info, b)) {
@@ -552,6 +503,122 @@ static int batch_stage(gh_kernel* k, GhBatchBufs* bb, hipStream_t st, const doub
   return GH_OK;
 }
 
+// The shape of one call's panels (the file header has the three).
+struct BatchShape {
+  long ld, rt;                                   // pitch (np, or np + 128: the corner tile is in the panel) and tile rows
+  int rows;                                      // carried below the residual tile: 0 nothing, 1 test rows, 2 identity rows
+  long carry0, carry1;                           // carried tile rows in play at step j: carry0 + carry1 * j
+  long q; int kss;                               // output tiles per member; the K** ones among them: 0 none, 1 diagonal, 2 lower
+  long blocks;                                   // the largest per-member grid of what follows the chain (the launch-size guard)
+};
+// A call's stream and buffers (gh_chol_batch_begin, by the entry point) and what batch_chain leaves to it, all on the device.
+struct BatchChain {
+  hipStream_t st; GhBatchBufs* bb; BatchInputs in;
+  long B, np, nt, ld, stride;                    // member b's panel: A + b * stride
+  double* A;
+  double* O; long ostride;                       // member b's output tile u: O + b * ostride + u * 128 * 128
+  double* logdet; double* quad; long long* info; // (B) each, contiguous: bb->out
+};
+// The launch-size guard: no grid of the call may pass 2^31 - 1 workgroups (the build's is the largest of the chain's).
+static int batch_guard(const char* who, long B, long nt, const BatchShape& sh) {
+  const long tiles = nt * (nt + 1) / 2 + (sh.rt - nt) * nt + sh.q;
+  if (B * tiles * 4 > 0x7fffffffL || B * sh.blocks > 0x7fffffffL) {
+    gh_set_error("%s: batch too large for one call", who);
+    return GH_ERR_BAD_ARG;
+  }
+  return GH_OK;
+}
+// Prologue of all three entry points: the launch-size guard, ONE staging copy, the buffers of the panels and output tiles.
+static int batch_prepare(gh_kernel* k, const char* who, const double* params, long B, const double* x, long n,
+                       int ndim, const double* yerr, const double* r, const double* xs, long m, const BatchShape& sh,
+                       BatchChain* c) {
+  const long np = gh_round_up(n, T), nt = np / T, ld = sh.ld, tc = ld / T;
+  const long stride = sh.rt * T * ld, dstride = nt * T * T;
+  GH_CHECK(batch_guard(who, B, nt, sh));
+  hipStream_t st = c->st;
+  GhBatchBufs* bb = c->bb;
+  GH_CHECK(batch_stage(k, bb, st, params, B, x, n, ndim, yerr, r, xs, m, &c->in));
+  GH_CHECK(bb->A.ensure((size_t)B * stride * sizeof(double)));
+  GH_CHECK(bb->dinv.ensure((size_t)B * dstride * sizeof(double)));
+  GH_CHECK(bb->out.ensure((size_t)3 * B * sizeof(double)));
+  const bool corner = tc > nt;                   // the one output tile is the panel's corner tile
+  if (!corner) GH_CHECK(bb->O.ensure((size_t)B * sh.q * T * T * sizeof(double)));
+  double* A = bb->A.d();
+  double* dinv = bb->dinv.d();
+  c->B = B; c->np = np; c->nt = nt; c->ld = ld; c->stride = stride;
+  c->A = A;
+  c->O = corner ? A + np * ld + np : bb->O.d();
+  c->ostride = corner ? stride : sh.q * T * T;
+  c->logdet = bb->out.d();
+  c->quad = c->logdet + B;
+  c->info = (long long*)(c->logdet + 2 * B);
+  return GH_OK;
+}
+// Build and factorisation chain of all three entry points: every panel and output tile, then three launches per 128-column
+// step over every member.
+static int batch_chain(gh_kernel* k, long n, int ndim, long m, const BatchShape& sh, BatchChain* c) {
+  const long B = c->B, np = c->np, nt = c->nt, ld = c->ld, tc = ld / T, stride = c->stride, dstride = nt * T * T;
+  const long ktiles = nt * (nt + 1) / 2, ptiles = (sh.rt - nt) * nt, tiles = ktiles + ptiles + sh.q;
+  hipStream_t st = c->st;
+  double* A = c->A;
+  double* dinv = c->bb->dinv.d();
+  const long long* info = c->info;
+
+  // ---- build: K, the residual tile and the carried rows below it, the output tiles
+  BatchPBuild a;
+  a.nodes = c->in.nodes; a.n_nodes = (int)k->nodes.size(); a.ndim = ndim;
+  a.fast = c->in.fast;
+  a.x = c->in.x; a.n = n; a.xs = c->in.xs; a.m = m;
+  a.yerr = c->in.yerr; a.r = c->in.r;
+  a.A = A; a.ld = ld; a.np = np; a.stride = stride;
+  a.O = c->O; a.ostride = c->ostride;
+  a.mt = (int)(sh.rt - nt - 1); a.kss = sh.kss;
+  a.info = c->info; a.ktiles = ktiles; a.ptiles = ptiles; a.tiles = tiles;
+  const dim3 gb((unsigned)(B * tiles * 4)), blk(256);
+  void (*build)(BatchPBuild) =
+      sh.rows == 0 ? (a.fast ? batch_pbuild_kernel<true, 0> : batch_pbuild_kernel<false, 0>)
+      : sh.rows == 1 ? (a.fast ? batch_pbuild_kernel<true, 1> : batch_pbuild_kernel<false, 1>)
+                     : (a.fast ? batch_pbuild_kernel<true, 2> : batch_pbuild_kernel<false, 2>);
+  hipLaunchKernelGGL(build, gb, blk, 0, st, a);
+  GH_HIP(hipGetLastError());
+
+  // ---- factorisation of K, the residual tile and the carried rows in play carried along
+  for (long j = 0; j < nt; ++j) {
+    hipLaunchKernelGGL(batch_potf2_kernel, dim3((unsigned)B), blk, 0, st, A, ld, stride, dinv, dstride, c->info, (int)j);
+    const long rows = nt + 1 + sh.carry0 + sh.carry1 * j;     // tile rows in play: K, the residual tile, the carried tiles
+    const long below = rows - j - 1;
+    hipLaunchKernelGGL(batch_trsm_kernel, dim3((unsigned)(B * below)), blk, 0, st, A, ld, stride, (const double*)dinv, dstride,
+                       info, (int)j, (int)below);
+    const long w = tc - j - 1;                   // trailing tile columns
+    if (w > 0) {
+      const long pairs = w * (w + 1) / 2 + (rows - tc) * w;   // their triangle, the rectangle of the rows below it
+      hipLaunchKernelGGL(batch_trap_kernel, dim3((unsigned)(B * pairs)), blk, 0, st, A, ld, stride, info, (int)j, (int)tc, pairs);
+    }
+    GH_HIP(hipGetLastError());
+  }
+  return GH_OK;
+}
+// logdet[b] from the factor's diagonal and quad[b] = -(output tile 0)[0][0]
+static void batch_logdet_quad(const BatchChain& c) {
+  hipLaunchKernelGGL(batch_reduce_kernel, dim3((unsigned)c.B), dim3(256), 0, c.st, (const double*)c.A, c.ld, c.stride, c.np,
+                     (const double*)c.O, c.ostride, (const long long*)c.info, c.logdet, c.quad);
+}
+// [logdet | quad | info]: one copy back, the call's one synchronisation, then the caller's pointers (logdet, quad: optional)
+static int batch_finish(const BatchChain& c, double* logdet, double* quad, int64_t* info) {
+  const size_t B = (size_t)c.B;
+  c.bb->back.resize(3 * B);
+  GH_HIP(hipMemcpyAsync(c.bb->back.data(), c.logdet, 3 * B * sizeof(double), hipMemcpyDeviceToHost, c.st));
+  GH_HIP(hipStreamSynchronize(c.st));
+  const double* hb = c.bb->back.data();
+  if (logdet) GH_CHECK(batch_put(logdet, hb, B * sizeof(double)));
+  if (quad) GH_CHECK(batch_put(quad, hb + B, B * sizeof(double)));
+  GH_CHECK(batch_put(info, hb + 2 * B, B * sizeof(int64_t)));
+  return GH_OK;
+}
+static hipMemcpyKind batch_from_device(const void* dst) {
+  return gh_is_device_ptr(dst) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+}
+
 extern "C" int gh_chol_objective_batch(gh_chol* s, gh_kernel* k, const double* params, int32_t nbatch,
                                        const double* x, int64_t n, int32_t ndim, const double* yerr, const double* r,
                                        double* logdet, double* quad, int64_t* info) {
@@ -561,63 +628,17 @@ extern "C" int gh_chol_objective_batch(gh_chol* s, gh_kernel* k, const double* p
   }
   if (ndim != k->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
   if (nbatch == 0) return GH_OK;
-  hipStream_t st = nullptr;
-  GhBatchBufs* bb = nullptr;
-  GH_CHECK(gh_chol_batch_begin(s, &st, &bb));
-  const long B = nbatch, np = gh_round_up(n, T), nt = np / T, ld = np + T;
-  const long stride = ld * ld, dstride = nt * T * T;
-  const long tiles = (nt + 1) * (nt + 2) / 2;
-  if (B * tiles * 4 > 0x7fffffffL) { gh_set_error("objective_batch: batch too large for one call"); return GH_ERR_BAD_ARG; }
-  BatchInputs in;
-  GH_CHECK(batch_stage(k, bb, st, params, B, x, n, ndim, yerr, r, nullptr, 0, &in));
-  GH_CHECK(bb->A.ensure((size_t)B * stride * sizeof(double)));
-  GH_CHECK(bb->dinv.ensure((size_t)B * dstride * sizeof(double)));
-  GH_CHECK(bb->out.ensure((size_t)3 * B * sizeof(double)));
-  double* A = bb->A.d();
-  double* dinv = bb->dinv.d();
-  double* d_logdet = bb->out.d();
-  double* d_quad = d_logdet + B;
-  long long* d_info = (long long*)(d_logdet + 2 * B);
-
-  // ---- build
-  BatchBuild a;
-  a.nodes = in.nodes; a.n_nodes = (int)k->nodes.size(); a.ndim = ndim;
-  a.fast = in.fast;
-  a.x = in.x; a.n = n;
-  a.yerr = in.yerr;
-  a.r = in.r;
-  a.A = A; a.ld = ld; a.np = np; a.stride = stride; a.info = d_info; a.tiles = tiles;
-  const dim3 gb((unsigned)(B * tiles * 4)), blk(256);
-  if (a.fast) hipLaunchKernelGGL(batch_build_kernel<true>, gb, blk, 0, st, a);
-  else      hipLaunchKernelGGL(batch_build_kernel<false>, gb, blk, 0, st, a);
+  const long np = gh_round_up(n, T), nt = np / T;
+  BatchShape sh;
+  sh.ld = np + T; sh.rt = nt + 1; sh.rows = 0; sh.carry0 = sh.carry1 = 0; sh.q = 1; sh.kss = 0; sh.blocks = 0;
+  BatchChain c;
+  GH_CHECK(gh_chol_batch_begin(s, &c.st, &c.bb));
+  GH_CHECK(batch_prepare(k, "objective_batch", params, nbatch, x, n, ndim, yerr, r, nullptr, 0, sh, &c));
+  GH_CHECK(batch_chain(k, n, ndim, 0, sh, &c));
+  batch_logdet_quad(c);
   GH_HIP(hipGetLastError());
-
-  // ---- factorisation: three launches per 128-column step, each over every member
-  for (long j = 0; j < nt; ++j) {
-    hipLaunchKernelGGL(batch_potf2_kernel, dim3((unsigned)B), blk, 0, st, A, ld, stride, dinv, dstride, d_info, (int)j);
-    const long m = nt - j;                       // tiles j + 1 .. nt (the border tile is tile nt)
-    hipLaunchKernelGGL(batch_trsm_kernel, dim3((unsigned)(B * m)), blk, 0, st, A, ld, stride, (const double*)dinv, dstride,
-                       (const long long*)d_info, (int)j, (int)m);
-    const long pairs = m * (m + 1) / 2;
-    hipLaunchKernelGGL(batch_syrk_kernel, dim3((unsigned)(B * pairs)), blk, 0, st, A, ld, stride, (const long long*)d_info,
-                       (int)j, pairs);
-    GH_HIP(hipGetLastError());
-  }
-  hipLaunchKernelGGL(batch_reduce_kernel, dim3((unsigned)B), blk, 0, st, (const double*)A, ld, stride, np,
-                     (const double*)A + np * ld + np, stride, (const long long*)d_info, d_logdet, d_quad);
-  GH_HIP(hipGetLastError());
-
-  // ---- results: one copy back, one synchronisation
-  bb->back.resize((size_t)3 * B);
-  GH_HIP(hipMemcpyAsync(bb->back.data(), d_logdet, (size_t)3 * B * sizeof(double), hipMemcpyDeviceToHost, st));
-  GH_HIP(hipStreamSynchronize(st));
-  const double* hb = bb->back.data();
-  GH_CHECK(batch_put(logdet, hb, (size_t)B * sizeof(double)));
-  GH_CHECK(batch_put(quad, hb + B, (size_t)B * sizeof(double)));
-  GH_CHECK(batch_put(info, hb + 2 * B, (size_t)B * sizeof(int64_t)));
-  return GH_OK;
+  return batch_finish(c, logdet, quad, info);
 }
-
 
 extern "C" int gh_chol_predict_batch(gh_chol* s, gh_kernel* k, const double* params, int32_t nbatch,
                                      const double* x, int64_t n, int32_t ndim, const double* yerr, const double* r,
@@ -630,95 +651,41 @@ extern "C" int gh_chol_predict_batch(gh_chol* s, gh_kernel* k, const double* par
   }
   if (ndim != k->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
   if (nbatch == 0) return GH_OK;
-  hipStream_t st = nullptr;
-  GhBatchBufs* bb = nullptr;
-  GH_CHECK(gh_chol_batch_begin(s, &st, &bb));
-  const long B = nbatch, np = gh_round_up(n, T), nt = np / T, mp = gh_round_up(m, T), mt = mp / T;
+  const long B = nbatch, np = gh_round_up(n, T), nt = np / T, mt = gh_round_up(m, T) / T;
   const int kss = cov ? 2 : var ? 1 : 0;
-  const long ld = np, rt = nt + 1 + mt, stride = rt * T * ld, dstride = nt * T * T;
   const long q = mt + 1 + (kss == 2 ? mt * (mt + 1) / 2 : kss == 1 ? mt : 0);     // output tiles per member
-  const long ostride = q * T * T;
-  const long ktiles = nt * (nt + 1) / 2, ptiles = (1 + mt) * nt, tiles = ktiles + ptiles + q;
   const long per = m + (kss == 2 ? m * m : kss == 1 ? m : 0), fblocks = (per + 255) / 256;
-  if (B * tiles * 4 > 0x7fffffffL || B * fblocks > 0x7fffffffL) {
-    gh_set_error("predict_batch: batch too large for one call");
-    return GH_ERR_BAD_ARG;
-  }
-  BatchInputs in;
-  GH_CHECK(batch_stage(k, bb, st, params, B, x, n, ndim, yerr, r, xs, m, &in));
-  GH_CHECK(bb->A.ensure((size_t)B * stride * sizeof(double)));
-  GH_CHECK(bb->dinv.ensure((size_t)B * dstride * sizeof(double)));
-  GH_CHECK(bb->out.ensure((size_t)3 * B * sizeof(double)));
-  GH_CHECK(bb->O.ensure((size_t)B * ostride * sizeof(double)));
-  if (per > 0) GH_CHECK(bb->res.ensure((size_t)B * per * sizeof(double)));
-  double* A = bb->A.d();
-  double* dinv = bb->dinv.d();
-  double* O = bb->O.d();
-  double* d_logdet = bb->out.d();
-  double* d_quad = d_logdet + B;
-  long long* d_info = (long long*)(d_logdet + 2 * B);
-  double* d_mu = per > 0 ? bb->res.d() : nullptr;
+  BatchShape sh;
+  sh.ld = np; sh.rt = nt + 1 + mt; sh.rows = 1; sh.carry0 = mt; sh.carry1 = 0; sh.q = q; sh.kss = kss; sh.blocks = fblocks;
+  BatchChain c;
+  GH_CHECK(gh_chol_batch_begin(s, &c.st, &c.bb));
+  GH_CHECK(batch_prepare(k, "predict_batch", params, B, x, n, ndim, yerr, r, xs, m, sh, &c));
+  GH_CHECK(batch_chain(k, n, ndim, m, sh, &c));
+  if (per > 0) GH_CHECK(c.bb->res.ensure((size_t)B * per * sizeof(double)));
+  double* d_mu = per > 0 ? c.bb->res.d() : nullptr;
   double* d_second = per > 0 ? d_mu + B * m : nullptr;            // var (B, m) or cov (B, m, m)
+  hipStream_t st = c.st;
+  const dim3 blk(256);
 
-  // ---- build: K, the residual and test rows below it, the output tiles
-  BatchPBuild a;
-  a.nodes = in.nodes; a.n_nodes = (int)k->nodes.size(); a.ndim = ndim;
-  a.fast = in.fast;
-  a.x = in.x; a.n = n; a.xs = in.xs; a.m = m;
-  a.yerr = in.yerr; a.r = in.r;
-  a.A = A; a.np = np; a.stride = stride;
-  a.O = O; a.ostride = ostride; a.mt = (int)mt; a.kss = kss;
-  a.info = d_info; a.ktiles = ktiles; a.ptiles = ptiles; a.tiles = tiles;
-  const dim3 gb((unsigned)(B * tiles * 4)), blk(256);
-  if (a.fast) hipLaunchKernelGGL(batch_pbuild_kernel<true>, gb, blk, 0, st, a);
-  else        hipLaunchKernelGGL(batch_pbuild_kernel<false>, gb, blk, 0, st, a);
-  GH_HIP(hipGetLastError());
-
-  // ---- factorisation of K, every panel row below it carried along: three launches per step, each over every member
-  for (long j = 0; j < nt; ++j) {
-    hipLaunchKernelGGL(batch_potf2_kernel, dim3((unsigned)B), blk, 0, st, A, ld, stride, dinv, dstride, d_info, (int)j);
-    const long below = rt - j - 1;               // K's tiles below (j, j), the residual tile, the test tiles
-    hipLaunchKernelGGL(batch_trsm_kernel, dim3((unsigned)(B * below)), blk, 0, st, A, ld, stride, (const double*)dinv, dstride,
-                       (const long long*)d_info, (int)j, (int)below);
-    const long w = nt - j - 1;                   // trailing tile columns of K
-    if (w > 0) {
-      const long pairs = w * (w + 1) / 2 + (1 + mt) * w;
-      hipLaunchKernelGGL(batch_trap_kernel, dim3((unsigned)(B * pairs)), blk, 0, st, A, ld, stride, (const long long*)d_info,
-                         (int)j, (int)nt, pairs);
-    }
-    GH_HIP(hipGetLastError());
-  }
   // ---- the border: one launch of K = np tile products, then logdet and the caller's layout
-  hipLaunchKernelGGL(batch_schur_kernel, dim3((unsigned)(B * q)), blk, 0, st, (const double*)A, ld, stride, O, ostride, (long)T,
-                     (const long long*)d_info, (int)nt, (int)mt, kss, q);
-  hipLaunchKernelGGL(batch_reduce_kernel, dim3((unsigned)B), blk, 0, st, (const double*)A, ld, stride, np, (const double*)O,
-                     ostride, (const long long*)d_info, d_logdet, d_quad);
+  hipLaunchKernelGGL(batch_schur_kernel<false>, dim3((unsigned)(B * q)), blk, 0, st, (const double*)c.A, c.ld, c.stride, c.O,
+                     c.ostride, (long)T, (const long long*)c.info, (int)nt, (int)mt, kss, q);
+  batch_logdet_quad(c);
   if (per > 0)
-    hipLaunchKernelGGL(batch_pfinal_kernel, dim3((unsigned)(B * fblocks)), blk, 0, st, (const double*)O, ostride,
-                       (const long long*)d_info, (long)m, (int)mt, kss, per, fblocks, d_mu, d_second, d_second);
+    hipLaunchKernelGGL(batch_pfinal_kernel, dim3((unsigned)(B * fblocks)), blk, 0, st, (const double*)c.O, c.ostride,
+                       (const long long*)c.info, (long)m, (int)mt, kss, per, fblocks, d_mu, d_second, d_second);
   GH_HIP(hipGetLastError());
 
-  // ---- results: straight into the caller's arrays, one synchronisation
-  auto kind = [](const void* p) { return gh_is_device_ptr(p) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost; };
+  // ---- results: straight into the caller's arrays
   double* second = kss == 2 ? cov : var;
-  if (m > 0) GH_HIP(hipMemcpyAsync(mu, d_mu, (size_t)B * m * sizeof(double), kind(mu), st));
-  if (kss) GH_HIP(hipMemcpyAsync(second, d_second, (size_t)B * (per - m) * sizeof(double), kind(second), st));
-  bb->back.resize((size_t)3 * B);
-  GH_HIP(hipMemcpyAsync(bb->back.data(), d_logdet, (size_t)3 * B * sizeof(double), hipMemcpyDeviceToHost, st));
-  GH_HIP(hipStreamSynchronize(st));
-  const double* hb = bb->back.data();
-  if (logdet) GH_CHECK(batch_put(logdet, hb, (size_t)B * sizeof(double)));
-  if (quad) GH_CHECK(batch_put(quad, hb + B, (size_t)B * sizeof(double)));
-  GH_CHECK(batch_put(info, hb + 2 * B, (size_t)B * sizeof(int64_t)));
-  return GH_OK;
+  if (m > 0) GH_HIP(hipMemcpyAsync(mu, d_mu, (size_t)B * m * sizeof(double), batch_from_device(mu), st));
+  if (kss) GH_HIP(hipMemcpyAsync(second, d_second, (size_t)B * (per - m) * sizeof(double), batch_from_device(second), st));
+  return batch_finish(c, logdet, quad, info);
 }
 
-
-// B rounds of objective + gradient (gh_chol_objective with a gradient, gh_chol.hip): predict_batch's panel with the np rows of
-// the identity in place of the test rows.  The chain turns them into W = L^-T, upper triangular, so at step j only the identity
-// row tiles 0 .. j are carried (the TRSM covers tiles j + 1 .. nt + 1 + j, the trapezoid rows nt .. nt + 1 + j); one Schur
-// launch from each tile's first non-zero k-tile on leaves -z^T z, -alpha and the lower tiles of -K^-1 (batch_gschur_kernel);
-// then logdet / quad (batch_reduce_kernel, as predict_batch) and the gradient reduction over all members.
+// B rounds of objective + gradient (gh_chol_objective with a gradient, gh_chol.hip): the chain turns the np identity rows into
+// W = L^-T; one Schur launch leaves -z^T z, -alpha and the lower tiles of -K^-1 (batch_schur_kernel<true>); then logdet / quad
+// and the gradient reduction over all members.
 extern "C" int gh_chol_objective_grad_batch(gh_chol* s, gh_kernel* k, const double* params, int32_t nbatch,
                                             const double* x, int64_t n, int32_t ndim, const double* yerr, const double* r,
                                             const uint32_t* which, double* logdet, double* quad, double* grad,
@@ -732,100 +699,52 @@ extern "C" int gh_chol_objective_grad_batch(gh_chol* s, gh_kernel* k, const doub
   if (ndim != k->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
   if (nbatch == 0) return GH_OK;
   const long B = nbatch, np = gh_round_up(n, T), nt = np / T;
-  const long ld = np, rt = 2 * nt + 1, stride = rt * T * ld, dstride = nt * T * T;
-  const long q = nt + 1 + nt * (nt + 1) / 2, ostride = q * T * T;            // output tiles per member
-  const long ktiles = nt * (nt + 1) / 2, ptiles = (1 + nt) * nt, tiles = ktiles + ptiles + q;
+  const long q = nt + 1 + nt * (nt + 1) / 2;                                   // output tiles per member
   const int P = k->size;
   const long gm = (n + GT - 1) / GT, nblk = gm * (gm + 1) / 2;
-  if (B * tiles * 4 > 0x7fffffffL || B * nblk > 0x7fffffffL) {
-    gh_set_error("objective_grad_batch: batch too large for one call");
-    return GH_ERR_BAD_ARG;
-  }
-  hipStream_t st = nullptr;
-  GhBatchBufs* bb = nullptr;
-  GH_CHECK(gh_chol_batch_begin(s, &st, &bb));
-  BatchInputs in;
-  GH_CHECK(batch_stage(k, bb, st, params, B, x, n, ndim, yerr, r, nullptr, 0, &in));
+  BatchShape sh;
+  sh.ld = np; sh.rt = 2 * nt + 1; sh.rows = 2; sh.carry0 = sh.carry1 = 1; sh.q = q; sh.kss = 2; sh.blocks = nblk;
+  BatchChain c;
+  GH_CHECK(batch_guard("objective_grad_batch", B, nt, sh));     // (before the handle is touched, as ever; batch_prepare repeats it)
+  GH_CHECK(gh_chol_batch_begin(s, &c.st, &c.bb));
+  GH_CHECK(batch_prepare(k, "objective_grad_batch", params, B, x, n, ndim, yerr, r, nullptr, 0, sh, &c));
   const size_t which_bytes = align256(sizeof(uint32_t) * (P > 0 ? P : 1));
-  GH_CHECK(bb->A.ensure((size_t)B * stride * sizeof(double)));
-  GH_CHECK(bb->dinv.ensure((size_t)B * dstride * sizeof(double)));
-  GH_CHECK(bb->out.ensure((size_t)3 * B * sizeof(double)));
-  GH_CHECK(bb->O.ensure((size_t)B * ostride * sizeof(double)));
-  GH_CHECK(bb->res.ensure((size_t)B * (P + 2 * n) * sizeof(double)));
-  GH_CHECK(bb->part.ensure(which_bytes + (size_t)B * nblk * (P > 0 ? P : 1) * sizeof(double)));
-  double* A = bb->A.d();
-  double* dinv = bb->dinv.d();
-  double* O = bb->O.d();
-  double* d_logdet = bb->out.d();
-  double* d_quad = d_logdet + B;
-  long long* d_info = (long long*)(d_logdet + 2 * B);
-  double* d_grad = bb->res.d();
+  GH_CHECK(c.bb->res.ensure((size_t)B * (P + 2 * n) * sizeof(double)));
+  GH_CHECK(c.bb->part.ensure(which_bytes + (size_t)B * nblk * (P > 0 ? P : 1) * sizeof(double)));
+  double* d_grad = c.bb->res.d();
   double* d_alpha = d_grad + B * P;
   double* d_diagA = d_alpha + B * n;
-  uint32_t* d_which = (uint32_t*)bb->part.p;
-  double* partial = (double*)((char*)bb->part.p + which_bytes);
+  uint32_t* d_which = (uint32_t*)c.bb->part.p;
+  double* partial = (double*)((char*)c.bb->part.p + which_bytes);
+  hipStream_t st = c.st;
+  const dim3 blk(256);
   if (P > 0)
     GH_HIP(hipMemcpyAsync(d_which, which, sizeof(uint32_t) * P,
                           gh_is_device_ptr(which) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+  GH_CHECK(batch_chain(k, n, ndim, 0, sh, &c));
 
-  // ---- build: K, the residual tile and the identity rows below it, the output tiles (zero)
-  BatchPBuild a;
-  a.nodes = in.nodes; a.n_nodes = (int)k->nodes.size(); a.ndim = ndim;
-  a.fast = in.fast;
-  a.x = in.x; a.n = n; a.xs = nullptr; a.m = np;
-  a.yerr = in.yerr; a.r = in.r;
-  a.A = A; a.np = np; a.stride = stride;
-  a.O = O; a.ostride = ostride; a.mt = (int)nt; a.kss = 2;
-  a.info = d_info; a.ktiles = ktiles; a.ptiles = ptiles; a.tiles = tiles;
-  const dim3 gb((unsigned)(B * tiles * 4)), blk(256);
-  if (a.fast) hipLaunchKernelGGL((batch_pbuild_kernel<true, true>), gb, blk, 0, st, a);
-  else        hipLaunchKernelGGL((batch_pbuild_kernel<false, true>), gb, blk, 0, st, a);
-  GH_HIP(hipGetLastError());
-
-  // ---- factorisation of K; the residual tile and the identity row tiles that are non-zero in column j carried along
-  for (long j = 0; j < nt; ++j) {
-    hipLaunchKernelGGL(batch_potf2_kernel, dim3((unsigned)B), blk, 0, st, A, ld, stride, dinv, dstride, d_info, (int)j);
-    const long below = nt + 1;                   // K's tiles below (j, j), the residual tile, identity row tiles 0 .. j
-    hipLaunchKernelGGL(batch_trsm_kernel, dim3((unsigned)(B * below)), blk, 0, st, A, ld, stride, (const double*)dinv, dstride,
-                       (const long long*)d_info, (int)j, (int)below);
-    const long w = nt - j - 1;                   // trailing tile columns of K
-    if (w > 0) {
-      const long pairs = w * (w + 1) / 2 + (j + 2) * w;      // rows nt (residual) .. nt + 1 + j (identity tile j)
-      hipLaunchKernelGGL(batch_trap_kernel, dim3((unsigned)(B * pairs)), blk, 0, st, A, ld, stride, (const long long*)d_info,
-                         (int)j, (int)nt, pairs);
-    }
-    GH_HIP(hipGetLastError());
-  }
   // ---- -z^T z, -alpha and -K^-1 in one launch; logdet and quad; the gradient reduction
-  hipLaunchKernelGGL(batch_gschur_kernel, dim3((unsigned)(B * q)), blk, 0, st, (const double*)A, ld, stride, O, ostride, (long)T,
-                     (const long long*)d_info, (int)nt, q);
-  hipLaunchKernelGGL(batch_reduce_kernel, dim3((unsigned)B), blk, 0, st, (const double*)A, ld, stride, np, (const double*)O,
-                     ostride, (const long long*)d_info, d_logdet, d_quad);
+  hipLaunchKernelGGL(batch_schur_kernel<true>, dim3((unsigned)(B * q)), blk, 0, st, (const double*)c.A, c.ld, c.stride, c.O,
+                     c.ostride, (long)T, (const long long*)c.info, (int)nt, (int)nt, 2, q);
+  batch_logdet_quad(c);
   BatchGrad g;
-  g.nodes = in.nodes; g.n_nodes = (int)k->nodes.size(); g.ndim = ndim; g.P = P;
-  g.which = d_which; g.x = in.x; g.n = n;
-  g.O = O; g.ostride = ostride; g.nt = nt;
-  g.info = d_info; g.partial = partial; g.alpha = d_alpha; g.diagA = d_diagA; g.nblk = nblk;
+  g.nodes = c.in.nodes; g.n_nodes = (int)k->nodes.size(); g.ndim = ndim; g.P = P;
+  g.which = d_which; g.x = c.in.x; g.n = n;
+  g.O = c.O; g.ostride = c.ostride; g.nt = nt;
+  g.info = c.info; g.partial = partial; g.alpha = d_alpha; g.diagA = d_diagA; g.nblk = nblk;
   const dim3 gg((unsigned)(B * nblk));
   if (P <= 4)       hipLaunchKernelGGL(batch_kgrad_kernel<4>, gg, blk, 0, st, g);
   else if (P <= 16) hipLaunchKernelGGL(batch_kgrad_kernel<16>, gg, blk, 0, st, g);
   else              hipLaunchKernelGGL(batch_kgrad_kernel<GH_MAX_GRAD>, gg, blk, 0, st, g);
   if (P > 0)
     hipLaunchKernelGGL(batch_kgrad_final_kernel, dim3((unsigned)(B * P)), blk, 0, st, (const double*)partial, nblk, P,
-                       (const long long*)d_info, d_grad);
+                       (const long long*)c.info, d_grad);
   GH_HIP(hipGetLastError());
 
-  // ---- results: straight into the caller's arrays, one synchronisation
-  auto kind = [](const void* p) { return gh_is_device_ptr(p) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost; };
-  if (P > 0) GH_HIP(hipMemcpyAsync(grad, d_grad, (size_t)B * P * sizeof(double), kind(grad), st));
-  if (alpha) GH_HIP(hipMemcpyAsync(alpha, d_alpha, (size_t)B * n * sizeof(double), kind(alpha), st));
-  if (diagA) GH_HIP(hipMemcpyAsync(diagA, d_diagA, (size_t)B * n * sizeof(double), kind(diagA), st));
-  bb->back.resize((size_t)3 * B);
-  GH_HIP(hipMemcpyAsync(bb->back.data(), d_logdet, (size_t)3 * B * sizeof(double), hipMemcpyDeviceToHost, st));
-  GH_HIP(hipStreamSynchronize(st));
-  const double* hb = bb->back.data();
-  GH_CHECK(batch_put(logdet, hb, (size_t)B * sizeof(double)));
-  GH_CHECK(batch_put(quad, hb + B, (size_t)B * sizeof(double)));
-  GH_CHECK(batch_put(info, hb + 2 * B, (size_t)B * sizeof(int64_t)));
-  return GH_OK;
+  // ---- results: straight into the caller's arrays
+  if (P > 0) GH_HIP(hipMemcpyAsync(grad, d_grad, (size_t)B * P * sizeof(double), batch_from_device(grad), st));
+  if (alpha) GH_HIP(hipMemcpyAsync(alpha, d_alpha, (size_t)B * n * sizeof(double), batch_from_device(alpha), st));
+  if (diagA) GH_HIP(hipMemcpyAsync(diagA, d_diagA, (size_t)B * n * sizeof(double), batch_from_device(diagA), st));
+  return batch_finish(c, logdet, quad, info);
 }
+

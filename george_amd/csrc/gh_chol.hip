@@ -21,6 +21,7 @@
 #include <algorithm>
 #include <chrono>
 #include "gh_common.h"
+#include "gh_device_util.h"
 #include "gh_spin.h"
 #include "../../include/george_amd_debug.h"
 
@@ -105,18 +106,7 @@ __global__ __launch_bounds__(256) void potf2_inv_kernel(double* A, long lda, dou
   }
 }
 
-// ================================================================= reductions
-__device__ __forceinline__ double wave_sum(double v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ double block_sum_256(double v, double* sh /* >= 4 */) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
+// ================================================================= reductions  (wave_sum, block_sum_256: gh_device_util.h)
 
 // out[0] (+)= 2 * sum_i log(A[i][i])   (basic.py:69); one workgroup, fixed order
 __global__ __launch_bounds__(256) void logdet_kernel(const double* A, long lda, long n, double* out, int accumulate) {

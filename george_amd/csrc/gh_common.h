@@ -102,7 +102,8 @@ struct gh_kernel {
 void gh_node_set_params(GhNode& d, const double* params, const double* metric);
 void gh_fast_form(const GhNode* nodes, int n_nodes, GhFast* f);
 
-// the buffers of gh_chol_objective_batch / gh_chol_predict_batch (gh_batch.hip), owned by a gh_chol handle
+// the buffers of gh_chol_objective_batch / gh_chol_predict_batch / gh_chol_objective_grad_batch (gh_batch.hip), owned by a
+// gh_chol handle
 struct GhBatchBufs;
 GhBatchBufs* gh_batch_new();
 size_t gh_batch_bytes(const GhBatchBufs* b);

@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <math.h>
 #include "gh_common.h"
+#include "gh_device_util.h"
 #include <mutex>
 
 // ------------------------------------------------------------------ errors
@@ -345,15 +346,7 @@ int gh_kernel::upload() {
 }
 
 // ================================================================= kernels
-#define KT 64            // kmat tile edge
-// lower-triangular tile enumeration: b -> (ti, tj), tj <= ti
-__device__ __forceinline__ void tri_index(long b, int& ti, int& tj) {
-  long t = (long)((sqrt(8.0 * (double)b + 1.0) - 1.0) * 0.5);
-  while (t * (t + 1) / 2 > b) --t;
-  while ((t + 1) * (t + 2) / 2 <= b) ++t;
-  ti = (int)t;
-  tj = (int)(b - t * (t + 1) / 2);
-}
+#define KT 64            // kmat tile edge  (tri_index, the lower-triangular tile enumeration: gh_device_util.h)
 
 struct KmatArgs {
   const GhNode* prog; int n_nodes; int ndim;

@@ -364,18 +364,50 @@ class GP(ModelSet):
         go through ``set_parameter_vector`` + ``log_likelihood`` one by one, with the same results.  A failed member is
         ``-inf`` with ``quiet=True``; with ``quiet=False`` the first one raises ``np.linalg.LinAlgError`` naming it.  The
         GP's parameter vector, ``computed`` flag and factorisation are what they were before the call."""
+        vectors, y = self._batch_args(vectors, y)
+        if len(vectors) == 0:
+            return np.empty(0)
+        if self._batch_on_device():
+            return self._log_likelihood_batch_device(vectors, y, quiet)
+        return self._log_likelihood_batch_loop(vectors, y, quiet)
+
+    def _batch_args(self, vectors, y):
+        """The checked ``(vectors (B, len(gp)), y)`` of every batched method."""
         if not (hasattr(self, "_x") and hasattr(self, "_yerr2")):
             raise RuntimeError("you must call 'compute' first")
         vectors = np.asarray(vectors, dtype=np.float64)
         if vectors.ndim != 2 or vectors.shape[1] != len(self):
             raise ValueError("vectors must have shape (B, {0})".format(len(self)))
-        y = np.asarray(self._check_dimensions(y), dtype=np.float64)
-        B = len(vectors)
-        if B == 0:
-            return np.empty(0)
-        if self.solver_type is BasicSolver and len(self._x) <= BasicSolver.BATCH_MAX_N:
-            return self._log_likelihood_batch_device(vectors, y, quiet)
-        return self._log_likelihood_batch_loop(vectors, y, quiet)
+        return vectors, np.asarray(self._check_dimensions(y), dtype=np.float64)
+
+    def _batch_on_device(self, member_bytes=None):
+        """Do the batched methods take the device path: the HIP BasicSolver itself, ``N <= BATCH_MAX_N`` and, where the
+        caller gives one member's device bytes, those within ``BATCH_MAX_BYTES``?"""
+        return (self.solver_type is BasicSolver and len(self._x) <= BasicSolver.BATCH_MAX_N
+                and (member_bytes is None or member_bytes <= BasicSolver.BATCH_MAX_BYTES))
+
+    def _each_member(self, members, fn, catch, vectors=None, quiet=False):
+        """The per-member loop: under :meth:`_state_kept`, for each b of ``members``, ``set_parameter_vector(vectors[b])``
+        (when ``vectors`` is given) and ``fn(b)``.  An exception of ``catch`` is raised again, as its own type, with the
+        member named in front of its message or, ``quiet``, skipped."""
+        with self._state_kept():
+            for b in members:
+                if vectors is not None:
+                    self.set_parameter_vector(vectors[b])
+                try:
+                    fn(b)
+                except catch as e:
+                    if not quiet:
+                        raise type(e)("member {0}: {1}".format(b, e))
+
+    @staticmethod
+    def _raise_not_positive_definite(info, names=None):
+        """Raises ``LinAlgError`` for the first member whose ``info`` is set (named ``names[b]`` when given)."""
+        bad = np.flatnonzero(info != 0)
+        if len(bad):
+            b = int(bad[0])
+            raise np.linalg.LinAlgError("member {0}: {1}-th leading minor of the array is not positive definite".format(
+                b if names is None else int(names[b]), int(info[b])))
 
     def _batch_blocks(self, vectors):
         """{model name: its FULL parameter rows (B, full size)} for rows in ``get_parameter_vector()`` order."""
@@ -459,11 +491,7 @@ class GP(ModelSet):
         solver = BasicSolver(self.kernel, **(self.solver_kwargs))      # (its own pooled handle: self.solver is untouched)
         logdet, quad, info = solver.objective_batch(kp, self._x, sigma, r)
         if not quiet:
-            bad = np.flatnonzero(info != 0)
-            if len(bad):
-                b = int(bad[0])
-                raise np.linalg.LinAlgError("member {0}: {1}-th leading minor of the array is not positive definite".format(
-                    b, int(info[b])))
+            self._raise_not_positive_definite(info)
         with np.errstate(invalid="ignore"):
             const = -0.5 * (len(self._x) * np.log(2 * np.pi) + logdet)
             ll = const - 0.5 * quad
@@ -491,13 +519,11 @@ class GP(ModelSet):
 
     def _log_likelihood_batch_loop(self, vectors, y, quiet):
         out = np.empty(len(vectors))
-        with self._state_kept():
-            for b, v in enumerate(vectors):
-                self.set_parameter_vector(v)
-                try:
-                    out[b] = self.log_likelihood(y, quiet=quiet)
-                except np.linalg.LinAlgError as e:
-                    raise np.linalg.LinAlgError("member {0}: {1}".format(b, e))
+
+        def one(b):
+            out[b] = self.log_likelihood(y, quiet=quiet)
+
+        self._each_member(range(len(vectors)), one, np.linalg.LinAlgError, vectors)
         return out
 
     def predict_batch(self, vectors, y, t, return_cov=True, return_var=False, quiet=False):
@@ -510,18 +536,11 @@ class GP(ModelSet):
         same results.  A member whose matrix is not positive definite, or whose mean model is not finite at ``x`` or
         ``t``, raises (``np.linalg.LinAlgError`` / ``ValueError`` naming it) unless ``quiet``, which gives it NaN rows.
         The GP's parameter vector, ``computed`` flag, factorisation and caches are what they were before the call."""
-        if not (hasattr(self, "_x") and hasattr(self, "_yerr2")):
-            raise RuntimeError("you must call 'compute' first")
-        vectors = np.asarray(vectors, dtype=np.float64)
-        if vectors.ndim != 2 or vectors.shape[1] != len(self):
-            raise ValueError("vectors must have shape (B, {0})".format(len(self)))
-        y = np.asarray(self._check_dimensions(y), dtype=np.float64)
+        vectors, y = self._batch_args(vectors, y)
         xs = np.ascontiguousarray(self.parse_samples(t), dtype=np.float64)
         want_var = bool(return_var)
         want_cov = bool(return_cov) and not want_var
-        n, m = len(self._x), len(xs)
-        if (self.solver_type is BasicSolver and n <= BasicSolver.BATCH_MAX_N
-                and BasicSolver.predict_batch_bytes(n, m, want_var, want_cov) <= BasicSolver.BATCH_MAX_BYTES):
+        if self._batch_on_device(BasicSolver.predict_batch_bytes(len(self._x), len(xs), want_var, want_cov)):
             mu, var, cov = self._predict_batch_device(vectors, y, xs, want_var, want_cov, quiet)
         else:
             mu, var, cov = self._predict_batch_loop(vectors, y, xs, want_var, want_cov, quiet)
@@ -539,11 +558,7 @@ class GP(ModelSet):
         solver = BasicSolver(self.kernel, **(self.solver_kwargs))      # (its own pooled handle: self.solver is untouched)
         mu, var, cov, info = solver.predict_batch(kp, self._x, sigma, r, xs, return_var=want_var, return_cov=want_cov)
         if not quiet:
-            bad = np.flatnonzero(info != 0)
-            if len(bad):
-                b = int(bad[0])
-                raise np.linalg.LinAlgError("member {0}: {1}-th leading minor of the array is not positive definite".format(
-                    b, int(info[b])))
+            self._raise_not_positive_definite(info)
         mu += mean_t
         failed = ~(ok & (info == 0))
         for a in (mu, var, cov):
@@ -556,21 +571,17 @@ class GP(ModelSet):
         mu = np.full((B, m), np.nan)
         var = np.full((B, m), np.nan) if want_var else None
         cov = np.full((B, m, m), np.nan) if want_cov else None
-        with self._state_kept():
-            for b, v in enumerate(vectors):
-                self.set_parameter_vector(v)
-                try:
-                    out = self.predict(y, xs, return_cov=want_cov, return_var=want_var)
-                except ValueError as e:                                # (np.linalg.LinAlgError is one)
-                    if quiet:
-                        continue
-                    raise type(e)("member {0}: {1}".format(b, e))
-                if want_var:
-                    mu[b], var[b] = out
-                elif want_cov:
-                    mu[b], cov[b] = out
-                else:
-                    mu[b] = out
+
+        def one(b):
+            out = self.predict(y, xs, return_cov=want_cov, return_var=want_var)
+            if want_var:
+                mu[b], var[b] = out
+            elif want_cov:
+                mu[b], cov[b] = out
+            else:
+                mu[b] = out
+
+        self._each_member(range(B), one, ValueError, vectors, quiet)   # (np.linalg.LinAlgError is a ValueError)
         return mu, var, cov
 
     def sample_conditional_batch(self, vectors, y, t, size=1, quiet=False):
@@ -598,26 +609,24 @@ class GP(ModelSet):
         has a zero gradient with ``quiet=True``; with ``quiet=False`` the first one raises (``np.linalg.LinAlgError`` /
         ``ValueError`` naming it).  The GP's parameter vector, ``computed`` flag, factorisation and caches are what they
         were before the call."""
-        vectors, y = self._grad_batch_args(vectors, y)
+        vectors, y = self._batch_args(vectors, y)
         if len(vectors) == 0:
             return np.empty((0, len(self)))
         if self._grad_batch_on_device():
             return self._grad_batch_device(vectors, y, quiet)[1]
         out = np.empty((len(vectors), len(self)))
-        with self._state_kept():
-            for b, v in enumerate(vectors):
-                self.set_parameter_vector(v)
-                try:
-                    out[b] = self.grad_log_likelihood(y, quiet=quiet)
-                except ValueError as e:                                # (np.linalg.LinAlgError is one)
-                    raise type(e)("member {0}: {1}".format(b, e))
+
+        def one(b):
+            out[b] = self.grad_log_likelihood(y, quiet=quiet)
+
+        self._each_member(range(len(vectors)), one, ValueError, vectors)   # (np.linalg.LinAlgError is a ValueError)
         return out
 
     def nll_and_grad_batch(self, vectors, y, quiet=True):
         """``nll_and_grad(v, y, quiet)`` at each row ``v`` of ``vectors``: ``(nll (B,), grad (B, len(gp)))``.  A row
         outside the prior gives ``(inf, 0)`` and is not evaluated; a failed member gives ``(inf, 0)`` with ``quiet=True``.
         Routing, errors and the GP's state as :meth:`grad_log_likelihood_batch`."""
-        vectors, y = self._grad_batch_args(vectors, y)
+        vectors, y = self._batch_args(vectors, y)
         B = len(vectors)
         nll, grad = np.full(B, np.inf), np.zeros((B, len(self)))
         if B == 0:
@@ -629,26 +638,15 @@ class GP(ModelSet):
             ll, g = self._grad_batch_device(vectors[idx], y, quiet, index=idx)
             nll[idx], grad[idx] = -ll, -g
             return nll, grad
-        with self._state_kept():
-            for b in idx:
-                try:
-                    nll[b], grad[b] = self.nll_and_grad(vectors[b], y, quiet=quiet)
-                except ValueError as e:
-                    raise type(e)("member {0}: {1}".format(b, e))
+
+        def one(b):
+            nll[b], grad[b] = self.nll_and_grad(vectors[b], y, quiet=quiet)
+
+        self._each_member(idx, one, ValueError)
         return nll, grad
 
-    def _grad_batch_args(self, vectors, y):
-        if not (hasattr(self, "_x") and hasattr(self, "_yerr2")):
-            raise RuntimeError("you must call 'compute' first")
-        vectors = np.asarray(vectors, dtype=np.float64)
-        if vectors.ndim != 2 or vectors.shape[1] != len(self):
-            raise ValueError("vectors must have shape (B, {0})".format(len(self)))
-        return vectors, np.asarray(self._check_dimensions(y), dtype=np.float64)
-
     def _grad_batch_on_device(self):
-        n = len(self._x)
-        return (self.solver_type is BasicSolver and n <= BasicSolver.BATCH_MAX_N
-                and BasicSolver.grad_batch_bytes(n) <= BasicSolver.BATCH_MAX_BYTES)
+        return self._batch_on_device(BasicSolver.grad_batch_bytes(len(self._x)))
 
     def _batch_in_prior(self, vectors):
         """(B,) bool: is ``log_prior()`` finite at each row (evaluated on the GP's own models, then restored)?"""
@@ -676,9 +674,8 @@ class GP(ModelSet):
             if not ok[b]:
                 raise ValueError("member {0}: mean function returned NaN or Inf for parameters:\n{1}".format(
                     name, self._batch_blocks(vectors[b:b + 1])["mean"][0]))
-            if info[b] != 0:
-                raise np.linalg.LinAlgError("member {0}: {1}-th leading minor of the array is not positive definite".format(
-                    name, int(info[b])))
+            if info[b] != 0:                                       # (b is then the first member whose info is set)
+                self._raise_not_positive_definite(info, index)
             raise ValueError("member {0}: mean gradient function returned NaN or Inf for parameters:\n{1}".format(
                 name, self._batch_blocks(vectors[b:b + 1])["mean"][0]))
         ll[bad | ~np.isfinite(ll)] = -np.inf

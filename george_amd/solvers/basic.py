@@ -262,9 +262,23 @@ class BasicSolver(object):
         ``sigma[b]`` (white noise included) and residual ``r[b]``.  Returns ``(logdet (B,), quad (B,), info (B,))``;
         ``info[b] != 0`` (the 1-based failing pivot) marks a member that is not positive definite -- its logdet / quad
         are NaN.  Runs on a pooled handle of its own: this solver's factor, if any, is untouched."""
+        params, x, sigma, r, _, dk, B, n = self._batch_args(params, x, sigma, r)
+        logdet, quad, info = np.empty(B), np.empty(B), np.zeros(B, dtype=np.int64)
+        self._batch_chunks(B, self.objective_batch_bytes(n), lambda hh, b0, b1: N.lib.gh_chol_objective_batch(
+            hh, dk.handle, N.ptr(params[b0:b1]), b1 - b0, N.ptr(x), n, x.shape[1], N.ptr(sigma[b0:b1]), N.ptr(r[b0:b1]),
+            N.ptr(logdet[b0:]), N.ptr(quad[b0:]), N.ptr(info[b0:])))
+        return logdet, quad, info
+
+    def _batch_args(self, params, x, sigma, r, xs=None):
+        """The checked, contiguous arguments of a batched call: ``(params, x, sigma (B, n), r, xs, DeviceKernel, B, n)``."""
         x = N.as_f64(x)
-        if x.ndim != 2:
-            raise ValueError("x must be (nsamples, ndim)")
+        if xs is None:
+            if x.ndim != 2:
+                raise ValueError("x must be (nsamples, ndim)")
+        else:
+            xs = N.as_f64(xs)
+            if x.ndim != 2 or xs.ndim != 2:
+                raise ValueError("x and xs must be (nsamples, ndim)")
         n = len(x)
         params = N.as_f64(params)
         B = params.shape[0] if params.ndim == 2 else -1
@@ -275,56 +289,42 @@ class BasicSolver(object):
         r = N.as_f64(r)
         if r.shape != (B, n):
             raise ValueError("dimension mismatch")
-        if x.shape[1] != dk.ndim:
+        if x.shape[1] != dk.ndim or (xs is not None and xs.shape[1] != dk.ndim):
             raise RuntimeError("dimension mismatch")
-        logdet, quad, info = np.empty(B), np.empty(B), np.zeros(B, dtype=np.int64)
-        if B == 0:
-            return logdet, quad, info
-        np_ = -(-n // 128) * 128
-        per = ((np_ + 128) ** 2 + np_ * 128) * 8
+        return params, x, sigma, r, xs, dk, B, n
+
+    def _batch_chunks(self, B, per, call):
+        """Members 0 .. B - 1 in chunks whose device buffers (``per`` bytes a member) stay under BATCH_MAX_BYTES, one member
+        at least: ``call(handle, b0, b1)`` returns the native status of members b0 .. b1 - 1, on the pooled batch handle."""
         chunk = int(max(1, min(B, BasicSolver.BATCH_MAX_BYTES // per)))
         for b0 in range(0, B, chunk):
             b1 = min(B, b0 + chunk)
-            self._retry_without_parked_memory(lambda hh: N.check(N.lib.gh_chol_objective_batch(
-                hh, dk.handle, N.ptr(params[b0:b1]), b1 - b0, N.ptr(x), n, x.shape[1], N.ptr(sigma[b0:b1]), N.ptr(r[b0:b1]),
-                N.ptr(logdet[b0:]), N.ptr(quad[b0:]), N.ptr(info[b0:]))), ensure=self._ensure_batch_handle)
-        return logdet, quad, info
+            self._retry_without_parked_memory(lambda hh: N.check(call(hh, b0, b1)), ensure=self._ensure_batch_handle)
+
+    @staticmethod
+    def objective_batch_bytes(n):
+        """Device bytes of one member of objective_batch: its bordered block, (Np + 128)^2, and the inverses of its diagonal
+        blocks."""
+        np_ = -(-n // 128) * 128
+        return ((np_ + 128) ** 2 + np_ * 128) * 8
 
     def predict_batch(self, params, x, sigma, r, xs, return_var=False, return_cov=False):
         """B posterior predictions over one set of points (gh_chol_predict_batch): member b is objective_batch's member b,
         predicted at ``xs``.  Returns ``(mu (B, M), var (B, M) or None, cov (B, M, M) or None, info (B,))``; ``mu`` has no
         mean model (as :meth:`predict`), ``return_var`` wins over ``return_cov``, and a member with ``info[b] != 0`` has NaN
         rows.  Runs on objective_batch's pooled handle, in chunks under BATCH_MAX_BYTES."""
-        x, xs = N.as_f64(x), N.as_f64(xs)
-        if x.ndim != 2 or xs.ndim != 2:
-            raise ValueError("x and xs must be (nsamples, ndim)")
-        n, m = len(x), len(xs)
-        params = N.as_f64(params)
-        B = params.shape[0] if params.ndim == 2 else -1
-        dk = DeviceKernel(self.kernel)
-        if B < 0 or params.shape[1] != dk.size:
-            raise ValueError("params must be (B, {0})".format(dk.size))
-        sigma = N.as_f64(np.broadcast_to(sigma, (B, n)))
-        r = N.as_f64(r)
-        if r.shape != (B, n):
-            raise ValueError("dimension mismatch")
-        if x.shape[1] != dk.ndim or xs.shape[1] != dk.ndim:
-            raise RuntimeError("dimension mismatch")
+        params, x, sigma, r, xs, dk, B, n = self._batch_args(params, x, sigma, r, xs)
+        m = len(xs)
         want_var = bool(return_var)
         want_cov = bool(return_cov) and not want_var
         mu = np.empty((B, m))
         var = np.empty((B, m)) if want_var else None
         cov = np.empty((B, m, m)) if want_cov else None
         info = np.zeros(B, dtype=np.int64)
-        if B == 0:
-            return mu, var, cov, info
-        chunk = int(max(1, min(B, BasicSolver.BATCH_MAX_BYTES // self.predict_batch_bytes(n, m, want_var, want_cov))))
-        for b0 in range(0, B, chunk):
-            b1 = min(B, b0 + chunk)
-            self._retry_without_parked_memory(lambda hh: N.check(N.lib.gh_chol_predict_batch(
-                hh, dk.handle, N.ptr(params[b0:b1]), b1 - b0, N.ptr(x), n, x.shape[1], N.ptr(sigma[b0:b1]), N.ptr(r[b0:b1]),
-                N.ptr(xs), m, N.ptr(mu[b0:]), N.ptr(var[b0:]) if want_var else None,
-                N.ptr(cov[b0:]) if want_cov else None, None, None, N.ptr(info[b0:]))), ensure=self._ensure_batch_handle)
+        self._batch_chunks(B, self.predict_batch_bytes(n, m, want_var, want_cov), lambda hh, b0, b1: N.lib.gh_chol_predict_batch(
+            hh, dk.handle, N.ptr(params[b0:b1]), b1 - b0, N.ptr(x), n, x.shape[1], N.ptr(sigma[b0:b1]), N.ptr(r[b0:b1]),
+            N.ptr(xs), m, N.ptr(mu[b0:]), N.ptr(var[b0:]) if want_var else None,
+            N.ptr(cov[b0:]) if want_cov else None, None, None, N.ptr(info[b0:])))
         return mu, var, cov, info
 
     @staticmethod
@@ -344,21 +344,7 @@ class BasicSolver(object):
         ``grad[b] = 1/2 sum_ij A_ij dK_ij/dtheta`` (masked entries 0), ``alpha[b] = K_b^-1 r_b`` and ``diagA[b] =
         diag(alpha alpha^T - K_b^-1)``; a member with ``info[b] != 0`` has NaN rows.  Runs on objective_batch's pooled
         handle, in chunks under BATCH_MAX_BYTES."""
-        x = N.as_f64(x)
-        if x.ndim != 2:
-            raise ValueError("x must be (nsamples, ndim)")
-        n = len(x)
-        params = N.as_f64(params)
-        B = params.shape[0] if params.ndim == 2 else -1
-        dk = DeviceKernel(self.kernel)
-        if B < 0 or params.shape[1] != dk.size:
-            raise ValueError("params must be (B, {0})".format(dk.size))
-        sigma = N.as_f64(np.broadcast_to(sigma, (B, n)))
-        r = N.as_f64(r)
-        if r.shape != (B, n):
-            raise ValueError("dimension mismatch")
-        if x.shape[1] != dk.ndim:
-            raise RuntimeError("dimension mismatch")
+        params, x, sigma, r, _, dk, B, n = self._batch_args(params, x, sigma, r)
         wh = np.ones(max(dk.size, 1), dtype=np.uint32)
         if which is not None:
             which = np.asarray(which)
@@ -367,14 +353,10 @@ class BasicSolver(object):
             wh[:dk.size] = which != 0
         logdet, quad, info = np.empty(B), np.empty(B), np.zeros(B, dtype=np.int64)
         grad, alpha, diagA = np.zeros((B, max(dk.size, 1))), np.empty((B, n)), np.empty((B, n))
-        if B > 0:
-            chunk = int(max(1, min(B, BasicSolver.BATCH_MAX_BYTES // self.grad_batch_bytes(n))))
-            for b0 in range(0, B, chunk):
-                b1 = min(B, b0 + chunk)
-                self._retry_without_parked_memory(lambda hh: N.check(N.lib.gh_chol_objective_grad_batch(
-                    hh, dk.handle, N.ptr(params[b0:b1]), b1 - b0, N.ptr(x), n, x.shape[1], N.ptr(sigma[b0:b1]),
-                    N.ptr(r[b0:b1]), N.ptr(wh), N.ptr(logdet[b0:]), N.ptr(quad[b0:]), N.ptr(grad[b0:]), N.ptr(alpha[b0:]),
-                    N.ptr(diagA[b0:]), N.ptr(info[b0:]))), ensure=self._ensure_batch_handle)
+        self._batch_chunks(B, self.grad_batch_bytes(n), lambda hh, b0, b1: N.lib.gh_chol_objective_grad_batch(
+            hh, dk.handle, N.ptr(params[b0:b1]), b1 - b0, N.ptr(x), n, x.shape[1], N.ptr(sigma[b0:b1]),
+            N.ptr(r[b0:b1]), N.ptr(wh), N.ptr(logdet[b0:]), N.ptr(quad[b0:]), N.ptr(grad[b0:]), N.ptr(alpha[b0:]),
+            N.ptr(diagA[b0:]), N.ptr(info[b0:])))
         return logdet, quad, grad[:, :dk.size], alpha, diagA, info
 
     @staticmethod
