@@ -118,6 +118,7 @@ SIGNATURES = {
     "gh_debug_set_hodlr_core_fused": (C.c_int, [C.c_int]),
     "gh_debug_set_hodlr_coop_singles": (C.c_int, [C.c_int]),
     "gh_debug_set_hodlr_leaf_fused": (C.c_int, [C.c_int]),
+    "gh_debug_set_hodlr_strip_cols": (C.c_int, [C.c_int]),
     "gh_debug_stream_overlap": (C.c_int, [_vp, C.POINTER(C.c_double), C.c_int]),
     "gh_debug_stream_dispatch": (C.c_int, [_vp, C.POINTER(C.c_double), C.c_int]),
     "gh_microbench_suite": (C.c_int, [C.POINTER(C.c_double), C.c_int]),
@@ -167,6 +168,8 @@ SIGNATURES = {
     "gh_hodlr_dot_solve": (C.c_int, [_vp, _dp, C.POINTER(C.c_double)]),
     "gh_hodlr_get_inverse": (C.c_int, [_vp, _dp]),
     "gh_hodlr_ranks": (C.c_int, [_vp, C.POINTER(C.c_int32), _i32, C.POINTER(C.c_int32)]),
+    "gh_hodlr_predict": (C.c_int, [_vp, _vp, _dp, _dp, _i64, _dp, _dp, _dp]),
+    "gh_hodlr_grad": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _dp, _dp]),
     "gh_mgpu_create": (C.c_int, [C.POINTER(gh_mgpu_opts), C.POINTER(_vp)]),
     "gh_mgpu_destroy": (None, [_vp]),
     "gh_mgpu_compute": (C.c_int, [_vp, _vp, _dp, _i64, _i32, _dp, C.POINTER(C.c_double)]),

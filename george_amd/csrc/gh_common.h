@@ -131,6 +131,10 @@ int gh_launch_kgrad_reduce(const gh_kernel* k, const uint32_t* which_host, const
                            const double* alpha, const double* kinv, int64_t ld, double* grad_dev /* size */,
                            double* diagA /* n or NULL */, GhBuf& scratch, hipStream_t st);
 
+// grad_dev[p] = sum over the nblk rows of partial (nblk x P) in a fixed-order tree: bitwise reproducible (the second stage of
+// gh_launch_kgrad_reduce, and of the strip form in gh_hodlr.hip)
+int gh_launch_kgrad_final(const double* partial, int64_t nblk, int P, double* grad_dev, hipStream_t st);
+
 // fp64 GEMM family on the MFMA pipe:  C = beta*C + alpha * op(A) * op(B)^T-ish.  See gh_gemm.hip.
 struct GhGemm {
   double* C; int64_t ldc;

@@ -37,8 +37,11 @@ struct GhNode {
 
 // ---------------------------------------------------------------- metrics
 // r2 and (optionally) d r2 / d metric-params.   metrics.h:76-91 (iso), :108-130 (axis), :183-234 (general)
+// ws: optional caller-provided work space of GH_EVAL_WS doubles for the runtime-indexed temporaries (a kernel that passes LDS
+// here keeps them out of scratch memory); nullptr: private arrays.  Same arithmetic either way.
+#define GH_EVAL_WS (2 * GH_MAX_AXES)
 template <bool GRAD>
-GH_HD double gh_metric(const GhNode& nd, const double* x1, const double* x2, double* g) {
+GH_HD double gh_metric(const GhNode& nd, const double* x1, const double* x2, double* g, double* ws = nullptr) {
   if (nd.mtype == 0) {
     double s = 0.0;
     for (int i = 0; i < nd.naxes; ++i) {
@@ -61,7 +64,9 @@ GH_HD double gh_metric(const GhNode& nd, const double* x1, const double* x2, dou
     return r2;
   } else {
     const int n = nd.naxes;
-    double r[GH_MAX_AXES], lir[GH_MAX_AXES];
+    double r_[GH_MAX_AXES], lir_[GH_MAX_AXES];
+    double* const r = ws ? ws : r_;
+    double* const lir = ws ? ws + GH_MAX_AXES : lir_;
     for (int i = 0; i < n; ++i) { const int a = nd.axes[i]; r[i] = x1[a] - x2[a]; }
     // _custom_forward_sub, metrics.h:144-151 (diagonal slots hold 1/L_ii)
     for (int i = 0, k = 0; i < n; ++i) {
@@ -263,13 +268,13 @@ GH_HD double gh_leaf_value(const GhNode& nd, const double* x1, const double* x2)
 }
 
 // value + gradient wrt this leaf's parameters into g[0 .. psize)
-GH_HD double gh_leaf_grad(const GhNode& nd, const double* x1, const double* x2, double* g) {
+GH_HD double gh_leaf_grad(const GhNode& nd, const double* x1, const double* x2, double* g, double* ws = nullptr) {
   if (nd.mtype >= 0) {                    // templates/kernels.h:312-365
     if (gh_out_of_block(nd, x1, x2)) {
       for (int i = 0; i < nd.psize; ++i) g[i] = 0.0;
       return 0.0;
     }
-    const double r2 = gh_metric<true>(nd, x1, x2, g + nd.npar);
+    const double r2 = gh_metric<true>(nd, x1, x2, g + nd.npar, ws);
     double rg = 0.0, pg = 0.0;
     const double v = gh_radial<true>(nd, r2, rg, pg);
     if (nd.npar > 0) g[0] = pg;
@@ -277,7 +282,8 @@ GH_HD double gh_leaf_grad(const GhNode& nd, const double* x1, const double* x2, 
     return v;
   }
   double v = 0.0, da, db;                 // templates/kernels.h:604-630
-  double pg[2];
+  double pg_[2];
+  double* const pg = ws ? ws : pg_;
   for (int p = 0; p < nd.npar; ++p) g[p] = 0.0;
   for (int i = 0; i < nd.naxes; ++i) {
     const int a = nd.axes[i];
@@ -374,13 +380,13 @@ GH_HD double gh_eval_value(const GhNode* prog, int n_nodes, const double* x1, co
 }
 
 // value + full parameter gradient g[0 .. size).  Product rule: kernels.h:117-141.
-GH_HD double gh_eval_grad(const GhNode* prog, int n_nodes, const double* x1, const double* x2, double* g) {
+GH_HD double gh_eval_grad(const GhNode* prog, int n_nodes, const double* x1, const double* x2, double* g, double* ws = nullptr) {
   GhStack st;
   st.s0 = st.s1 = st.s2 = st.s3 = st.s4 = st.s5 = st.s6 = st.s7 = 0.0;
   for (int i = 0; i < n_nodes; ++i) {
     const GhNode& nd = prog[i];
     if (nd.op == GH_OP_LEAF) {
-      st.push(gh_leaf_grad(nd, x1, x2, g + nd.poff));
+      st.push(gh_leaf_grad(nd, x1, x2, g + nd.poff, ws));
     } else {
       const double b = st.s0, a = st.s1;
       st.drop();

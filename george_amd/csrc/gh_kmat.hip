@@ -677,6 +677,13 @@ __global__ void kgrad_final_kernel(const double* partial, long nblk, int P, doub
   if (threadIdx.x == 0) grad[p] = s[0];
 }
 
+int gh_launch_kgrad_final(const double* partial, int64_t nblk, int P, double* grad_dev, hipStream_t st) {
+  if (P <= 0) return GH_OK;
+  hipLaunchKernelGGL(kgrad_final_kernel, dim3(P), dim3(256), 0, st, partial, (long)nblk, P, grad_dev);
+  GH_HIP(hipGetLastError());
+  return GH_OK;
+}
+
 int gh_launch_kgrad_reduce(const gh_kernel* k, const uint32_t* which_host, const double* x, int64_t n,
                            const double* alpha, const double* kinv, int64_t ld, double* grad_dev,
                            double* diagA, GhBuf& scratch, hipStream_t st) {
@@ -698,11 +705,7 @@ int gh_launch_kgrad_reduce(const gh_kernel* k, const uint32_t* which_host, const
   else GH_LAUNCH_RED(GH_MAX_GRAD);
 #undef GH_LAUNCH_RED
   GH_HIP(hipGetLastError());
-  if (P > 0) {
-    hipLaunchKernelGGL(kgrad_final_kernel, dim3(P), dim3(256), 0, st, partial, nblk, P, grad_dev);
-    GH_HIP(hipGetLastError());
-  }
-  return GH_OK;
+  return gh_launch_kgrad_final(partial, nblk, P, grad_dev, st);
 }
 
 // ============================================================ C-ABI: evaluator

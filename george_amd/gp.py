@@ -8,10 +8,12 @@ the import.  Differences are behind the API:
 
 * the default solver is the HIP :class:`george_amd.BasicSolver`;
 * ``predict`` and ``grad_log_likelihood`` use the solver's fused device-resident
-  entry points when it has them (the N x M cross-covariance, K^-1 and the
-  (N, N, P) gradient tensor of gp.py:532-541 / :436-466 never reach the host);
-  any other duck-typed solver takes the generic NumPy path below, formula for
-  formula as the reference.
+  entry points when it has them -- ``BasicSolver`` (``gh_chol_predict`` /
+  ``gh_chol_grad``) and ``HODLRSolver`` (``gh_hodlr_predict`` / ``gh_hodlr_grad``,
+  column strips on the factor) both do: the N x M cross-covariance, K^-1 and the
+  (N, N, P) gradient tensor of gp.py:532-541 / :436-466 never reach the host;
+  any other duck-typed solver (the multi-device HODLR split among them) takes the
+  generic NumPy path below, formula for formula as the reference.
 """
 import contextlib
 import warnings

@@ -212,9 +212,45 @@ class HODLRSolver(BasicSolver):
             raise RuntimeError("you must call 'compute' first")
         return self._handle
 
-    # the fused dense-only extensions do not apply
-    predict = None
-    grad = None
+    # -- fused, device-resident GP glue on the factor (gh_hodlr_predict / gh_hodlr_grad: column strips, no M x N or N x N
+    #    array on the host); a dense-fallback solver answers with the dense forms
+    def predict(self, kernel, r, xs, return_var=False, return_cov=False):
+        """``BasicSolver.predict`` on the HODLR factor: ``K* K^-1 r`` and (optionally) the diagonal or the whole of
+        ``K** - K* K^-1 K*^T`` (gp.py:532-545).  The covariance keeps two N x M blocks on the device and raises
+        ``MemoryError`` when they do not fit."""
+        if self._computed and self._dense is not None:
+            return self._dense.predict(kernel, r, xs, return_var=return_var, return_cov=return_cov)
+        h = self._need()
+        dk = DeviceKernel(kernel) if kernel is not self.kernel else self._dk
+        r, xs = N.as_f64(r).reshape(-1), N.as_f64(xs)
+        if len(r) != self._n:
+            raise ValueError("dimension mismatch")
+        want_var = bool(return_var)
+        want_cov = bool(return_cov) and not want_var
+        m = len(xs)
+        mu = np.empty(m)
+        var = np.empty(m) if want_var else None
+        cov = np.empty((m, m)) if want_cov else None
+        if m > 0:
+            N.check(N.lib.gh_hodlr_predict(h, dk.handle, N.ptr(r), N.ptr(xs), m, N.ptr(mu), N.ptr(var), N.ptr(cov)))
+        return mu, var, cov
+
+    def grad(self, r, which):
+        """``BasicSolver.grad`` on the HODLR factor: (grad over ALL kernel parameters (masked ones 0), alpha = K^-1 r,
+        diag(alpha alpha^T - K^-1)) with the solver's own K^-1, a strip of its columns at a time (gp.py:429-466)."""
+        if self._computed and self._dense is not None:
+            return self._dense.grad(r, which)
+        h = self._need()
+        r = N.as_f64(r).reshape(-1)
+        if len(r) != self._n:
+            raise ValueError("dimension mismatch")
+        which = np.ascontiguousarray(which, dtype=np.uint32)
+        g = np.zeros(max(self._dk.size, 1))
+        alpha, diagA = np.empty(self._n), np.empty(self._n)
+        N.check(N.lib.gh_hodlr_grad(h, self._dk.handle, N.ptr(which), N.ptr(r), N.ptr(g), N.ptr(alpha), N.ptr(diagA)))
+        return g[:self._dk.size], alpha, diagA
+
+    # compute + gradient in one call, and the dense solver's profile counters, are not offered
     profile = None
     objective = None
 

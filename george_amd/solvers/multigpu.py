@@ -218,7 +218,10 @@ class MultiGPUHODLRSolver(MultiGPUSolver):
     ``min_size=100, tol=0.1, seed=42``) plus ``devices``; same node-by-node random streams as the
     single-GPU solver, so ranks and answers agree with it to rounding.  ``len(devices)`` must be a power
     of two and ``N / len(devices) >= 2 * min_size``.  ``apply_sqrt`` raises ``NotImplementedError``
-    (hodlr.py:62-64); pickling drops the factor (:69-76)."""
+    (hodlr.py:62-64); pickling drops the factor (:69-76).  The device-resident ``predict`` / ``grad`` of the
+    single-GPU ``HODLRSolver`` (``gh_hodlr_predict`` / ``gh_hodlr_grad``) are not offered on the split: ``predict``
+    stays ``None`` and there is no ``grad``, so ``GP`` takes its generic branch on ``apply_inverse`` /
+    ``get_inverse`` here."""
 
     def __init__(self, kernel, min_size=100, tol=0.1, seed=42, devices=None, max_rank=0):
         if devices is None:                                  # all visible devices, cut down to a power of two (3, 6, 7 GPUs: 2, 4, 4)

@@ -277,6 +277,20 @@ int  gh_hodlr_solve(gh_hodlr* h, const double* b, int64_t nrhs, double* out);  /
 int  gh_hodlr_dot_solve(gh_hodlr* h, const double* y, double* out);
 int  gh_hodlr_get_inverse(gh_hodlr* h, double* out /* n*n */);
 int  gh_hodlr_ranks(const gh_hodlr* h, int32_t* ranks_out, int32_t max_out, int32_t* n_out);
+/* Fused device-resident forms of the GP glue on a computed handle, the HODLR counterparts of gh_chol_predict / gh_chol_grad.
+ * Both work over column strips of n x Ct doubles (Ct a multiple of 64 chosen from a byte budget, gh_hodlr.hip), leave the factor,
+ * log|K| and the computed state untouched, synchronise once at the end, and refuse a sub-tree handle of the multi-device split. */
+/* mu = K(xs,x) K^-1 r ; var = diag K(xs,xs) - diag(K(xs,x) K^-1 K(x,xs)) ; cov = K(xs,xs) - K(xs,x) K^-1 K(x,xs)
+ * (gp.py:482-545 with apply_inverse = hodlr.h:107-114).  k may differ from the kernel of compute() (GP.predict(kernel=...)).
+ * var / cov may be NULL (not both non-NULL).  Pointers may be host or device memory.  cov keeps K(x,xs) and K^-1 K(x,xs) whole on
+ * the device (2 * 8 * n * m bytes): GH_ERR_NOMEM when they do not fit. */
+int  gh_hodlr_predict(gh_hodlr* h, gh_kernel* k, const double* r /* n: y - mean */, const double* xs, int64_t m,
+                      double* mu /* m */, double* var /* m or NULL */, double* cov /* m*m or NULL */);
+/* alpha = K^-1 r; A = alpha alpha^T - K^-1 (the solver's K^-1: solve against the identity, _hodlr.cpp get_inverse);
+ * grad[p] = 1/2 sum_ij A_ij dK_ij/dtheta_p over ALL (i, j) for the parameters selected by `which` (others exactly 0);
+ * diagA = diag(A).  (gp.py:429-466).  K^-1 is never formed as a whole; two calls give the same bits. */
+int  gh_hodlr_grad(gh_hodlr* h, gh_kernel* k, const uint32_t* which, const double* r,
+                   double* grad /* size */, double* alpha /* n or NULL */, double* diagA /* n or NULL */);
 
 /* --------------------------------------------------- dense solver on several GPUs
  * The BasicSolver protocol of /root/reference/src/george/solvers/basic.py:51-102 (compute, log-determinant,

@@ -73,6 +73,10 @@ int gh_debug_set_hodlr_coop_singles(int on);
 /* 1 (default): 128-row leaves of kernels with the a + b F(r^2) fast form are evaluated inside the leaf factorisation kernel
  * (potf2_kinv_kernel<true>); 0: a build launch writes them first.  Same bits.  Returns the previous setting. */
 int gh_debug_set_hodlr_leaf_fused(int on);
+/* columns per strip of gh_hodlr_predict / gh_hodlr_grad (rounded up to a multiple of 64); 0 or a negative value: the automatic
+ * choice from the byte budget.  Returns the previous value (0: automatic).  Read once at the start of each of those calls.  Results
+ * agree to rounding across widths (the solve takes other passes), not bit for bit. */
+int gh_debug_set_hodlr_strip_cols(int cols);
 /* which of a dense handle's streams run concurrently (HIP maps streams onto few hardware queues):
  * out[i * 6 + j], i < j, n >= 36: milliseconds for two 300-us spin kernels launched together on
  * streams i and j (0 caller's null stream, 1 main, 2 chain, 3 rows-below, 4 near, 5 CU-masked); -1 = absent */
