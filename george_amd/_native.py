@@ -106,6 +106,10 @@ SIGNATURES = {
     "gh_debug_set_mfma": (C.c_int, [C.c_int]),
     "gh_debug_set_gemm_sp": (C.c_int, [C.c_int]),
     "gh_debug_set_adaptive_panels": (C.c_int, [C.c_int]),
+    "gh_debug_set_update_group": (C.c_int, [C.c_int]),
+    "gh_debug_set_update_hide": (C.c_double, [C.c_double]),
+    "gh_debug_chol_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32),
+                                     C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "gh_debug_set_build_on_chain": (C.c_int, [C.c_int]),
     "gh_debug_set_gemm_grouped": (C.c_int, [C.c_int]),
     "gh_debug_set_hodlr_passes": (C.c_int, [C.c_int]),

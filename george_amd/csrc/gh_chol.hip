@@ -23,6 +23,7 @@
 #include "gh_common.h"
 #include "gh_device_util.h"
 #include "gh_spin.h"
+#include "gh_chol_plan.h"
 #include "../../include/george_amd_debug.h"
 
 #define T 128                 // tile edge
@@ -527,6 +528,8 @@ struct gh_chol {
   hipEvent_t ev_diag[32] = {};             // one per 128-column step of a panel (panels of up to 4096 columns)
   hipEvent_t ev_aux = nullptr, ev_aux2 = nullptr;
   std::vector<hipEvent_t> ev_p, ev_w, ev_nf;   // deep look-ahead: panel j factored / W(j) done / U(j, j+2) done
+  GhCholPlan plan;                         // two-level driver: the launch list (rebuilt only when Np, the panel starts or the group maximum change)
+  std::vector<hipEvent_t> ev_plan;         // ... and its events, owned by index in the list
   hipStream_t st_mask = nullptr;         // main-stream stand-in that leaves CUs to the panel chain (small N)
   hipStream_t tail = nullptr;            // where the last factor() ended: the stream on which its results are complete in stream order
 
@@ -564,7 +567,7 @@ struct gh_chol {
     if (ev_xfer) (void)hipEventDestroy(ev_xfer);
     if (ev_aux) (void)hipEventDestroy(ev_aux);
     if (ev_aux2) (void)hipEventDestroy(ev_aux2);
-    for (auto* v : {&ev_p, &ev_w, &ev_nf}) for (auto e : *v) (void)hipEventDestroy(e);
+    for (auto* v : {&ev_p, &ev_w, &ev_nf, &ev_plan}) for (auto e : *v) (void)hipEventDestroy(e);
     for (auto& e : ev_diag) if (e) (void)hipEventDestroy(e);
     if (st4 && !shared_streams) (void)hipStreamDestroy(st4);
     if (st3 && !shared_streams) (void)hipStreamDestroy(st3);
@@ -948,20 +951,13 @@ extern "C" int gh_debug_set_adaptive_panels(int on) {
   return prev;
 }
 static std::vector<int64_t> panel_starts(const gh_chol* s) {
-  std::vector<int64_t> pc;
-  const int64_t np = s->np, nb = panel_width(s);
   const bool adaptive = s->opts.nb == 0 && g_adaptive_panels && !use_simple_potf2();
-  for (int64_t k0 = 0; k0 < np;) {
-    pc.push_back(k0);
-    const int64_t bound = g_adaptive_panels > 1 ? g_adaptive_panels : GH_WIDE_PANEL_MIN_TRAILING;
-    int64_t w = (adaptive && np - (k0 + 2 * nb) >= bound) ? 2 * nb : nb;
+  const int64_t bound = g_adaptive_panels > 1 ? g_adaptive_panels : GH_WIDE_PANEL_MIN_TRAILING;
 #ifdef GH_WIDE_PANEL_TIER2
-    if (adaptive && np - (k0 + 4 * nb) >= GH_WIDE_PANEL_TIER2) w = 4 * nb;
+  return gh_plan_panel_starts(s->np, panel_width(s), adaptive ? bound : 0, GH_WIDE_PANEL_TIER2);
+#else
+  return gh_plan_panel_starts(s->np, panel_width(s), adaptive ? bound : 0);
 #endif
-    k0 += std::min<int64_t>(w, np - k0);
-  }
-  pc.push_back(np);
-  return pc;
 }
 
 // One panel step: factor the nb x nb diagonal block at k0, TRSM the rows below it.
@@ -1209,6 +1205,92 @@ static int factor_lookahead_deep(gh_chol* s, int depth) {
   return GH_OK;
 }
 
+// ---- the two-level driver: inner panels for the chain, groups of them for the trailing update (gh_chol_plan.h)
+// The maximum number of inner panels per group; 1 = the one-level driver above, launch for launch.
+#ifndef GH_UPDATE_GROUP_DEFAULT
+#define GH_UPDATE_GROUP_DEFAULT 2
+#endif
+static int g_update_group = GH_UPDATE_GROUP_DEFAULT;
+extern "C" int gh_debug_set_update_group(int gmax) {
+  const int prev = g_update_group;
+  g_update_group = gmax < 1 ? GH_UPDATE_GROUP_DEFAULT : gmax;
+  return prev;
+}
+static double g_update_hide = GH_PLAN_HIDE;
+extern "C" double gh_debug_set_update_hide(double hide) {
+  const double prev = g_update_hide;
+  g_update_hide = hide > 0.0 ? hide : GH_PLAN_HIDE;
+  return prev;
+}
+extern "C" int gh_debug_chol_plan(int64_t np, int64_t nb, int64_t bound, int32_t gmax, double hide, int64_t* panel_starts_out, int32_t max_starts,
+                                  int32_t* n_starts, int64_t* ops_out, int32_t max_ops, int32_t* n_ops, int32_t* n_events) {
+  if (np <= 0 || nb <= 0 || np % T || nb % T || gmax < 1 || !n_starts || !n_ops || (max_starts > 0 && !panel_starts_out) || (max_ops > 0 && !ops_out)) {
+    gh_set_error("chol_plan: Np and nb must be positive multiples of 128, the group maximum at least 1");
+    return GH_ERR_BAD_ARG;
+  }
+  const GhCholPlan pl = gh_plan_build(np, gh_plan_panel_starts(np, nb, bound), gmax, hide);
+  *n_starts = (int32_t)pl.pc.size();
+  *n_ops = (int32_t)pl.ops.size();
+  if (n_events) *n_events = pl.n_events;
+  for (int32_t i = 0; i < *n_starts && i < max_starts; ++i) panel_starts_out[i] = pl.pc[i];
+  for (int32_t i = 0; i < *n_ops && i < max_ops; ++i) {
+    const GhPlanOp& o = pl.ops[i];
+    const int64_t row[GH_PLAN_COLS] = {o.kind, o.stream, o.r0, o.r1, o.c0, o.c1, o.k0, o.k1, o.wait0, o.wait1, o.record, o.lower};
+    memcpy(ops_out + (size_t)i * GH_PLAN_COLS, row, sizeof(row));
+  }
+  return GH_OK;
+}
+// Executes the list: nothing here decides an order.  Only where the trailing updates run on the unmasked main stream
+// (Np >= 24576); the remarks in factor_lookahead_deep on where barrier packets may sit hold: the main stream's only waits
+// are F(G)'s for the event of its group's last panel -- the kind W(j) has -- and the join at its end.
+static int factor_two_level(gh_chol* s) {
+  hipStream_t sm = s->st, sp = s->st2;
+  const std::vector<int64_t> pc = panel_starts(s);
+  if (s->plan.np != s->np || s->plan.gmax != g_update_group || s->plan.hide != g_update_hide || s->plan.pc != pc)
+    s->plan = gh_plan_build(s->np, pc, g_update_group, g_update_hide);
+  const GhCholPlan& pl = s->plan;
+  while ((int)s->ev_plan.size() < pl.n_events) {
+    hipEvent_t e;
+    GH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    s->ev_plan.push_back(e);
+  }
+  double* A = s->A.d();
+  const int64_t ld = s->np;
+  const bool prof = s->opts.profile != 0;
+  if (!s->build_on_chain) {                              // everything queued so far (the build, on s->st) before the chain starts
+    GH_HIP(hipEventRecord(s->ev_sync[0], s->st));
+    GH_HIP(hipStreamWaitEvent(sp, s->ev_sync[0], 0));
+    GH_HIP(hipStreamWaitEvent(s->st3, s->ev_sync[0], 0));
+  }
+  for (const GhPlanOp& o : pl.ops) {
+    hipStream_t st = o.stream == GH_PLAN_MAIN ? sm : sp;
+    if (o.wait0 >= 0) GH_HIP(hipStreamWaitEvent(st, s->ev_plan[o.wait0], 0));
+    if (o.wait1 >= 0) GH_HIP(hipStreamWaitEvent(st, s->ev_plan[o.wait1], 0));
+    if (o.kind == GH_PLAN_PANEL) {
+      const long ep = prof ? s->next_ev() : -1;
+      if (ep >= 0) { GH_HIP(hipEventRecord(s->ev_pool[ep].a, st)); s->ev_panel.push_back((size_t)ep); }
+      GH_CHECK(panel_step(s, st, o.c0, o.c1 - o.c0));
+      if (ep >= 0) GH_HIP(hipEventRecord(s->ev_pool[ep].b, st));
+    } else if (o.kind != GH_PLAN_JOIN) {
+      const int64_t m = o.r1 - o.r0, n = o.c1 - o.c0, k = o.k1 - o.k0;
+      // (algorithmic flops: the lower tiles only, with the K of this launch -- as the one-level driver counts its block columns)
+      const double fl = gh_plan_trap_tiles(m, n) * 2.0 * T * T * (double)k;
+      const long eu = prof ? s->next_ev() : -1;
+      if (eu >= 0) {
+        GH_HIP(hipEventRecord(s->ev_pool[eu].a, st));
+        s->ev_update.push_back((size_t)eu); s->ev_update_flops.push_back(fl);
+        if (o.kind == GH_PLAN_F) s->ev_trailing.push_back((size_t)eu);
+      }
+      GH_CHECK(gemm_nt(st, blk(A, ld, o.r0, o.c0), ld, blk(A, ld, o.r0, o.k0), ld, blk(A, ld, o.c0, o.k0), ld, m, n, k, -1.0, 1.0, o.lower != 0));
+      if (eu >= 0) GH_HIP(hipEventRecord(s->ev_pool[eu].b, st));
+      s->prof.update_flops += fl;
+      if (o.kind == GH_PLAN_F) { s->prof.trailing_flops += fl; s->prof.n_trailing += 1; }
+    }
+    if (o.record >= 0) GH_HIP(hipEventRecord(s->ev_plan[o.record], st));
+  }
+  return GH_OK;                                          // (the JOIN op left everything ordered on the main stream: s->tail stays s->st)
+}
+
 #ifndef GH_LOOKAHEAD_DEPTH
 #define GH_LOOKAHEAD_DEPTH 1
 #endif
@@ -1226,7 +1308,10 @@ static int factor(gh_chol* s) {
       guard(s->opts.lookahead && s->st2 && trailing_stream(s) == s->st);       // no CUs kept free of the SYRK
   // (a matrix of ONE panel has nothing to look ahead to: on the main stream it saves the two cross-stream hand-overs,
   //  ~35 us each -- a tenth of the step at N = 1024)
-  if (s->opts.lookahead && s->st2 && s->st3 && s->st4 && s->np > panel_width(s)) return factor_lookahead_deep(s, lookahead_depth(s));      // (panel widths: panel_starts())
+  if (s->opts.lookahead && s->st2 && s->st3 && s->st4 && s->np > panel_width(s)) {      // (panel widths: panel_starts())
+    if (g_update_group > 1 && lookahead_depth(s) == 1 && !use_simple_potf2() && trailing_stream(s) == s->st) return factor_two_level(s);
+    return factor_lookahead_deep(s, lookahead_depth(s));
+  }
   hipStream_t st = s->st;
   double* A = s->A.d();
   const int64_t np = s->np, ld = np;

@@ -241,12 +241,13 @@ typedef struct gh_chol_profile {
   double ms_total;          /* build + factor, device time                     */
   double ms_build;          /* kernel-matrix build                             */
   double ms_panel;          /* potf2 + trsm + inner updates                    */
-  double ms_trailing;       /* sum of trailing-update (SYRK) launches          */
+  double ms_trailing;       /* sum of trailing-update (SYRK) launches: the wide lower-triangular ones on the main stream
+                             * (one per inner panel, or one per group of panels -- the two-level driver's far launches) */
   double trailing_flops;    /* algorithmic flops of those launches             */
   int64_t n_trailing;       /* number of trailing-update launches              */
   double ms_solve;          /* last dot_solve / solve                          */
   double ms_update_union;   /* time during which ANY trailing-update launch ran (wide SYRKs on the main
-                             * stream + block-column GEMMs on the chain stream): union of their intervals */
+                             * stream + block-column / in-group / next-group GEMMs on the chain stream): union of their intervals */
   double update_flops;      /* algorithmic flops of all those launches          */
   double reserved[2];
 } gh_chol_profile;

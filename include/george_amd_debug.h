@@ -34,6 +34,24 @@ int gh_debug_set_build_on_chain(int on);
  * trailing matrix behind them has more than 25 600 columns and 1024 after; 0: 1024 throughout; n > 1: the bound is n columns.
  * Returns the previous setting.  Same bits whatever the widths (the update adds the same k in the same order). */
 int gh_debug_set_adaptive_panels(int on);
+/* Trailing updates of the look-ahead factorisation at Np >= 24576: 1 = one wide launch per inner panel (the one-level driver,
+ * launch for launch as before); n > 1 = the two-level driver, groups of up to n consecutive inner panels updated left-looking
+ * inside and applied to everything behind them in one launch of K = the group's width (gh_chol_plan.h); < 1 restores the
+ * default.  Returns the previous value.  Same bits whatever the groups (every column receives the same k in the same order). */
+int gh_debug_set_update_group(int gmax);
+/* the margin of the rule that sizes those groups: a group is kept while the estimated time of its chain (panels, in-group updates,
+ * the trapezoid for the group after it) is at most `hide` times that of the far update running beside it; <= 0 restores the
+ * default.  Returns the previous value.  Moves time only: same bits. */
+double gh_debug_set_update_hide(double hide);
+/* The two-level driver's launch list for a matrix of np columns (a multiple of 128) with inner panels of nb columns, 2 * nb while
+ * at least `bound` trailing columns lie behind them (bound <= 0: nb throughout), and groups of at most gmax panels -- built as the
+ * driver builds it, at ANY np, without a device; hide: the margin above (<= 0: the default).  panel_starts_out[0 .. *n_starts) = the panel starts with np at the end;
+ * ops_out = *n_ops rows of 12 int64: kind (0 panel, 1 in-group block column L, 2 trapezoid T for the next group, 3 far update F,
+ * 4 join), stream (0 main, 1 chain), rows [r0, r1) and columns [c0, c1) written, columns [k0, k1) of L read as the K range, two
+ * events waited for (-1: none), event recorded (-1: none), lower (1: launched as a lower trapezoid, 0: as the full rectangle).
+ * Counts beyond max_starts / max_ops are reported, not written.  tests/test_chol_plan.py replays the list on the CPU. */
+int gh_debug_chol_plan(int64_t np, int64_t nb, int64_t bound, int32_t gmax, double hide, int64_t* panel_starts_out, int32_t max_starts,
+                       int32_t* n_starts, int64_t* ops_out, int32_t max_ops, int32_t* n_ops, int32_t* n_events);
 /* The gh_debug_set_hodlr_* switches below take effect at the next gh_hodlr_compute(): every compute() reads all of them once, at
  * its start, and a compute() running on another thread keeps the settings it started with.  (The passes mask is read the same way
  * by every solve.) */
