@@ -42,7 +42,7 @@ class gh_chol_profile(C.Structure):
     _fields_ = [("ms_total", C.c_double), ("ms_build", C.c_double), ("ms_panel", C.c_double),
                 ("ms_trailing", C.c_double), ("trailing_flops", C.c_double), ("n_trailing", C.c_int64),
                 ("ms_solve", C.c_double), ("ms_update_union", C.c_double), ("update_flops", C.c_double),
-                ("reserved", C.c_double * 2)]
+                ("ms_append_relayout", C.c_double), ("reserved", C.c_double * 1)]
 
 
 class gh_hodlr_opts(C.Structure):
@@ -111,6 +111,7 @@ SIGNATURES = {
     "gh_debug_chol_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32),
                                      C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "gh_debug_set_build_on_chain": (C.c_int, [C.c_int]),
+    "gh_debug_set_append_path": (C.c_int, [C.c_int]),
     "gh_debug_set_gemm_grouped": (C.c_int, [C.c_int]),
     "gh_debug_set_hodlr_passes": (C.c_int, [C.c_int]),
     "gh_debug_set_hodlr_leaf_gj": (C.c_int, [C.c_int]),
@@ -141,6 +142,9 @@ SIGNATURES = {
     "gh_chol_create": (C.c_int, [C.POINTER(gh_chol_opts), C.POINTER(_vp)]),
     "gh_chol_destroy": (None, [_vp]),
     "gh_chol_compute": (C.c_int, [_vp, _vp, _dp, _i64, _i32, _dp, C.POINTER(C.c_double)]),
+    "gh_chol_append": (C.c_int, [_vp, _vp, _dp, _i64, _dp, C.POINTER(C.c_double)]),
+    "gh_chol_truncate": (C.c_int, [_vp, _i64, C.POINTER(C.c_double)]),
+    "gh_chol_set_yerr": (C.c_int, [_vp, _dp]),
     "gh_chol_info": (_i64, [_vp]),
     "gh_chol_size": (_i64, [_vp]),
     "gh_chol_device_bytes": (_i64, [_vp]),

@@ -24,6 +24,7 @@
 #include "gh_device_util.h"
 #include "gh_spin.h"
 #include "gh_chol_plan.h"
+#include "gh_gemm_tile.h"
 #include "../../include/george_amd_debug.h"
 
 #define T 128                 // tile edge
@@ -284,6 +285,23 @@ __device__ __forceinline__ double transpose_sum16(double (&v)[16], int lane) {
   t += __shfl_xor(t, 32, 64);
   return t;
 }
+// The two arithmetic steps of a link, per right-hand side: shared by trsv_fwd_chain_direct and trsv_fwd_chain_multi, so that
+// the compiler contracts them into the same multiply-adds in both (gh_chol_append's paths 1 and 2 give the same bits).
+// acc[q] += (row q of the block) . z_j, this lane's two columns
+__device__ __forceinline__ void chain_fold16(double (&acc)[16], const double2 (&blk)[16], const double2 zj) {
+#pragma unroll
+  for (int q = 0; q < 16; ++q) acc[q] += blk[q].x * zj.x + blk[q].y * zj.y;
+}
+// an empty statement that reads the sixteen sums and may touch memory: arithmetic on them stays in front of it, loads behind it
+__device__ __forceinline__ void chain_pin16(double (&a)[16]) {
+  asm volatile("" : : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]), "v"(a[6]), "v"(a[7]), "v"(a[8]), "v"(a[9]),
+               "v"(a[10]), "v"(a[11]), "v"(a[12]), "v"(a[13]), "v"(a[14]), "v"(a[15]) : "memory");
+}
+// acc[q] = (row q of the diagonal block's inverse) . w, this lane's two columns
+__device__ __forceinline__ void chain_rows16(double (&acc)[16], const double2 (&dv)[16], const double wx, const double wy) {
+#pragma unroll
+  for (int q = 0; q < 16; ++q) acc[q] = dv[q].x * wx + dv[q].y * wy;
+}
 __global__ __launch_bounds__(CHAIN_THREADS) void trsv_fwd_chain_direct(const double* L, long ld, const double* dinv,
                                                                        const double* y, double* z, int* fail) {
   __shared__ double zs[2][T];
@@ -330,8 +348,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void trsv_fwd_chain_direct(const dou
     __syncthreads();
     if (gave_up) break;
     const double2 zj = *reinterpret_cast<const double2*>(&zs[j & 1][2 * lane]);
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc[q] += blk[q].x * zj.x + blk[q].y * zj.y;
+    chain_fold16(acc, blk, zj);
     if (j + 1 < b) {
 #pragma unroll
       for (int q = 0; q < 16; ++q)
@@ -344,11 +361,103 @@ __global__ __launch_bounds__(CHAIN_THREADS) void trsv_fwd_chain_direct(const dou
   if (lane < 16) ws[wave * 16 + lane] = yv - tot;
   __syncthreads();
   const double wx = ws[2 * lane], wy = ws[2 * lane + 1];
-#pragma unroll
-  for (int q = 0; q < 16; ++q) acc[q] = dv[q].x * wx + dv[q].y * wy;
+  chain_rows16(acc, dv, wx, wy);
   double v = transpose_sum16(acc, lane);
   if (!chain_ready(v)) v = __longlong_as_double(0x7FF8000000000000LL);      // (a NaN with every bit set must not look unpublished)
   if (lane < 16) __hip_atomic_store(z + row0 + lane, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The same sweep for R right-hand sides in one launch (gh_chol_append: R new rows of the factor against its full tiles): the
+// factor is read ONCE for all of them.  Same protocol -- the outputs are pre-filled with the sentinel and are the message,
+// agent-scope relaxed atomics and no fences, the patient probing by distance (on the first right-hand side), GhSpin -- and,
+// per right-hand side, the same operation sequence through chain_fold16 / transpose_sum16 / chain_rows16: the bits of R runs
+// of trsv_fwd_chain_direct.  y: R vectors ldy apart, read only, no alias of z; z: R vectors ldz apart.
+// Registers at 512 threads (256 per lane): acc[R][16] is 32 R, blk 64; the diagonal block's inverse (64 more) would not fit
+// beside them at R = 4, so it waits in LDS (128 KiB; a wavefront stages and reads back its own 16 rows) until blk is dead.
+template <int R>
+__global__ __launch_bounds__(CHAIN_THREADS) void trsv_fwd_chain_multi(const double* L, long ld, const double* dinv,
+                                                                      const double* y, long ldy, double* z, long ldz, int* fail) {
+  __shared__ double zs[2][R][T];
+  __shared__ double ws[R][T];
+  __shared__ double dls[T * T];
+  __shared__ int gave_up;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (wave-uniform row addresses: scalar bases, not sixteen 64-bit vector pointers)
+  const long row0 = (long)b * T + wave * 16;
+  double acc[R][16];
+  double2 blk[16];
+  if (tid == 0) gave_up = 0;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    if (lane < 16) ws[r][wave * 16 + lane] = y[r * ldy + row0 + lane];      // (waits in LDS: R registers fewer across the loop)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) acc[r][q] = 0.0;
+  }
+#pragma unroll
+  for (int q = 0; q < 16; ++q)
+    *reinterpret_cast<double2*>(&dls[(wave * 16 + q) * T + 2 * lane]) =
+        *reinterpret_cast<const double2*>(dinv + (long)b * T * T + (wave * 16 + q) * T + 2 * lane);
+  __builtin_amdgcn_sched_barrier(0);                      // (staged before the first block is asked for: its 64 registers are free again)
+  if (b > 0) {
+#pragma unroll
+    for (int q = 0; q < 16; ++q) blk[q] = *reinterpret_cast<const double2*>(L + (row0 + q) * ld + 2 * lane);
+  }
+  __syncthreads();
+  for (int j = 0; j < b; ++j) {
+    if (wave == 0) {
+      const int dist = b - j;
+      GhSpin spin(fail);
+      bool ok = true;
+      if (dist > 2) {
+        while (!chain_ready(__hip_atomic_load(z + (long)j * T, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
+          for (int q = dist > 64 ? 16 : dist >> 2; q > 0; --q) __builtin_amdgcn_s_sleep(8);
+          if (!spin.keep_waiting(63u)) { ok = false; break; }
+        }
+      }
+      // one right-hand side after the other (they are published together; polling them side by side costs 6 R registers)
+#pragma unroll 1
+      for (int r = 0; r < R; ++r) {
+        const double* zp = z + r * ldz + (long)j * T + 2 * lane;
+        double2 zj = ld_coherent2(zp);
+        while (ok && !__all(chain_ready(zj.x) && chain_ready(zj.y))) {
+          if (!spin.keep_waiting(1023u)) { ok = false; break; }
+          zj = ld_coherent2(zp);
+        }
+        *reinterpret_cast<double2*>(&zs[j & 1][r][2 * lane]) = zj;
+      }
+      if (!ok && lane == 0) gave_up = 1;
+    }
+    __syncthreads();
+    if (gave_up) break;
+#pragma unroll
+    for (int r = 0; r < R; ++r) chain_fold16(acc[r], blk, *reinterpret_cast<const double2*>(&zs[j & 1][r][2 * lane]));
+    // (the next block's loads must land in blk itself -- a second copy, which the compiler makes of its own accord by issuing them
+    //  ahead of the multiply-adds, does not fit beside acc at R = 4: every sum is complete before the first load is issued)
+#pragma unroll
+    for (int r = 0; r < R; ++r) chain_pin16(acc[r]);
+    if (j + 1 < b) {
+#pragma unroll
+      for (int q = 0; q < 16; ++q)
+        blk[q] = *reinterpret_cast<const double2*>(L + (row0 + q) * ld + (long)(j + 1) * T + 2 * lane);
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const double yv = ws[r][wave * 16 + (lane & 15)];
+    const double tot = transpose_sum16(acc[r], lane);
+    if (lane < 16) ws[r][wave * 16 + lane] = yv - tot;
+  }
+  __syncthreads();
+  double2 dv[16];
+#pragma unroll
+  for (int q = 0; q < 16; ++q) dv[q] = *reinterpret_cast<const double2*>(&dls[(wave * 16 + q) * T + 2 * lane]);
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    chain_rows16(acc[r], dv, ws[r][2 * lane], ws[r][2 * lane + 1]);
+    double v = transpose_sum16(acc[r], lane);
+    if (!chain_ready(v)) v = __longlong_as_double(0x7FF8000000000000LL);
+    if (lane < 16) __hip_atomic_store(z + r * ldz + row0 + lane, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
 }
 
 // Backward step j of L^T x = z.  x_j = L_jj^-T w_j; columns c < j0: w[c] -= sum_r L[j0+r][c] x_j[r].
@@ -539,10 +648,13 @@ struct gh_chol {
   hipEvent_t ev_sync[3] = {nullptr, nullptr, nullptr};
   int64_t n = 0, np = 0;
   int ndim = 0;
+  bool have_yerr = false;                // yerr holds the n error bars of compute() / append() (import_factor brings none: gh_chol_set_yerr)
+  hipEvent_t ev_lay[2] = {nullptr, nullptr};   // profile: the relayout of the last append()
   bool computed = false;
   int64_t info = 0;
   double logdet = 0.0;
   GhBuf A, dinv, x, yerr, v0, v1, v2, scal, rhs, work, work2, scratch, chain;
+  GhBuf A_spare;                         // the buffer the factor left when append / truncate last moved it: where the next move goes (freed by trim)
   long long* d_info = nullptr;           // = (long long*)(scal + 2): the failure word lives beside the scalars (set in compute_enqueue)
   bool build_on_chain = false;           // this compute(): inputs + kernel-matrix build were enqueued on the chain stream (st2)
   GhBatchBufs* batch = nullptr;          // gh_chol_objective_batch's buffers (gh_batch.hip), grown once and re-used
@@ -564,6 +676,7 @@ struct gh_chol {
   ~gh_chol() {
     for (auto& p : ev_pool) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto& e : ev_sync) if (e) (void)hipEventDestroy(e);
+    for (auto& e : ev_lay) if (e) (void)hipEventDestroy(e);
     if (ev_xfer) (void)hipEventDestroy(ev_xfer);
     if (ev_aux) (void)hipEventDestroy(ev_aux);
     if (ev_aux2) (void)hipEventDestroy(ev_aux2);
@@ -784,7 +897,7 @@ extern "C" int64_t gh_chol_size(const gh_chol* s) { return s ? s->n : 0; }
 extern "C" int64_t gh_chol_device_bytes(const gh_chol* s) {
   if (!s) return 0;
   size_t tot = 0;
-  for (const GhBuf* b : {&s->A, &s->dinv, &s->x, &s->yerr, &s->v0, &s->v1, &s->v2, &s->scal, &s->rhs, &s->work, &s->work2,
+  for (const GhBuf* b : {&s->A, &s->A_spare, &s->dinv, &s->x, &s->yerr, &s->v0, &s->v1, &s->v2, &s->scal, &s->rhs, &s->work, &s->work2,
                          &s->scratch, &s->chain}) tot += b->p ? b->bytes : 0;
   return (int64_t)(tot + gh_batch_bytes(s->batch));
 }
@@ -1360,7 +1473,7 @@ static int compute_enqueue(gh_chol* s, gh_kernel* k, const double* x, int64_t n,
   s->computed = false;
   s->info = 0;
   const int64_t np = gh_round_up(n, T);
-  s->n = n; s->np = np; s->ndim = ndim;
+  s->n = n; s->np = np; s->ndim = ndim; s->have_yerr = true;
   GH_CHECK(s->A.ensure((size_t)np * np * sizeof(double)));
   GH_CHECK(s->dinv.ensure((size_t)(np / T) * T * T * sizeof(double)));
   GH_CHECK(s->x.ensure((size_t)n * ndim * sizeof(double)));
@@ -1849,7 +1962,7 @@ extern "C" int gh_chol_import_factor(gh_chol* s, int64_t n, int32_t ndim, const 
   GH_CHECK(set_device(s));
   s->computed = false;
   const int64_t np = gh_round_up(n, T);
-  s->n = n; s->np = np; s->ndim = ndim; s->info = 0;
+  s->n = n; s->np = np; s->ndim = ndim; s->info = 0; s->have_yerr = false;
   const size_t cnt = (size_t)n * (n + 1) / 2;
   GH_CHECK(s->A.ensure((size_t)np * np * sizeof(double)));
   GH_CHECK(s->dinv.ensure((size_t)(np / T) * T * T * sizeof(double)));
@@ -1872,7 +1985,7 @@ extern "C" void gh_chol_release_buffers(gh_chol* s) {
   (void)hipSetDevice(s->opts.device);
   if (s->st) (void)hipStreamSynchronize(s->st);
   s->computed = false;
-  for (GhBuf* b : {&s->A, &s->dinv, &s->x, &s->yerr, &s->v0, &s->v1, &s->v2, &s->rhs, &s->work, &s->work2, &s->scratch, &s->chain}) b->release();
+  for (GhBuf* b : {&s->A, &s->A_spare, &s->dinv, &s->x, &s->yerr, &s->v0, &s->v1, &s->v2, &s->rhs, &s->work, &s->work2, &s->scratch, &s->chain}) b->release();
   gh_batch_free(s->batch);
   s->batch = nullptr;
 }
@@ -1881,7 +1994,305 @@ extern "C" void gh_chol_trim(gh_chol* s) {
   if (!s) return;
   (void)hipSetDevice(s->opts.device);
   if (s->st) (void)hipStreamSynchronize(s->st);
-  for (GhBuf* b : {&s->rhs, &s->work, &s->work2, &s->scratch}) b->release();
+  for (GhBuf* b : {&s->rhs, &s->work, &s->work2, &s->scratch, &s->A_spare}) b->release();
   gh_batch_free(s->batch);
   s->batch = nullptr;
+}
+
+// ============================================================ append / truncate
+// Sequential use: the data set gains (or loses) a few trailing points and the factor is kept.  With n = n0 + t, n0 = 128 * (n / 128):
+//   * a Cholesky factor's leading rows do not depend on later rows: the n0 x n0 part of L and its diagonal-block inverses stay as they
+//     are -- in place while the new points fit into the last partial tile, re-laid into buffers of the new Np (leading dimension = Np
+//     throughout the solver) when the tile count grows;
+//   * the new rows against the full tiles, X = K(x_new, x[:n0]) L00^-T: a row of X is the result of one forward sweep over L00 with
+//     a row of the cross-covariance as its right-hand side -- contiguous, where the chained sweep kernels write it;
+//   * the tail block, rows and columns [n0, n + m) padded to 128: S = K(tail, tail) + diag(yerr^2) - L_tail,0 L_tail,0^T, then
+//     potrf_block.  The product has K = n0 and one or a few output tiles: split over K (tail_syrk_splitk_kernel), summed in a fixed
+//     order.  The t old tail rows of the diagonal tile are formed again (last bits may differ from what compute() left there).
+// DESIGN.md, "Appending points".
+static int g_append_path = 0;
+extern "C" int gh_debug_set_append_path(int path) {
+  const int prev = g_append_path;
+  g_append_path = (path >= 1 && path <= 3) ? path : 0;
+  return prev;
+}
+// new rows up to which the chained sweeps (4 rows per pass over the factor) are taken; above, the blocked substitution, whose time does
+// not depend on m up to 128.  Measured (profiles/append/append_paths.json) at n = 4032 / 16320: the substitution 0.75 / 3.3 ms; the
+// sweeps 0.48 / 1.5 ms at m = 4 and 1.36 / 5.1 ms at m = 16, so about 0.77 / 2.7 ms at 8 and 1.07 / 3.9 ms at 12 (interpolated).
+#define GH_APPEND_MULTI_MAX 8
+
+static void swap_bufs(GhBuf& a, GhBuf& b) { std::swap(a.p, b.p); std::swap(a.bytes, b.bytes); std::swap(a.pooled, b.pooled); }
+
+// Where a factor of np2 rows moves to.  Allocating it per call is what a move costs: hipMalloc + hipFree of 34 GB took 960 ms of a 971-ms
+// append at N = 65536 (profiles/append/append_paths.json), the copy 6.5 ms.  So the handle keeps the buffer the factor left at its last
+// move (A_spare) and the next move goes there; when that is too small the new one gets room for np2 / 32 (at least 1024) more rows, which
+// the next 8 or more tile crossings find large enough.  A buffer of more rows holds a matrix of fewer: the leading dimension is Np.
+static int take_factor_buffer(gh_chol* s, GhBuf& out, int64_t np2) {
+  const size_t need = (size_t)np2 * np2 * sizeof(double);
+  if (s->A_spare.p && s->A_spare.bytes >= need) { swap_bufs(out, s->A_spare); return GH_OK; }
+  const int64_t cap = np2 + std::max<int64_t>(1024, gh_round_up(np2 / 32, T));
+  if (out.ensure((size_t)cap * cap * sizeof(double)) == GH_OK) return GH_OK;
+  return out.ensure(need);
+}
+// the lower 128-tiles of dst (nn x nn, nn a multiple of 128): src where row and column are below nvalid, identity elsewhere
+__global__ __launch_bounds__(256) void relayout_lower_kernel(const double* src, long lds, long nvalid, double* dst, long ldd) {
+  const long i = blockIdx.x, jend = (i / T + 1) * T;
+  const double* sr = src + i * lds;
+  double* dr = dst + i * ldd;
+  if (i < nvalid) {
+    for (long j = threadIdx.x; j < jend; j += 256) dr[j] = (j < nvalid) ? sr[j] : 0.0;
+  } else {
+    for (long j = threadIdx.x; j < jend; j += 256) dr[j] = (j == i) ? 1.0 : 0.0;
+  }
+}
+// The last tile row of A (rows [t0, t0 + 128), one per workgroup) cut to n_keep points: rows from n_keep on become identity padding
+// (columns up to the end of the diagonal tile), and the kept rows lose columns n_keep .. of the diagonal tile (zeros already, as
+// potf2 leaves the strict upper triangle: written all the same, so that the tile is what compute() at n_keep builds).
+__global__ __launch_bounds__(256) void pad_rows_kernel(double* A, long ld, long t0, long n_keep) {
+  const long i = t0 + blockIdx.x, jend = t0 + T;
+  double* r = A + i * ld;
+  if (i >= n_keep) { for (long j = threadIdx.x; j < jend; j += 256) r[j] = (j == i) ? 1.0 : 0.0; }
+  else { for (long j = n_keep + threadIdx.x; j < jend; j += 256) r[j] = 0.0; }
+}
+// a 128 x 128 diagonal-block inverse cut to its leading keep x keep part, identity behind it
+__global__ __launch_bounds__(256) void dinv_clip_kernel(double* d, int keep) {
+  for (int idx = threadIdx.x; idx < T * T; idx += 256) {
+    const int i = idx >> 7, j = idx & 127;
+    if (i >= keep || j >= keep) d[idx] = (i == j) ? 1.0 : 0.0;
+  }
+}
+// Split-K stage 1 of Lt Lt^T (Lt: 128 * tiles rows, k contiguous, K = ktot): workgroup (p, sl) forms the 128 x 128 tile p of the
+// lower triangle over the k-slice sl -- the dense solver's tile function -- into part[sl][p].  Stage 2 adds the slices in index order
+// and subtracts the total from S: bitwise reproducible, like the log-det and the dot product.
+__global__ __launch_bounds__(256, 2) void tail_syrk_splitk_kernel(const double* Lt, long ld, long kslice, long ktot, double* part) {
+  __shared__ __attribute__((aligned(1024))) double sm[4 * BM * BK];
+  int ti = 0;
+  while ((ti + 1) * (ti + 2) / 2 <= (int)blockIdx.x) ++ti;
+  const int tj = (int)blockIdx.x - ti * (ti + 1) / 2;
+  const long k0 = (long)blockIdx.y * kslice;
+  const long K = kslice < ktot - k0 ? kslice : ktot - k0;
+  double* C = part + ((long)blockIdx.y * gridDim.x + blockIdx.x) * T * T;
+  gh_tile128_nt_sp<false>(sm, C, T, Lt + (long)ti * T * ld + k0, ld, Lt + (long)tj * T * ld + k0, ld, K);
+}
+__global__ __launch_bounds__(256) void tail_syrk_reduce_kernel(double* S, long ld, const double* part, int nslice) {
+  int ti = 0;
+  while ((ti + 1) * (ti + 2) / 2 <= (int)blockIdx.x) ++ti;
+  const int tj = (int)blockIdx.x - ti * (ti + 1) / 2;
+  const long npairs = gridDim.x;
+  for (int idx = blockIdx.y * 256 + threadIdx.x; idx < T * T; idx += gridDim.y * 256) {
+    double acc = 0.0;
+    for (int sl = 0; sl < nslice; ++sl) acc += part[((long)sl * npairs + blockIdx.x) * T * T + idx];
+    S[((long)ti * T + (idx >> 7)) * ld + (long)tj * T + (idx & 127)] -= acc;
+  }
+}
+
+// X (mr x n0, ld = ldx, mr a multiple of 128) <- X L00^-T, right-looking in row form on the matrix pipe: X_j <- X_j L_jj^-T with the
+// stored inverse, then X[:, j+1:] -= X_j L[j+1:, j]^T -- inside super-blocks of 8 tiles, and ONE K = 1024 update of everything right
+// of a super-block (as trsm_multi).  Every product has both operands k-major; the update is as wide as what is left of the row.
+static int append_trsm_rows(hipStream_t st, const double* L, int64_t ld, const double* dinv, double* X, int64_t ldx, int64_t mr, int64_t nt0) {
+  const int64_t SB = 8;
+  for (int64_t J = 0; J < nt0; J += SB) {
+    const int64_t Je = std::min<int64_t>(J + SB, nt0);
+    for (int64_t j = J; j < Je; ++j) {
+      double* Xj = X + j * T;
+      GH_CHECK(gemm_nt(st, Xj, ldx, Xj, ldx, dinv + j * T * T, T, mr, T, T, 1.0, 0.0, false));
+      if (j + 1 < Je)
+        GH_CHECK(gemm_nt(st, X + (j + 1) * T, ldx, Xj, ldx, L + (j + 1) * T * ld + j * T, ld, mr, (Je - j - 1) * T, T, -1.0, 1.0, false));
+    }
+    if (Je < nt0)
+      GH_CHECK(gemm_nt(st, X + Je * T, ldx, X + J * T, ldx, L + Je * T * ld + J * T, ld, mr, (nt0 - Je) * T, (Je - J) * T, -1.0, 1.0, false));
+  }
+  return GH_OK;
+}
+
+extern "C" int gh_chol_append(gh_chol* s, gh_kernel* k, const double* x_new, int64_t m, const double* yerr_new, double* logdet_out) {
+  if (!s || !k || !x_new || !yerr_new || m <= 0) { gh_set_error("bad argument to append"); return GH_ERR_BAD_ARG; }
+  GH_CHECK(need_computed(s));
+  if (k->ndim != s->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
+  // (the old rows of the last, partial tile are formed again from the kernel and the error bars)
+  if (!s->have_yerr) { gh_set_error("append: the handle was rebuilt by import_factor and holds no error bars (gh_chol_set_yerr)"); return GH_ERR_BAD_ARG; }
+  GH_CHECK(k->upload());
+  const int64_t n = s->n, np = s->np, ndim = s->ndim, n2 = n + m, np2 = gh_round_up(n2, T);
+  const int64_t n0 = (n / T) * T, nt0 = n0 / T, tailp = np2 - n0, tt = tailp / T;
+  const bool grow = np2 > np;
+  const int path = nt0 == 0 ? 0 : g_append_path ? g_append_path : (m <= GH_APPEND_MULTI_MAX ? 2 : 3);
+  hipStream_t st = s->st;
+  // ---- every allocation first: a failure up to here leaves the handle as it was
+  GhBuf A2, dinv2, x2, yerr2;
+  GhPooledBuf saved, part;
+  if (grow) {
+    GH_CHECK(take_factor_buffer(s, A2, np2));
+    GH_CHECK(dinv2.ensure((size_t)(np2 / T) * T * T * sizeof(double)));
+  } else {
+    GH_CHECK(saved.ensure((size_t)2 * T * T * sizeof(double)));
+  }
+  const bool grow_x = s->x.bytes < (size_t)n2 * ndim * sizeof(double) || s->yerr.bytes < (size_t)n2 * sizeof(double);
+  if (grow_x) {
+    GH_CHECK(x2.ensure((size_t)np2 * ndim * sizeof(double)));
+    GH_CHECK(yerr2.ensure((size_t)np2 * sizeof(double)));
+  }
+  const int64_t mr = path == 3 ? gh_round_up(m, T) : m;
+  if (nt0 > 0) GH_CHECK(s->work.ensure((size_t)mr * n0 * sizeof(double)));
+  const int64_t npairs = tt * (tt + 1) / 2;
+  // k-slices in units of 128: as many workgroups as keep the chip busy, at most 256 slices
+  const int64_t want = std::max<int64_t>(1, std::min<int64_t>(256, 2048 / npairs));
+  const int64_t ktiles = nt0 > 0 ? (nt0 + want - 1) / want : 0, nslice = nt0 > 0 ? (nt0 + ktiles - 1) / ktiles : 0;
+  if (nt0 > 0) GH_CHECK(part.ensure((size_t)nslice * npairs * T * T * sizeof(double)));
+  GH_CHECK(s->chain.ensure((size_t)(2 * (np2 / T) + 2) * sizeof(unsigned)));
+  GH_CHECK(s->scal.ensure(256 * sizeof(double)));
+  int* fail = (int*)s->chain.p;
+  s->d_info = (long long*)(s->scal.d() + 2);
+  // ---- inputs
+  double* xd = grow_x ? x2.d() : s->x.d();
+  double* yd = grow_x ? yerr2.d() : s->yerr.d();
+  if (grow_x) {
+    GH_HIP(hipMemcpyAsync(xd, s->x.d(), (size_t)n * ndim * sizeof(double), hipMemcpyDeviceToDevice, st));
+    GH_HIP(hipMemcpyAsync(yd, s->yerr.d(), (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
+  }
+  GH_CHECK(gh_to_device(xd + n * ndim, x_new, (size_t)m * ndim, st));
+  GH_CHECK(gh_to_device(yd + n, yerr_new, (size_t)m, st));
+  GH_HIP(hipMemsetAsync(s->d_info, 0, sizeof(long long), st));
+  GH_HIP(hipMemsetAsync(fail, 0, sizeof(int), st));
+  // ---- 1. grow (or save what is overwritten in place)
+  double* Ad = grow ? A2.d() : s->A.d();
+  double* dd = grow ? dinv2.d() : s->dinv.d();
+  const int64_t ld = grow ? np2 : np;
+  s->prof.ms_append_relayout = 0.0;
+  // From here on the in-place case writes into the handle's own factor.  GH_ERR_NOT_PD and a sweep time-out put the old bits back; any
+  // other error return (a failed HIP call) leaves the tail tile half written, and the handle NOT computed.
+  struct Dirty { gh_chol* s; bool armed; ~Dirty() { if (armed) s->computed = false; } } dirty{s, false};
+  long e_lay = -1;                                        // (profile: the relayout's share, gh_chol_profile.ms_append_relayout)
+  if (grow && s->opts.profile) {                          // (events of its own: the pool belongs to the last compute()'s profile)
+    for (auto& e : s->ev_lay) if (!e) GH_HIP(hipEventCreate(&e));
+    e_lay = 0;
+  }
+  if (e_lay >= 0) GH_HIP(hipEventRecord(s->ev_lay[0], st));
+  if (grow) {
+    hipLaunchKernelGGL(relayout_lower_kernel, dim3((unsigned)np2), dim3(256), 0, st, s->A.d(), (long)np, (long)np, Ad, (long)ld);
+    GH_HIP(hipGetLastError());
+    GH_HIP(hipMemcpyAsync(dd, s->dinv.d(), (size_t)(np / T) * T * T * sizeof(double), hipMemcpyDeviceToDevice, st));
+    if (e_lay >= 0) GH_HIP(hipEventRecord(s->ev_lay[1], st));
+  } else {
+    dirty.armed = true;
+    GH_HIP(hipMemcpy2DAsync(saved.d(), T * sizeof(double), Ad + n0 * ld + n0, ld * sizeof(double), T * sizeof(double), T, hipMemcpyDeviceToDevice, st));
+    GH_HIP(hipMemcpyAsync(saved.d() + T * T, dd + nt0 * T * T, (size_t)T * T * sizeof(double), hipMemcpyDeviceToDevice, st));
+  }
+  // ---- 2. the new rows against the full tiles
+  if (nt0 > 0) {
+    double* Kc = s->work.d();
+    GH_CHECK(gh_launch_kmat(k, xd + n * ndim, m, xd, n0, nullptr, Kc, n0, mr, n0, n, 0, true, false, st));
+    if (path == 3) {
+      GH_CHECK(append_trsm_rows(st, Ad, ld, dd, Kc, n0, mr, nt0));
+      GH_HIP(hipMemcpy2DAsync(Ad + n * ld, ld * sizeof(double), Kc, n0 * sizeof(double), n0 * sizeof(double), m, hipMemcpyDeviceToDevice, st));
+    } else {
+      GH_HIP(hipMemset2DAsync(Ad + n * ld, ld * sizeof(double), 0xFF, n0 * sizeof(double), m, st));
+      const dim3 grid((unsigned)nt0), block(CHAIN_THREADS);
+      int64_t i = 0;
+      if (path == 2) {
+        for (; m - i >= 4; i += 4)
+          hipLaunchKernelGGL(trsv_fwd_chain_multi<4>, grid, block, 0, st, Ad, (long)ld, dd, Kc + i * n0, (long)n0, Ad + (n + i) * ld, (long)ld, fail);
+        for (; m - i >= 2; i += 2)
+          hipLaunchKernelGGL(trsv_fwd_chain_multi<2>, grid, block, 0, st, Ad, (long)ld, dd, Kc + i * n0, (long)n0, Ad + (n + i) * ld, (long)ld, fail);
+      }
+      for (; i < m; ++i)
+        hipLaunchKernelGGL(trsv_fwd_chain_direct, grid, block, 0, st, Ad, (long)ld, dd, Kc + i * n0, Ad + (n + i) * ld, fail);
+      GH_HIP(hipGetLastError());
+    }
+  }
+  // ---- 3. the tail block
+  double* S = Ad + n0 * ld + n0;
+  GH_CHECK(gh_launch_kmat(k, xd + n0 * ndim, n2 - n0, xd + n0 * ndim, n2 - n0, yd + n0, S, ld, tailp, tailp, n0, n0, true, true, st));
+  if (nt0 > 0) {
+    hipLaunchKernelGGL(tail_syrk_splitk_kernel, dim3((unsigned)npairs, (unsigned)nslice), dim3(256), 0, st,
+                       Ad + n0 * ld, (long)ld, (long)(ktiles * T), (long)n0, part.d());
+    hipLaunchKernelGGL(tail_syrk_reduce_kernel, dim3((unsigned)npairs, 16), dim3(256), 0, st, S, (long)ld, part.d(), (int)nslice);
+    GH_HIP(hipGetLastError());
+  }
+  GH_CHECK(potrf_block(st, S, ld, tailp, dd + nt0 * T * T, s->d_info, n0));
+  // ---- 4. log-det over the whole diagonal; one synchronisation brings it back with the failure word and the sweeps' time-out flag
+  GH_CHECK(launch_logdet(Ad, (long)ld, (long)np2, s->scal.d(), s->scal.d() + 8, st));
+  double back[3] = {0.0, 0.0, 0.0};
+  int failed = 0;
+  GH_HIP(hipMemcpyAsync(back, s->scal.d(), 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+  GH_HIP(hipMemcpyAsync(&failed, fail, sizeof(int), hipMemcpyDeviceToHost, st));
+  GH_HIP(hipStreamSynchronize(st));
+  long long info_host = 0;
+  memcpy(&info_host, &back[2], sizeof(long long));
+  if (e_lay >= 0) { float ms = 0; GH_HIP(hipEventElapsedTime(&ms, s->ev_lay[0], s->ev_lay[1])); s->prof.ms_append_relayout = ms; }
+  if (info_host != 0 || failed) {
+    if (!grow) {                                          // put back what was overwritten in place: the old bits
+      GH_HIP(hipMemcpy2DAsync(S, ld * sizeof(double), saved.d(), T * sizeof(double), T * sizeof(double), T, hipMemcpyDeviceToDevice, st));
+      GH_HIP(hipMemcpyAsync(dd + nt0 * T * T, saved.d() + T * T, (size_t)T * T * sizeof(double), hipMemcpyDeviceToDevice, st));
+      if (nt0 > 0) GH_HIP(hipMemset2DAsync(Ad + n * ld, ld * sizeof(double), 0, n0 * sizeof(double), m, st));
+    }
+    GH_HIP(hipStreamSynchronize(st));                     // (the buffers of this call go back to the allocator on return)
+    if (grow && !s->A_spare.p) swap_bufs(s->A_spare, A2);  // (... but not the large one)
+    dirty.armed = false;
+    if (failed) { gh_set_error("append: a workgroup of the forward sweep waited more than 2 s for its predecessor"); return GH_ERR_HIP; }
+    s->info = info_host;
+    gh_set_error("%lld-th leading minor of the array is not positive definite", info_host);
+    return GH_ERR_NOT_PD;
+  }
+  dirty.armed = false;
+  if (grow) { swap_bufs(s->A, A2); swap_bufs(s->A_spare, A2); swap_bufs(s->dinv, dinv2); }   // (the old factor buffer is the spare now)
+  if (grow_x) { swap_bufs(s->x, x2); swap_bufs(s->yerr, yerr2); }
+  s->n = n2; s->np = np2; s->info = 0;
+  s->logdet = back[0];
+  if (logdet_out) *logdet_out = back[0];
+  return GH_OK;
+}
+
+extern "C" int gh_chol_set_yerr(gh_chol* s, const double* yerr) {
+  if (!s || !yerr) { gh_set_error("null argument"); return GH_ERR_BAD_ARG; }
+  GH_CHECK(need_computed(s));
+  GH_CHECK(s->yerr.ensure((size_t)s->np * sizeof(double)));
+  GH_CHECK(gh_to_device(s->yerr.d(), yerr, (size_t)s->n, s->st));
+  GH_HIP(hipStreamSynchronize(s->st));
+  s->have_yerr = true;
+  return GH_OK;
+}
+
+extern "C" int gh_chol_truncate(gh_chol* s, int64_t n_keep, double* logdet_out) {
+  if (!s) { gh_set_error("null solver"); return GH_ERR_BAD_ARG; }
+  GH_CHECK(need_computed(s));
+  if (n_keep <= 0 || n_keep > s->n) { gh_set_error("truncate: n_keep must be in 1 .. %lld", (long long)s->n); return GH_ERR_BAD_ARG; }
+  if (n_keep == s->n) { if (logdet_out) *logdet_out = s->logdet; return GH_OK; }
+  const int64_t np = s->np, np2 = gh_round_up(n_keep, T);
+  hipStream_t st = s->st;
+  GhBuf A2, dinv2, x2, yerr2;
+  GH_CHECK(s->scal.ensure(256 * sizeof(double)));
+  if (np2 < np) {
+    // fewer tiles: the leading dimension is Np, so the lower tiles move into a buffer of the new size -- and dinv, x and yerr with
+    // them: the handle holds what it holds after an append that ended at this size
+    const int64_t ndim = s->ndim;
+    GH_CHECK(take_factor_buffer(s, A2, np2));
+    GH_CHECK(dinv2.ensure((size_t)(np2 / T) * T * T * sizeof(double)));
+    GH_CHECK(x2.ensure((size_t)np2 * ndim * sizeof(double)));
+    if (s->have_yerr) GH_CHECK(yerr2.ensure((size_t)np2 * sizeof(double)));
+    GH_HIP(hipMemcpyAsync(dinv2.d(), s->dinv.d(), (size_t)(np2 / T) * T * T * sizeof(double), hipMemcpyDeviceToDevice, st));
+    GH_HIP(hipMemcpyAsync(x2.d(), s->x.d(), (size_t)n_keep * ndim * sizeof(double), hipMemcpyDeviceToDevice, st));
+    if (s->have_yerr) GH_HIP(hipMemcpyAsync(yerr2.d(), s->yerr.d(), (size_t)n_keep * sizeof(double), hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(relayout_lower_kernel, dim3((unsigned)np2), dim3(256), 0, st, s->A.d(), (long)np, (long)n_keep, A2.d(), (long)np2);
+  } else if (np2 > n_keep) {
+    // dropped rows in the same tile row: a leading principal block of L is the factor of that block of K
+    hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)T), dim3(256), 0, st, s->A.d(), (long)np, (long)(np2 - T), (long)n_keep);
+  }
+  GH_HIP(hipGetLastError());
+  if (n_keep % T) {                                       // ... and of a diagonal block's inverse the inverse of that block
+    hipLaunchKernelGGL(dinv_clip_kernel, dim3(1), dim3(256), 0, st, (np2 < np ? dinv2.d() : s->dinv.d()) + (np2 / T - 1) * T * T, (int)(n_keep % T));
+    GH_HIP(hipGetLastError());
+  }
+  const double* Ad = np2 < np ? A2.d() : s->A.d();
+  GH_CHECK(launch_logdet(Ad, (long)np2, (long)np2, s->scal.d(), s->scal.d() + 8, st));
+  double ldv = 0.0;
+  GH_HIP(hipMemcpyAsync(&ldv, s->scal.d(), sizeof(double), hipMemcpyDeviceToHost, st));
+  GH_HIP(hipStreamSynchronize(st));
+  if (np2 < np) {
+    swap_bufs(s->A, A2); swap_bufs(s->A_spare, A2); swap_bufs(s->dinv, dinv2); swap_bufs(s->x, x2);
+    if (s->have_yerr) swap_bufs(s->yerr, yerr2);
+  }
+  s->n = n_keep; s->np = np2; s->info = 0;
+  s->logdet = ldv;
+  if (logdet_out) *logdet_out = ldv;
+  return GH_OK;
 }

@@ -171,13 +171,80 @@ class GP(ModelSet):
         else:
             sig = self._check_dimensions(yerr)
         self._yerr2 = np.ascontiguousarray(sig ** 2, dtype=np.float64)
+        self._factorize(**kwargs)
 
+    def _factorize(self, **kwargs):
+        """A fresh solver computed on the recorded ``_x`` / ``_yerr2``."""
         self.solver = self.solver_type(self.kernel, **(self.solver_kwargs))
         sigma = np.sqrt(self._yerr2 + np.exp(self._call_white_noise(self._x)))
         self.solver.compute(self._x, sigma, **kwargs)
 
         self._const = -0.5 * (len(self._x) * np.log(2 * np.pi) + self.solver.log_determinant)
         self.computed = True
+        self._alpha = None
+
+    # -- sequential use: the data set gains or loses trailing points ---------------
+    # (no reference counterpart: gp.py:303-337 always rebuilds)
+    def _refactorize_or_restore(self, x, yerr2, **kwargs):
+        """``compute`` on already parsed inputs; whatever it raises leaves the GP as it was."""
+        keep = (self._x, self._yerr2, self.solver, self._computed, getattr(self, "_const", None), self._alpha,
+                getattr(self, "_obj_cache", None))
+        self._obj_cache = None
+        self._x, self._yerr2 = x, yerr2
+        try:
+            self._factorize(**kwargs)
+        except Exception:
+            self._x, self._yerr2, self.solver, self._computed, self._const, self._alpha, self._obj_cache = keep
+            raise
+
+    def append(self, x, yerr=0.0, **kwargs):
+        """Add the points ``x`` (error bars ``yerr``, a scalar or one per new point) behind the ones of the last ``compute``.
+        With a computed GP and a solver that offers ``append`` (the HIP :class:`BasicSolver`) the factor is extended in
+        place -- one pass over it and a small Schur block instead of a factorisation; white noise is evaluated at the new
+        points only.  Otherwise (not computed yet, parameters changed since, any other solver) the concatenated inputs are
+        computed afresh.  ``y`` of later calls has the new length.  On ``LinAlgError`` the GP is unchanged."""
+        xn = np.ascontiguousarray(self.parse_samples(x), dtype=np.float64)
+        m = len(xn)
+        if np.ndim(yerr) == 0 or (np.size(yerr) == 1 and m != 1):
+            sig = np.full(m, float(np.reshape(yerr, ())))
+        else:
+            sig = np.atleast_1d(np.asarray(yerr, dtype=np.float64))
+            if sig.ndim > 1 or len(sig) != m:
+                raise ValueError("Dimension mismatch")
+        if not (hasattr(self, "_x") and hasattr(self, "_yerr2")):
+            return self.compute(xn, sig, **kwargs)
+        if xn.shape[1] != self._x.shape[1]:
+            raise ValueError("Dimension mismatch")
+        if m == 0:
+            return
+        x_all = np.ascontiguousarray(np.concatenate([self._x, xn]))
+        yerr2_all = np.ascontiguousarray(np.concatenate([self._yerr2, sig ** 2]))
+        if not (self.computed and callable(getattr(self.solver, "append", None)) and getattr(self.solver, "appendable", True)):
+            return self._refactorize_or_restore(x_all, yerr2_all, **kwargs)
+        sigma_new = np.sqrt(sig ** 2 + np.exp(self._call_white_noise(xn)))
+        self.solver.append(xn, sigma_new)                # (raises with the solver as it was)
+        self._obj_cache = None
+        self._x, self._yerr2 = x_all, yerr2_all
+        self._const = -0.5 * (len(self._x) * np.log(2 * np.pi) + self.solver.log_determinant)
+        self._alpha = None
+
+    def truncate(self, n, **kwargs):
+        """Keep the first ``n`` points of the last ``compute`` / ``append`` (``0 < n <= len(x)``): undoes a tentative
+        ``append``.  Data movement on the device with the HIP :class:`BasicSolver`, a fresh ``compute`` otherwise."""
+        if not (hasattr(self, "_x") and hasattr(self, "_yerr2")):
+            raise RuntimeError("You need to compute the model first")
+        n = int(n)
+        if not 0 < n <= len(self._x):
+            raise ValueError("truncate: n must be in 1 .. {0}".format(len(self._x)))
+        if n == len(self._x):
+            return
+        x_cut, yerr2_cut = np.ascontiguousarray(self._x[:n]), np.ascontiguousarray(self._yerr2[:n])
+        if not (self.computed and callable(getattr(self.solver, "truncate", None))):
+            return self._refactorize_or_restore(x_cut, yerr2_cut, **kwargs)
+        self.solver.truncate(n)
+        self._obj_cache = None
+        self._x, self._yerr2 = x_cut, yerr2_cut
+        self._const = -0.5 * (len(self._x) * np.log(2 * np.pi) + self.solver.log_determinant)
         self._alpha = None
 
     def recompute(self, quiet=False, **kwargs):

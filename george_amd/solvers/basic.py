@@ -193,6 +193,8 @@ class BasicSolver(object):
         h = self._ensure_handle()
         N.check(N.lib.gh_chol_import_factor(h, self._n, self._x_host.shape[1], N.ptr(self._x_host), N.ptr(L), N.ptr(dinv),
                                             float(self._log_det)))
+        if getattr(self, "_yerr_host", None) is not None:       # (append forms the last tile's old rows again: it needs them)
+            N.check(N.lib.gh_chol_set_yerr(h, N.ptr(self._yerr_host)))
         self._factor_state = None
 
     # -- the solver protocol
@@ -213,6 +215,7 @@ class BasicSolver(object):
             hh, self._dk.handle, N.ptr(x), len(x), x.shape[1], N.ptr(yerr), C.byref(logdet))))
         self._n = len(x)
         self._x_host = x                     # (the inputs travel with a pickled factor: predict / grad need them)
+        self._yerr_host = yerr               # (... and append)
         self.log_determinant = logdet.value
         self.computed = True
 
@@ -246,6 +249,7 @@ class BasicSolver(object):
             C.byref(logdet), C.byref(quad), N.ptr(g), N.ptr(alpha), N.ptr(diagA))))
         self._n = n
         self._x_host = x
+        self._yerr_host = yerr
         self.log_determinant = logdet.value
         self.computed = True
         return logdet.value, quad.value, (g[:self._dk.size] if g is not None else None), alpha, diagA
@@ -377,6 +381,53 @@ class BasicSolver(object):
             raise RuntimeError("you must call 'compute' first")
         return self._handle
 
+    # -- sequential use (no reference counterpart: basic.py:51-70 always refactorises)
+    @property
+    def appendable(self):
+        """Does the solver hold what ``append`` needs beside the factor -- the error bars of its points?  (Not when it was
+        restored from a state pickled without them; ``GP.append`` then computes afresh.)"""
+        return getattr(self, "_yerr_host", None) is not None
+
+    def append(self, x_new, yerr_new):
+        """Extend the computed factor by the points ``x_new`` (m, ndim) with standard deviations ``yerr_new`` (white noise
+        included), gh_chol_append: the rows of the full 128-row tiles are not touched.  The kernel is the one of
+        ``compute``.  ``LinAlgError`` (the extended matrix is not positive definite) leaves the solver as it was."""
+        self._need()
+        if not self.appendable:
+            raise RuntimeError("this solver was restored without the error bars of its points: compute() again")
+        x_new = N.as_f64(x_new)
+        if x_new.ndim != 2:
+            raise ValueError("x_new must be (nsamples, ndim)")
+        if x_new.shape[1] != self._x_host.shape[1]:
+            raise RuntimeError("dimension mismatch")
+        m = len(x_new)
+        if m == 0:
+            return
+        yerr_new = N.as_f64(np.zeros(m) + yerr_new)
+        logdet = C.c_double(0.0)
+        self._retry_without_parked_memory(lambda hh: N.check(N.lib.gh_chol_append(
+            hh, self._dk.handle, N.ptr(x_new), m, N.ptr(yerr_new), C.byref(logdet))))
+        self._n += m
+        self._x_host = np.ascontiguousarray(np.concatenate([self._x_host, x_new]))
+        self._yerr_host = np.ascontiguousarray(np.concatenate([self._yerr_host, yerr_new]))
+        self.log_determinant = logdet.value
+
+    def truncate(self, n):
+        """Keep the first ``n`` points of the computed factor (gh_chol_truncate): data movement and one log-det reduction."""
+        self._need()
+        n = int(n)
+        if not 0 < n <= self._n:
+            raise ValueError("truncate: n must be in 1 .. {0}".format(self._n))
+        if n == self._n:
+            return
+        logdet = C.c_double(0.0)
+        self._retry_without_parked_memory(lambda hh: N.check(N.lib.gh_chol_truncate(hh, n, C.byref(logdet))))
+        self._n = n
+        self._x_host = np.ascontiguousarray(self._x_host[:n])
+        if self.appendable:
+            self._yerr_host = np.ascontiguousarray(self._yerr_host[:n])
+        self.log_determinant = logdet.value
+
     def apply_inverse(self, y, in_place=False):
         """basic.py:72-87 (``cho_solve``): ``y`` is (n,) or (n, nrhs)."""
         h = self._need()
@@ -457,7 +508,8 @@ class BasicSolver(object):
         p = N.gh_chol_profile()
         N.check(N.lib.gh_chol_get_profile(self._need(), C.byref(p)))
         return dict(ms_total=p.ms_total, ms_build=p.ms_build, ms_panel=p.ms_panel, ms_trailing=p.ms_trailing,
-                    trailing_flops=p.trailing_flops, n_trailing=p.n_trailing, ms_solve=p.ms_solve)
+                    trailing_flops=p.trailing_flops, n_trailing=p.n_trailing, ms_solve=p.ms_solve,
+                    ms_append_relayout=p.ms_append_relayout)
 
 
 atexit.register(BasicSolver.release_pool)

@@ -160,6 +160,22 @@ void gh_chol_destroy(gh_chol* s);
 /* yerr: (n,) standard deviations ALREADY including white noise (gp.py:330). */
 int  gh_chol_compute(gh_chol* s, gh_kernel* k, const double* x, int64_t n, int32_t ndim,
                      const double* yerr, double* logdet_out);
+/* Sequential use (no reference counterpart: gp.py:303-337 always rebuilds).
+ * K' = [[K, k(x, xn)], [k(xn, x), k(xn, xn) + diag(yerr_new^2)]]: extend the computed factor by m rows.  The rows of the
+ * full 128-row tiles of the factor and their diagonal-block inverses are not touched (bit for bit); the rows of the last,
+ * partial tile are formed again.  The kernel must be the one (same parameters) the handle was computed with; that is the
+ * caller's contract.  x_new (m, ndim), yerr_new (m): host or device.  On GH_OK the handle is computed at n + m and
+ * *logdet_out = log|K'|.  On GH_ERR_NOT_PD, gh_chol_info() is the 1-based index in the extended matrix, and the handle is
+ * left computed at the OLD n with the old factor bits; so it is after GH_ERR_NOMEM.  Any other error (a failed HIP call) while
+ * the last tile is being rewritten in place leaves the handle NOT computed.  A handle rebuilt by gh_chol_import_factor needs
+ * gh_chol_set_yerr first (GH_ERR_BAD_ARG otherwise): the old rows of the last, partial tile are formed again from the kernel
+ * and the error bars.  When the tile count grows the factor moves into another buffer; the handle keeps the one it left as a
+ * spare for the next move (counted by gh_chol_device_bytes, freed by gh_chol_trim). */
+int  gh_chol_append(gh_chol* s, gh_kernel* k, const double* x_new, int64_t m, const double* yerr_new, double* logdet_out);
+/* keep the first n_keep points (0 < n_keep <= n); *logdet_out = log|K[:n_keep, :n_keep]|.  Data movement and one reduction. */
+int  gh_chol_truncate(gh_chol* s, int64_t n_keep, double* logdet_out);
+/* the error bars (n, as given to compute / append) of a computed handle: what gh_chol_import_factor does not bring */
+int  gh_chol_set_yerr(gh_chol* s, const double* yerr);
 int64_t gh_chol_info(const gh_chol* s);     /* 1-based index of the failing pivot after GH_ERR_NOT_PD, else 0 */
 int64_t gh_chol_size(const gh_chol* s);
 int64_t gh_chol_device_bytes(const gh_chol* s);  /* HBM bytes the handle holds right now (factor + work arrays) */
@@ -249,7 +265,8 @@ typedef struct gh_chol_profile {
   double ms_update_union;   /* time during which ANY trailing-update launch ran (wide SYRKs on the main
                              * stream + block-column / in-group / next-group GEMMs on the chain stream): union of their intervals */
   double update_flops;      /* algorithmic flops of all those launches          */
-  double reserved[2];
+  double ms_append_relayout; /* last gh_chol_append(): moving the factor into buffers of the new Np (0: it stayed in place) */
+  double reserved[1];
 } gh_chol_profile;
 int  gh_chol_get_profile(const gh_chol* s, gh_chol_profile* out);
 /* per trailing-update launch of the last profiled compute(): (start ms, end ms, algorithmic flops), times from the

@@ -30,6 +30,11 @@ int gh_debug_set_gemm_grouped(int mode);
 /* 1 (default): with look-ahead, a compute()'s inputs and kernel-matrix build are enqueued on the chain stream (whose first panel is
  * the first thing that needs them); 0: on the main stream with a cross-stream hand-over, as until round 6.  Returns the previous setting. */
 int gh_debug_set_build_on_chain(int on);
+/* How gh_chol_append solves the new rows against the full tiles of the factor, X = K(x_new, x[:n0]) L00^-T: 0 the library's rule
+ * (by the number of new rows), 1 one chained forward sweep per new row (trsv_fwd_chain_direct), 2 chained sweeps that carry 4 or 2
+ * rows each (trsv_fwd_chain_multi; a last odd row takes the one-row kernel), 3 blocked right-looking substitution on the matrix
+ * pipe.  Returns the previous setting.  1 and 2 give the same bits; 3 agrees with them to rounding. */
+int gh_debug_set_append_path(int path);
 /* 1 (default): with the panel width left to the solver (gh_chol_opts.nb == 0) the outer panels are 2048 columns wide while the
  * trailing matrix behind them has more than 25 600 columns and 1024 after; 0: 1024 throughout; n > 1: the bound is n columns.
  * Returns the previous setting.  Same bits whatever the widths (the update adds the same k in the same order). */
