@@ -624,6 +624,115 @@ __global__ void copy2d_kernel(const double* in, long ldi, double* out, long ldo,
   out[i * ldo + j] = in[i * ldi + j];
 }
 
+// ================================================= leave-one-out cross-validation
+#define LT 64                 // tile edge of the leave-one-out kernels
+// Column sums of squares of a LOWER-triangular row-major matrix (L^-1): part[s][c] = sum over the rows r >= c of the s-th row
+// chunk of V[r][c]^2.  A workgroup takes 64 columns of one chunk, a wavefront every fourth row: each load instruction reads
+// 512 contiguous bytes, four rows are in flight per trip.  Rows above the tile's first column hold zeros and are not read.
+// The four wavefronts' sums meet in LDS in a fixed order; colsumsq_final_kernel adds the chunks in index order: no atomics,
+// bitwise reproducible.
+__global__ __launch_bounds__(256) void colsumsq_kernel(const double* V, long ld, long np, long rows_per, double* part) {
+  __shared__ double sh[4][LT];
+  const int lc = threadIdx.x & 63, lr = threadIdx.x >> 6;
+  const long c0 = (long)blockIdx.x * LT, c = c0 + lc;
+  long r0 = (long)blockIdx.y * rows_per;
+  const long r1 = r0 + rows_per < np ? r0 + rows_per : np;
+  if (r0 < c0) r0 = c0;
+  double acc = 0.0;
+  long r = r0 + lr;
+  for (; r + 12 < r1; r += 16) {
+    double a[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) a[q] = V[(r + 4 * q) * ld + c];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc += (r + 4 * q >= c) ? a[q] * a[q] : 0.0;
+  }
+  for (; r < r1; r += 4) {
+    const double a = V[r * ld + c];
+    acc += (r >= c) ? a * a : 0.0;
+  }
+  sh[lr][lc] = acc;
+  __syncthreads();
+  if (lr == 0) part[(long)blockIdx.y * np + c] = (sh[0][lc] + sh[1][lc]) + (sh[2][lc] + sh[3][lc]);
+}
+__global__ void colsumsq_final_kernel(const double* part, long nchunks, long np, double* c) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= np) return;
+  double v = 0.0;
+  for (long s = 0; s < nchunks; ++s) v += part[s * np + i];
+  c[i] = v;
+}
+// The per-point quantities from alpha and c_i = (K^-1)_ii (c[i * cstride]: a vector, or the diagonal of a matrix):
+//   resid = u = alpha / c,  var = 1 / c,  lpd = 1/2 log c - 1/2 alpha^2 / c - 1/2 log 2 pi,  sw = sqrt(w),  w = 1/2 (1 + alpha^2 / c) / c.
+// Padded rows i >= n get zeros everywhere: nothing of them reaches the sum of lpd or S = K^-1 diag(sqrt(w)).
+// `u` is a second copy of resid that the solve for v = K^-1 u consumes.
+__global__ void loo_point_kernel(const double* alpha, const double* c, long cstride, long n, long np,
+                                 double* resid, double* u, double* var, double* lpd, double* sw) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= np) return;
+  double ui = 0.0, vi = 0.0, li = 0.0, si = 0.0;
+  if (i < n) {
+    const double ci = c[i * cstride], a = alpha[i];
+    ui = a / ci;
+    vi = 1.0 / ci;
+    const double q = a * ui;
+    li = 0.5 * log(ci) - 0.5 * q - 0.91893853320467274178;
+    si = sqrt(0.5 * (1.0 + q) / ci);
+  }
+  resid[i] = ui;
+  if (u) u[i] = ui;
+  var[i] = vi;
+  lpd[i] = li;
+  sw[i] = si;
+}
+// S = Kinv diag(sw) as a FULL matrix from the lower triangle of Kinv, one pass: a workgroup reads the 64 x 64 tile (ti, tj),
+// tj <= ti, into LDS and writes tile (ti, tj) of S as it lies and tile (tj, ti) transposed, column k scaled by sw[k].  Reads and
+// both writes are coalesced (a row of 64 doubles per wavefront); the transposed LDS reads walk a pitch of 65: no bank conflicts.
+__global__ __launch_bounds__(256) void loo_mirror_scale_kernel(const double* W, long ld, const double* sw, double* S) {
+  __shared__ double t[LT][LT + 1];
+  int ti, tj;
+  tri_index(blockIdx.x, ti, tj);
+  const long r0 = (long)ti * LT, c0 = (long)tj * LT;
+  const int lc = threadIdx.x & 63, lr = threadIdx.x >> 6;
+#pragma unroll 4
+  for (int rr = lr; rr < LT; rr += 4) t[rr][lc] = W[(r0 + rr) * ld + c0 + lc];
+  __syncthreads();
+  const double sc = sw[c0 + lc];
+  if (ti != tj) {
+    const double sr = sw[r0 + lc];
+#pragma unroll 4
+    for (int rr = lr; rr < LT; rr += 4) {
+      S[(r0 + rr) * ld + c0 + lc] = t[rr][lc] * sc;
+      S[(c0 + rr) * ld + r0 + lc] = t[lc][rr] * sr;
+    }
+  } else {
+#pragma unroll 4
+    for (int rr = lr; rr < LT; rr += 4) S[(r0 + rr) * ld + c0 + lc] = (lc <= rr ? t[rr][lc] : t[lc][rr]) * sc;
+  }
+}
+// out[0] = sum_{i < n} a[i]: one workgroup, or slices added in index order (launch_sum, as launch_dot)
+__global__ __launch_bounds__(256) void sum_part_kernel(const double* a, long n, double* part) {
+  __shared__ double sh[4];
+  const long per = (n + gridDim.x - 1) / gridDim.x;
+  const long lo = (long)blockIdx.x * per, hi = lo + per < n ? lo + per : n;
+  double v = 0.0;
+  for (long i = lo + threadIdx.x; i < hi; i += 256) v += a[i];
+  v = block_sum_256(v, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = v;
+}
+static int launch_sum(const double* a, long n, double* out, double* part, hipStream_t st) {
+  const int g = (int)std::max<long>(1, std::min<long>(RED_SLICES, (n + 4095) / 4096));
+  hipLaunchKernelGGL(sum_part_kernel, dim3(g), dim3(256), 0, st, a, n, part);
+  hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(64), 0, st, part, g, 1.0, out, 0, (const int*)nullptr);
+  GH_HIP(hipGetLastError());
+  return GH_OK;
+}
+// *acc = 1 when one of the chained sweeps just enqueued gave up waiting: several deferred pairs of sweeps share the flag words,
+// which every launch clears
+__global__ void chain_fail_note_kernel(const int* ff, const int* fb, double* acc) {
+  if (threadIdx.x == 0 && blockIdx.x == 0 && (*ff != 0 || *fb != 0)) *acc = 1.0;
+}
+
 // ================================================================= the solver
 struct EvPair { hipEvent_t a, b; };
 
@@ -655,6 +764,7 @@ struct gh_chol {
   double logdet = 0.0;
   GhBuf A, dinv, x, yerr, v0, v1, v2, scal, rhs, work, work2, scratch, chain;
   GhBuf A_spare;                         // the buffer the factor left when append / truncate last moved it: where the next move goes (freed by trim)
+  GhBuf lv;                              // gh_chol_loo's N-vectors: resid, var, lpd, sqrt(w), c, alpha, v (7 Np doubles)
   long long* d_info = nullptr;           // = (long long*)(scal + 2): the failure word lives beside the scalars (set in compute_enqueue)
   bool build_on_chain = false;           // this compute(): inputs + kernel-matrix build were enqueued on the chain stream (st2)
   GhBatchBufs* batch = nullptr;          // gh_chol_objective_batch's buffers (gh_batch.hip), grown once and re-used
@@ -898,7 +1008,7 @@ extern "C" int64_t gh_chol_device_bytes(const gh_chol* s) {
   if (!s) return 0;
   size_t tot = 0;
   for (const GhBuf* b : {&s->A, &s->A_spare, &s->dinv, &s->x, &s->yerr, &s->v0, &s->v1, &s->v2, &s->scal, &s->rhs, &s->work, &s->work2,
-                         &s->scratch, &s->chain}) tot += b->p ? b->bytes : 0;
+                         &s->scratch, &s->chain, &s->lv}) tot += b->p ? b->bytes : 0;
   return (int64_t)(tot + gh_batch_bytes(s->batch));
 }
 int gh_chol_batch_begin(gh_chol* s, hipStream_t* st, GhBatchBufs** bufs) {
@@ -1743,16 +1853,19 @@ extern "C" int gh_chol_apply_sqrt(gh_chol* s, const double* r, int64_t nrows, do
   return GH_OK;
 }
 
-// W (np x np) <- K^-1, lower triangle valid.  Uses K^-1 = L^-T L^-1:
-//   Linv = L^-1 (forward substitution on the identity), K^-1 = Linv^T Linv (k >= max(i, j)).
-static int inverse_lower(gh_chol* s, double* W /* np*np */, double* Linv /* np*np scratch */) {
-  const int64_t np = s->np, nt = np / T;
-  const double* L = s->A.d();
+// Linv (np x np) <- L^-1: forward substitution on the identity, exploiting the lower-triangular right-hand side (tri = true)
+static int linv_into(gh_chol* s, double* Linv) {
+  const int64_t np = s->np;
   GH_HIP(hipMemsetAsync(Linv, 0, (size_t)np * np * sizeof(double), s->st));
   hipLaunchKernelGGL(eye_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s->st, Linv, (long)np, (long)np);
   GH_HIP(hipGetLastError());
-  // forward substitution exploiting the lower-triangular right-hand side (tri = true)
-  GH_CHECK(trsm_multi(s, Linv, np, true, false, true));
+  return trsm_multi(s, Linv, np, true, false, true);
+}
+// W (np x np) <- K^-1, lower triangle valid.  Uses K^-1 = L^-T L^-1:
+//   Linv = L^-1 (forward substitution on the identity), K^-1 = Linv^T Linv (k >= max(i, j)).
+static int inverse_lower(gh_chol* s, double* W /* np*np */, double* Linv /* np*np scratch */) {
+  const int64_t np = s->np;
+  GH_CHECK(linv_into(s, Linv));
   GhGemm q{};
   q.C = W; q.ldc = np; q.A = Linv; q.lda = np; q.B = Linv; q.ldb = np;
   q.M = np; q.N = np; q.K = np; q.alpha = 1.0; q.beta = 0.0; q.a_km = false; q.b_km = false;
@@ -1920,6 +2033,140 @@ extern "C" int gh_chol_objective(gh_chol* s, gh_kernel* k, const double* x, int6
   return GH_OK;
 }
 
+// ============================================================ leave-one-out cross-validation
+// (no reference counterpart: src/george/gp.py has no cross-validation.)  With c_i = (K^-1)_ii and alpha = K^-1 r the prediction of
+// y_i from all other points has residual alpha_i / c_i and variance 1 / c_i (GPML 5.4.2), and the gradient of the log
+// pseudo-likelihood is sum_ij B_ij dK_ij/dtheta with B = 1/2 (v alpha^T + alpha v^T) - S S^T, S = K^-1 diag(sqrt(w)), v = K^-1 u:
+// ONE triangular N^3 product for any number of parameters ("Leave-one-out cross-validation").
+//   value path:    alpha -> work = L^-1 -> c = column sums of squares -> per-point kernel -> sum of lpd.   K^-1 is never formed.
+//   gradient path: alpha -> work = K^-1 (work2 = L^-1) -> c = diag -> per-point kernel -> v -> work2 = S -> work = S S^T (lower)
+//                  -> the contraction (gh_launch_kgrad_reduce_loo).
+// Everything is enqueued on s->st; results stay on the device (s->lv, s->v0 = grad, s->v1 = diagB, s->scal[1] = sum of lpd,
+// s->scal[3] != 0: a chained sweep timed out) until loo_fetch().
+enum { LV_RESID = 0, LV_VAR, LV_LPD, LV_SW, LV_C, LV_ALPHA, LV_V, LV_COUNT };     // (alpha and v adjacent: gh_launch_kgrad_reduce_loo)
+static int loo_note_fail(gh_chol* s) {
+  static const bool stepwise = getenv("GEORGE_AMD_TRSV_STEPS") != nullptr;
+  if (stepwise) return GH_OK;
+  const int64_t nt = s->np / T;
+  const int* flags = (const int*)s->chain.p;
+  hipLaunchKernelGGL(chain_fail_note_kernel, dim3(1), dim3(64), 0, s->st, flags + nt, flags + (nt + 1) + nt, s->scal.d() + 3);
+  GH_HIP(hipGetLastError());
+  return GH_OK;
+}
+static int loo_enqueue(gh_chol* s, gh_kernel* k, const uint32_t* which, const double* r, bool grad_path) {
+  const int64_t n = s->n, np = s->np;
+  hipStream_t st = s->st;
+  GH_CHECK(s->lv.ensure((size_t)LV_COUNT * np * sizeof(double)));
+  GH_CHECK(s->v0.ensure((size_t)std::max<int64_t>(np, GH_MAX_GRAD) * sizeof(double)));
+  GH_CHECK(s->v1.ensure((size_t)np * sizeof(double)));
+  double* lv = s->lv.d();
+  GH_HIP(hipMemsetAsync(s->scal.d() + 3, 0, sizeof(double), st));
+  // alpha = K^-1 r
+  double* alpha = lv + LV_ALPHA * np;
+  GH_CHECK(load_vec(s, s->v0, r));
+  GH_CHECK(trsv_forward(s, s->v0.d(), s->v1.d(), true));
+  GH_CHECK(trsv_backward(s, s->v1.d(), alpha, true));
+  GH_CHECK(loo_note_fail(s));
+  const unsigned gv = (unsigned)((np + 255) / 256);
+  if (!grad_path) {
+    // c_i = sum_{k >= i} (L^-1)_ki^2: the diagonal of K^-1 = L^-T L^-1 without the product
+    GH_CHECK(s->work.ensure((size_t)np * np * sizeof(double)));
+    double* Linv = s->work.d();
+    GH_CHECK(linv_into(s, Linv));
+    const int64_t nchunks = std::min<int64_t>(64, np / T);
+    const int64_t rows_per = (np + nchunks - 1) / nchunks;
+    GH_CHECK(s->scratch.ensure((size_t)nchunks * np * sizeof(double)));
+    hipLaunchKernelGGL(colsumsq_kernel, dim3((unsigned)(np / LT), (unsigned)nchunks), dim3(256), 0, st,
+                       Linv, (long)np, (long)np, (long)rows_per, s->scratch.d());
+    hipLaunchKernelGGL(colsumsq_final_kernel, dim3(gv), dim3(256), 0, st, s->scratch.d(), (long)nchunks, (long)np, lv + LV_C * np);
+    hipLaunchKernelGGL(loo_point_kernel, dim3(gv), dim3(256), 0, st, alpha, lv + LV_C * np, 1L, (long)n, (long)np,
+                       lv + LV_RESID * np, (double*)nullptr, lv + LV_VAR * np, lv + LV_LPD * np, lv + LV_SW * np);
+    GH_HIP(hipGetLastError());
+  } else {
+    GH_CHECK(s->work.ensure((size_t)np * np * sizeof(double)));
+    GH_CHECK(s->work2.ensure((size_t)np * np * sizeof(double)));
+    GH_CHECK(inverse_lower(s, s->work.d(), s->work2.d()));
+    hipLaunchKernelGGL(loo_point_kernel, dim3(gv), dim3(256), 0, st, alpha, s->work.d(), (long)np + 1, (long)n, (long)np,
+                       lv + LV_RESID * np, s->v0.d(), lv + LV_VAR * np, lv + LV_LPD * np, lv + LV_SW * np);
+    GH_HIP(hipGetLastError());
+    // v = K^-1 u
+    GH_CHECK(trsv_forward(s, s->v0.d(), s->v1.d(), true));
+    GH_CHECK(trsv_backward(s, s->v1.d(), lv + LV_V * np, true));
+    GH_CHECK(loo_note_fail(s));
+    // work2 <- S = K^-1 diag(sqrt(w)), then work <- M = S S^T (lower tiles)
+    const long tm = (long)(np / LT);
+    hipLaunchKernelGGL(loo_mirror_scale_kernel, dim3((unsigned)(tm * (tm + 1) / 2)), dim3(256), 0, st,
+                       s->work.d(), (long)np, lv + LV_SW * np, s->work2.d());
+    GH_HIP(hipGetLastError());
+    GhGemm g{};
+    g.C = s->work.d(); g.ldc = np; g.A = s->work2.d(); g.lda = np; g.B = s->work2.d(); g.ldb = np;
+    g.M = np; g.N = np; g.K = np; g.alpha = 1.0; g.beta = 0.0; g.a_km = true; g.b_km = true; g.lower = true;
+    GH_CHECK(gh_launch_gemm(g, st));
+    static const uint32_t none[GH_MAX_GRAD] = {0};
+    static_assert(LV_V == LV_ALPHA + 1, "gh_launch_kgrad_reduce_loo reads v one leading dimension (np) behind alpha");
+    GH_CHECK(gh_launch_kgrad_reduce_loo(k, which ? which : none, s->x.d(), n, alpha, s->work.d(), np,
+                                        s->v0.d(), s->v1.d(), s->scratch, st));       // (v0, v1 are free again)
+  }
+  return launch_sum(lv + LV_LPD * np, (long)n, s->scal.d() + 1, s->scal.d() + 72, st);
+}
+// the copies out (host or device destinations), enqueued on s->st
+static int loo_fetch(gh_chol* s, gh_kernel* k, double* resid, double* var, double* lpd, double* grad, double* v, double* diagB) {
+  const int64_t n = s->n, np = s->np;
+  hipStream_t st = s->st;
+  const double* lv = s->lv.d();
+  GH_CHECK(gh_from_device(resid, lv + LV_RESID * np, (size_t)n, st));
+  GH_CHECK(gh_from_device(var, lv + LV_VAR * np, (size_t)n, st));
+  if (lpd) GH_CHECK(gh_from_device(lpd, lv + LV_LPD * np, (size_t)n, st));
+  if (grad && k->size > 0) GH_CHECK(gh_from_device(grad, s->v0.d(), (size_t)k->size, st));
+  if (v) GH_CHECK(gh_from_device(v, lv + LV_V * np, (size_t)n, st));
+  if (diagB) GH_CHECK(gh_from_device(diagB, s->v1.d(), (size_t)n, st));
+  return GH_OK;
+}
+
+extern "C" int gh_chol_loo(gh_chol* s, gh_kernel* k, const uint32_t* which, const double* r, double* lpd_sum, double* resid,
+                           double* var, double* lpd, double* grad, double* v, double* diagB) {
+  GH_CHECK(need_computed(s));
+  if (!k || !r || !lpd_sum || !resid || !var) { gh_set_error("bad argument to loo"); return GH_ERR_BAD_ARG; }
+  if (grad && !which) { gh_set_error("loo: gradient requested without a parameter mask"); return GH_ERR_BAD_ARG; }
+  if (k->ndim != s->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
+  GH_CHECK(k->upload());
+  GH_CHECK(loo_enqueue(s, k, grad ? which : nullptr, r, grad || v || diagB));
+  double host[4] = {0.0, 0.0, 0.0, 0.0};                // (log-det), sum of lpd, (failure word), the chains' time-out flag
+  GH_HIP(hipMemcpyAsync(host, s->scal.d(), 4 * sizeof(double), hipMemcpyDeviceToHost, s->st));
+  GH_CHECK(loo_fetch(s, k, resid, var, lpd, grad, v, diagB));
+  GH_HIP(hipStreamSynchronize(s->st));
+  if (host[3] != 0.0) { gh_set_error("loo: a chained solve waited more than 2 s for its predecessor"); return GH_ERR_HIP; }
+  *lpd_sum = host[1];
+  return GH_OK;
+}
+
+// build K -> factor -> log-det -> the sequence of gh_chol_loo, ONE synchronisation: the analogue of gh_chol_objective for the
+// leave-one-out objective.  The same launches as gh_chol_compute followed by gh_chol_loo: the same bits.
+extern "C" int gh_chol_loo_objective(gh_chol* s, gh_kernel* k, const double* x, int64_t n, int32_t ndim, const double* yerr,
+                                     const double* r, const uint32_t* which, double* logdet, double* lpd_sum,
+                                     double* resid, double* var, double* grad, double* v, double* diagB) {
+  if (!r || !logdet || !lpd_sum || !resid || !var) { gh_set_error("bad argument to loo_objective"); return GH_ERR_BAD_ARG; }
+  if (grad && !which) { gh_set_error("loo_objective: gradient requested without a parameter mask"); return GH_ERR_BAD_ARG; }
+  ComputeCtx c;
+  GH_CHECK(compute_enqueue(s, k, x, n, ndim, yerr, c));
+  hipStream_t st = s->st;
+  if (s->tail && s->tail != st && s->ev_sync[1]) {      // (the solves and the products run on the main stream: it joins here)
+    GH_HIP(hipEventRecord(s->ev_sync[1], s->tail));
+    GH_HIP(hipStreamWaitEvent(st, s->ev_sync[1], 0));
+  }
+  GH_CHECK(loo_enqueue(s, k, grad ? which : nullptr, r, grad || v || diagB));
+  double host[4] = {0.0, 0.0, 0.0, 0.0};                // log-det, sum of lpd, failure word (bits), the chains' time-out flag
+  GH_HIP(hipMemcpyAsync(host, s->scal.d(), 4 * sizeof(double), hipMemcpyDeviceToHost, st));
+  GH_CHECK(loo_fetch(s, k, resid, var, nullptr, grad, v, diagB));
+  GH_HIP(hipStreamSynchronize(st));
+  long long info_host = 0;
+  memcpy(&info_host, &host[2], sizeof(long long));
+  GH_CHECK(compute_finish(s, c, host[0], info_host, logdet));
+  if (host[3] != 0.0) { gh_set_error("loo_objective: a chained solve waited more than 2 s for its predecessor"); return GH_ERR_HIP; }
+  *lpd_sum = host[1];
+  return GH_OK;
+}
+
 // ============================================================ factor export / import
 // The reference's BasicSolver survives pickling COMPUTED (tests/test_pickle.py:21-36: its factor is a
 // NumPy array).  Here the factor lives in HBM, so it is packed on the device -- row i of the lower
@@ -1985,7 +2232,7 @@ extern "C" void gh_chol_release_buffers(gh_chol* s) {
   (void)hipSetDevice(s->opts.device);
   if (s->st) (void)hipStreamSynchronize(s->st);
   s->computed = false;
-  for (GhBuf* b : {&s->A, &s->A_spare, &s->dinv, &s->x, &s->yerr, &s->v0, &s->v1, &s->v2, &s->rhs, &s->work, &s->work2, &s->scratch, &s->chain}) b->release();
+  for (GhBuf* b : {&s->A, &s->A_spare, &s->dinv, &s->x, &s->yerr, &s->v0, &s->v1, &s->v2, &s->rhs, &s->work, &s->work2, &s->scratch, &s->chain, &s->lv}) b->release();
   gh_batch_free(s->batch);
   s->batch = nullptr;
 }

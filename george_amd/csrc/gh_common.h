@@ -130,6 +130,12 @@ int gh_launch_kxgrad(const gh_kernel* k, int which_arg, const double* x1, int64_
 int gh_launch_kgrad_reduce(const gh_kernel* k, const uint32_t* which_host, const double* x, int64_t n,
                            const double* alpha, const double* kinv, int64_t ld, double* grad_dev /* size */,
                            double* diagA /* n or NULL */, GhBuf& scratch, hipStream_t st);
+// the leave-one-out form (gh_chol_loo): grad[p] = sum_{i>=j} w_ij B_ij dK_ij/dtheta_p, B_ij = 1/2 (alpha_i beta_j + beta_i alpha_j) - M[i][j],
+// w = 1 on the diagonal, 2 below (== sum_ij B_ij dK_ij/dtheta_p); diagB[i] = B_ii.  alpha_beta: alpha, and beta `ld` doubles
+// behind it.  Same tiles, same fixed-order sums.
+int gh_launch_kgrad_reduce_loo(const gh_kernel* k, const uint32_t* which_host, const double* x, int64_t n,
+                               const double* alpha_beta, const double* m, int64_t ld, double* grad_dev /* size */,
+                               double* diagB /* n or NULL */, GhBuf& scratch, hipStream_t st);
 
 // grad_dev[p] = sum over the nblk rows of partial (nblk x P) in a fixed-order tree: bitwise reproducible (the second stage of
 // gh_launch_kgrad_reduce, and of the strip form in gh_hodlr.hip)

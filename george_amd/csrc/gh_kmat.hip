@@ -610,57 +610,24 @@ int gh_launch_kxgrad(const gh_kernel* k, int which_arg, const double* x1, int64_
 #ifndef GH_KGRAD_WAVES
 #define GH_KGRAD_WAVES 4
 #endif
+// (the body, shared with the leave-one-out form below: gh_kgrad_body.h)
 template <int PMAX>
 __global__ __launch_bounds__(256, PMAX <= 16 ? GH_KGRAD_WAVES : 1) void kgrad_reduce_kernel(const GhNode* __restrict__ prog, int n_nodes, int nd, int P,
                                                            const uint32_t* which, const double* x, long n,
                                                            const double* alpha, const double* kinv, long ld,
                                                            double* partial, double* diagA) {
-  __shared__ double xr[KT * GH_MAX_NDIM];
-  __shared__ double xc[KT * GH_MAX_NDIM];
-  __shared__ double red[4][PMAX];
-  int ti, tj;
-  tri_index(blockIdx.x, ti, tj);
-  const long r0 = (long)ti * KT, c0 = (long)tj * KT;
-  for (int t = threadIdx.x; t < KT * nd; t += 256) {
-    const long r = r0 + t / nd;
-    xr[t] = (r < n) ? x[r * nd + (t % nd)] : 0.0;
-    const long c = c0 + t / nd;
-    xc[t] = (c < n) ? x[c * nd + (t % nd)] : 0.0;
-  }
-  __syncthreads();
-  double acc[PMAX];
-#pragma unroll
-  for (int p = 0; p < PMAX; ++p) acc[p] = 0.0;
-  const int lc = threadIdx.x & 63;
-  const int lr = threadIdx.x >> 6;
-#pragma unroll 1
-  for (int pass = 0; pass < KT / 4; ++pass) {
-    const int rr = lr + pass * 4;
-    const long r = r0 + rr, c = c0 + lc;
-    if (r < n && c <= r) {
-      double g[PMAX];
-      // ordered arguments (x_min, x_max) = (x_c, x_r) since c <= r  (kernel_interface.cpp:117-121)
-      gh_eval_grad(prog, n_nodes, &xc[lc * nd], &xr[rr * nd], g);
-      const double kin = kinv[r * ld + c];
-      const double aij = alpha[r] * alpha[c] - kin;
-      const double w = (r == c) ? 0.5 * aij : aij;
-      if (r == c && diagA) diagA[r] = aij;
-#pragma unroll
-      for (int p = 0; p < PMAX; ++p) if (p < P) acc[p] += w * g[p];
-    }
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int p = 0; p < PMAX; ++p) {
-    double v = acc[p];
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if (lane == 0) red[wave][p] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < PMAX && threadIdx.x < P) {
-    const int p = threadIdx.x;
-    partial[(long)blockIdx.x * P + p] = which[p] ? (red[0][p] + red[1][p]) + (red[2][p] + red[3][p]) : 0.0;
-  }
+#define GH_KGRAD_LOO 0
+#include "gh_kgrad_body.h"
+#undef GH_KGRAD_LOO
+}
+template <int PMAX>
+__global__ __launch_bounds__(256, PMAX <= 16 ? GH_KGRAD_WAVES : 1) void kgrad_loo_reduce_kernel(const GhNode* __restrict__ prog, int n_nodes, int nd, int P,
+                                                           const uint32_t* which, const double* x, long n,
+                                                           const double* alpha, const double* kinv, long ld,
+                                                           double* partial, double* diagA) {
+#define GH_KGRAD_LOO 1
+#include "gh_kgrad_body.h"
+#undef GH_KGRAD_LOO
 }
 __global__ void kgrad_final_kernel(const double* partial, long nblk, int P, double* grad) {
   // one workgroup per parameter; fixed-order tree -> bitwise reproducible
@@ -684,9 +651,10 @@ int gh_launch_kgrad_final(const double* partial, int64_t nblk, int P, double* gr
   return GH_OK;
 }
 
-int gh_launch_kgrad_reduce(const gh_kernel* k, const uint32_t* which_host, const double* x, int64_t n,
-                           const double* alpha, const double* kinv, int64_t ld, double* grad_dev,
-                           double* diagA, GhBuf& scratch, hipStream_t st) {
+// (loo: the leave-one-out form -- `alpha` is alpha and beta, ld apart, `kinv` is M)
+static int launch_kgrad_reduce(const gh_kernel* k, const uint32_t* which_host, const double* x, int64_t n, bool loo,
+                               const double* alpha, const double* kinv, int64_t ld, double* grad_dev,
+                               double* diagA, GhBuf& scratch, hipStream_t st) {
   const int P = k->size;
   if (n <= 0) return GH_OK;
   const long tm = (n + KT - 1) / KT;
@@ -697,15 +665,31 @@ int gh_launch_kgrad_reduce(const gh_kernel* k, const uint32_t* which_host, const
   double* partial = (double*)((char*)scratch.p + which_bytes);
   if (P > 0) GH_HIP(hipMemcpyAsync(d_which, which_host, sizeof(uint32_t) * P, hipMemcpyHostToDevice, st));
   const int nn = (int)k->nodes.size();
-#define GH_LAUNCH_RED(PM)                                                                        \
-  hipLaunchKernelGGL(kgrad_reduce_kernel<PM>, dim3((unsigned)nblk), dim3(256), 0, st, k->d_nodes, \
+#define GH_LAUNCH_RED(KERNEL, PM)                                                                \
+  hipLaunchKernelGGL(KERNEL<PM>, dim3((unsigned)nblk), dim3(256), 0, st, k->d_nodes,             \
                      nn, k->ndim, P, d_which, x, (long)n, alpha, kinv, (long)ld, partial, diagA)
-  if (P <= 4) GH_LAUNCH_RED(4);
-  else if (P <= 16) GH_LAUNCH_RED(16);
-  else GH_LAUNCH_RED(GH_MAX_GRAD);
+  if (loo) {
+    if (P <= 4) GH_LAUNCH_RED(kgrad_loo_reduce_kernel, 4);
+    else if (P <= 16) GH_LAUNCH_RED(kgrad_loo_reduce_kernel, 16);
+    else GH_LAUNCH_RED(kgrad_loo_reduce_kernel, GH_MAX_GRAD);
+  } else {
+    if (P <= 4) GH_LAUNCH_RED(kgrad_reduce_kernel, 4);
+    else if (P <= 16) GH_LAUNCH_RED(kgrad_reduce_kernel, 16);
+    else GH_LAUNCH_RED(kgrad_reduce_kernel, GH_MAX_GRAD);
+  }
 #undef GH_LAUNCH_RED
   GH_HIP(hipGetLastError());
   return gh_launch_kgrad_final(partial, nblk, P, grad_dev, st);
+}
+int gh_launch_kgrad_reduce(const gh_kernel* k, const uint32_t* which_host, const double* x, int64_t n,
+                           const double* alpha, const double* kinv, int64_t ld, double* grad_dev,
+                           double* diagA, GhBuf& scratch, hipStream_t st) {
+  return launch_kgrad_reduce(k, which_host, x, n, false, alpha, kinv, ld, grad_dev, diagA, scratch, st);
+}
+int gh_launch_kgrad_reduce_loo(const gh_kernel* k, const uint32_t* which_host, const double* x, int64_t n,
+                               const double* alpha_beta, const double* m, int64_t ld, double* grad_dev,
+                               double* diagB, GhBuf& scratch, hipStream_t st) {
+  return launch_kgrad_reduce(k, which_host, x, n, true, alpha_beta, m, ld, grad_dev, diagB, scratch, st);
 }
 
 // ============================================================ C-ABI: evaluator

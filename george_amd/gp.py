@@ -424,6 +424,133 @@ class GP(ModelSet):
         self._obj_cache = (np.array(vector, dtype=np.float64), np.array(y, dtype=np.float64), g)
         return -g
 
+    # -- leave-one-out cross-validation (no reference counterpart; GPML section 5.4.2) ---------------
+    # With alpha = K^-1 r and c_i = (K^-1)_ii the prediction of y_i from all OTHER points is mu_i = y_i - alpha_i / c_i with
+    # variance 1 / c_i, and L = sum_i log p(y_i | y_-i) = sum_i 1/2 log c_i - 1/2 alpha_i^2 / c_i - 1/2 log 2 pi.  Its gradient
+    # is sum_ij B_ij dK_ij/dtheta with B = 1/2 (v alpha^T + alpha v^T) - K^-1 diag(w) K^-1, u = alpha / c, v = K^-1 u,
+    # w = 1/2 (1 + alpha^2 / c) / c: one N^3 product for any number of parameters.  A solver that offers
+    # ``loo`` (the HIP BasicSolver) keeps all of it on the device; any other one with ``apply_inverse`` and ``get_inverse``
+    # takes the NumPy branch, formula for formula.
+    def _loo_parts(self, r, want_grad):
+        """``(L, resid, var, lpd, kgrad | None, v | None, diagB | None)`` for the residual ``r`` on the computed solver;
+        ``kgrad`` over the unfrozen kernel parameters."""
+        n_k = len(self.kernel)
+        if callable(getattr(self.solver, "loo", None)):
+            which = self.kernel.unfrozen_mask.astype(np.uint32) if want_grad else None
+            L, resid, var, lpd, kg_full, v, diagB = self.solver.loo(r, which)
+            kgrad = kg_full[self.kernel.unfrozen_mask] if (want_grad and n_k) else None
+            return L, resid, var, lpd, kgrad, v, diagB
+        alpha = np.asarray(self.solver.apply_inverse(np.array(r, dtype=np.float64))).flatten()
+        Kinv = np.asarray(self.solver.get_inverse())
+        c = np.array(np.diag(Kinv), dtype=np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            resid = alpha / c
+            var = 1.0 / c
+            lpd = 0.5 * np.log(c) - 0.5 * alpha * resid - 0.5 * np.log(2 * np.pi)
+            L = float(np.sum(lpd))
+            if not want_grad:
+                return L, resid, var, lpd, None, None, None
+            w = 0.5 * (1.0 + alpha * resid) / c
+            v = np.asarray(self.solver.apply_inverse(np.array(resid, dtype=np.float64))).flatten()
+            B = 0.5 * (np.einsum("i,j", v, alpha) + np.einsum("i,j", alpha, v)) - np.dot(Kinv * w[None, :], Kinv)
+        kgrad = np.einsum("ijk,ij", self.kernel.get_gradient(self._x), B) if n_k else None
+        return L, resid, var, lpd, kgrad, v, np.array(np.diag(B))
+
+    def _assemble_loo_grad(self, v, diagB, kgrad, quiet):
+        """mean | white_noise | kernel blocks of the leave-one-out gradient (the layout of :meth:`_assemble_grad`)."""
+        n_wn, n_k = len(self.white_noise), len(self.kernel)
+        grad = np.empty(len(self))
+        at = 0
+        n_m = len(self.mean)
+        if n_m:
+            try:
+                mg = self._call_mean_gradient(self._x)
+            except ValueError:
+                if quiet:
+                    return np.zeros(len(self), dtype=np.float64)
+                raise
+            grad[at:at + n_m] = np.dot(mg, v)
+            at += n_m
+        if n_wn:
+            wn = self._call_white_noise(self._x)
+            wng = self._call_white_noise_gradient(self._x)
+            grad[at:at + n_wn] = np.sum((np.exp(wn) * diagB)[None, :] * wng, axis=1)
+            at += n_wn
+        if n_k:
+            grad[at:at + n_k] = kgrad
+        return grad
+
+    def loo_predict(self, y, return_var=True):
+        """Leave-one-out predictions: ``mu[i]`` (and ``var[i]``) of ``y[i]`` from all other points, mean model included, without
+        N refits.  ``(y - mu) / sqrt(var)`` are the standardised leave-one-out residuals."""
+        self.recompute()
+        y = self._check_dimensions(y)
+        _, resid, var, _, _, _, _ = self._loo_parts(self._residual(y), False)
+        mu = np.asarray(y, dtype=np.float64) - resid
+        return (mu, var) if return_var else mu
+
+    def loo_log_likelihood(self, y, quiet=False, pointwise=False):
+        """The log pseudo-likelihood ``sum_i log p(y_i | y_-i)`` (GPML eq. 5.11), or its N terms with ``pointwise=True``."""
+        bad = np.full(len(np.atleast_1d(y)), -np.inf) if pointwise else -np.inf
+        if not self.recompute(quiet=quiet):
+            return bad
+        r = self._residual_quiet(y, quiet)
+        if r is None:
+            return bad
+        L, _, _, lpd, _, _, _ = self._loo_parts(r, False)
+        if not np.isfinite(L):
+            return bad
+        return lpd if pointwise else L
+
+    def grad_loo_log_likelihood(self, y, quiet=False):
+        """Gradient of :meth:`loo_log_likelihood` wrt the unfrozen parameters, ordered mean | white_noise | kernel."""
+        if not self.recompute(quiet=quiet):
+            return np.zeros(len(self), dtype=np.float64)
+        r = self._residual_quiet(y, quiet)
+        if r is None:
+            return np.zeros(len(self), dtype=np.float64)
+        _, _, _, _, kgrad, v, diagB = self._loo_parts(r, True)
+        return self._assemble_loo_grad(v, diagB, kgrad, quiet)
+
+    def loo_nll_and_grad(self, vector, y, quiet=True):
+        """``(-loo_log_likelihood, -grad_loo_log_likelihood)`` at ``vector`` for ``scipy.optimize.minimize(..., jac=True)``:
+        one fused device call per iterate (build, factor, leave-one-out value and gradient) with a solver that offers
+        ``loo_objective``; ``(inf, zeros)`` outside the prior."""
+        self.set_parameter_vector(vector)
+        if not np.isfinite(self.log_prior()):
+            return np.inf, np.zeros(len(vector))
+        bad = (np.inf, np.zeros(len(self)))
+        fused = (callable(getattr(self.solver_type, "loo_objective", None))
+                 and hasattr(self, "_x") and hasattr(self, "_yerr2"))
+        if self.computed or not fused:
+            if not self.recompute(quiet=quiet):
+                return bad
+            r = self._residual_quiet(y, quiet)
+            if r is None:
+                return bad
+            L, _, _, _, kgrad, v, diagB = self._loo_parts(r, True)
+        else:
+            r = self._residual_quiet(y, quiet)
+            if r is None:
+                return bad
+            self._obj_cache = None
+            self.solver = self.solver_type(self.kernel, **(self.solver_kwargs))
+            sigma = np.sqrt(self._yerr2 + np.exp(self._call_white_noise(self._x)))
+            which = self.kernel.unfrozen_mask.astype(np.uint32)
+            try:
+                logdet, L, _, _, kg_full, v, diagB = self.solver.loo_objective(self._x, sigma, r, which, want_grad=True)
+            except (ValueError, np.linalg.LinAlgError):
+                if quiet:
+                    return bad
+                raise
+            self._const = -0.5 * (len(self._x) * np.log(2 * np.pi) + logdet)
+            self.computed = True
+            self._alpha = None
+            kgrad = kg_full[self.kernel.unfrozen_mask] if len(self.kernel) else None
+        if not np.isfinite(L):
+            return bad
+        return -L, -self._assemble_loo_grad(v, diagB, kgrad, quiet)
+
     # -- ensembles (emcee ``vectorize=True``) ------------------------------------------------------
     def log_likelihood_batch(self, vectors, y, quiet=True):
         """``log_likelihood(y, quiet)`` at each row of ``vectors`` (shape ``(B, len(gp))``, ``get_parameter_vector()``

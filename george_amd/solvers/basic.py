@@ -504,6 +504,68 @@ class BasicSolver(object):
         N.check(N.lib.gh_chol_grad(h, self._dk.handle, N.ptr(which), N.ptr(r), N.ptr(g), N.ptr(alpha), N.ptr(diagA)))
         return g[:self._dk.size], alpha, diagA
 
+    # -- leave-one-out cross-validation (no reference counterpart; GPML 5.4.2)
+    def loo(self, r, which=None):
+        """Leave-one-out quantities of the computed factor for residual ``r = y - mean`` (gh_chol_loo).  Returns
+        ``(lpd_sum, resid, var, lpd, grad_full | None, v | None, diagB | None)``: ``resid = y - mu_loo``, ``var`` the
+        leave-one-out variances, ``lpd`` the N log predictive densities and ``lpd_sum`` their sum.  ``which=None``: values only
+        -- K^-1 is not formed.  With a parameter mask also ``grad_full`` = d lpd_sum / d theta over ALL kernel parameters
+        (masked ones exactly 0), ``v`` = d lpd_sum / d mean_i and ``diagB`` = d lpd_sum / d K_ii."""
+        h = self._need()
+        r = N.as_f64(r).reshape(-1)
+        if len(r) != self._n:
+            raise ValueError("dimension mismatch")
+        n = self._n
+        total = C.c_double(0.0)
+        resid, var, lpd = np.empty(n), np.empty(n), np.empty(n)
+        g = v = diagB = wh = None
+        if which is not None:
+            wh = np.zeros(max(self._dk.size, 1), dtype=np.uint32)
+            which = np.asarray(which)
+            if which.shape != (self._dk.size,):
+                raise ValueError("which must have shape ({0},)".format(self._dk.size))
+            wh[:self._dk.size] = which != 0
+            g = np.zeros(max(self._dk.size, 1))
+            v, diagB = np.empty(n), np.empty(n)
+        self._retry_without_parked_memory(lambda hh: N.check(N.lib.gh_chol_loo(
+            hh, self._dk.handle, N.ptr(wh), N.ptr(r), C.byref(total), N.ptr(resid), N.ptr(var), N.ptr(lpd),
+            N.ptr(g), N.ptr(v), N.ptr(diagB))))
+        return total.value, resid, var, lpd, (g[:self._dk.size] if g is not None else None), v, diagB
+
+    def loo_objective(self, x, yerr, r, which=None, want_grad=True):
+        """``compute(x, yerr)`` + :meth:`loo` in ONE device call (gh_chol_loo_objective), the leave-one-out analogue of
+        :meth:`objective`.  Returns ``(log_det, lpd_sum, resid, var, grad_full | None, v | None, diagB | None)`` and leaves
+        the solver computed."""
+        x = N.as_f64(x)
+        if x.ndim != 2:
+            raise ValueError("x must be (nsamples, ndim)")
+        n = len(x)
+        yerr = N.as_f64(np.zeros(n) + yerr)
+        r = N.as_f64(r).reshape(-1)
+        if len(r) != n:
+            raise ValueError("dimension mismatch")
+        self._computed = False
+        self._factor_state = None
+        self._dk = DeviceKernel(self.kernel)
+        if x.shape[1] != self._dk.ndim:
+            raise RuntimeError("dimension mismatch")
+        logdet, total = C.c_double(0.0), C.c_double(0.0)
+        resid, var = np.empty(n), np.empty(n)
+        g = v = diagB = wh = None
+        if want_grad:
+            wh = np.ascontiguousarray(np.ones(max(self._dk.size, 1)) if which is None else which, dtype=np.uint32)
+            g = np.zeros(max(self._dk.size, 1))
+            v, diagB = np.empty(n), np.empty(n)
+        self._retry_without_parked_memory(lambda hh: N.check(N.lib.gh_chol_loo_objective(
+            hh, self._dk.handle, N.ptr(x), n, x.shape[1], N.ptr(yerr), N.ptr(r), N.ptr(wh),
+            C.byref(logdet), C.byref(total), N.ptr(resid), N.ptr(var), N.ptr(g), N.ptr(v), N.ptr(diagB))))
+        self._n = n
+        self._x_host = x
+        self._yerr_host = yerr
+        self.log_determinant = logdet.value
+        self.computed = True
+        return logdet.value, total.value, resid, var, (g[:self._dk.size] if g is not None else None), v, diagB
+
     def profile(self):
         p = N.gh_chol_profile()
         N.check(N.lib.gh_chol_get_profile(self._need(), C.byref(p)))

@@ -250,9 +250,12 @@ class HODLRSolver(BasicSolver):
         N.check(N.lib.gh_hodlr_grad(h, self._dk.handle, N.ptr(which), N.ptr(r), N.ptr(g), N.ptr(alpha), N.ptr(diagA)))
         return g[:self._dk.size], alpha, diagA
 
-    # compute + gradient in one call, and the dense solver's profile counters, are not offered
+    # compute + gradient in one call, the dense solver's profile counters and its leave-one-out entry points (they take a
+    # dense handle; GP's NumPy branch serves this solver through apply_inverse / get_inverse) are not offered
     profile = None
     objective = None
+    loo = None
+    loo_objective = None
 
 
 atexit.register(HODLRSolver.release_pool)

@@ -202,6 +202,26 @@ int  gh_chol_objective(gh_chol* s, gh_kernel* k, const double* x, int64_t n, int
                        const double* yerr, const double* r /* n: y - mean */, const uint32_t* which,
                        double* logdet, double* quad, double* grad /* size or NULL */,
                        double* alpha /* n or NULL */, double* diagA /* n or NULL */);
+/* Leave-one-out cross-validation on a computed handle (no reference counterpart: src/george/gp.py has none; GPML section 5.4.2).
+ * With alpha = K^-1 r and c_i = (K^-1)_ii:
+ *   resid[i] = alpha_i / c_i = y_i - mu_i   (mu_i: the prediction of y_i from all other points)
+ *   var[i]   = 1 / c_i
+ *   lpd[i]   = 1/2 log c_i - 1/2 alpha_i^2 / c_i - 1/2 log 2 pi;      *lpd_sum = sum_i lpd[i]   (GPML eq. 5.11)
+ * and, with u = resid, w_i = 1/2 (1 + alpha_i^2 / c_i) / c_i, v = K^-1 u, B = 1/2 (v alpha^T + alpha v^T) - K^-1 diag(w) K^-1:
+ *   grad[p]  = sum_ij B_ij dK_ij/dtheta_p  for the parameters selected by `which` (others exactly 0)
+ *   v (n)    : d lpd_sum / d mean_i;      diagB (n) = diag(B): d lpd_sum / d K_ii.
+ * grad, v and diagB all NULL: K^-1 is not formed (c from L^-1; one N x N work buffer); otherwise two, as gh_chol_grad.
+ * which == NULL: no gradient (grad must be NULL too).  Pointers may be host or device memory.  Two calls give the same bits. */
+int  gh_chol_loo(gh_chol* s, gh_kernel* k, const uint32_t* which /* NULL: no gradient */, const double* r,
+                 double* lpd_sum, double* resid /* n: alpha_i / c_i = y_i - mu_i */, double* var /* n */,
+                 double* lpd /* n or NULL */, double* grad /* size, or NULL */, double* v /* n or NULL */,
+                 double* diagB /* n or NULL */);
+/* Fused leave-one-out objective: gh_chol_compute + gh_chol_loo as ONE device-resident call with one synchronisation (what
+ * gh_chol_objective is to compute + dot_solve + grad), bit for bit the results of the two calls; *logdet = log|K|.  The handle
+ * is left computed; on GH_ERR_NOT_PD gh_chol_info() is set and it is not. */
+int  gh_chol_loo_objective(gh_chol* s, gh_kernel* k, const double* x, int64_t n, int32_t ndim, const double* yerr,
+                           const double* r, const uint32_t* which, double* logdet, double* lpd_sum,
+                           double* resid, double* var, double* grad, double* v, double* diagB);
 /* B independent problems that share the points x (n, ndim) and the kernel's STRUCTURE, each with its own parameters, error bars
  * and residual (B rounds of compute gp.py:303-337 + log_likelihood :369-397, one device call):
  *   K_b = k(params_b)(x, x) + diag(yerr_b^2);  logdet[b] = log|K_b|;  quad[b] = r_b^T K_b^-1 r_b;
