@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libgeorge_amd.so")
 
 GH_MAX_AXES, GH_MAX_NDIM, GH_MAX_PARAMS, GH_MAX_METRIC = 8, 16, 4, 36
 GH_MAX_NODES, GH_MAX_GRAD, GH_MAX_STACK = 64, 64, 8
-GH_OK, GH_ERR_NOT_PD, GH_ERR_BAD_ARG, GH_ERR_HIP, GH_ERR_NOT_COMPUTED, GH_ERR_DIM, GH_ERR_NOMEM, GH_ERR_RANK = range(8)
+GH_OK, GH_ERR_NOT_PD, GH_ERR_BAD_ARG, GH_ERR_HIP, GH_ERR_NOT_COMPUTED, GH_ERR_DIM, GH_ERR_NOMEM, GH_ERR_RANK, GH_REFACTORIZE = range(9)
 GH_OP_LEAF, GH_OP_SUM, GH_OP_PRODUCT = 0, 1, 2
 
 
@@ -112,6 +112,8 @@ SIGNATURES = {
                                      C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "gh_debug_set_build_on_chain": (C.c_int, [C.c_int]),
     "gh_debug_set_append_path": (C.c_int, [C.c_int]),
+    "gh_debug_set_remove_path": (C.c_int, [C.c_int]),
+    "gh_debug_check_remove_args": (C.c_int, [_i64, _dp, _i64]),
     "gh_debug_set_gemm_grouped": (C.c_int, [C.c_int]),
     "gh_debug_set_hodlr_passes": (C.c_int, [C.c_int]),
     "gh_debug_set_hodlr_leaf_gj": (C.c_int, [C.c_int]),
@@ -144,6 +146,7 @@ SIGNATURES = {
     "gh_chol_compute": (C.c_int, [_vp, _vp, _dp, _i64, _i32, _dp, C.POINTER(C.c_double)]),
     "gh_chol_append": (C.c_int, [_vp, _vp, _dp, _i64, _dp, C.POINTER(C.c_double)]),
     "gh_chol_truncate": (C.c_int, [_vp, _i64, C.POINTER(C.c_double)]),
+    "gh_chol_remove": (C.c_int, [_vp, _dp, _i64, C.POINTER(C.c_double)]),
     "gh_chol_set_yerr": (C.c_int, [_vp, _dp]),
     "gh_chol_info": (_i64, [_vp]),
     "gh_chol_size": (_i64, [_vp]),

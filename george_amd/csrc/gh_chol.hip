@@ -2543,3 +2543,244 @@ extern "C" int gh_chol_truncate(gh_chol* s, int64_t n_keep, double* logdet_out) 
   if (logdet_out) *logdet_out = ldv;
   return GH_OK;
 }
+
+// ============================================================ removing points
+// K[keep, keep] = L[keep, :] L[keep, :]^T = Lk Lk^T + W W^T with Lk = L[keep, keep] (lower triangular, positive diagonal) and
+// W = L[keep, rem] (zero where keep[p] < rem[j]): taking points out is a rank-m Cholesky UPDATE of the gathered factor -- it adds a
+// positive semi-definite term, so it cannot lose positive definiteness -- and rows before the first removed index do not change.
+// Per pass of at most 128 columns of W and per diagonal tile j from the first affected one, with Wj the tile's rows of W:
+//   V = Ljj^-1 Wj;   L' = chol(Ljj Ljj^T + Wj Wj^T) and L'^-1;   C C^T = I + V^T V and C^-1   (Ri = C^-T)
+//   Q = [[Ljj^T L'^-T, -V Ri], [Wj^T L'^-T, Ri]]   (orthogonal);   [Lij' | Wi'] = [Lij | Wi] Q for every tile row i below j.
+// The gathered tile has no stored inverse (it is a principal submatrix of old tiles), so V comes from a substitution.  Everything is
+// written into buffers the handle does not use yet; they are swapped in after the one synchronisation has reported success.
+// DESIGN.md section 4, "Removing points".
+static int g_remove_path = 0;
+extern "C" int gh_debug_set_remove_path(int path) {
+  const int prev = g_remove_path;
+  g_remove_path = (path == 1 || path == 2) ? path : 0;
+  return prev;
+}
+// the argument rule of gh_chol_remove for a factor of n points: host code, no handle and no device needed
+extern "C" int gh_debug_check_remove_args(int64_t n, const int64_t* idx, int64_t m) {
+  if (!idx) { gh_set_error("remove: null index array"); return GH_ERR_BAD_ARG; }
+  if (m <= 0 || m >= n) { gh_set_error("remove: the number of removed points must be in 1 .. %lld", (long long)(n - 1)); return GH_ERR_BAD_ARG; }
+  for (int64_t i = 0; i < m; ++i) {
+    if (idx[i] < 0 || idx[i] >= n) { gh_set_error("remove: index %lld is out of range for %lld points", (long long)idx[i], (long long)n); return GH_ERR_BAD_ARG; }
+    if (i > 0 && idx[i] <= idx[i - 1]) { gh_set_error("remove: indices must be strictly increasing"); return GH_ERR_BAD_ARG; }
+  }
+  return GH_OK;
+}
+
+// dst (np2 x np2, lower 128-tiles) = src[keep, keep] with identity padding; one row per workgroup.  keep is increasing, so a column
+// at or left of the diagonal stays there; the rest of the diagonal tile is written as zero (what potf2 leaves there).
+__global__ __launch_bounds__(256) void remove_gather_lower_kernel(const double* src, long lds, const int* keep, long n2, double* dst, long ldd) {
+  const long p = blockIdx.x, qend = (p / T + 1) * T;
+  double* dr = dst + p * ldd;
+  if (p < n2) {
+    const double* sr = src + (long)keep[p] * lds;
+    for (long q = threadIdx.x; q < qend; q += 256) dr[q] = (q <= p) ? sr[keep[q]] : 0.0;
+  } else {
+    for (long q = threadIdx.x; q < qend; q += 256) dr[q] = (q == p) ? 1.0 : 0.0;
+  }
+}
+// W (rows [row0, np2) x 128, ld 128): W[p, c] = src[keep[p], rem[c]] where c < kc and rem[c] < keep[p], else 0
+__global__ __launch_bounds__(128) void remove_gather_w_kernel(const double* src, long lds, const int* keep, long n2, const int* rem, int kc,
+                                                             double* W, long row0) {
+  const long p = row0 + blockIdx.x;
+  const int c = threadIdx.x;
+  double v = 0.0;
+  if (p < n2 && c < kc) {
+    const long kp = keep[p], rc = rem[c];
+    if (rc < kp) v = src[kp * lds + rc];
+  }
+  W[p * T + c] = v;
+}
+__global__ void remove_gather_vec_kernel(const double* x, const double* yerr, const int* keep, long n2, int ndim, double* x2, double* yerr2) {
+  const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n2) return;
+  const long kp = keep[p];
+  for (int d = 0; d < ndim; ++d) x2[p * ndim + d] = x[kp * ndim + d];
+  if (yerr2) yerr2[p] = yerr[kp];
+}
+// The small step's substitution, two workgroups (64 columns of Wj each, one column per lane of the first wavefront, its solution in
+// LDS): V = Ljj^-1 Wj.  The other wavefronts save the tile (Lold = Ljj: the tile itself receives Ljj Ljj^T + Wj Wj^T next) and set
+// G = I (it receives V^T V).  Columns from kc on are zero columns of Wj.
+__global__ __launch_bounds__(256) void remove_tile_solve_kernel(const double* __restrict__ Ljj, long ld, const double* __restrict__ Wj, int kc,
+                                                               double* __restrict__ V, double* __restrict__ Lold, double* __restrict__ G) {
+  __shared__ double X[T * 64];
+  const int tid = threadIdx.x, half = blockIdx.x;
+  if (tid >= 64) {
+    for (int idx = tid - 64; idx < 64 * T; idx += 192) {
+      const int i = half * 64 + idx / T, j = idx % T;
+      Lold[i * T + j] = Ljj[(long)i * ld + j];
+      G[i * T + j] = (i == j) ? 1.0 : 0.0;
+    }
+    return;
+  }
+  const int c = half * 64 + tid;
+  if (half * 64 >= kc) {
+    for (int i = 0; i < T; ++i) V[i * T + c] = 0.0;
+    return;
+  }
+  for (int i = 0; i < T; ++i) {
+    const double* Li = Ljj + (long)i * ld;
+    double a0 = Wj[i * T + c], a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    int k = 0;
+    for (; k + 4 <= i; k += 4) {
+      a0 -= Li[k] * X[k * 64 + tid];
+      a1 -= Li[k + 1] * X[(k + 1) * 64 + tid];
+      a2 -= Li[k + 2] * X[(k + 2) * 64 + tid];
+      a3 -= Li[k + 3] * X[(k + 3) * 64 + tid];
+    }
+    for (; k < i; ++k) a0 -= Li[k] * X[k * 64 + tid];
+    const double x = ((a0 + a1) + (a2 + a3)) / Li[i];
+    X[i * 64 + tid] = x;
+    V[i * T + c] = x;
+  }
+}
+// The hot path: [Lij' | Wi'] = [Lij | Wi] Q for the 128 rows of one tile row i below j per workgroup, on the fp64 matrix pipe.  The
+// two halves of the slab live in two buffers (the factor, leading dimension ld; W, 128 wide); Q arrives as four k-major blocks,
+//   B11 = (Ljj^T L'^-T)^T,  nB21 = -(Wj^T L'^-T)^T,  nB12 = (V Ri)^T,  B22 = Ri^T   (128 x 128 each, ld 128),
+// streamed through LDS in 16-deep slabs by the tile function of gh_gemm_tile.h.  The workgroup owns its rows, and no product reads
+// what the launch has written: W' goes to the OTHER W buffer (Wn), the accumulating products read their C through the thread that
+// wrote it, and L' = L B11^T is written in place only after every slab of L has been read (gh_tile128_nt_sp's contract).  Only the
+// first kc (a multiple of 32) columns of W are summed over; the columns of W' from kc on come out as zeros.
+__global__ __launch_bounds__(256, 2) void remove_apply_q_kernel(double* A, long ld, long row0, long col0, const double* Wo, double* Wn,
+                                                               const double* B11, const double* nB21, const double* nB12,
+                                                               const double* B22, long kc) {
+  __shared__ __attribute__((aligned(1024))) double sm[4 * BM * BK];
+  const long r = row0 + (long)blockIdx.x * T;
+  double* Lt = A + r * ld + col0;
+  const double* wo = Wo + r * T;
+  double* wn = Wn + r * T;
+  // (one inlined copy of each form of the tile function, not four: the kernel must fit its registers -- check_kernels.py)
+#pragma unroll 1
+  for (int step = 0; step < 2; ++step) {
+    double* const C = step ? Lt : wn;
+    const long ldc = step ? ld : (long)T;
+    const double* const A0 = step ? (const double*)Lt : wo;      // W' = W Ri               | L' = L Ljj^T L'^-T
+    const double* const A1 = step ? wo : (const double*)Lt;      // W' -= L (V Ri)          | L' += W Wj^T L'^-T
+    const long lda0 = step ? ld : (long)T, lda1 = step ? (long)T : ld;
+    gh_tile128_nt_sp<false>(sm, C, ldc, A0, lda0, step ? B11 : B22, T, step ? (long)T : kc);
+    gh_tile128_nt_sp<true>(sm, C, ldc, A1, lda1, step ? nB21 : nB12, T, step ? kc : (long)T);
+  }
+}
+
+static int gemm_any(hipStream_t st, double* C, int64_t ldc, const double* A, int64_t lda, bool a_km, const double* B, int64_t ldb, bool b_km,
+                    double alpha, double beta) {
+  GhGemm g{};
+  g.C = C; g.ldc = ldc; g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.M = T; g.N = T; g.K = T;
+  g.alpha = alpha; g.beta = beta; g.a_km = a_km; g.b_km = b_km;
+  return gh_launch_gemm(g, st);
+}
+
+extern "C" int gh_chol_remove(gh_chol* s, const int64_t* idx, int64_t m, double* logdet_out) {
+  if (!s) { gh_set_error("null solver"); return GH_ERR_BAD_ARG; }
+  GH_CHECK(need_computed(s));
+  GH_CHECK(gh_debug_check_remove_args(s->n, idx, m));
+  const int64_t n = s->n, np = s->np, ndim = s->ndim, n2 = n - m, np2 = gh_round_up(n2, T), nt2 = np2 / T;
+  if (idx[0] == n - m) return gh_chol_truncate(s, n2, logdet_out);          // (strictly increasing below n: the trailing run)
+  if (g_remove_path == 2) { gh_set_error("remove: compute afresh on the kept points"); return GH_REFACTORIZE; }
+  if (n >= (1LL << 31)) { gh_set_error("remove: too many points"); return GH_ERR_BAD_ARG; }
+  hipStream_t st = s->st;
+  // ---- the index maps (host)
+  std::vector<int> maps((size_t)(n2 + m));
+  {
+    int64_t r = 0, p = 0;
+    for (int64_t i = 0; i < n; ++i) {
+      if (r < m && idx[r] == i) { maps[(size_t)(n2 + r)] = (int)i; ++r; }
+      else maps[(size_t)p++] = (int)i;
+    }
+  }
+  const int64_t j0t = idx[0] / T;                          // first affected tile: idx[0] points are kept in front of the first removed one
+  // ---- every allocation first: a failure up to here leaves the handle as it was (and so does every failure after it)
+  GhBuf A2, dinv2, x2, yerr2;
+  GhPooledBuf wb, qs, ib;
+  GH_CHECK(take_factor_buffer(s, A2, np2));
+  GH_CHECK(dinv2.ensure((size_t)nt2 * T * T * sizeof(double)));
+  GH_CHECK(x2.ensure((size_t)np2 * ndim * sizeof(double)));
+  if (s->have_yerr) GH_CHECK(yerr2.ensure((size_t)np2 * sizeof(double)));
+  GH_CHECK(wb.ensure((size_t)2 * np2 * T * sizeof(double)));
+  GH_CHECK(qs.ensure((size_t)7 * T * T * sizeof(double)));
+  GH_CHECK(ib.ensure(maps.size() * sizeof(int)));
+  GH_CHECK(s->scal.ensure(256 * sizeof(double)));
+  s->d_info = (long long*)(s->scal.d() + 2);
+  // (on an early error return the factor buffer goes back to the handle as its spare, not to the allocator)
+  struct Spare { gh_chol* s; GhBuf& b; bool armed; ~Spare() { if (armed && b.p && !s->A_spare.p) { (void)hipStreamSynchronize(s->st); swap_bufs(s->A_spare, b); } } }
+      spare{s, A2, true};
+  const int* keepd = (const int*)ib.p;
+  const int* remd = keepd + n2;
+  double* const Ad = A2.d();
+  double* const W0 = wb.d();
+  double* const W1 = W0 + np2 * T;
+  double* const V = qs.d();
+  double* const Lold = V + T * T, * const G = Lold + T * T, * const dG = G + T * T, * const B11 = dG + T * T, * const nB21 = B11 + T * T,
+        * const nB12 = nB21 + T * T;
+  GH_HIP(hipMemcpyAsync(ib.p, maps.data(), maps.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  GH_HIP(hipMemsetAsync(s->d_info, 0, sizeof(long long), st));
+  // ---- 1. gather
+  long e_lay = -1;
+  if (s->opts.profile) {
+    for (auto& e : s->ev_lay) if (!e) GH_HIP(hipEventCreate(&e));
+    e_lay = 0;
+    GH_HIP(hipEventRecord(s->ev_lay[0], st));
+  }
+  hipLaunchKernelGGL(remove_gather_lower_kernel, dim3((unsigned)np2), dim3(256), 0, st, s->A.d(), (long)np, keepd, (long)n2, Ad, (long)np2);
+  hipLaunchKernelGGL(remove_gather_vec_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, st, s->x.d(),
+                     s->have_yerr ? s->yerr.d() : (const double*)nullptr, keepd, (long)n2, (int)ndim, x2.d(), s->have_yerr ? yerr2.d() : (double*)nullptr);
+  GH_HIP(hipGetLastError());
+  if (j0t > 0) GH_HIP(hipMemcpyAsync(dinv2.d(), s->dinv.d(), (size_t)j0t * T * T * sizeof(double), hipMemcpyDeviceToDevice, st));
+  if (e_lay >= 0) GH_HIP(hipEventRecord(s->ev_lay[1], st));
+  // ---- 2. the passes: at most 128 columns of W each, read from the OLD factor
+  for (int64_t c0 = 0; c0 < m; c0 += T) {
+    const int64_t kc = std::min<int64_t>(T, m - c0), kcp = gh_round_up(kc, 32);
+    const int64_t pc0 = idx[c0] - c0;                      // kept points in front of this pass's first column: rows of W before it are zero
+    if (pc0 >= n2) break;                                  // (the rest of rem lies behind every kept point)
+    const int64_t jt0 = pc0 / T;
+    hipLaunchKernelGGL(remove_gather_w_kernel, dim3((unsigned)(np2 - jt0 * T)), dim3(128), 0, st, s->A.d(), (long)np, keepd, (long)n2,
+                       remd + c0, (int)kc, W0, (long)(jt0 * T));
+    GH_HIP(hipGetLastError());
+    double* cur = W0;
+    double* oth = W1;
+    for (int64_t j = jt0; j < nt2; ++j) {
+      double* Ljj = Ad + j * T * np2 + j * T;
+      double* Wj = cur + j * T * T;
+      double* dS = dinv2.d() + j * T * T;
+      hipLaunchKernelGGL(remove_tile_solve_kernel, dim3(2), dim3(256), 0, st, Ljj, (long)np2, Wj, (int)kc, V, Lold, G);
+      GH_HIP(hipGetLastError());
+      GH_CHECK(gemm_any(st, Ljj, np2, Lold, T, true, Lold, T, true, 1.0, 0.0));        // S = Ljj Ljj^T
+      GH_CHECK(gemm_any(st, Ljj, np2, Wj, T, true, Wj, T, true, 1.0, 1.0));            //   + Wj Wj^T
+      GH_CHECK(gh_launch_potf2_mfma(Ljj, np2, dS, s->d_info, j * T, st));              // L', L'^-1
+      if (j + 1 == nt2) break;
+      GH_CHECK(gemm_any(st, G, T, V, T, false, V, T, false, 1.0, 1.0));                // G = I + V^T V
+      GH_CHECK(gh_launch_potf2_mfma(G, T, dG, s->d_info, j * T, st));                  // C, C^-1 = Ri^T
+      GH_CHECK(gemm_any(st, B11, T, dS, T, true, Lold, T, false, 1.0, 0.0));           // L'^-1 Ljj
+      GH_CHECK(gemm_any(st, nB21, T, dS, T, true, Wj, T, false, -1.0, 0.0));           // -L'^-1 Wj
+      GH_CHECK(gemm_any(st, nB12, T, dG, T, true, V, T, true, 1.0, 0.0));              // Ri^T V^T
+      hipLaunchKernelGGL(remove_apply_q_kernel, dim3((unsigned)(nt2 - j - 1)), dim3(256), 0, st, Ad, (long)np2, (long)((j + 1) * T), (long)(j * T),
+                         cur, oth, B11, nB21, nB12, dG, (long)kcp);
+      GH_HIP(hipGetLastError());
+      std::swap(cur, oth);
+    }
+  }
+  // ---- 3. log-det over the new diagonal; one synchronisation brings it back with the failure word
+  GH_CHECK(launch_logdet(Ad, (long)np2, (long)np2, s->scal.d(), s->scal.d() + 8, st));
+  double back[3] = {0.0, 0.0, 0.0};
+  GH_HIP(hipMemcpyAsync(back, s->scal.d(), 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+  GH_HIP(hipStreamSynchronize(st));
+  long long info_host = 0;
+  memcpy(&info_host, &back[2], sizeof(long long));
+  if (e_lay >= 0) { float ms = 0; GH_HIP(hipEventElapsedTime(&ms, s->ev_lay[0], s->ev_lay[1])); s->prof.reserved[0] = ms; }
+  if (info_host != 0 || !std::isfinite(back[0])) {
+    gh_set_error("remove: the update met a pivot that is not positive and finite (tile row of index %lld); the factor is unchanged", info_host);
+    return GH_ERR_NOT_PD;
+  }
+  spare.armed = false;
+  swap_bufs(s->A, A2); swap_bufs(s->A_spare, A2);          // (the old factor buffer is the spare now)
+  swap_bufs(s->dinv, dinv2); swap_bufs(s->x, x2);
+  if (s->have_yerr) swap_bufs(s->yerr, yerr2);
+  s->n = n2; s->np = np2; s->info = 0;
+  s->logdet = back[0];
+  if (logdet_out) *logdet_out = back[0];
+  return GH_OK;
+}

@@ -247,6 +247,56 @@ class GP(ModelSet):
         self._const = -0.5 * (len(self._x) * np.log(2 * np.pi) + self.solver.log_determinant)
         self._alpha = None
 
+    def remove(self, indices, **kwargs):
+        """Take points out of the data set of the last ``compute`` / ``append``, anywhere in it.  ``indices`` means what it
+        means to ``np.delete(np.arange(n), indices)``: integers (negative ones count from the end), a slice or a boolean
+        mask -- ``gp.remove(slice(0, m))`` is a sliding window.  With a computed GP and a solver that offers ``remove`` (the HIP
+        :class:`BasicSolver`) the factor is updated on the device (a rank-m Cholesky update, no kernel evaluations);
+        otherwise (parameters changed since, any other solver, a solver that cannot) the kept inputs are computed afresh.
+        Removing nothing does nothing; removing every point is a ``ValueError``; an index out of range an ``IndexError``.
+        ``y`` of later calls has the new length.  On any exception the GP is unchanged."""
+        if not (hasattr(self, "_x") and hasattr(self, "_yerr2")):
+            raise RuntimeError("You need to compute the model first")
+        n = len(self._x)
+        if isinstance(indices, slice):
+            rem = np.arange(n, dtype=np.int64)[indices]
+        else:
+            idx = np.asarray(indices)
+            if idx.dtype == bool:
+                if idx.shape != (n,):
+                    raise IndexError("remove: a boolean mask must have one entry per point ({0})".format(n))
+                rem = np.flatnonzero(idx)
+            else:
+                idx = np.atleast_1d(idx)
+                if idx.size == 0:
+                    rem = np.empty(0, dtype=np.int64)
+                elif idx.ndim != 1 or idx.dtype.kind not in "iu":
+                    raise IndexError("remove: indices must be integers, a slice or a boolean mask")
+                else:
+                    idx = idx.astype(np.int64)
+                    if idx.min() < -n or idx.max() >= n:
+                        raise IndexError("remove: index out of range for {0} points".format(n))
+                    rem = np.where(idx < 0, idx + n, idx)
+        rem = np.unique(rem).astype(np.int64)
+        if len(rem) == 0:
+            return
+        if len(rem) == n:
+            raise ValueError("remove: every point would be removed")
+        keep = np.ones(n, dtype=bool)
+        keep[rem] = False
+        x_keep, yerr2_keep = np.ascontiguousarray(self._x[keep]), np.ascontiguousarray(self._yerr2[keep])
+        if self.computed and callable(getattr(self.solver, "remove", None)):
+            try:
+                self.solver.remove(rem)                   # (raises with the solver as it was)
+            except RuntimeError:
+                return self._refactorize_or_restore(x_keep, yerr2_keep, **kwargs)
+            self._obj_cache = None
+            self._x, self._yerr2 = x_keep, yerr2_keep
+            self._const = -0.5 * (len(self._x) * np.log(2 * np.pi) + self.solver.log_determinant)
+            self._alpha = None
+            return
+        return self._refactorize_or_restore(x_keep, yerr2_keep, **kwargs)
+
     def recompute(self, quiet=False, **kwargs):
         if not self.computed:
             if not (hasattr(self, "_x") and hasattr(self, "_yerr2")):

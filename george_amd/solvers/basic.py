@@ -428,6 +428,58 @@ class BasicSolver(object):
             self._yerr_host = np.ascontiguousarray(self._yerr_host[:n])
         self.log_determinant = logdet.value
 
+    # Where ``remove`` computes afresh on the kept points instead of updating the factor: above REMOVE_MAX_POINTS removed points,
+    # below REMOVE_MIN_N points in the factor.  NOT yet set from a measurement: scripts/bench_remove.py writes the table
+    # (profiles/remove/remove_time.json) these are to be read from, and that file does not exist yet.  Until then, from the
+    # counts ("Removing points"): a pass of up to 128 points costs at most N^2 * 512 flops against
+    # compute's N^3 / 3, so eight passes stay below compute from N = 12288 up; no lower bound on N.
+    REMOVE_MAX_POINTS = 1024
+    REMOVE_MIN_N = 0
+
+    def remove(self, indices):
+        """Take the points ``indices`` (strictly increasing integers in ``0 .. n-1``, fewer than ``n``) out of the computed
+        factor, gh_chol_remove: a rank-m update of the gathered factor -- no kernel evaluations, no error bars; the rows in
+        front of the first removed index keep their bits.  A trailing run is ``truncate``.  More than ``REMOVE_MAX_POINTS``
+        points, or a factor below ``REMOVE_MIN_N``, are computed afresh on the kept points by this solver's own ``compute``
+        (which needs the error bars: ``RuntimeError`` when the solver is not ``appendable``).  ``last_remove_path`` records
+        which way the call went: "update", "truncate" or "compute".  Any exception leaves the solver as it was."""
+        h = self._need()
+        idx = np.ascontiguousarray(np.atleast_1d(np.asarray(indices)))
+        if idx.ndim != 1 or (idx.size and idx.dtype.kind not in "iu"):
+            raise ValueError("remove: indices must be a one-dimensional integer array")
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        m, n = len(idx), self._n
+        N.check(N.lib.gh_debug_check_remove_args(n, N.ptr(idx), m))      # (the native rule, before any routing)
+        trailing = int(idx[0]) == n - m
+        keep = np.ones(n, dtype=bool)
+        keep[idx] = False
+        rc = N.GH_REFACTORIZE
+        if trailing or (m <= self.REMOVE_MAX_POINTS and n >= self.REMOVE_MIN_N):
+            logdet = C.c_double(0.0)
+
+            def call(hh):
+                rc = N.lib.gh_chol_remove(hh, N.ptr(idx), m, C.byref(logdet))
+                if rc != N.GH_REFACTORIZE:
+                    N.check(rc)
+                return rc
+            rc = self._retry_without_parked_memory(call)
+        if rc == N.GH_REFACTORIZE:
+            if not self.appendable:
+                raise RuntimeError("this solver was restored without the error bars of its points: compute() again")
+            # (on a solver of its own, adopted only once it is computed: whatever compute() raises leaves this one as it was)
+            fresh = type(self)(self.kernel, **self._opts)
+            fresh.compute(self._x_host[keep], self._yerr_host[keep])
+            self.__dict__, fresh.__dict__ = fresh.__dict__, self.__dict__
+            del fresh                                     # (the old handle goes back to the pool)
+            self.last_remove_path = "compute"
+            return
+        self._n = n - m
+        self._x_host = np.ascontiguousarray(self._x_host[keep])
+        if self.appendable:
+            self._yerr_host = np.ascontiguousarray(self._yerr_host[keep])
+        self.log_determinant = logdet.value
+        self.last_remove_path = "truncate" if trailing else "update"
+
     def apply_inverse(self, y, in_place=False):
         """basic.py:72-87 (``cho_solve``): ``y`` is (n,) or (n, nrhs)."""
         h = self._need()
@@ -571,7 +623,7 @@ class BasicSolver(object):
         N.check(N.lib.gh_chol_get_profile(self._need(), C.byref(p)))
         return dict(ms_total=p.ms_total, ms_build=p.ms_build, ms_panel=p.ms_panel, ms_trailing=p.ms_trailing,
                     trailing_flops=p.trailing_flops, n_trailing=p.n_trailing, ms_solve=p.ms_solve,
-                    ms_append_relayout=p.ms_append_relayout)
+                    ms_append_relayout=p.ms_append_relayout, ms_remove_gather=p.reserved[0])
 
 
 atexit.register(BasicSolver.release_pool)

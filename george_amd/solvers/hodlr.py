@@ -256,6 +256,7 @@ class HODLRSolver(BasicSolver):
     objective = None
     loo = None
     loo_objective = None
+    remove = None                     # (GP.remove computes afresh on the kept points)
 
 
 atexit.register(HODLRSolver.release_pool)

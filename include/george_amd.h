@@ -48,7 +48,8 @@ enum {
   GH_ERR_NOT_COMPUTED = 4,
   GH_ERR_DIM = 5,
   GH_ERR_NOMEM = 6,
-  GH_ERR_RANK = 7        /* HODLR: a block needs a rank above the solver's ceiling (1024) for the requested tol */
+  GH_ERR_RANK = 7,       /* HODLR: a block needs a rank above the solver's ceiling (1024) for the requested tol */
+  GH_REFACTORIZE = 8     /* gh_chol_remove: nothing was done; the caller computes afresh on the kept points (not an error) */
 };
 
 /* node operators */
@@ -174,6 +175,16 @@ int  gh_chol_compute(gh_chol* s, gh_kernel* k, const double* x, int64_t n, int32
 int  gh_chol_append(gh_chol* s, gh_kernel* k, const double* x_new, int64_t m, const double* yerr_new, double* logdet_out);
 /* keep the first n_keep points (0 < n_keep <= n); *logdet_out = log|K[:n_keep, :n_keep]|.  Data movement and one reduction. */
 int  gh_chol_truncate(gh_chol* s, int64_t n_keep, double* logdet_out);
+/* Take the m points idx[0] < idx[1] < ... (host array, 0 <= idx[i] < n, 0 < m < n) out of the computed factor, anywhere in the data
+ * set (no reference lines correspond: basic.py:51-70 always refactorises).  With keep / rem the kept / removed indices,
+ * K[keep, keep] = L[keep, keep] L[keep, keep]^T + W W^T, W = L[keep, rem]: a rank-m Cholesky UPDATE of the gathered factor, in
+ * passes of at most 128 columns of W -- no kernel evaluations and no error bars, so it works on an imported factor too.  Rows of
+ * the 128-row tiles in front of the first removed index, and their diagonal-block inverses, keep their bits.  On GH_OK the handle
+ * is computed at n - m and *logdet_out = log|K[keep, keep]|.  idx == n-m .. n-1 is gh_chol_truncate(n - m), bit for bit.  The new
+ * factor is built in other buffers (the factor's spare, as append) and swapped in after one final synchronisation: on ANY failure
+ * -- GH_ERR_BAD_ARG for a bad idx, GH_ERR_NOMEM, a failed HIP call, GH_ERR_NOT_PD for a pivot that is not finite and positive --
+ * the handle keeps its factor, size, info and log-determinant bit for bit.  GH_REFACTORIZE: see gh_debug_set_remove_path. */
+int  gh_chol_remove(gh_chol* s, const int64_t* idx, int64_t m, double* logdet_out);
 /* the error bars (n, as given to compute / append) of a computed handle: what gh_chol_import_factor does not bring */
 int  gh_chol_set_yerr(gh_chol* s, const double* yerr);
 int64_t gh_chol_info(const gh_chol* s);     /* 1-based index of the failing pivot after GH_ERR_NOT_PD, else 0 */
@@ -286,7 +297,7 @@ typedef struct gh_chol_profile {
                              * stream + block-column / in-group / next-group GEMMs on the chain stream): union of their intervals */
   double update_flops;      /* algorithmic flops of all those launches          */
   double ms_append_relayout; /* last gh_chol_append(): moving the factor into buffers of the new Np (0: it stayed in place) */
-  double reserved[1];
+  double reserved[1];       /* [0]: last gh_chol_remove() of a profiled handle: gathering the kept rows and columns into the new buffers, ms */
 } gh_chol_profile;
 int  gh_chol_get_profile(const gh_chol* s, gh_chol_profile* out);
 /* per trailing-update launch of the last profiled compute(): (start ms, end ms, algorithmic flops), times from the

@@ -35,6 +35,13 @@ int gh_debug_set_build_on_chain(int on);
  * rows each (trsv_fwd_chain_multi; a last odd row takes the one-row kernel), 3 blocked right-looking substitution on the matrix
  * pipe.  Returns the previous setting.  1 and 2 give the same bits; 3 agrees with them to rounding. */
 int gh_debug_set_append_path(int path);
+/* gh_chol_remove: 0 the library's rule (the update), 1 the rank-m update of the gathered factor, 2 always answer GH_REFACTORIZE --
+ * "compute afresh on the kept points", nothing touched (the trailing run still goes to gh_chol_truncate).  Host state; unknown
+ * values mean 0.  Returns the previous setting. */
+int gh_debug_set_remove_path(int path);
+/* the argument rule of gh_chol_remove for a factor of n points (host code: no handle, no device): GH_OK, or GH_ERR_BAD_ARG for a
+ * null idx, m outside 1 .. n - 1, an index outside 0 .. n - 1, or indices that are not strictly increasing */
+int gh_debug_check_remove_args(int64_t n, const int64_t* idx, int64_t m);
 /* 1 (default): with the panel width left to the solver (gh_chol_opts.nb == 0) the outer panels are 2048 columns wide while the
  * trailing matrix behind them has more than 25 600 columns and 1024 after; 0: 1024 throughout; n > 1: the bound is n columns.
  * Returns the previous setting.  Same bits whatever the widths (the update adds the same k in the same order). */
