@@ -141,6 +141,7 @@ SIGNATURES = {
     "gh_kernel_gradient_symmetric": (C.c_int, [_vp, _dp, _dp, _i64, _dp]),
     "gh_kernel_x1_gradient_general": (C.c_int, [_vp, _dp, _i64, _dp, _i64, _dp]),
     "gh_kernel_x2_gradient_general": (C.c_int, [_vp, _dp, _i64, _dp, _i64, _dp]),
+    "gh_kernel_sample": (C.c_int, [_vp, _dp, _i64, C.c_double, _dp, _i64, C.c_double, _dp, _dp, _dp]),
     "gh_chol_create": (C.c_int, [C.POINTER(gh_chol_opts), C.POINTER(_vp)]),
     "gh_chol_destroy": (None, [_vp]),
     "gh_chol_compute": (C.c_int, [_vp, _vp, _dp, _i64, _i32, _dp, C.POINTER(C.c_double)]),
@@ -156,6 +157,7 @@ SIGNATURES = {
     "gh_chol_apply_sqrt": (C.c_int, [_vp, _dp, _i64, _dp]),
     "gh_chol_get_inverse": (C.c_int, [_vp, _dp]),
     "gh_chol_predict": (C.c_int, [_vp, _vp, _dp, _dp, _i64, _dp, _dp, _dp]),
+    "gh_chol_sample_conditional": (C.c_int, [_vp, _vp, _dp, _dp, _i64, _dp, _i64, C.c_double, _dp, _dp, _dp, _dp]),
     "gh_chol_grad": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _dp, _dp]),
     "gh_chol_objective": (C.c_int, [_vp, _vp, _dp, _i64, _i32, _dp, _dp, _dp, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                     _dp, _dp, _dp]),
@@ -165,6 +167,8 @@ SIGNATURES = {
     "gh_chol_objective_batch": (C.c_int, [_vp, _vp, _dp, _i32, _dp, _i64, _i32, _dp, _dp, _dp, _dp, _dp]),
     "gh_chol_predict_batch": (C.c_int, [_vp, _vp, _dp, _i32, _dp, _i64, _i32, _dp, _dp, _dp, _i64, _dp, _dp, _dp, _dp, _dp,
                                         _dp]),
+    "gh_chol_sample_conditional_batch": (C.c_int, [_vp, _vp, _dp, _i32, _dp, _i64, _i32, _dp, _dp, _dp, _i64, _dp, _i64, C.c_double,
+                                                   _dp, _dp, _dp, _dp, _dp]),
     "gh_chol_objective_grad_batch": (C.c_int, [_vp, _vp, _dp, _i32, _dp, _i64, _i32, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
                                                _dp, _dp]),
     "gh_chol_factor_size": (_i64, [_vp]),
@@ -213,6 +217,7 @@ SIGNATURES = {
     "gh_dev_gemm_nt": (C.c_int, [_dp, _i64, _dp, _i64, _dp, _i64, _i64, _i64, _i64, _i32, _vp]),
     "gh_dev_gemm_nt_stair": (C.c_int, [_dp, _i64, _dp, _i64, _dp, _i64, _i64, _i32, C.POINTER(C.c_int64), _i64, _vp]),
     "gh_dev_gemm": (C.c_int, [_dp, _i64, _dp, _i64, _dp, _i64, _i64, _i64, _i64, C.c_double, C.c_double, _i32, _vp]),
+    "gh_dev_pstrf": (C.c_int, [_dp, _i64, _i64, _i64, _i32, C.c_double, _dp, _i64, _i64, _dp, _dp, _dp, _vp]),
     "gh_dev_logdet_accum": (C.c_int, [_dp, _i64, _i64, _dp, _vp]),
     "gh_dev_trsv_lower": (C.c_int, [_dp, _i64, _dp, _i64, _dp, _dp, _vp, _vp]),
     "gh_dev_trsv_lower_t": (C.c_int, [_dp, _i64, _dp, _i64, _dp, _dp, _vp, _vp]),

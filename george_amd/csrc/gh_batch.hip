@@ -49,6 +49,7 @@ struct GhBatchBufs {
   GhBuf O;                     // predict: B x (mt + 1 + K** tiles) 128 x 128 output tiles of the Schur complement; grad: -z^T z, -alpha, -K^-1
   GhBuf res;                   // predict: [mu (B, m) | var (B, m) or cov (B, m, m)]; grad: [grad (B, P) | alpha (B, n) | diagA (B, n)]
   GhBuf part;                  // grad: [which (P) | partial rows of the reduction (B, 64-tiles, P)]
+  GhBuf samp;                  // sample: [thresholds (B) | the factor / draw work arrays of gh_sample_enqueue]
   std::vector<char> stage;     // host image of `in`: ONE host-to-device copy per call
   std::vector<double> back;    // host image of `out`: ONE device-to-host copy per call
 };
@@ -56,7 +57,7 @@ GhBatchBufs* gh_batch_new() { return new GhBatchBufs(); }
 size_t gh_batch_bytes(const GhBatchBufs* b) {
   if (!b) return 0;
   size_t tot = 0;
-  for (const GhBuf* x : {&b->A, &b->dinv, &b->in, &b->out, &b->O, &b->res, &b->part}) tot += x->p ? x->bytes : 0;
+  for (const GhBuf* x : {&b->A, &b->dinv, &b->in, &b->out, &b->O, &b->res, &b->part, &b->samp}) tot += x->p ? x->bytes : 0;
   return tot;
 }
 void gh_batch_free(GhBatchBufs* b) { delete b; }
@@ -640,24 +641,35 @@ extern "C" int gh_chol_objective_batch(gh_chol* s, gh_kernel* k, const double* p
   return batch_finish(c, logdet, quad, info);
 }
 
-extern "C" int gh_chol_predict_batch(gh_chol* s, gh_kernel* k, const double* params, int32_t nbatch,
-                                     const double* x, int64_t n, int32_t ndim, const double* yerr, const double* r,
-                                     const double* xs, int64_t m, double* mu, double* var, double* cov,
-                                     double* logdet, double* quad, int64_t* info) {
-  if (!s || !k || nbatch < 0 || n <= 0 || m < 0 || !x || !yerr || !r || (m > 0 && (!xs || !mu)) || !info || (var && cov) ||
-      (k->size > 0 && !params)) {
-    gh_set_error("bad argument to predict_batch");
-    return GH_ERR_BAD_ARG;
+// tol[b] = m eps max(max_i k_b(xs_i, xs_i), 0): the default threshold of a member's pivoted Cholesky, on the scale of ITS prior
+// (gh_chol_sample_conditional's rule).  One workgroup per member.
+template <bool FAST>
+__global__ __launch_bounds__(256) void batch_prior_tol_kernel(const GhNode* nodes, int n_nodes, const GhFast* fast, int ndim,
+                                                              const double* xs, long m, double* tol) {
+  __shared__ double sh[4];
+  const int b = blockIdx.x;
+  const GhNode* prog = nodes + (long)b * n_nodes;
+  double v = 0.0;
+  for (long i = threadIdx.x; i < m; i += 256) {
+    const double* p = xs + i * ndim;
+    v = fmax(v, FAST ? gh_fast_value(fast[b], p, p) : gh_eval_value(prog, n_nodes, p, p));
   }
-  if (ndim != k->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
-  if (nbatch == 0) return GH_OK;
-  const long B = nbatch, np = gh_round_up(n, T), nt = np / T, mt = gh_round_up(m, T) / T;
-  const int kss = cov ? 2 : var ? 1 : 0;
+  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) tol[b] = ((double)m * 2.220446049250313e-16) * fmax(fmax(sh[0], sh[1]), fmax(sh[2], sh[3]));
+}
+
+// gh_chol_predict_batch up to its results on the device: *d_mu (B, m) and *d_second, var (B, m) or cov (B, m, m) in the caller's
+// layout (c.bb->res); kss: 2 cov, 1 var, 0 neither.  batch_finish() is left to the caller.
+static int predict_batch_enqueue(gh_chol* s, gh_kernel* k, const double* params, long B, const double* x, int64_t n, int32_t ndim,
+                                 const double* yerr, const double* r, const double* xs, int64_t m, int kss, BatchChain& c,
+                                 double** d_mu_out, double** d_second_out, long* per_out) {
+  const long np = gh_round_up(n, T), nt = np / T, mt = gh_round_up(m, T) / T;
   const long q = mt + 1 + (kss == 2 ? mt * (mt + 1) / 2 : kss == 1 ? mt : 0);     // output tiles per member
   const long per = m + (kss == 2 ? m * m : kss == 1 ? m : 0), fblocks = (per + 255) / 256;
   BatchShape sh;
   sh.ld = np; sh.rt = nt + 1 + mt; sh.rows = 1; sh.carry0 = mt; sh.carry1 = 0; sh.q = q; sh.kss = kss; sh.blocks = fblocks;
-  BatchChain c;
   GH_CHECK(gh_chol_batch_begin(s, &c.st, &c.bb));
   GH_CHECK(batch_prepare(k, "predict_batch", params, B, x, n, ndim, yerr, r, xs, m, sh, &c));
   GH_CHECK(batch_chain(k, n, ndim, m, sh, &c));
@@ -675,12 +687,72 @@ extern "C" int gh_chol_predict_batch(gh_chol* s, gh_kernel* k, const double* par
     hipLaunchKernelGGL(batch_pfinal_kernel, dim3((unsigned)(B * fblocks)), blk, 0, st, (const double*)c.O, c.ostride,
                        (const long long*)c.info, (long)m, (int)mt, kss, per, fblocks, d_mu, d_second, d_second);
   GH_HIP(hipGetLastError());
+  *d_mu_out = d_mu; *d_second_out = d_second; *per_out = per;
+  return GH_OK;
+}
+
+extern "C" int gh_chol_predict_batch(gh_chol* s, gh_kernel* k, const double* params, int32_t nbatch,
+                                     const double* x, int64_t n, int32_t ndim, const double* yerr, const double* r,
+                                     const double* xs, int64_t m, double* mu, double* var, double* cov,
+                                     double* logdet, double* quad, int64_t* info) {
+  if (!s || !k || nbatch < 0 || n <= 0 || m < 0 || !x || !yerr || !r || (m > 0 && (!xs || !mu)) || !info || (var && cov) ||
+      (k->size > 0 && !params)) {
+    gh_set_error("bad argument to predict_batch");
+    return GH_ERR_BAD_ARG;
+  }
+  if (ndim != k->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
+  if (nbatch == 0) return GH_OK;
+  const long B = nbatch;
+  const int kss = cov ? 2 : var ? 1 : 0;
+  BatchChain c;
+  double* d_mu = nullptr; double* d_second = nullptr; long per = 0;
+  GH_CHECK(predict_batch_enqueue(s, k, params, B, x, n, ndim, yerr, r, xs, m, kss, c, &d_mu, &d_second, &per));
+  hipStream_t st = c.st;
 
   // ---- results: straight into the caller's arrays
   double* second = kss == 2 ? cov : var;
   if (m > 0) GH_HIP(hipMemcpyAsync(mu, d_mu, (size_t)B * m * sizeof(double), batch_from_device(mu), st));
   if (kss) GH_HIP(hipMemcpyAsync(second, d_second, (size_t)B * (per - m) * sizeof(double), batch_from_device(second), st));
   return batch_finish(c, logdet, quad, info);
+}
+
+// B rounds of compute + gh_chol_sample_conditional: gh_chol_predict_batch's launches, then -- the covariances staying where they
+// are, (B, m, m) in the caller's layout -- one batched pivoted Cholesky (gh_pstrf.hip; one launch for the whole chunk up to
+// m = 512) and one GEMM per member for the draws.  A failed member has a NaN covariance: rank -1 and NaN draws.
+extern "C" int gh_chol_sample_conditional_batch(gh_chol* s, gh_kernel* k, const double* params, int32_t nbatch,
+                                                const double* x, int64_t n, int32_t ndim, const double* yerr, const double* r,
+                                                const double* xs, int64_t m, const double* z, int64_t nz, double tol,
+                                                double* mu, double* draws, double* fac, int64_t* rank, int64_t* info) {
+  if (!s || !k || nbatch < 0 || n <= 0 || m <= 0 || nz <= 0 || !x || !yerr || !r || !xs || !z || !draws || !rank || !info ||
+      (k->size > 0 && !params)) {
+    gh_set_error("bad argument to sample_conditional_batch");
+    return GH_ERR_BAD_ARG;
+  }
+  if (ndim != k->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
+  if (nbatch == 0) return GH_OK;
+  const long B = nbatch;
+  BatchChain c;
+  double* d_mu = nullptr; double* d_cov = nullptr; long per = 0;
+  GH_CHECK(predict_batch_enqueue(s, k, params, B, x, n, ndim, yerr, r, xs, m, 2, c, &d_mu, &d_cov, &per));
+  hipStream_t st = c.st;
+  const size_t head = align256((size_t)B * sizeof(double));
+  GH_CHECK(c.bb->samp.ensure(head + gh_sample_work_bytes(m, nz, B)));
+  double* tol_dev = c.bb->samp.d();
+  if (tol < 0.0) {
+    if (c.in.fast) hipLaunchKernelGGL(batch_prior_tol_kernel<true>, dim3((unsigned)B), dim3(256), 0, st, c.in.nodes,
+                                      (int)k->nodes.size(), c.in.fast, (int)ndim, c.in.xs, (long)m, tol_dev);
+    else           hipLaunchKernelGGL(batch_prior_tol_kernel<false>, dim3((unsigned)B), dim3(256), 0, st, c.in.nodes,
+                                      (int)k->nodes.size(), c.in.fast, (int)ndim, c.in.xs, (long)m, tol_dev);
+    GH_HIP(hipGetLastError());
+  }
+  if (mu) GH_HIP(hipMemcpyAsync(mu, d_mu, (size_t)B * m * sizeof(double), batch_from_device(mu), st));
+  GhSample q{};
+  q.cov = d_cov; q.lda = m; q.stride = m * m; q.m = m; q.nbatch = B;
+  q.tol = tol; q.tol_dev = tol < 0.0 ? tol_dev : nullptr; q.mu = d_mu;
+  q.z = z; q.nz = nz; q.draws = draws; q.fac = fac; q.rank = rank;
+  q.work = (char*)c.bb->samp.p + head; q.work_bytes = c.bb->samp.bytes - head;
+  GH_CHECK(gh_sample_enqueue(q, st));
+  return batch_finish(c, nullptr, nullptr, info);
 }
 
 // B rounds of objective + gradient (gh_chol_objective with a gradient, gh_chol.hip): the chain turns the np identity rows into

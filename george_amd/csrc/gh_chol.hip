@@ -764,6 +764,7 @@ struct gh_chol {
   double logdet = 0.0;
   GhBuf A, dinv, x, yerr, v0, v1, v2, scal, rhs, work, work2, scratch, chain;
   GhBuf A_spare;                         // the buffer the factor left when append / truncate last moved it: where the next move goes (freed by trim)
+  GhBuf samp;                            // gh_chol_sample_conditional: prior diagonal, threshold and the factor / draw work arrays (freed by trim)
   GhBuf lv;                              // gh_chol_loo's N-vectors: resid, var, lpd, sqrt(w), c, alpha, v (7 Np doubles)
   long long* d_info = nullptr;           // = (long long*)(scal + 2): the failure word lives beside the scalars (set in compute_enqueue)
   bool build_on_chain = false;           // this compute(): inputs + kernel-matrix build were enqueued on the chain stream (st2)
@@ -1008,7 +1009,7 @@ extern "C" int64_t gh_chol_device_bytes(const gh_chol* s) {
   if (!s) return 0;
   size_t tot = 0;
   for (const GhBuf* b : {&s->A, &s->A_spare, &s->dinv, &s->x, &s->yerr, &s->v0, &s->v1, &s->v2, &s->scal, &s->rhs, &s->work, &s->work2,
-                         &s->scratch, &s->chain, &s->lv}) tot += b->p ? b->bytes : 0;
+                         &s->scratch, &s->chain, &s->lv, &s->samp}) tot += b->p ? b->bytes : 0;
   return (int64_t)(tot + gh_batch_bytes(s->batch));
 }
 int gh_chol_batch_begin(gh_chol* s, hipStream_t* st, GhBatchBufs** bufs) {
@@ -1888,12 +1889,13 @@ extern "C" int gh_chol_get_inverse(gh_chol* s, double* out) {
   return gh_from_device(out, full, (size_t)tot, s->st);
 }
 
-extern "C" int gh_chol_predict(gh_chol* s, gh_kernel* k, const double* r, const double* xs, int64_t m,
-                               double* mu, double* var, double* cov) {
-  GH_CHECK(need_computed(s));
-  if (!k || !r || !xs || !mu || m <= 0) { gh_set_error("bad argument to predict"); return GH_ERR_BAD_ARG; }
-  if (k->ndim != s->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
-  GH_CHECK(k->upload());
+// Everything of gh_chol_predict but its synchronisation, enqueued on the main stream.  keep_cov: the covariance is formed in
+// s->work (mp x mp, pitch mp; the caller's cov may then be NULL) for a caller that goes on with it on the device
+// (gh_chol_sample_conditional); *dmu_out: the mean on the device (in s->scratch), *xs_dev_out: the test points there (xsd owns
+// them when they came from the host).  mu may be NULL with keep_cov.
+static int predict_enqueue(gh_chol* s, gh_kernel* k, const double* r, const double* xs, int64_t m,
+                           double* mu, double* var, double* cov, bool keep_cov, GhBuf& xsd, double** dmu_out,
+                           const double** xs_dev_out) {
   const int64_t n = s->n, np = s->np, mp = gh_round_up(m, T);
   hipStream_t st = s->st;
   // z = L^-1 r
@@ -1902,7 +1904,6 @@ extern "C" int gh_chol_predict(gh_chol* s, gh_kernel* k, const double* r, const 
   GH_CHECK(trsv_forward(s, s->v0.d(), s->v1.d()));
   // V = L^-1 K(x, xs)   (np x mp): built on the device, forward substitution only, because
   // K*s K^-1 K*s^T = V^T V and K*s K^-1 r = V^T z  (gp.py:532-545 does both sweeps on the host)
-  GhBuf xsd;
   const double* xs_dev = xs;
   if (!gh_is_device_ptr(xs)) {
     GH_CHECK(xsd.ensure((size_t)m * s->ndim * sizeof(double)));
@@ -1927,9 +1928,9 @@ extern "C" int gh_chol_predict(gh_chol* s, gh_kernel* k, const double* r, const 
   hipLaunchKernelGGL(colfinal_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
                      pmu, pvar, (long)nchunks, (long)mp, (long)m, dmu, var ? dvar : nullptr);
   GH_HIP(hipGetLastError());
-  GH_CHECK(gh_from_device(mu, dmu, (size_t)m, st));
+  if (mu) GH_CHECK(gh_from_device(mu, dmu, (size_t)m, st));
   if (var) GH_CHECK(gh_from_device(var, dvar, (size_t)m, st));
-  if (cov) {
+  if (cov || keep_cov) {
     // cov = K(xs, xs) - V^T V      (gp.py:543-545)
     GH_CHECK(s->work.ensure((size_t)mp * mp * sizeof(double)));
     GH_CHECK(gh_launch_kmat(k, xs_dev, m, xs_dev, m, nullptr, s->work.d(), mp, mp, mp, 0, 0, true, false, st));
@@ -1937,11 +1938,61 @@ extern "C" int gh_chol_predict(gh_chol* s, gh_kernel* k, const double* r, const 
     g.C = s->work.d(); g.ldc = mp; g.A = s->rhs.d(); g.lda = mp; g.B = s->rhs.d(); g.ldb = mp;
     g.M = mp; g.N = mp; g.K = np; g.alpha = -1.0; g.beta = 1.0; g.a_km = false; g.b_km = false;
     GH_CHECK(gh_launch_gemm(g, st));
-    GH_HIP(hipMemcpy2DAsync(cov, m * sizeof(double), s->work.d(), mp * sizeof(double), m * sizeof(double), m,
-                            gh_is_device_ptr(cov) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+    if (cov)
+      GH_HIP(hipMemcpy2DAsync(cov, m * sizeof(double), s->work.d(), mp * sizeof(double), m * sizeof(double), m,
+                              gh_is_device_ptr(cov) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
   }
-  GH_HIP(hipStreamSynchronize(st));
+  if (dmu_out) *dmu_out = dmu;
+  if (xs_dev_out) *xs_dev_out = xs_dev;
   return GH_OK;
+}
+
+extern "C" int gh_chol_predict(gh_chol* s, gh_kernel* k, const double* r, const double* xs, int64_t m,
+                               double* mu, double* var, double* cov) {
+  GH_CHECK(need_computed(s));
+  if (!k || !r || !xs || !mu || m <= 0) { gh_set_error("bad argument to predict"); return GH_ERR_BAD_ARG; }
+  if (k->ndim != s->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
+  GH_CHECK(k->upload());
+  GhBuf xsd;
+  GH_CHECK(predict_enqueue(s, k, r, xs, m, mu, var, cov, false, xsd, nullptr, nullptr));
+  GH_HIP(hipStreamSynchronize(s->st));
+  return GH_OK;
+}
+
+// Posterior draws on a computed handle: mu and cov exactly as gh_chol_predict forms them (the same launches), cov left on the
+// device and factored there by the pivoted Cholesky of gh_pstrf.hip, draws = mu + z L^T as one GEMM.  The default threshold
+// is on the PRIOR's scale, m eps max diag K(xs, xs): the rounding error of cov = K** - V^T V is that of its two terms, however
+// small the posterior variances are.  DESIGN.md section 4, "Sampling".
+extern "C" int gh_chol_sample_conditional(gh_chol* s, gh_kernel* k, const double* r, const double* xs, int64_t m,
+                                          const double* z, int64_t nz, double tol, double* mu, double* draws, double* fac,
+                                          int64_t* rank) {
+  GH_CHECK(need_computed(s));
+  if (!k || !r || !xs || !z || !draws || !rank || m <= 0 || nz <= 0) { gh_set_error("bad argument to sample_conditional"); return GH_ERR_BAD_ARG; }
+  if (k->ndim != s->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
+  GH_CHECK(k->upload());
+  hipStream_t st = s->st;
+  const int64_t mp = gh_round_up(m, T);
+  GhBuf xsd;
+  double* dmu = nullptr;
+  const double* xs_dev = nullptr;
+  GH_CHECK(predict_enqueue(s, k, r, xs, m, mu, nullptr, nullptr, true, xsd, &dmu, &xs_dev));
+  // [prior diagonal (mp) | tol (1, padded to 32 doubles) | the work arrays of gh_sample_enqueue]
+  const size_t head = (size_t)(mp + 32) * sizeof(double), wb = gh_sample_work_bytes(m, nz, 1);
+  GH_CHECK(s->samp.ensure(head + wb));
+  double* diag = s->samp.d();
+  double* tol_dev = diag + mp;
+  if (tol < 0.0) {
+    GH_CHECK(gh_launch_kdiag(k, xs_dev, xs_dev, m, diag, st));
+    GH_CHECK(gh_launch_prior_tol(diag, m, tol_dev, st));
+  }
+  GhSample q{};
+  q.cov = s->work.d(); q.lda = mp; q.stride = mp * mp; q.m = m; q.nbatch = 1;
+  q.tol = tol; q.tol_dev = tol < 0.0 ? tol_dev : nullptr; q.mu = dmu;
+  q.z = z; q.nz = nz; q.draws = draws; q.fac = fac; q.rank = rank;
+  q.work = (char*)s->samp.p + head; q.work_bytes = s->samp.bytes - head;
+  const int rc = gh_sample_enqueue(q, st);
+  GH_HIP(hipStreamSynchronize(st));
+  return rc;
 }
 
 extern "C" int gh_chol_grad(gh_chol* s, gh_kernel* k, const uint32_t* which, const double* r,
@@ -2232,7 +2283,7 @@ extern "C" void gh_chol_release_buffers(gh_chol* s) {
   (void)hipSetDevice(s->opts.device);
   if (s->st) (void)hipStreamSynchronize(s->st);
   s->computed = false;
-  for (GhBuf* b : {&s->A, &s->A_spare, &s->dinv, &s->x, &s->yerr, &s->v0, &s->v1, &s->v2, &s->rhs, &s->work, &s->work2, &s->scratch, &s->chain, &s->lv}) b->release();
+  for (GhBuf* b : {&s->A, &s->A_spare, &s->dinv, &s->x, &s->yerr, &s->v0, &s->v1, &s->v2, &s->rhs, &s->work, &s->work2, &s->scratch, &s->chain, &s->lv, &s->samp}) b->release();
   gh_batch_free(s->batch);
   s->batch = nullptr;
 }
@@ -2241,7 +2292,7 @@ extern "C" void gh_chol_trim(gh_chol* s) {
   if (!s) return;
   (void)hipSetDevice(s->opts.device);
   if (s->st) (void)hipStreamSynchronize(s->st);
-  for (GhBuf* b : {&s->rhs, &s->work, &s->work2, &s->scratch, &s->A_spare}) b->release();
+  for (GhBuf* b : {&s->rhs, &s->work, &s->work2, &s->scratch, &s->A_spare, &s->samp}) b->release();
   gh_batch_free(s->batch);
   s->batch = nullptr;
 }

@@ -162,6 +162,37 @@ struct GhGemm {
 };
 #define GH_GEMM_STAIR_MAX 128
 int gh_launch_gemm(const GhGemm& g, hipStream_t st);
+// Diagonally pivoted Cholesky with rank truncation, batched (gh_pstrf.hip; the definition is at the top of that file).
+// All pointers are device memory.  The launcher enqueues on st; for m > 512 it also synchronises st once per 128 pivots.
+struct GhPstrf {
+  double* A; int64_t lda, stride_a;       // nbatch symmetric m x m matrices; destroyed
+  int64_t m, nbatch;
+  double tol; const double* tol_dev;      // stop threshold; tol_dev (nbatch) replaces tol when not null; < 0: m eps max(d_0, 0)
+  double* L; int64_t ldl, stride_l;       // the factors; rows_l x cols_l (>= m each) of every member are zeroed first
+  int64_t rows_l, cols_l;
+  long long* piv; long long* rank;        // (nbatch, m) and (nbatch)
+  double* resid;                          // (nbatch) largest remaining diagonal entry, or nullptr
+  void* work; size_t work_bytes;          // >= gh_pstrf_work_bytes(m, nbatch)
+};
+size_t gh_pstrf_work_bytes(int64_t m, int64_t nbatch);
+int gh_launch_pstrf(const GhPstrf& p, hipStream_t st);
+// draws[b] (nz, m) = mu[b] + z[b] L_b^T with L_b the pivoted factor of cov[b] (gh_pstrf.hip): the tail of every sampling
+// entry point.  cov, mu (nbatch, m; or nullptr: zero mean), tol_dev and work are device memory; z (nbatch, nz, m), draws
+// (nbatch, nz, m), fac (nbatch, m, m; or nullptr) and rank (nbatch, int64) may be host or device memory.  Copies to host
+// memory are enqueued: the caller synchronises st.
+struct GhSample {
+  double* cov; int64_t lda, stride;       // destroyed
+  int64_t m, nbatch;
+  double tol; const double* tol_dev;
+  const double* mu;
+  const double* z; int64_t nz;
+  double* draws; double* fac; int64_t* rank;
+  void* work; size_t work_bytes;          // >= gh_sample_work_bytes(m, nz, nbatch)
+};
+size_t gh_sample_work_bytes(int64_t m, int64_t nz, int64_t nbatch);
+int gh_sample_enqueue(const GhSample& q, hipStream_t st);
+// tol_dev[0] = m eps max(max_i diag[i], 0)
+int gh_launch_prior_tol(const double* diag, int64_t m, double* tol_dev, hipStream_t st);
 // Process-wide streams of a device, shared by every solver handle (gh_chol.hip): q[0] main (blocking,
 // normal priority), q[1..3] non-blocking high-priority.  nullptr where creation failed.  Never destroyed.
 // Why shared: HIP maps streams onto a few hardware queues; every further handle with streams of its

@@ -23,7 +23,7 @@ import numpy as np
 from . import kernels
 from .modeling import ModelSet, ConstantModel
 from .solvers import TrivialSolver, BasicSolver
-from .utils import multivariate_gaussian_samples
+from .utils import multivariate_gaussian_samples, pivoted_cholesky
 
 __all__ = ["GP"]
 
@@ -830,12 +830,22 @@ class GP(ModelSet):
         self._each_member(range(B), one, ValueError, vectors, quiet)   # (np.linalg.LinAlgError is a ValueError)
         return mu, var, cov
 
-    def sample_conditional_batch(self, vectors, y, t, size=1, quiet=False):
+    def sample_conditional_batch(self, vectors, y, t, size=1, quiet=False, factor="svd"):
         """``sample_conditional(y, t, size)`` at each row of ``vectors``: ``predict_batch(..., return_cov=True)`` and then,
         for b = 0, 1, ... in order, ``multivariate_gaussian_samples(cov_b, size, mean=mu_b)`` -- the random stream is
         consumed as the loop of ``set_parameter_vector`` + ``sample_conditional`` consumes it.  The draws are made on the
         host (SVD, as the reference).  Returns (B, M) for ``size == 1``, else (B, size, M).  A member that failed under
-        ``quiet=True`` has NaN draws and consumes no random numbers."""
+        ``quiet=True`` has NaN draws and consumes no random numbers.
+
+        ``factor="cholesky"``: the covariances are factored by the pivoted Cholesky of :meth:`sample_conditional` -- with the
+        HIP :class:`BasicSolver`, under ``predict_batch``'s routing rule (``N <= BATCH_MAX_N``, one member's device bytes
+        within ``BATCH_MAX_BYTES``), all B members in one device call (gh_chol_sample_conditional_batch), the covariances
+        never leaving the device.  The random-number rule differs from the SVD path's: ONE call
+        ``np.random.standard_normal((B, size, M))`` is made before anything else, member b uses block b, and a failed
+        member's numbers are drawn and discarded (its rows are NaN under ``quiet=True``)."""
+        self._check_factor(factor)
+        if factor == "cholesky":
+            return self._sample_conditional_batch_cholesky(vectors, y, t, size, quiet)
         mu, cov = self.predict_batch(vectors, y, t, return_cov=True, quiet=quiet)
         B, m = mu.shape
         out = np.full((B, m) if size == 1 else (B, size, m), np.nan)
@@ -843,6 +853,53 @@ class GP(ModelSet):
             if np.all(np.isfinite(mu[b])):
                 out[b] = multivariate_gaussian_samples(cov[b], size, mean=mu[b])
         return out
+
+    def _sample_conditional_batch_cholesky(self, vectors, y, t, size, quiet):
+        vectors, y = self._batch_args(vectors, y)
+        xs = np.ascontiguousarray(self.parse_samples(t), dtype=np.float64)
+        B, m = len(vectors), len(xs)
+        z = np.random.standard_normal((B, size, m))
+        if B == 0:
+            return np.empty((0, m) if size == 1 else (0, size, m))
+        if self._batch_on_device(BasicSolver.sample_batch_bytes(len(self._x), m, size)):
+            kp, sigma, r, ok, mean_t = self._batch_inputs(vectors, y, quiet, t=xs)
+            solver = BasicSolver(self.kernel, **(self.solver_kwargs))  # (its own pooled handle: self.solver is untouched)
+            out, _, _, info = solver.sample_conditional_batch(kp, self._x, sigma, r, xs, z)
+            if not quiet:
+                self._raise_not_positive_definite(info)
+            out += mean_t[:, None, :]
+            out[~(ok & (info == 0))] = np.nan
+        else:
+            out = np.full((B, size, m), np.nan)
+
+            def one(b):
+                out[b] = self._sample_conditional_cholesky(y, xs, z[b])
+
+            self._each_member(range(B), one, ValueError, vectors, quiet)   # (np.linalg.LinAlgError is a ValueError)
+        return out[:, 0] if size == 1 else out
+
+    @staticmethod
+    def _check_factor(factor):
+        if factor not in ("svd", "cholesky"):
+            raise ValueError("factor must be 'svd' or 'cholesky', not {0!r}".format(factor))
+
+    @staticmethod
+    def _cholesky_draws(mu, cov, z, tol=None):
+        """``mu + z[:, :rank] @ L[:, :rank].T`` with ``L`` the pivoted Cholesky factor of ``cov``: the host form of what the
+        device does (the same formula: the same ``z`` gives the same draws up to rounding whenever the pivots agree)."""
+        L, _, rank = pivoted_cholesky(cov, tol)
+        if rank < 0:
+            return np.full(z.shape, np.nan)
+        return mu + np.dot(z[:, :rank], L[:, :rank].T)
+
+    def _sample_conditional_cholesky(self, y, xs, z):
+        """(size, M) draws of ``sample_conditional(factor="cholesky")`` for the normals ``z``, mean model included."""
+        self.recompute()
+        if callable(getattr(self.solver, "sample_conditional", None)):
+            out, _, _ = self.solver.sample_conditional(self.kernel, self._residual(y), xs, z)
+            return out + self._call_mean(xs)
+        mu, cov = self.predict(y, xs, return_cov=True)
+        return self._cholesky_draws(mu, cov, z)
 
     # -- many gradients at once (multi-start fits, per-iteration re-fits, gradient-based ensembles) -----------------------
     def grad_log_likelihood_batch(self, vectors, y, quiet=True):
@@ -1002,11 +1059,34 @@ class GP(ModelSet):
         return b.flatten() if r.ndim == 1 else b
 
     # -- sampling -------------------------------------------------------------------
-    def sample_conditional(self, y, t, size=1):
-        mu, cov = self.predict(y, t)
-        return multivariate_gaussian_samples(cov, size, mean=mu)
+    def sample_conditional(self, y, t, size=1, factor="svd"):
+        """Draws from the predictive distribution at ``t`` given ``y``: (M,) for ``size == 1``, else (size, M).
 
-    def sample(self, t=None, size=1):
+        ``factor="svd"`` (the default) is the reference's path, draw for draw: ``predict`` and
+        ``multivariate_gaussian_samples`` (an SVD of the M x M covariance on the host).  ``factor="cholesky"`` factors the
+        covariance by a diagonally pivoted Cholesky with rank truncation (a predictive covariance is numerically
+        semidefinite: a plain Cholesky fails on it) and returns ``mu + z[:, :rank] @ L[:, :rank].T``.  Its random-number
+        rule differs from the SVD path's: ONE call ``z = np.random.standard_normal((size, M))`` is made before the factor.
+        A solver that offers ``sample_conditional`` (the HIP :class:`BasicSolver`) does all of it on the device -- the
+        covariance never reaches the host; the mean model at ``t`` is added on the host, as in ``predict``.  Any other solver
+        goes through ``predict(..., return_cov=True)`` and :func:`george_amd.utils.pivoted_cholesky` with the same formula."""
+        self._check_factor(factor)
+        if factor == "svd":
+            mu, cov = self.predict(y, t)
+            return multivariate_gaussian_samples(cov, size, mean=mu)
+        xs = np.ascontiguousarray(self.parse_samples(t), dtype=np.float64)
+        z = np.random.standard_normal((size, len(xs)))
+        out = self._sample_conditional_cholesky(y, xs, z)
+        return out[0] if size == 1 else out
+
+    def sample(self, t=None, size=1, factor="svd"):
+        """Draws from the prior: at the computed points (``t=None``: ``apply_sqrt`` of the solver, whatever ``factor``) or
+        at ``t``, where ``factor`` chooses as in :meth:`sample_conditional` -- ``"svd"``: ``get_matrix`` + ``TINY`` on the
+        diagonal + ``multivariate_gaussian_samples``, the reference's path; ``"cholesky"``: ONE call
+        ``z = np.random.standard_normal((size, M))``, then ``mean(t) + z @ L.T`` with ``L`` the pivoted Cholesky factor of
+        ``K(t, t) + TINY I``, built and factored on the device (gh_kernel_sample) when the GP's solver is a device solver
+        (one that offers ``sample_conditional``), else on the host."""
+        self._check_factor(factor)
         if t is None:
             self.recompute()
             n = self._x.shape[0]
@@ -1014,6 +1094,17 @@ class GP(ModelSet):
             out += self._call_mean(self._x)
             return out[0] if size == 1 else out
         x = self.parse_samples(t)
+        if factor == "cholesky":
+            x = np.ascontiguousarray(x, dtype=np.float64)
+            z = np.random.standard_normal((size, len(x)))
+            if callable(getattr(self.solver_type, "sample_conditional", None)):
+                out, _ = self.kernel.kernel.sample(x, z, jitter=TINY)
+            else:
+                cov = self.get_matrix(x)
+                cov[np.diag_indices_from(cov)] += TINY
+                out = self._cholesky_draws(0.0, cov, z)
+            out = out + self._call_mean(x)
+            return out[0] if size == 1 else out
         cov = self.get_matrix(x)
         cov[np.diag_indices_from(cov)] += TINY
         return multivariate_gaussian_samples(cov, size, mean=self._call_mean(x))

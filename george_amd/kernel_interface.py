@@ -86,6 +86,23 @@ class KernelInterface(object):
         N.check(N.lib.gh_kernel_x2_gradient_general(self.handle, N.ptr(x1), len(x1), N.ptr(x2), len(x2), N.ptr(out)))
         return out
 
+    def sample(self, t, z, jitter=0.0, tol=None, return_factor=False):
+        """Prior draws at ``t`` on the device (gh_kernel_sample; no reference counterpart -- gp.py ``sample`` goes through
+        ``get_matrix`` and an SVD on the host): ``z @ L.T`` with ``L`` the pivoted Cholesky factor of ``K(t, t) + jitter I``
+        and ``z`` (size, M) the caller's standard normals.  Returns ``(draws (size, M), rank)``, with ``L`` (M, M) in between
+        when ``return_factor``."""
+        t = self._x(t)
+        m = len(t)
+        z = np.ascontiguousarray(z, dtype=np.float64)
+        if z.ndim != 2 or z.shape[1] != m:
+            raise ValueError("z must be (size, {0})".format(m))
+        draws = np.empty_like(z)
+        fac = np.empty((m, m)) if return_factor else None
+        rank = np.zeros(1, dtype=np.int64)
+        N.check(N.lib.gh_kernel_sample(self.handle, N.ptr(t), m, float(jitter), N.ptr(z), len(z),
+                                       -1.0 if tol is None else float(tol), N.ptr(draws), N.ptr(fac), N.ptr(rank)))
+        return (draws, fac, int(rank[0])) if return_factor else (draws, int(rank[0]))
+
     # pickle support mirrors kernel_interface.cpp:159-167 (state == the spec)
     def __reduce__(self):
         return (KernelInterface, (self._spec,))

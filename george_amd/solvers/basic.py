@@ -341,6 +341,41 @@ class BasicSolver(object):
         res = m + (m if return_var else m * m if return_cov else 0)
         return ((np_ + 128 + mp) * np_ + np_ * 128 + (mt + 1 + kss) * 128 * 128 + res) * 8
 
+    def sample_conditional_batch(self, params, x, sigma, r, xs, z, tol=None, return_factor=False):
+        """B sets of posterior draws over one set of points (gh_chol_sample_conditional_batch): member b is predict_batch's
+        member b, its covariance factored on the device (pivoted Cholesky) and ``draws[b] = mu[b] + z[b] @ L_b.T`` for the
+        caller's standard normals ``z`` (B, size, M).  Returns ``(draws (B, size, M), mu (B, M), rank (B,), info (B,))``,
+        with ``fac`` (B, M, M) before ``rank`` when ``return_factor``; ``mu`` has no mean model.  A member with
+        ``info[b] != 0`` has NaN rows and ``rank[b] == -1``.  ``tol=None``: each member's ``M * eps * max diag K_b(xs, xs)``.
+        Runs on objective_batch's pooled handle, in chunks under BATCH_MAX_BYTES."""
+        params, x, sigma, r, xs, dk, B, n = self._batch_args(params, x, sigma, r, xs)
+        m = len(xs)
+        z = N.as_f64(z)
+        if z.ndim != 3 or z.shape[0] != B or z.shape[2] != m or z.shape[1] < 1:
+            raise ValueError("z must be (B, size, {0})".format(m))
+        nz = z.shape[1]
+        draws, mu = np.empty((B, nz, m)), np.empty((B, m))
+        fac = np.empty((B, m, m)) if return_factor else None
+        rank, info = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64)
+        t = -1.0 if tol is None else float(tol)
+        self._batch_chunks(B, self.sample_batch_bytes(n, m, nz), lambda hh, b0, b1: N.lib.gh_chol_sample_conditional_batch(
+            hh, dk.handle, N.ptr(params[b0:b1]), b1 - b0, N.ptr(x), n, x.shape[1], N.ptr(sigma[b0:b1]), N.ptr(r[b0:b1]),
+            N.ptr(xs), m, N.ptr(z[b0:b1]), nz, t, N.ptr(mu[b0:]), N.ptr(draws[b0:]),
+            N.ptr(fac[b0:]) if return_factor else None, N.ptr(rank[b0:]), N.ptr(info[b0:])))
+        if return_factor:
+            return draws, mu, fac, rank, info
+        return draws, mu, rank, info
+
+    @staticmethod
+    def sample_batch_bytes(n, m, nz):
+        """Device bytes of one member of sample_conditional_batch: predict_batch's with a covariance, the padded factor, the
+        padded normals and draws, their copies in the caller's layout, and the factor kernel's work arrays (its columns; above
+        M = 512 also the padded matrix it updates)."""
+        mp, zp = -(-m // 128) * 128, -(-nz // 128) * 128
+        work = (min(m, 512) if m <= 512 else 128) * mp + mp + (mp * mp if m > 512 else 0)
+        return BasicSolver.predict_batch_bytes(n, m, return_cov=True) + (
+            mp * mp + 2 * zp * mp + 2 * m + nz * m + m * m + work) * 8
+
     def objective_grad_batch(self, params, x, sigma, r, which=None):
         """B log-likelihood pieces and kernel gradients over one set of points (gh_chol_objective_grad_batch): member b is
         objective_batch's member b.  ``which``: the kernel's parameter mask (all by default), shared by the members.
@@ -544,6 +579,31 @@ class BasicSolver(object):
         cov = np.empty((m, m)) if return_cov else None
         N.check(N.lib.gh_chol_predict(h, dk.handle, N.ptr(r), N.ptr(xs), m, N.ptr(mu), N.ptr(var), N.ptr(cov)))
         return mu, var, cov
+
+    def sample_conditional(self, kernel, r, xs, z, tol=None, return_factor=False):
+        """Posterior draws for residual ``r = y - mean`` at ``xs`` (gh_chol_sample_conditional): the mean and covariance of
+        :meth:`predict`, the covariance factored on the device by a pivoted Cholesky with rank truncation (it never reaches
+        the host), ``draws = mu + z @ L.T`` for the caller's standard normals ``z`` (size, M).  Returns
+        ``(draws (size, M), mu (M,), rank)``, with ``L`` (M, M) before ``rank`` when ``return_factor``; ``mu`` has no mean
+        model.  ``tol=None``: ``M * eps * max diag K(xs, xs)``."""
+        h = self._need()
+        dk = DeviceKernel(kernel) if kernel is not self.kernel else self._dk
+        r, xs = N.as_f64(r).reshape(-1), N.as_f64(xs)
+        if len(r) != self._n:
+            raise ValueError("dimension mismatch")
+        m = len(xs)
+        z = N.as_f64(z)
+        if z.ndim != 2 or z.shape[1] != m or z.shape[0] < 1:
+            raise ValueError("z must be (size, {0})".format(m))
+        draws, mu = np.empty_like(z), np.empty(m)
+        fac = np.empty((m, m)) if return_factor else None
+        rank = np.zeros(1, dtype=np.int64)
+        self._retry_without_parked_memory(lambda hh: N.check(N.lib.gh_chol_sample_conditional(
+            hh, dk.handle, N.ptr(r), N.ptr(xs), m, N.ptr(z), len(z), -1.0 if tol is None else float(tol),
+            N.ptr(mu), N.ptr(draws), N.ptr(fac), N.ptr(rank))))
+        if return_factor:
+            return draws, mu, fac, int(rank[0])
+        return draws, mu, int(rank[0])
 
     def grad(self, r, which):
         """kernel part of gp.py:429-466: returns (grad over ALL kernel params (masked ones 0),

@@ -135,6 +135,12 @@ int  gh_kernel_x1_gradient_general(gh_kernel* k, const double* x1, int64_t n1,
                                    const double* x2, int64_t n2, double* out /* n1*n2*ndim */);
 int  gh_kernel_x2_gradient_general(gh_kernel* k, const double* x1, int64_t n1,
                                    const double* x2, int64_t n2, double* out /* n1*n2*ndim */);
+/* Prior draws at t (m, ndim) (replaces GP.sample(t), src/george/gp.py -- get_matrix + TINY on the diagonal -- and utils.py:11-33):
+ * K(t, t) + jitter * I is built and factored on the device (gh_dev_pstrf), draws (nz, m) = z[:, :rank] L[:, :rank]^T for the caller's
+ * standard normals z (nz, m).  tol < 0: m * eps * max diag (K(t, t) + jitter I).  fac (m, m) or NULL; *rank int64.  Pointers may be
+ * host or device memory; the current device and its null stream, as gh_kernel_value_symmetric. */
+int  gh_kernel_sample(gh_kernel* k, const double* t, int64_t m, double jitter, const double* z, int64_t nz, double tol,
+                      double* draws /* nz*m */, double* fac /* m*m or NULL */, int64_t* rank);
 
 /* ------------------------------------------------------- dense Cholesky solver
  * Replaces BasicSolver (src/george/solvers/basic.py) and the SciPy/LAPACK
@@ -199,6 +205,19 @@ int  gh_chol_get_inverse(gh_chol* s, double* out /* n*n */);
 int  gh_chol_predict(gh_chol* s, gh_kernel* k, const double* r /* n: y - mean */,
                      const double* xs, int64_t m, double* mu /* m */,
                      double* var /* m or NULL */, double* cov /* m*m or NULL */);
+/* Posterior draws on a computed handle, on the device (replaces GP.sample_conditional, src/george/gp.py, and the SVD of
+ * utils.py:11-33 behind it).  mu and cov are formed exactly as gh_chol_predict forms them; cov stays on the device and is factored
+ * there by the diagonally pivoted Cholesky with rank truncation of gh_dev_pstrf (a predictive covariance is numerically
+ * semidefinite: a plain Cholesky fails on it); then, as one GEMM,
+ *   draws (nz, m) = mu + z[:, :rank] L[:, :rank]^T        z (nz, m): standard normals supplied by the caller, host or device.
+ * tol: the factor's absolute stop threshold; tol < 0 means the default m * eps * max diag K(xs, xs) -- the PRIOR's scale, because
+ * the rounding error of cov scales with the prior, not with the possibly tiny posterior variances.  mu (m) or NULL (no mean model:
+ * the caller adds it); fac (m, m) or NULL receives L (columns >= rank exactly zero; L L^T approximates cov within tol entrywise);
+ * *rank (int64): the number of pivots taken.  Pointers may be host or device memory.  The covariance never reaches the host; the
+ * work buffers are counted by gh_chol_device_bytes and freed by gh_chol_trim. */
+int  gh_chol_sample_conditional(gh_chol* s, gh_kernel* k, const double* r /* n: y - mean */, const double* xs, int64_t m,
+                                const double* z /* nz*m */, int64_t nz, double tol, double* mu /* m or NULL */,
+                                double* draws /* nz*m */, double* fac /* m*m or NULL */, int64_t* rank);
 /* alpha = K^-1 r; A = alpha alpha^T - K^-1; grad[p] = 1/2 sum_ij A_ij dK_ij/dtheta_p
  * for the parameters selected by `which` (others 0); diagA (n) = diag(A). */
 int  gh_chol_grad(gh_chol* s, gh_kernel* k, const uint32_t* which, const double* r,
@@ -256,6 +275,18 @@ int  gh_chol_predict_batch(gh_chol* s, gh_kernel* k, const double* params, int32
                            const double* x, int64_t n, int32_t ndim, const double* yerr, const double* r,
                            const double* xs, int64_t m, double* mu, double* var, double* cov,
                            double* logdet, double* quad, int64_t* info);
+/* B rounds of compute + gh_chol_sample_conditional at B parameter vectors, one device call (replaces the loop of
+ * set_parameter_vector + GP.sample_conditional, gp.py, with utils.py:11-33 behind each round).  params, x, yerr, r, xs, info: as
+ * gh_chol_predict_batch, whose launches form mu[b] and cov[b]; the covariances stay on the device in their (B, m, m) layout and
+ * are factored there by ONE batched gh_dev_pstrf; then one GEMM per member:
+ *   draws[b] (nz, m) = mu[b] + z[b][:, :rank[b]] L_b[:, :rank[b]]^T        z (B, nz, m): standard normals supplied by the caller.
+ * tol < 0: member b's default m * eps * max diag K_b(xs, xs).  mu (B, m) or NULL; fac (B, m, m) or NULL; rank (B) int64.  A failed
+ * member (info[b] != 0) has NaN draws (and mu, fac) and rank[b] = -1; GH_OK whenever every member was evaluated.  Any pointer may
+ * be host or device memory.  The handle is left NOT computed. */
+int  gh_chol_sample_conditional_batch(gh_chol* s, gh_kernel* k, const double* params, int32_t nbatch,
+                                      const double* x, int64_t n, int32_t ndim, const double* yerr, const double* r,
+                                      const double* xs, int64_t m, const double* z, int64_t nz, double tol,
+                                      double* mu, double* draws, double* fac, int64_t* rank, int64_t* info);
 /* B rounds of compute gp.py:303-337 + log_likelihood :369-397 + the kernel part of grad_log_likelihood :429-466, one device
  * call.  params, x, yerr, r, info: as gh_chol_objective_batch.  which: (gh_kernel_size(k)) mask shared by all members.
  *   logdet[b], quad[b]      as gh_chol_objective_batch (logdet bit-identical to it)
@@ -279,7 +310,7 @@ int  gh_chol_export_factor(gh_chol* s, double* packed_lower, double* dinv_out);
 int  gh_chol_import_factor(gh_chol* s, int64_t n, int32_t ndim, const double* x,
                            const double* packed_lower, const double* dinv_in, double logdet);
 /* memory management of a long-lived handle: trim() frees the transient work buffers of predict /
- * grad / get_inverse (up to 3 x 8 N^2 bytes) and the buffers of objective_batch / predict_batch / objective_grad_batch, and keeps the factor;
+ * grad / get_inverse (up to 3 x 8 N^2 bytes) and the buffers of objective_batch / predict_batch / objective_grad_batch / sample_conditional(_batch), and keeps the factor;
  * release_buffers() frees everything but the handle (streams, events) -- the next compute() re-allocates. */
 void gh_chol_trim(gh_chol* s);
 void gh_chol_release_buffers(gh_chol* s);
@@ -492,6 +523,19 @@ enum {
 int gh_dev_gemm(double* c, int64_t ldc, const double* a, int64_t lda,
                 const double* b, int64_t ldb, int64_t m, int64_t n, int64_t k,
                 double alpha, double beta, int32_t flags, void* stream);
+/* Diagonally pivoted Cholesky with rank truncation (LAPACK dpstrf's job; the factorisation that replaces the SVD of
+ * utils.py:11-33 for sampling, gp.py sample_conditional / sample), batched: nbatch symmetric m x m matrices at a + b * stride_a
+ * (any m >= 1, any lda >= m; nothing needs to be a multiple of 128).  No rows or columns are swapped.  Per member, with d = diag(A)
+ * and every index free: for j = 0, 1, ...: p = the free index with the largest d (ties: the lowest); stop unless d[p] > tol;
+ * c = A[:, p] - L[:, :j] L[p, :j]; stop unless c[p] > 0 and finite; c[i] = 0 exactly for i no longer free; L[:, j] = c / sqrt(c[p]);
+ * d -= L[:, j]^2; p leaves the free set; piv[j] = p.  Outputs: l (m x m at l + b * stride_l, leading dimension ldl; columns >= rank
+ * exactly zero; lower triangular in pivot order, L[piv[i], j] == 0 for i < j; L L^T approximates A with no permutation, every
+ * entry within tol in exact arithmetic), piv (nbatch, m) int64 (entries >= rank are -1), rank (nbatch) int64, resid_diag (nbatch)
+ * or NULL: the largest remaining d over the free indices (0 when none is left).  tol < 0 means m * eps * max(d_0, 0).  A member
+ * whose diagonal holds a non-finite value on entry gets rank = -1 and NaN in l.  A is destroyed.  Work memory comes from the
+ * library's block cache; the call returns when the stream has completed.  Two calls give the same bits. */
+int gh_dev_pstrf(double* a, int64_t lda, int64_t stride_a, int64_t m, int32_t nbatch, double tol,
+                 double* l, int64_t ldl, int64_t stride_l, int64_t* piv, int64_t* rank, double* resid_diag, void* stream);
 /* sum_i 2*log(a[i*lda+i]) over the n diagonal entries, accumulated into *out_dev */
 int gh_dev_logdet_accum(const double* a, int64_t lda, int64_t n, double* out_dev, void* stream);
 
