@@ -158,6 +158,7 @@ SIGNATURES = {
     "gh_chol_get_inverse": (C.c_int, [_vp, _dp]),
     "gh_chol_predict": (C.c_int, [_vp, _vp, _dp, _dp, _i64, _dp, _dp, _dp]),
     "gh_chol_sample_conditional": (C.c_int, [_vp, _vp, _dp, _dp, _i64, _dp, _i64, C.c_double, _dp, _dp, _dp, _dp]),
+    "gh_chol_predict_grad": (C.c_int, [_vp, _vp, _dp, _dp, _i64, _dp, _dp, _dp, _dp]),
     "gh_chol_grad": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _dp, _dp]),
     "gh_chol_objective": (C.c_int, [_vp, _vp, _dp, _i64, _i32, _dp, _dp, _dp, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                     _dp, _dp, _dp]),

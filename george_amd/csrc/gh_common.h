@@ -141,6 +141,15 @@ int gh_launch_kgrad_reduce_loo(const gh_kernel* k, const uint32_t* which_host, c
 // gh_launch_kgrad_reduce, and of the strip form in gh_hodlr.hip)
 int gh_launch_kgrad_final(const double* partial, int64_t nblk, int P, double* grad_dev, hipStream_t st);
 
+// Input derivatives of the prediction (gh_predgrad.hip): dmu[c][d] = sum_i G_cid alpha_i and, when dvar != NULL,
+// dvar[c][d] = D_cd - 2 sum_i G_cid W[i * ldw + c], with G the x1-gradient of k at (xs_c, x_i) and D the sum of its x1- and
+// x2-gradient at (xs_c, xs_c); G is evaluated and reduced in one kernel and never stored.  Rows i >= n and columns c >= m of
+// W are not read.  partial: gh_predgrad_work_doubles(n, m, ndim, dvar != NULL) doubles.  Fixed-order sums, no atomics.
+size_t gh_predgrad_work_doubles(int64_t n, int64_t m, int ndim, bool want_var);
+int gh_launch_predgrad(const gh_kernel* k, const double* x, int64_t n, const double* xs, int64_t m, const double* alpha,
+                       const double* W /* or NULL */, int64_t ldw, double* dmu /* m*ndim */, double* dvar /* m*ndim or NULL */,
+                       double* partial, hipStream_t st);
+
 // fp64 GEMM family on the MFMA pipe:  C = beta*C + alpha * op(A) * op(B)^T-ish.  See gh_gemm.hip.
 struct GhGemm {
   double* C; int64_t ldc;

@@ -362,6 +362,59 @@ GH_HD double gh_fast_value(const GhFast& f, const double* x1, const double* x2) 
   }
 }
 
+// d k(x1, x2) / d x1 of the fast form in ND <= 3 input dimensions, into g[0 .. ND) (entries off the active axes 0): the
+// leaf's coordinate gradient as gh_leaf_xgrad forms it -- (m_i (x1_a - x2_a)) * (2 dF/dr2) -- times b, which is what the
+// interpreter's product node leaves of it (kb * 0 + b * g; the sum node adds the constant's zero gradient).  The value
+// is not formed.  x1 and g are register arrays indexed by compile-time constants only (the axis table is matched by
+// selects), so nothing here touches scratch memory; x2 may point anywhere.
+template <int ND>
+GH_HD void gh_fast_xgrad(const GhFast& f, const double (&x1)[ND], const double* x2, double (&g)[ND]) {
+  double r2 = 0.0;
+  if (f.mtype == 0) {
+    double s = 0.0;
+    for (int i = 0; i < f.naxes; ++i) {
+      const int a = f.axes[i];
+      double xa = 0.0;
+#pragma unroll
+      for (int d = 0; d < ND; ++d) xa = (a == d) ? x1[d] : xa;
+      const double dd = xa - x2[a];
+      s += dd * dd;
+    }
+    r2 = s * f.m[0];
+  } else {
+    for (int i = 0; i < f.naxes; ++i) {
+      const int a = f.axes[i];
+      double xa = 0.0;
+#pragma unroll
+      for (int d = 0; d < ND; ++d) xa = (a == d) ? x1[d] : xa;
+      const double dd = xa - x2[a];
+      r2 += dd * dd * f.m[i];
+    }
+  }
+  double rg;                                   // dF / dr2, as gh_radial<true>
+  switch (f.ktype) {
+    case GH_K_EXPSQUARED: rg = -0.5 * exp(-0.5 * r2); break;
+    case GH_K_MATERN32: rg = -3.0 * 0.5 * exp(-sqrt(3.0 * r2)); break;
+    case GH_K_MATERN52: { const double r = sqrt(5.0 * r2); rg = -5 * (1 + r) * exp(-r) / 6.0; break; }
+    case GH_K_EXP: { const double r = sqrt(r2); rg = (r2 < DBL_EPSILON) ? 0.0 : -0.5 * exp(-r) / r; break; }
+    default: rg = -0.5 * pow(1.0 + 0.5 * r2 / f.q0, -f.q0 - 1); break;       // GH_K_RATQUAD
+  }
+  const double fac = 2.0 * rg;
+#pragma unroll
+  for (int d = 0; d < ND; ++d) g[d] = 0.0;
+  for (int i = 0; i < f.naxes; ++i) {
+    const int a = f.axes[i];
+    double xa = 0.0;
+#pragma unroll
+    for (int d = 0; d < ND; ++d) xa = (a == d) ? x1[d] : xa;
+    double t = f.m[i] * (xa - x2[a]);            // (isotropic: every m[i] holds m[0], gh_fast_form)
+    t *= fac;
+    t = f.b * t;
+#pragma unroll
+    for (int d = 0; d < ND; ++d) g[d] = (a == d) ? t : g[d];
+  }
+}
+
 // Sum / Product: kernels.h:75-80, 111-116
 GH_HD double gh_eval_value(const GhNode* prog, int n_nodes, const double* x1, const double* x2) {
   GhStack st;

@@ -1049,6 +1049,86 @@ class GP(ModelSet):
         cov -= np.dot(Kxs, KinvKxs)
         return mu, cov
 
+    # -- derivatives of the prediction with respect to the test points (no reference counterpart: gp.py stops at predict) --
+    # With alpha = K^-1 r, w_c = K^-1 K(x, t_c), G_cid = d k(t_c, x_i) / d t_cd and D_cd the x1- plus x2-gradient of k at (t_c, t_c):
+    #     dmu_cd = sum_i G_cid alpha_i + d mean / d t_cd,        dvar_cd = D_cd - 2 sum_i G_cid w_ic.
+    # A solver that offers ``predict_gradient`` (the HIP BasicSolver) does it in one device call and never stores G; any other
+    # one takes the NumPy branch on ``apply_inverse``, formula for formula, in blocks of test points that keep the host
+    # tensor G under PREDICT_GRADIENT_BLOCK_ELEMENTS doubles.
+    PREDICT_GRADIENT_BLOCK_ELEMENTS = 1 << 24            # 128 MB of G per block
+
+    def _mean_gradient_at(self, xs, mean_gradient):
+        """d mean / d t at ``xs``, (M, ndim): the caller's ``mean_gradient``, or exactly 0 for a ConstantModel mean."""
+        if mean_gradient is None:
+            if isinstance(self.mean, ConstantModel):
+                return None
+            raise ValueError("the mean model {0} has no derivative with respect to its input: pass mean_gradient=, a "
+                             "callable t -> (M, ndim)".format(type(self.mean).__name__))
+        g = np.asarray(mean_gradient(self._model_arg(xs)), dtype=np.float64)
+        if g.ndim == 1 and xs.shape[1] == 1:
+            g = g[:, None]
+        if g.shape != xs.shape:
+            raise ValueError("mean_gradient must return an array of shape (M, ndim) = {0}".format(xs.shape))
+        return g
+
+    def _predict_gradient_generic(self, kernel, alpha, xs, want_var, want_value):
+        """the NumPy branch: (mu | None, var | None, dmu, dvar | None) without the mean model"""
+        x = self._x
+        m, n, nd = len(xs), len(x), xs.shape[1]
+        step = max(1, int(self.PREDICT_GRADIENT_BLOCK_ELEMENTS // max(1, max(n, 1) * nd)))
+        if want_var:                                     # D needs the (B, B, ndim) gradients of a block against itself
+            step = max(1, min(step, int(np.sqrt(self.PREDICT_GRADIENT_BLOCK_ELEMENTS / nd))))
+        mu = np.empty(m) if want_value else None
+        var = np.empty(m) if (want_value and want_var) else None
+        dmu = np.empty((m, nd))
+        dvar = np.empty((m, nd)) if want_var else None
+        for c0 in range(0, m, step):
+            tb = np.ascontiguousarray(xs[c0:c0 + step])
+            sl = slice(c0, c0 + len(tb))
+            G = np.asarray(kernel.get_x1_gradient(tb, x))                     # (B, N, ndim)
+            dmu[sl] = np.einsum("cid,i->cd", G, alpha)
+            Kxs = kernel.get_value(tb, x) if (want_value or want_var) else None
+            if want_value:
+                mu[sl] = np.dot(Kxs, alpha)
+            if want_var:
+                Wb = np.asarray(self.solver.apply_inverse(np.ascontiguousarray(Kxs.T)))      # (N, B)
+                idx = np.arange(len(tb))
+                D = (np.asarray(kernel.get_x1_gradient(tb, tb))[idx, idx] + np.asarray(kernel.get_x2_gradient(tb, tb))[idx, idx])
+                dvar[sl] = D - 2.0 * np.einsum("cid,ic->cd", G, Wb)
+                if want_value:
+                    var[sl] = kernel.get_value(tb, diag=True) - np.sum(Kxs.T * Wb, axis=0)
+        return mu, var, dmu, dvar
+
+    def predict_gradient(self, y, t, return_var=False, return_value=False, cache=True, kernel=None, mean_gradient=None):
+        """Derivatives of :meth:`predict` with respect to the test points ``t``: ``dmu`` (M, ndim); ``(dmu, dvar)`` with
+        ``return_var``; ``(mu, dmu)`` with ``return_value``; ``(mu, var, dmu, dvar)`` with both -- values and derivatives of
+        one evaluation, the shape ``scipy.optimize.minimize(..., jac=True)`` asks for.
+
+        ``mean_gradient``: a callable ``t -> (M, ndim)``, the derivative of the mean model with respect to its input (the
+        modelling protocol has none).  With ``None`` a constant mean contributes exactly 0 and any other mean model raises
+        ``ValueError``.  The mean model's value at ``t`` is added to ``mu`` as in :meth:`predict`."""
+        self.recompute()
+        xs = np.ascontiguousarray(self.parse_samples(t), dtype=np.float64)
+        if kernel is None:
+            kernel = self.kernel
+        want_var, want_value = bool(return_var), bool(return_value)
+        mg = self._mean_gradient_at(xs, mean_gradient)
+
+        if callable(getattr(self.solver, "predict_gradient", None)):
+            if cache:
+                self._compute_alpha(y, True)       # the alpha-cache semantics of predict
+            mu, var, dmu, dvar = self.solver.predict_gradient(kernel, self._residual(y), xs, return_var=want_var,
+                                                              return_value=want_value)
+        else:
+            alpha = self._compute_alpha(y, cache)
+            mu, var, dmu, dvar = self._predict_gradient_generic(kernel, alpha, xs, want_var, want_value)
+        if mg is not None:
+            dmu = dmu + mg
+        if want_value:
+            mu = mu + self._call_mean(xs)
+            return (mu, var, dmu, dvar) if want_var else (mu, dmu)
+        return (dmu, dvar) if want_var else dmu
+
     def apply_inverse(self, y):
         """K^-1 (y - mean) for a vector or an (n, K) matrix  (gp.py:277-301)."""
         self.recompute(quiet=False)

@@ -580,6 +580,31 @@ class BasicSolver(object):
         N.check(N.lib.gh_chol_predict(h, dk.handle, N.ptr(r), N.ptr(xs), m, N.ptr(mu), N.ptr(var), N.ptr(cov)))
         return mu, var, cov
 
+    def predict_gradient(self, kernel, r, xs, return_var=False, return_value=True):
+        """:meth:`predict` and its derivatives with respect to the test points for residual ``r = y - mean``
+        (gh_chol_predict_grad, one device call): returns ``(mu (M,), var | None, dmu (M, ndim), dvar | None)`` with
+        ``dmu[c, d] = sum_i G[c, i, d] alpha[i]`` and ``dvar[c, d] = D[c, d] - 2 sum_i G[c, i, d] (K^-1 K(x, xs))[i, c]``,
+        ``G = kernel.get_x1_gradient(xs, x)`` (never stored) and ``D`` the x1- plus x2-gradient of the kernel at
+        ``(xs_c, xs_c)``; ``mu`` and ``var`` are :meth:`predict`'s bit for bit, without a mean model.  ``return_value=False``
+        leaves ``mu`` and ``var`` out (``None``); without ``return_var`` too the call needs ``alpha`` only -- two sweeps instead
+        of a substitution with M right-hand sides -- and ``dmu`` has the same bits."""
+        h = self._need()
+        dk = DeviceKernel(kernel) if kernel is not self.kernel else self._dk
+        r, xs = N.as_f64(r).reshape(-1), N.as_f64(xs)
+        if len(r) != self._n:
+            raise ValueError("dimension mismatch")
+        if xs.ndim != 2 or xs.shape[1] != dk.ndim:
+            raise ValueError("xs must be (M, {0})".format(dk.ndim))
+        m = len(xs)
+        dmu = np.empty((m, dk.ndim))
+        mu = np.empty(m) if return_value else None
+        var = np.empty(m) if (return_var and return_value) else None
+        dvar = np.empty((m, dk.ndim)) if return_var else None
+        if m > 0:
+            self._retry_without_parked_memory(lambda hh: N.check(N.lib.gh_chol_predict_grad(
+                hh, dk.handle, N.ptr(r), N.ptr(xs), m, N.ptr(mu), N.ptr(var), N.ptr(dmu), N.ptr(dvar))))
+        return mu, var, dmu, dvar
+
     def sample_conditional(self, kernel, r, xs, z, tol=None, return_factor=False):
         """Posterior draws for residual ``r = y - mean`` at ``xs`` (gh_chol_sample_conditional): the mean and covariance of
         :meth:`predict`, the covariance factored on the device by a pivoted Cholesky with rank truncation (it never reaches

@@ -257,6 +257,7 @@ class HODLRSolver(BasicSolver):
     loo = None
     loo_objective = None
     remove = None                     # (GP.remove computes afresh on the kept points)
+    predict_gradient = None           # (GP.predict_gradient takes its NumPy branch on apply_inverse)
 
 
 atexit.register(HODLRSolver.release_pool)

@@ -218,6 +218,22 @@ int  gh_chol_predict(gh_chol* s, gh_kernel* k, const double* r /* n: y - mean */
 int  gh_chol_sample_conditional(gh_chol* s, gh_kernel* k, const double* r /* n: y - mean */, const double* xs, int64_t m,
                                 const double* z /* nz*m */, int64_t nz, double tol, double* mu /* m or NULL */,
                                 double* draws /* nz*m */, double* fac /* m*m or NULL */, int64_t* rank);
+/* Derivatives of the prediction with respect to the test points, on a computed handle (no lines of the reference correspond:
+ * src/george/gp.py stops at predict; the two formulas below are the definition).  With alpha = K^-1 r, k_c = K(x, xs_c),
+ * w_c = K^-1 k_c, G_cid = d k(xs_c, x_i) / d xs_cd (the evaluator's x1-gradient) and D_cd = [x1-gradient + x2-gradient]_d of k
+ * at (xs_c, xs_c) -- zero for stationary kernels, taken from the evaluator for every kernel:
+ *   dmu[c][d]  = sum_i G_cid alpha_i                      (no mean model: the caller adds its derivative)
+ *   dvar[c][d] = D_cd - 2 sum_i G_cid w_ic
+ * mu and var are gh_chol_predict's, bit for bit (the same launches).  G is evaluated and reduced in one kernel and never stored;
+ * the sums run in a fixed order (no atomics: two calls give the same bits).  mu, var and dvar may be NULL, each on its own (dvar
+ * without var is allowed); dmu may not.  Pointers may be host or device memory; the results leave in one batch of copies
+ * followed by one synchronisation, after the one of predict's forward sweep.  With dmu alone (mu, var and dvar all NULL) neither
+ * K(x, xs) nor a substitution with m right-hand sides is formed: two sweeps for alpha, the kernel, one synchronisation; dmu has
+ * the same bits either way.  Memory is that of gh_chol_predict with var (W = K^-1 K(x, xs) overwrites V = L^-1 K(x, xs) in
+ * place), counted by gh_chol_device_bytes and freed by gh_chol_trim. */
+int  gh_chol_predict_grad(gh_chol* s, gh_kernel* k, const double* r /* n: y - mean */, const double* xs, int64_t m,
+                          double* mu /* m or NULL */, double* var /* m or NULL */,
+                          double* dmu /* m*ndim */, double* dvar /* m*ndim or NULL */);
 /* alpha = K^-1 r; A = alpha alpha^T - K^-1; grad[p] = 1/2 sum_ij A_ij dK_ij/dtheta_p
  * for the parameters selected by `which` (others 0); diagA (n) = diag(A). */
 int  gh_chol_grad(gh_chol* s, gh_kernel* k, const uint32_t* which, const double* r,
