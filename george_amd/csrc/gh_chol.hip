@@ -765,6 +765,7 @@ struct gh_chol {
   GhBuf A, dinv, x, yerr, v0, v1, v2, scal, rhs, work, work2, scratch, chain;
   GhBuf A_spare;                         // the buffer the factor left when append / truncate last moved it: where the next move goes (freed by trim)
   GhBuf samp;                            // gh_chol_sample_conditional: prior diagonal, threshold and the factor / draw work arrays (freed by trim)
+  GhBuf fish;                            // gh_chol_fisher's planes (freed by trim)
   GhBuf lv;                              // gh_chol_loo's N-vectors: resid, var, lpd, sqrt(w), c, alpha, v (7 Np doubles)
   long long* d_info = nullptr;           // = (long long*)(scal + 2): the failure word lives beside the scalars (set in compute_enqueue)
   bool build_on_chain = false;           // this compute(): inputs + kernel-matrix build were enqueued on the chain stream (st2)
@@ -1009,7 +1010,7 @@ extern "C" int64_t gh_chol_device_bytes(const gh_chol* s) {
   if (!s) return 0;
   size_t tot = 0;
   for (const GhBuf* b : {&s->A, &s->A_spare, &s->dinv, &s->x, &s->yerr, &s->v0, &s->v1, &s->v2, &s->scal, &s->rhs, &s->work, &s->work2,
-                         &s->scratch, &s->chain, &s->lv, &s->samp}) tot += b->p ? b->bytes : 0;
+                         &s->scratch, &s->chain, &s->lv, &s->samp, &s->fish}) tot += b->p ? b->bytes : 0;
   return (int64_t)(tot + gh_batch_bytes(s->batch));
 }
 int gh_chol_batch_begin(gh_chol* s, hipStream_t* st, GhBatchBufs** bufs) {
@@ -2088,6 +2089,134 @@ extern "C" int gh_chol_grad(gh_chol* s, gh_kernel* k, const uint32_t* which, con
   return GH_OK;
 }
 
+// ============================================================ information of the hyper-parameters
+// (no reference counterpart.)  F_ab = 1/2 tr(K^-1 D_a K^-1 D_b) in its symmetric form: with W_a = L^-1 D_a L^-T,
+// F_ab = 1/2 sum_ij W_a[i,j] W_b[i,j].  K^-1 is never formed; work2 = L^-1, work = the intermediate T_a = L^-1 D_a (lower
+// tiles), and a plane first holds D_a, then W_a (lower tiles).  Both products are triangular in k: N^3 / 3 + N^3 / 6
+// multiply-adds per kernel parameter, N^3 / 6 per diagonal one (its T_a is a column scaling of L^-1).  Resident when every
+// plane fits, else in blocks: one block resident, every later plane formed into one scratch plane and contracted against
+// the block -- a pair's per-tile sums and their final tree are the same launches' arithmetic either way, so the bits do
+// not depend on the blocking.  DESIGN.md section 4, "Information of the hyper-parameters".
+// plane <- W of one parameter.  A kernel parameter's plane holds D already when have_d (a resident call evaluates all of them
+// in one launch: one gh_eval_grad per pair of points); a diagonal parameter (kernel_param < 0) has drow, np entries.
+static int fisher_form_plane(gh_chol* s, gh_kernel* k, int kernel_param, bool have_d, const double* drow, double* plane) {
+  const int64_t np = s->np;
+  hipStream_t st = s->st;
+  double* Linv = s->work2.d();
+  double* Tm = s->work.d();
+  if (kernel_param >= 0) {
+    if (!have_d) {
+      GhFisherSel sel{};
+      sel.n = 1; sel.idx[0] = (short)kernel_param;
+      GH_CHECK(gh_launch_fisher_planes(k, sel, s->x.d(), s->n, np, plane, st));
+    }
+    GhGemm g{};                                        // T = L^-1 D (lower tiles; L^-1 lower-triangular: k <= row)
+    g.C = Tm; g.ldc = np; g.A = Linv; g.lda = np; g.B = plane; g.ldb = np;
+    g.M = np; g.N = np; g.K = np; g.alpha = 1.0; g.beta = 0.0; g.a_km = true; g.b_km = false; g.lower = true; g.khi_row = true;
+    GH_CHECK(gh_launch_gemm(g, st));
+  } else {
+    GH_CHECK(gh_launch_fisher_scale(Linv, np, drow, Tm, st));
+  }
+  GhGemm g{};                                          // W = T L^-T (lower tiles; k <= column)
+  g.C = plane; g.ldc = np; g.A = Tm; g.lda = np; g.B = Linv; g.ldb = np;
+  g.M = np; g.N = np; g.K = np; g.alpha = 1.0; g.beta = 0.0; g.a_km = true; g.b_km = true; g.lower = true; g.khi_col = true;
+  return gh_launch_gemm(g, st);
+}
+
+extern "C" int gh_chol_fisher(gh_chol* s, gh_kernel* k, const uint32_t* which, const double* diag_rows, int32_t n_diag,
+                              int64_t max_bytes, double* fisher) {
+  GH_CHECK(need_computed(s));
+  if (!k || !fisher || n_diag < 0 || n_diag > GH_FISHER_MAX_DIAG || (n_diag > 0 && !diag_rows) || (k->size > 0 && !which)) {
+    gh_set_error("bad argument to fisher"); return GH_ERR_BAD_ARG;
+  }
+  if (k->ndim != s->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
+  GH_CHECK(k->upload());
+  const int64_t n = s->n, np = s->np;
+  hipStream_t st = s->st;
+  const int ptot = n_diag + k->size;
+  if (ptot == 0) return GH_OK;
+  // the active planes: the diagonal ones, then the selected kernel parameters
+  GhFisherMap map{};
+  int kpar[GH_MAX_GRAD + GH_FISHER_MAX_DIAG];          // kernel parameter of an active plane, -1 - p for diagonal row p
+  int Q = 0;
+  for (int p = 0; p < n_diag; ++p) { kpar[Q] = -1 - p; map.out[Q++] = (short)p; }
+  for (int p = 0; p < k->size; ++p) if (which[p]) { kpar[Q] = p; map.out[Q++] = (short)(n_diag + p); }
+  map.q = Q; map.ptot = ptot;
+  if (Q == 0) {                                        // everything masked: zeros
+    GH_CHECK(s->scratch.ensure((size_t)ptot * ptot * sizeof(double)));
+    GH_HIP(hipMemsetAsync(s->scratch.d(), 0, (size_t)ptot * ptot * sizeof(double), st));
+    GH_CHECK(gh_from_device(fisher, s->scratch.d(), (size_t)ptot * ptot, st));
+    GH_HIP(hipStreamSynchronize(st));
+    return GH_OK;
+  }
+  // how many planes beside L^-1 and T: the caller's budget and what the device can give (what the handle's own work
+  // buffers hold now is re-used)
+  const size_t pb = (size_t)np * np * sizeof(double);
+  int64_t fit = Q;
+  if (max_bytes > 0) fit = std::min<int64_t>(fit, max_bytes / (int64_t)pb - 2);
+  size_t mfree = 0, mtot = 0;
+  GH_HIP(hipMemGetInfo(&mfree, &mtot));
+  const size_t have = mfree + s->work.bytes + s->work2.bytes + s->fish.bytes + gh_pool_parked_bytes();
+  fit = std::min<int64_t>(fit, (int64_t)(have / pb) - 2);
+  if (Q > 1 && fit < 2) {
+    gh_set_error("fisher: not even two planes of %zu bytes fit beside L^-1 and the intermediate (max_bytes %lld, device %zu)",
+                 pb, (long long)max_bytes, have);
+    return GH_ERR_NOMEM;
+  }
+  if (fit < 1) { gh_set_error("fisher: no room for a plane of %zu bytes", pb); return GH_ERR_NOMEM; }
+  const bool resident = fit >= Q;
+  const int blk = resident ? Q : (int)fit - 1;         // planes of a block; blocked: one more plane is the scratch
+  const int nslots = resident ? Q : blk + 1;
+  GH_CHECK(s->work.ensure(pb));
+  GH_CHECK(s->work2.ensure(pb));
+  GH_CHECK(s->fish.ensure((size_t)nslots * pb));
+  const int64_t tm = np / T, nblk = tm * (tm + 1) / 2;
+  const int64_t npairs = (int64_t)Q * (Q + 1) / 2;
+  // scratch: [diagonal rows (n_diag np) | partial (nblk npairs) | pair sums | F (ptot^2)]
+  const size_t n_rows = (size_t)n_diag * np, n_part = (size_t)(nblk * npairs);
+  GH_CHECK(s->scratch.ensure((n_rows + n_part + (size_t)npairs + (size_t)ptot * ptot) * sizeof(double)));
+  double* drows = s->scratch.d();
+  double* partial = drows + n_rows;
+  double* pairsum = partial + n_part;
+  double* F = pairsum + npairs;
+  GH_HIP(hipMemsetAsync(F, 0, (size_t)ptot * ptot * sizeof(double), st));
+  if (n_diag > 0) {
+    GH_HIP(hipMemsetAsync(drows, 0, n_rows * sizeof(double), st));
+    GH_HIP(hipMemcpy2DAsync(drows, np * sizeof(double), diag_rows, n * sizeof(double), n * sizeof(double), n_diag,
+                            gh_is_device_ptr(diag_rows) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+  }
+  GH_CHECK(linv_into(s, s->work2.d()));
+  auto slot = [&](int i) { return s->fish.d() + (size_t)i * np * np; };
+  auto form = [&](int a, double* plane) -> int {
+    return fisher_form_plane(s, k, kpar[a], resident, kpar[a] < 0 ? drows + (size_t)(-1 - kpar[a]) * np : nullptr, plane);
+  };
+  if (resident && Q > n_diag) {                        // every kernel plane's D in one launch: the slots behind the diagonal ones
+    GhFisherSel sel{};
+    for (int a = n_diag; a < Q; ++a) sel.idx[sel.n++] = (short)kpar[a];
+    GH_CHECK(gh_launch_fisher_planes(k, sel, s->x.d(), n, np, slot(n_diag), st));
+  }
+  const double* pa[GH_MAX_GRAD + GH_FISHER_MAX_DIAG];
+  int ia[GH_MAX_GRAD + GH_FISHER_MAX_DIAG];
+  for (int b0 = 0; b0 < Q; b0 += blk) {
+    const int b1 = std::min(b0 + blk, Q);
+    for (int a = b0; a < b1; ++a) {
+      GH_CHECK(form(a, slot(a - b0)));
+      pa[a - b0] = slot(a - b0); ia[a - b0] = a;
+    }
+    GH_CHECK(gh_launch_fisher_pairs(pa, ia, b1 - b0, nullptr, nullptr, 0, Q, np, partial, st));
+    for (int c = b1; c < Q; ++c) {                     // (blocked only: a resident call has one block)
+      const double* pc = slot(blk);
+      GH_CHECK(form(c, slot(blk)));
+      GH_CHECK(gh_launch_fisher_pairs(pa, ia, b1 - b0, &pc, &c, 1, Q, np, partial, st));
+    }
+  }
+  GH_CHECK(gh_launch_kgrad_final(partial, nblk, (int)npairs, pairsum, st));
+  GH_CHECK(gh_launch_fisher_mirror(pairsum, map, F, st));
+  GH_CHECK(gh_from_device(fisher, F, (size_t)ptot * ptot, st));
+  GH_HIP(hipStreamSynchronize(st));
+  return GH_OK;
+}
+
 // ============================================================ fused objective
 // nll and its gradient (gp.py:470-480; the optimiser loop of docs/tutorials/hyper.rst:131-152) as
 // ONE call: build K -> factor -> log-det -> z = L^-1 r (used for r^T K^-1 r = |z|^2 AND, through
@@ -2346,7 +2475,7 @@ extern "C" void gh_chol_release_buffers(gh_chol* s) {
   (void)hipSetDevice(s->opts.device);
   if (s->st) (void)hipStreamSynchronize(s->st);
   s->computed = false;
-  for (GhBuf* b : {&s->A, &s->A_spare, &s->dinv, &s->x, &s->yerr, &s->v0, &s->v1, &s->v2, &s->rhs, &s->work, &s->work2, &s->scratch, &s->chain, &s->lv, &s->samp}) b->release();
+  for (GhBuf* b : {&s->A, &s->A_spare, &s->dinv, &s->x, &s->yerr, &s->v0, &s->v1, &s->v2, &s->rhs, &s->work, &s->work2, &s->scratch, &s->chain, &s->lv, &s->samp, &s->fish}) b->release();
   gh_batch_free(s->batch);
   s->batch = nullptr;
 }
@@ -2355,7 +2484,7 @@ extern "C" void gh_chol_trim(gh_chol* s) {
   if (!s) return;
   (void)hipSetDevice(s->opts.device);
   if (s->st) (void)hipStreamSynchronize(s->st);
-  for (GhBuf* b : {&s->rhs, &s->work, &s->work2, &s->scratch, &s->A_spare, &s->samp}) b->release();
+  for (GhBuf* b : {&s->rhs, &s->work, &s->work2, &s->scratch, &s->A_spare, &s->samp, &s->fish}) b->release();
   gh_batch_free(s->batch);
   s->batch = nullptr;
 }

@@ -150,7 +150,34 @@ int gh_launch_predgrad(const gh_kernel* k, const double* x, int64_t n, const dou
                        const double* W /* or NULL */, int64_t ldw, double* dmu /* m*ndim */, double* dvar /* m*ndim or NULL */,
                        double* partial, hipStream_t st);
 
-// fp64 GEMM family on the MFMA pipe:  C = beta*C + alpha * op(A) * op(B)^T-ish.  See gh_gemm.hip.
+// The pieces of gh_chol_fisher (gh_fisher.hip).  A "plane" is a dense np x np matrix of pitch np, np a multiple of 128.
+#define GH_FISHER_GROUP 4                   // planes per side of one contraction launch (4 x 4 pairs from registers)
+#define GH_FISHER_MAX_DIAG 64               // diagonal parameters of one call
+struct GhFisherSel { int n; short idx[GH_MAX_GRAD]; };                          // kernel parameters to store, plane s = idx[s]
+struct GhFisherMap { int q, ptot; short out[GH_MAX_GRAD + GH_FISHER_MAX_DIAG]; };   // active plane -> row / column of the result
+struct GhFisherPairs {
+  const double* a[GH_FISHER_GROUP]; const double* b[GH_FISHER_GROUP];
+  int na, nb, same;                         // same: the b side IS the a side (b is not read); pairs i <= j only
+  int col[GH_FISHER_GROUP * GH_FISHER_GROUP];   // column of partial for the pair (a[i], b[j]), -1: not wanted
+  long ld, ncols;
+  double* partial;                          // (number of lower 128-tiles) x ncols
+};
+// column of the pair a <= b among q active planes (upper triangle by rows)
+static inline __host__ __device__ int gh_fisher_pair(int a, int b, int q) { return a * q - a * (a - 1) / 2 + (b - a); }
+// planes[s] (s < sel.n) = dK/dtheta_{sel.idx[s]} over the n points x, zero in rows and columns >= n
+int gh_launch_fisher_planes(const gh_kernel* k, const GhFisherSel& sel, const double* x, int64_t n, int64_t np, double* planes,
+                            hipStream_t st);
+// out = linv diag(d): d has np entries, zero from n on
+int gh_launch_fisher_scale(const double* linv, int64_t np, const double* d, double* out, hipStream_t st);
+// partial[tile][pair(a_idx[i], b_idx[j])] = the weighted lower-triangle sum of a[i] .* b[j] over the tile, for every i, j
+// (b == nullptr: the set a with itself, pairs i <= j), in launches of GH_FISHER_GROUP x GH_FISHER_GROUP pairs.  a_idx / b_idx:
+// the planes' indices among the q_active active ones (host arrays).
+int gh_launch_fisher_pairs(const double* const* a, const int* a_idx, int na, const double* const* b, const int* b_idx, int nb,
+                           int q_active, int64_t np, double* partial, hipStream_t st);
+// F (ptot x ptot, zeroed by the caller) <- the pair sums, mirrored
+int gh_launch_fisher_mirror(const double* pairsum, const GhFisherMap& m, double* F, hipStream_t st);
+
+// fp64 GEMM family on the MFMA pipe: C = beta*C + alpha * op(A) * op(B)^T-ish.  See gh_gemm.hip.
 struct GhGemm {
   double* C; int64_t ldc;
   const double* A; int64_t lda;   // a_km: A(m,k) at A[m*lda + k];  else at A[k*lda + m]

@@ -601,6 +601,69 @@ class GP(ModelSet):
             return bad
         return -L, -self._assemble_loo_grad(v, diagB, kgrad, quiet)
 
+    # -- expected information of the hyper-parameters ---------------------------------------------
+    # (no reference counterpart.)  For the Gaussian likelihood the expected (Fisher) information is
+    #   F_ab = 1/2 tr(K^-1 dK/dtheta_a K^-1 dK/dtheta_b)      white-noise and kernel parameters
+    #   F_mn = (d mean / d m)^T K^-1 (d mean / d n)           mean parameters; their cross block with the others is exactly 0
+    # It needs no y and is positive semidefinite by construction.  A solver that offers ``fisher`` (the HIP BasicSolver)
+    # keeps the derivative matrices and every N^3 product on the device; any other one with ``get_inverse`` takes the NumPy
+    # branch, formula for formula.
+    def fisher_information(self):
+        """The expected (Fisher) information of the unfrozen parameters at their current values, ``(len(gp), len(gp))``,
+        ordered mean | white_noise | kernel like :meth:`grad_log_likelihood`.  It does not depend on ``y``.  Its inverse is
+        :meth:`parameter_covariance`; small eigenvalues are directions the data cannot separate.  For a kernel with a general
+        (full-matrix) metric the parameter derivatives are the reference's, not the derivatives of the value (DESIGN.md
+        section 9, "Known discrepancy"), and the information inherits that; isotropic and axis-aligned metrics are right."""
+        self.recompute()
+        n_m, n_wn, n_k = len(self.mean), len(self.white_noise), len(self.kernel)
+        F = np.zeros((len(self), len(self)))
+        if n_m:
+            mg = np.ascontiguousarray(np.atleast_2d(self._call_mean_gradient(self._x)), dtype=np.float64)
+            Fm = np.dot(mg, np.asarray(self.solver.apply_inverse(np.array(mg.T, dtype=np.float64, order="C"))))
+            F[:n_m, :n_m] = 0.5 * (Fm + Fm.T)
+        if not (n_wn or n_k):
+            return F
+        rows = None
+        if n_wn:
+            wn = self._call_white_noise(self._x)
+            wng = np.atleast_2d(self._call_white_noise_gradient(self._x))
+            rows = np.ascontiguousarray(np.exp(wn)[None, :] * wng, dtype=np.float64)
+        if callable(getattr(self.solver, "fisher", None)):
+            mask = self.kernel.unfrozen_mask
+            full = self.solver.fisher(mask.astype(np.uint32), rows)
+            keep = np.concatenate([np.arange(n_wn), n_wn + np.flatnonzero(mask)]).astype(int)
+            F[n_m:, n_m:] = full[np.ix_(keep, keep)]
+            return F
+        Kinv = np.asarray(self.solver.get_inverse())
+        M = [Kinv * rows[p][None, :] for p in range(n_wn)]
+        if n_k:
+            G = self.kernel.get_gradient(self._x)
+            M += [np.dot(Kinv, G[:, :, p]) for p in range(n_k)]
+        M = np.stack(M)
+        Fk = 0.5 * np.einsum("aij,bji->ab", M, M)
+        F[n_m:, n_m:] = 0.5 * (Fk + Fk.T)
+        return F
+
+    def parameter_covariance(self):
+        """The inverse of :meth:`fisher_information`: the Cramer-Rao bound on the covariance of any unbiased estimate of the
+        unfrozen parameters, evaluated AT THE CURRENT parameters -- the asymptotic covariance of a maximum-likelihood fit
+        when they are its optimum.  It is not a posterior: no prior enters and nothing is integrated over.  Computed by a
+        Cholesky factor of the information scaled to unit diagonal; ``numpy.linalg.LinAlgError`` when it is singular -- a
+        parameter the data cannot identify: a zero diagonal entry, or a pivot of the scaled matrix at or below
+        ``len(gp) * eps**0.75``, which is below the accuracy the information itself is computed with."""
+        F = self.fisher_information()
+        if not len(F):
+            return F
+        d = np.sqrt(np.diag(F))
+        if not np.all(np.isfinite(F)) or np.any(d <= 0.0):
+            raise np.linalg.LinAlgError("the information matrix is singular: a parameter with no information")
+        L = np.linalg.cholesky(F / np.outer(d, d))
+        if np.min(np.diag(L)) ** 2 <= len(F) * np.finfo(np.float64).eps ** 0.75:
+            raise np.linalg.LinAlgError("the information matrix is singular to working precision")
+        Li = np.linalg.solve(L, np.eye(len(F)))
+        C = np.dot(Li.T, Li) / np.outer(d, d)
+        return 0.5 * (C + C.T)
+
     # -- ensembles (emcee ``vectorize=True``) ------------------------------------------------------
     def log_likelihood_batch(self, vectors, y, quiet=True):
         """``log_likelihood(y, quiet)`` at each row of ``vectors`` (shape ``(B, len(gp))``, ``get_parameter_vector()``

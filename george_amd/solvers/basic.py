@@ -703,6 +703,54 @@ class BasicSolver(object):
         self.computed = True
         return logdet.value, total.value, resid, var, (g[:self._dk.size] if g is not None else None), v, diagB
 
+    # -- expected information of the hyper-parameters (no reference counterpart)
+    # The default budget of fisher().  Nobody has measured a good value: it stands on what _POOL_MAX_BYTES already assumes
+    # about the card -- that solver handles may hold that much of it, work arrays included.  The planes belong to the handle
+    # and are parked with it; a call that grew them beyond this would only have its handle trimmed or destroyed at the next
+    # park.  Blocking only ever adds products (every plane behind a block is formed again for it), so a larger budget is
+    # only ever faster.
+    FISHER_MAX_BYTES = _POOL_MAX_BYTES
+
+    @staticmethod
+    def fisher_bytes(n, n_planes):
+        """Device bytes of :meth:`fisher` with ``n_planes`` derivative planes resident beside L^-1 and the intermediate
+        product: ``(2 + n_planes) * 8 * Np^2``, Np = n rounded up to 128.  As ``max_bytes`` it makes the call keep exactly
+        that many planes (a block of ``n_planes - 1`` and one scratch plane when there are more parameters)."""
+        np_ = -(-n // 128) * 128
+        return (2 + int(n_planes)) * 8 * np_ * np_
+
+    def fisher(self, which=None, diag_rows=None, max_bytes=None):
+        """Expected (Fisher) information ``F[a, b] = 1/2 tr(K^-1 D_a K^-1 D_b)`` of the computed factor (gh_chol_fisher):
+        ``(n_diag + size, n_diag + size)`` over the ``n_diag`` diagonal derivative matrices ``diag(diag_rows[p])`` followed by
+        ALL kernel parameters (those masked out by ``which`` have rows and columns of exactly 0; ``which=None``: all of
+        them).  ``max_bytes`` (default ``FISHER_MAX_BYTES``) bounds the call's work arrays (:meth:`fisher_bytes`); the result
+        has the same bits for every budget the call accepts and ``MemoryError`` is raised when not even two planes fit."""
+        h = self._need()
+        size = self._dk.size
+        wh = np.ones(max(size, 1), dtype=np.uint32)
+        if which is not None:
+            which = np.asarray(which)
+            if which.shape != (size,):
+                raise ValueError("which must have shape ({0},)".format(size))
+            wh[:size] = which != 0
+        rows = None
+        n_diag = 0
+        if diag_rows is not None:
+            rows = N.as_f64(diag_rows)
+            if rows.ndim != 2 or rows.shape[1] != self._n:
+                raise ValueError("diag_rows must be (n_diag, {0})".format(self._n))
+            n_diag = rows.shape[0]
+            if n_diag > 64:
+                raise ValueError("at most 64 diagonal parameters")
+        p = n_diag + size
+        out = np.zeros((p, p))
+        if p == 0:
+            return out
+        budget = int(self.FISHER_MAX_BYTES if max_bytes is None else max_bytes)
+        self._retry_without_parked_memory(lambda hh: N.check(N.lib.gh_chol_fisher(
+            hh, self._dk.handle, N.ptr(wh), N.ptr(rows) if n_diag else None, n_diag, budget, N.ptr(out))))
+        return out
+
     def profile(self):
         p = N.gh_chol_profile()
         N.check(N.lib.gh_chol_get_profile(self._need(), C.byref(p)))

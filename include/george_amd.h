@@ -268,6 +268,27 @@ int  gh_chol_loo(gh_chol* s, gh_kernel* k, const uint32_t* which /* NULL: no gra
 int  gh_chol_loo_objective(gh_chol* s, gh_kernel* k, const double* x, int64_t n, int32_t ndim, const double* yerr,
                            const double* r, const uint32_t* which, double* logdet, double* lpd_sum,
                            double* resid, double* var, double* grad, double* v, double* diagB);
+/* Expected (Fisher) information of the hyper-parameters on a computed handle (no reference lines correspond: src/george/gp.py
+ * stops at the gradient; GPML eq. 5.9 differentiated once more and averaged over y ~ N(0, K)):
+ *   fisher[a][b] = 1/2 tr(K^-1 D_a K^-1 D_b),    (n_diag + size)^2 doubles, row-major, symmetric bit for bit.
+ * The "parameters" are, in this order, the n_diag DIAGONAL derivative matrices D_p = diag(diag_rows[p]) -- how a white-noise
+ * model enters: dK/dtheta_p = diag(exp(wn(x)) dwn_p(x)) -- and the kernel's `size` parameters, D = dK/dtheta from the evaluator;
+ * those masked out by `which` have rows and columns of exactly 0.  It does not depend on y.  n_diag <= 64.
+ * Formed as W_a = L^-1 D_a L^-T (two triangular GEMMs per kernel parameter, one per diagonal one; K^-1 is not formed) and
+ * fisher[a][b] = 1/2 sum_ij W_a[i][j] W_b[i][j] over dense planes of 8 Np^2 bytes (Np = n rounded up to 128), contracted in
+ * fixed-order sums (no atomics: two calls give the same bits).
+ * Memory: L^-1, one intermediate and the planes.  max_bytes > 0 bounds these (2 + planes) * 8 Np^2 bytes; <= 0: no limit of
+ * its own.  When every active plane fits (the budget, and what the device can allocate) they are resident at once; otherwise
+ * the call works in blocks -- (planes that fit) - 1 resident, every later plane formed again into the remaining one for every
+ * block -- and the result has the same bits for every max_bytes the call accepts.  When not even two planes fit: GH_ERR_NOMEM.
+ * The factor is not modified and on any failure the handle keeps its factor, size, info and log-determinant.  Pointers may be
+ * host or device memory.  Everything runs on the handle's main stream with one synchronisation at the end; the buffers are
+ * counted by gh_chol_device_bytes and freed by gh_chol_trim.  For a general (full-matrix) metric the evaluator's
+ * parameter-gradient entries are the reference's, and the information inherits them. */
+int  gh_chol_fisher(gh_chol* s, gh_kernel* k, const uint32_t* which /* size */,
+                    const double* diag_rows /* (n_diag, n) or NULL */, int32_t n_diag,
+                    int64_t max_bytes /* <= 0: no limit of its own */,
+                    double* fisher /* (n_diag + size)^2, row-major */);
 /* B independent problems that share the points x (n, ndim) and the kernel's STRUCTURE, each with its own parameters, error bars
  * and residual (B rounds of compute gp.py:303-337 + log_likelihood :369-397, one device call):
  *   K_b = k(params_b)(x, x) + diag(yerr_b^2);  logdet[b] = log|K_b|;  quad[b] = r_b^T K_b^-1 r_b;
