@@ -14,21 +14,13 @@
 //        update(gemm): remaining panel columns -= ...          (MFMA)
 //     trailing SYRK   : A22 -= L21 L21^T, K = NB, lower tiles  (MFMA; >95 % of the flops)
 //
-// Solves are blocked substitutions that multiply by the stored 128x128 diagonal
-// inverses: TRSV kernels for one right-hand side, the same MFMA GEMM for many.
+// This unit is the factorisation: the handle, the process-wide streams, the tile operations, the panel schedules and
+// compute().  What is done with a computed factor is in gh_chol_solve.hip, what moves or edits one in gh_chol_update.hip
+// (gh_chol_impl.h).
 #include <math.h>
-#include <string.h>
-#include <algorithm>
 #include <chrono>
-#include "gh_common.h"
-#include "gh_device_util.h"
-#include "gh_spin.h"
-#include "gh_chol_plan.h"
-#include "gh_gemm_tile.h"
+#include "gh_chol_impl.h"
 #include "../../include/george_amd_debug.h"
-
-#define T 128                 // tile edge
-#define LP 129                // LDS row pitch of the potf2 tile (odd -> conflict-free columns)
 
 // ============================================================= potf2 + inverse
 // One workgroup factorises a 128x128 block held entirely in LDS (129 KiB) and
@@ -107,703 +99,6 @@ __global__ __launch_bounds__(256) void potf2_inv_kernel(double* A, long lda, dou
     dinv[idx] = v;
   }
 }
-
-// ================================================================= reductions  (wave_sum, block_sum_256: gh_device_util.h)
-
-// out[0] (+)= 2 * sum_i log(A[i][i])   (basic.py:69); one workgroup, fixed order
-__global__ __launch_bounds__(256) void logdet_kernel(const double* A, long lda, long n, double* out, int accumulate) {
-  __shared__ double sh[4];
-  double v = 0.0;
-  for (long i = threadIdx.x; i < n; i += 256) v += log(A[i * lda + i]);
-  v = block_sum_256(v, sh);
-  if (threadIdx.x == 0) out[0] = (accumulate ? out[0] : 0.0) + 2.0 * v;
-}
-// out[0] = sum_i a[i] * b[i]
-// (fail != nullptr: the chained solve's time-out flag travels with the result, out[2] = flag: one copy back instead of two)
-__global__ __launch_bounds__(256) void dot_kernel(const double* a, const double* b, long n, double* out, const int* fail) {
-  __shared__ double sh[4];
-  double v = 0.0;
-  for (long i = threadIdx.x; i < n; i += 256) v += a[i] * b[i];
-  v = block_sum_256(v, sh);
-  if (threadIdx.x == 0) { out[0] = v; if (fail) out[2] = (double)*fail; }
-}
-
-// Two-stage versions for long vectors: `part[g]` = the g-th contiguous slice, then one workgroup adds
-// the slices in index order (fixed order: bitwise reproducible).  One workgroup walking 65536
-// diagonal entries, each in its own cache line, took 195 us; the dot product 97 us.
-__global__ __launch_bounds__(256) void logdet_part_kernel(const double* A, long lda, long n, double* part) {
-  __shared__ double sh[4];
-  const long per = (n + gridDim.x - 1) / gridDim.x;
-  const long lo = (long)blockIdx.x * per, hi = lo + per < n ? lo + per : n;
-  double v = 0.0;
-  for (long i = lo + threadIdx.x; i < hi; i += 256) v += log(A[i * lda + i]);
-  v = block_sum_256(v, sh);
-  if (threadIdx.x == 0) part[blockIdx.x] = v;
-}
-__global__ __launch_bounds__(256) void dot_part_kernel(const double* a, const double* b, long n, double* part) {
-  __shared__ double sh[4];
-  const long per = (n + gridDim.x - 1) / gridDim.x;
-  const long lo = (long)blockIdx.x * per, hi = lo + per < n ? lo + per : n;
-  double v = 0.0;
-  for (long i = lo + threadIdx.x; i < hi; i += 256) v += a[i] * b[i];
-  v = block_sum_256(v, sh);
-  if (threadIdx.x == 0) part[blockIdx.x] = v;
-}
-// out[0] (+)= scale * sum_{g < m} part[g], m <= 64, added in index order by one lane
-__global__ void reduce_final_kernel(const double* part, int m, double scale, double* out, int accumulate, const int* fail) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  double v = 0.0;
-  for (int g = 0; g < m; ++g) v += part[g];
-  out[0] = (accumulate ? out[0] : 0.0) + scale * v;
-  if (fail) out[2] = (double)*fail;
-}
-#define RED_SLICES 64
-static int launch_logdet(const double* A, long lda, long n, double* out, double* part, hipStream_t st) {
-  const int g = (int)std::min<long>(RED_SLICES, (n + 2047) / 2048);
-  if (g <= 1) {
-    hipLaunchKernelGGL(logdet_kernel, dim3(1), dim3(256), 0, st, A, lda, n, out, 0);
-  } else {
-    hipLaunchKernelGGL(logdet_part_kernel, dim3(g), dim3(256), 0, st, A, lda, n, part);
-    hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(64), 0, st, part, g, 2.0, out, 0, (const int*)nullptr);
-  }
-  GH_HIP(hipGetLastError());
-  return GH_OK;
-}
-static int launch_dot(const double* a, const double* b, long n, double* out, double* part, hipStream_t st, const int* fail = nullptr) {
-  const int g = (int)std::min<long>(RED_SLICES, (n + 4095) / 4096);
-  if (g <= 1) {
-    hipLaunchKernelGGL(dot_kernel, dim3(1), dim3(256), 0, st, a, b, n, out, fail);
-  } else {
-    hipLaunchKernelGGL(dot_part_kernel, dim3(g), dim3(256), 0, st, a, b, n, part);
-    hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(64), 0, st, part, g, 1.0, out, 0, fail);
-  }
-  GH_HIP(hipGetLastError());
-  return GH_OK;
-}
-
-// ======================================================== single-RHS solves
-// Forward step j of L z = y (right-looking).  Every workgroup recomputes
-// z_j = L_jj^-1 w_j from the current working vector w (128x128 mat-vec from L2), workgroup 0
-// publishes it into z, workgroups b >= 1 update their 128 rows: w[i] -= L[i, jblock] . z_j.
-__global__ __launch_bounds__(256) void trsv_fwd_step(const double* L, long ld, const double* dinv_j,
-                                                     long j0, double* w, double* z) {
-  __shared__ double zj[T];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const double2 wv = *reinterpret_cast<const double2*>(w + j0 + 2 * lane);
-  // 8 rows per trip: all eight 1-KiB row loads are in flight before the first reduction
-  // (one load per trip left this kernel latency-bound: 52 us per step at N = 16384)
-  for (int r0 = wave * 8; r0 < T; r0 += 32) {
-    double2 a[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) a[q] = *reinterpret_cast<const double2*>(dinv_j + (r0 + q) * T + 2 * lane);
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const double v = wave_sum(a[q].x * wv.x + a[q].y * wv.y);
-      if (lane == 0) zj[r0 + q] = v;
-    }
-  }
-  __syncthreads();
-  if (blockIdx.x == 0) {
-    if (tid < T) z[j0 + tid] = zj[tid];
-    return;
-  }
-  const long row0 = j0 + (long)blockIdx.x * T;
-  const double zx = zj[2 * lane], zy = zj[2 * lane + 1];
-  for (int r0 = wave * 8; r0 < T; r0 += 32) {
-    double2 a[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) a[q] = *reinterpret_cast<const double2*>(L + (row0 + r0 + q) * ld + j0 + 2 * lane);
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const double v = wave_sum(a[q].x * zx + a[q].y * zy);
-      if (lane == 0) w[row0 + r0 + q] -= v;
-    }
-  }
-}
-// The whole forward sweep L z = y as ONE launch: workgroup b owns block row b.  It walks the blocks
-// L[b, 0..b-1] left to right, folding each z_j into per-lane partial sums as soon as workgroup j
-// has published it, then solves its own diagonal block with the stored inverse and publishes z_b.
-// The step-per-launch version above costs a launch gap plus two dependent 128x128 mat-vecs per block
-// row (25-27 us, 14.3 ms at N = 65536 against 2.2 ms of HBM time for the triangle); here a link of the
-// chain is  z_j seen -> 128 FMAs per lane -> reduce -> one mat-vec -> store,  and the L blocks of a
-// row stream in ahead of the wait (the next block is loaded into registers before it).  512 threads:
-// wavefront w takes rows 16w..16w+15, a lane two columns.  Deadlock freedom: workgroup b only waits
-// for workgroups j < b, and a 1-D grid is dispatched in blockIdx order, so whatever it waits for is
-// resident or finished (the grid need not fit the chip).  A wait that outlasts ~2 s raises *fail
-// instead of hanging.
-//
-// z ITSELF IS THE MESSAGE (round 3; the flag-per-block-row predecessor, 10.7 us per link, is
-// scripts/dev/arms/trsv_chain_flags.hip.inc).  z is pre-filled with a sentinel (all bits set: a NaN no
-// arithmetic produces), workgroup j publishes its 128 values as agent-scope atomic stores (write-through
-// past its XCD's L2; no fences: a release/acquire pair costs an L2 write-back on one side and an
-// invalidate on the other at every link -- chain neighbours sit on different XCDs -- 16-29 us measured),
-// and a consumer's first wavefront polls those 128 values directly -- lane l its two -- until none is
-// the sentinel, then hands them to the other wavefronts through LDS.  Against the flag version a link
-// loses one L2 round trip (flag seen -> THEN z fetched), the producer's s_waitcnt + barrier + flag
-// store, the sixteen one-lane stores of a wavefront (now one 128-byte store from lanes 0-15) and 5/6 of
-// its cross-lane traffic: the 16 row sums of a wavefront are formed by a transposing butterfly (8 + 4 +
-// 2 + 1 exchanges inside a row of 16 lanes, then 2 across rows: 17 instead of 96), which leaves row q's
-// total in lane q; y is fetched before the loop (it was a dependent load on the critical path).
-// Measured: 3.4 us per link; the solve part of compute()+log_likelihood() 0.68 -> 0.22 ms at N = 8192,
-// apply_inverse(y) 9.0 -> 6.6 ms at N = 65536 (two sweeps over 17 GB: 5.2 TB/s, 0.65 of HBM; was 0.39).
-#define CHAIN_THREADS 512
-__device__ __forceinline__ double2 ld_coherent2(const double* p) {
-  double2 v;
-  v.x = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  v.y = __hip_atomic_load(p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  return v;
-}
-#define CHAIN_SENTINEL 0xFFFFFFFFFFFFFFFFull
-__device__ __forceinline__ bool chain_ready(double v) { return (unsigned long long)__double_as_longlong(v) != CHAIN_SENTINEL; }
-// v[0..15] per lane -> returns, in lane l, the sum over all 64 lanes of v[l & 15]
-__device__ __forceinline__ double transpose_sum16(double (&v)[16], int lane) {
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const bool up = (lane & 8) != 0;
-    const double keep = up ? v[i + 8] : v[i], send = up ? v[i] : v[i + 8];
-    v[i] = keep + __shfl_xor(send, 8, 64);
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const bool up = (lane & 4) != 0;
-    const double keep = up ? v[i + 4] : v[i], send = up ? v[i] : v[i + 4];
-    v[i] = keep + __shfl_xor(send, 4, 64);
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const bool up = (lane & 2) != 0;
-    const double keep = up ? v[i + 2] : v[i], send = up ? v[i] : v[i + 2];
-    v[i] = keep + __shfl_xor(send, 2, 64);
-  }
-  {
-    const bool up = (lane & 1) != 0;
-    const double keep = up ? v[1] : v[0], send = up ? v[0] : v[1];
-    v[0] = keep + __shfl_xor(send, 1, 64);
-  }
-  double t = v[0];
-  t += __shfl_xor(t, 16, 64);
-  t += __shfl_xor(t, 32, 64);
-  return t;
-}
-// The two arithmetic steps of a link, per right-hand side: shared by trsv_fwd_chain_direct and trsv_fwd_chain_multi, so that
-// the compiler contracts them into the same multiply-adds in both (gh_chol_append's paths 1 and 2 give the same bits).
-// acc[q] += (row q of the block) . z_j, this lane's two columns
-__device__ __forceinline__ void chain_fold16(double (&acc)[16], const double2 (&blk)[16], const double2 zj) {
-#pragma unroll
-  for (int q = 0; q < 16; ++q) acc[q] += blk[q].x * zj.x + blk[q].y * zj.y;
-}
-// an empty statement that reads the sixteen sums and may touch memory: arithmetic on them stays in front of it, loads behind it
-__device__ __forceinline__ void chain_pin16(double (&a)[16]) {
-  asm volatile("" : : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]), "v"(a[6]), "v"(a[7]), "v"(a[8]), "v"(a[9]),
-               "v"(a[10]), "v"(a[11]), "v"(a[12]), "v"(a[13]), "v"(a[14]), "v"(a[15]) : "memory");
-}
-// acc[q] = (row q of the diagonal block's inverse) . w, this lane's two columns
-__device__ __forceinline__ void chain_rows16(double (&acc)[16], const double2 (&dv)[16], const double wx, const double wy) {
-#pragma unroll
-  for (int q = 0; q < 16; ++q) acc[q] = dv[q].x * wx + dv[q].y * wy;
-}
-__global__ __launch_bounds__(CHAIN_THREADS) void trsv_fwd_chain_direct(const double* L, long ld, const double* dinv,
-                                                                       const double* y, double* z, int* fail) {
-  __shared__ double zs[2][T];
-  __shared__ double ws[T];
-  __shared__ int gave_up;
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long row0 = (long)b * T + wave * 16;
-  double acc[16];
-  double2 dv[16], blk[16];
-  if (tid == 0) gave_up = 0;
-  const double yv = y[row0 + (lane & 15)];
-#pragma unroll
-  for (int q = 0; q < 16; ++q) {
-    acc[q] = 0.0;
-    dv[q] = *reinterpret_cast<const double2*>(dinv + (long)b * T * T + (wave * 16 + q) * T + 2 * lane);
-  }
-  if (b > 0) {
-#pragma unroll
-    for (int q = 0; q < 16; ++q) blk[q] = *reinterpret_cast<const double2*>(L + (row0 + q) * ld + 2 * lane);
-  }
-  __syncthreads();
-  for (int j = 0; j < b; ++j) {
-    if (wave == 0) {
-      // The further from the front of the chain, the more patiently: a waiting workgroup first probes ONE value with one
-      // lane (one request; every waiting workgroup hammering all 128 was the L2 queue as the critical path), and only the
-      // next two in line poll the whole block at once.
-      const int dist = b - j;
-      GhSpin spin(fail);                                  // (gh_spin.h: the 2-s give-up and the abort word)
-      bool ok = true;
-      if (dist > 2) {
-        while (!chain_ready(__hip_atomic_load(z + (long)j * T, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-          for (int q = dist > 64 ? 16 : dist >> 2; q > 0; --q) __builtin_amdgcn_s_sleep(8);   // 0 .. 8k cycles
-          if (!spin.keep_waiting(63u)) { ok = false; break; }
-        }
-      }
-      double2 zj = ld_coherent2(z + (long)j * T + 2 * lane);
-      while (ok && !__all(chain_ready(zj.x) && chain_ready(zj.y))) {
-        if (!spin.keep_waiting(1023u)) { ok = false; break; }
-        zj = ld_coherent2(z + (long)j * T + 2 * lane);
-      }
-      if (!ok && lane == 0) gave_up = 1;
-      *reinterpret_cast<double2*>(&zs[j & 1][2 * lane]) = zj;
-    }
-    __syncthreads();
-    if (gave_up) break;
-    const double2 zj = *reinterpret_cast<const double2*>(&zs[j & 1][2 * lane]);
-    chain_fold16(acc, blk, zj);
-    if (j + 1 < b) {
-#pragma unroll
-      for (int q = 0; q < 16; ++q)
-        blk[q] = *reinterpret_cast<const double2*>(L + (row0 + q) * ld + (long)(j + 1) * T + 2 * lane);
-    }
-  }
-  // (after a time-out the values published are garbage but NOT the sentinel: the workgroups behind come through, the
-  //  host sees *fail)
-  const double tot = transpose_sum16(acc, lane);
-  if (lane < 16) ws[wave * 16 + lane] = yv - tot;
-  __syncthreads();
-  const double wx = ws[2 * lane], wy = ws[2 * lane + 1];
-  chain_rows16(acc, dv, wx, wy);
-  double v = transpose_sum16(acc, lane);
-  if (!chain_ready(v)) v = __longlong_as_double(0x7FF8000000000000LL);      // (a NaN with every bit set must not look unpublished)
-  if (lane < 16) __hip_atomic_store(z + row0 + lane, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// The same sweep for R right-hand sides in one launch (gh_chol_append: R new rows of the factor against its full tiles): the
-// factor is read ONCE for all of them.  Same protocol -- the outputs are pre-filled with the sentinel and are the message,
-// agent-scope relaxed atomics and no fences, the patient probing by distance (on the first right-hand side), GhSpin -- and,
-// per right-hand side, the same operation sequence through chain_fold16 / transpose_sum16 / chain_rows16: the bits of R runs
-// of trsv_fwd_chain_direct.  y: R vectors ldy apart, read only, no alias of z; z: R vectors ldz apart.
-// Registers at 512 threads (256 per lane): acc[R][16] is 32 R, blk 64; the diagonal block's inverse (64 more) would not fit
-// beside them at R = 4, so it waits in LDS (128 KiB; a wavefront stages and reads back its own 16 rows) until blk is dead.
-template <int R>
-__global__ __launch_bounds__(CHAIN_THREADS) void trsv_fwd_chain_multi(const double* L, long ld, const double* dinv,
-                                                                      const double* y, long ldy, double* z, long ldz, int* fail) {
-  __shared__ double zs[2][R][T];
-  __shared__ double ws[R][T];
-  __shared__ double dls[T * T];
-  __shared__ int gave_up;
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (wave-uniform row addresses: scalar bases, not sixteen 64-bit vector pointers)
-  const long row0 = (long)b * T + wave * 16;
-  double acc[R][16];
-  double2 blk[16];
-  if (tid == 0) gave_up = 0;
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    if (lane < 16) ws[r][wave * 16 + lane] = y[r * ldy + row0 + lane];      // (waits in LDS: R registers fewer across the loop)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc[r][q] = 0.0;
-  }
-#pragma unroll
-  for (int q = 0; q < 16; ++q)
-    *reinterpret_cast<double2*>(&dls[(wave * 16 + q) * T + 2 * lane]) =
-        *reinterpret_cast<const double2*>(dinv + (long)b * T * T + (wave * 16 + q) * T + 2 * lane);
-  __builtin_amdgcn_sched_barrier(0);                      // (staged before the first block is asked for: its 64 registers are free again)
-  if (b > 0) {
-#pragma unroll
-    for (int q = 0; q < 16; ++q) blk[q] = *reinterpret_cast<const double2*>(L + (row0 + q) * ld + 2 * lane);
-  }
-  __syncthreads();
-  for (int j = 0; j < b; ++j) {
-    if (wave == 0) {
-      const int dist = b - j;
-      GhSpin spin(fail);
-      bool ok = true;
-      if (dist > 2) {
-        while (!chain_ready(__hip_atomic_load(z + (long)j * T, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-          for (int q = dist > 64 ? 16 : dist >> 2; q > 0; --q) __builtin_amdgcn_s_sleep(8);
-          if (!spin.keep_waiting(63u)) { ok = false; break; }
-        }
-      }
-      // one right-hand side after the other (they are published together; polling them side by side costs 6 R registers)
-#pragma unroll 1
-      for (int r = 0; r < R; ++r) {
-        const double* zp = z + r * ldz + (long)j * T + 2 * lane;
-        double2 zj = ld_coherent2(zp);
-        while (ok && !__all(chain_ready(zj.x) && chain_ready(zj.y))) {
-          if (!spin.keep_waiting(1023u)) { ok = false; break; }
-          zj = ld_coherent2(zp);
-        }
-        *reinterpret_cast<double2*>(&zs[j & 1][r][2 * lane]) = zj;
-      }
-      if (!ok && lane == 0) gave_up = 1;
-    }
-    __syncthreads();
-    if (gave_up) break;
-#pragma unroll
-    for (int r = 0; r < R; ++r) chain_fold16(acc[r], blk, *reinterpret_cast<const double2*>(&zs[j & 1][r][2 * lane]));
-    // (the next block's loads must land in blk itself -- a second copy, which the compiler makes of its own accord by issuing them
-    //  ahead of the multiply-adds, does not fit beside acc at R = 4: every sum is complete before the first load is issued)
-#pragma unroll
-    for (int r = 0; r < R; ++r) chain_pin16(acc[r]);
-    if (j + 1 < b) {
-#pragma unroll
-      for (int q = 0; q < 16; ++q)
-        blk[q] = *reinterpret_cast<const double2*>(L + (row0 + q) * ld + (long)(j + 1) * T + 2 * lane);
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const double yv = ws[r][wave * 16 + (lane & 15)];
-    const double tot = transpose_sum16(acc[r], lane);
-    if (lane < 16) ws[r][wave * 16 + lane] = yv - tot;
-  }
-  __syncthreads();
-  double2 dv[16];
-#pragma unroll
-  for (int q = 0; q < 16; ++q) dv[q] = *reinterpret_cast<const double2*>(&dls[(wave * 16 + q) * T + 2 * lane]);
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    chain_rows16(acc[r], dv, ws[r][2 * lane], ws[r][2 * lane + 1]);
-    double v = transpose_sum16(acc[r], lane);
-    if (!chain_ready(v)) v = __longlong_as_double(0x7FF8000000000000LL);
-    if (lane < 16) __hip_atomic_store(z + r * ldz + row0 + lane, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-// Backward step j of L^T x = z.  x_j = L_jj^-T w_j; columns c < j0: w[c] -= sum_r L[j0+r][c] x_j[r].
-// Workgroup j0/128 (the last one) publishes x_j; workgroup b < j0/128 updates columns [128b, 128b+128).
-__global__ __launch_bounds__(256) void trsv_bwd_step(const double* L, long ld, const double* dinv_j,
-                                                     long j0, double* w, double* x) {
-  __shared__ double xj[T];
-  __shared__ double part[2][T];
-  const int tid = threadIdx.x, c = tid & 127, h = tid >> 7;
-  double acc = 0.0;
-#pragma unroll 16
-  for (int r = h * 64; r < h * 64 + 64; ++r) acc += dinv_j[r * T + c] * w[j0 + r];
-  part[h][c] = acc;
-  __syncthreads();
-  if (tid < T) xj[tid] = part[0][tid] + part[1][tid];
-  __syncthreads();
-  const long nb = j0 / T;
-  if ((long)blockIdx.x == nb) {
-    if (tid < T) x[j0 + tid] = xj[tid];
-    return;
-  }
-  const long col0 = (long)blockIdx.x * T;
-  acc = 0.0;
-#pragma unroll 16
-  for (int r = h * 64; r < h * 64 + 64; ++r) acc += L[(j0 + r) * ld + col0 + c] * xj[r];
-  __syncthreads();
-  part[h][c] = acc;
-  __syncthreads();
-  if (tid < T) w[col0 + tid] -= part[0][tid] + part[1][tid];
-}
-
-// The backward sweep L^T x = z as one chained launch, the mirror image of trsv_fwd_chain_direct: the
-// chain runs from the LAST block to the first, so workgroup w owns block column b = nt-1-w (its
-// predecessors in the chain then have smaller workgroup indices and are dispatched first).
-//   x_b = L_bb^-T ( z_b - sum_{j>b} L_jb^T x_j )
-// Wavefront v takes rows 16v..16v+15 of every block L_jb (row segments of 1 KiB, a lane two
-// columns), accumulates its lane's two columns of L_jb^T x_j over all j, and the eight wavefront
-// partials meet in LDS once, before the diagonal solve (same scheme again with L_bb^-1).
-// x itself is the message, as in trsv_fwd_chain_direct: x pre-filled with the sentinel, the first wavefront of a
-// consumer polls the 128 values of x_j and hands them on through LDS (they used to be sixteen broadcast loads from
-// L2 per wavefront, after the flag had been seen).
-__global__ __launch_bounds__(CHAIN_THREADS) void trsv_bwd_chain_direct(const double* L, long ld, const double* dinv, int nt,
-                                                                       const double* zin, double* x, int* fail) {
-  __shared__ double red[8][T];
-  __shared__ double wv[T];
-  __shared__ double xs[2][T];
-  __shared__ int gave_up;
-  const int w = blockIdx.x, b = nt - 1 - w;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long col0 = (long)b * T + 2 * lane;
-  double2 acc = make_double2(0.0, 0.0);
-  double2 dv[16], blk[16];
-  if (tid == 0) gave_up = 0;
-  const double zv = tid < T ? zin[(long)b * T + tid] : 0.0;
-#pragma unroll
-  for (int q = 0; q < 16; ++q)
-    dv[q] = *reinterpret_cast<const double2*>(dinv + (long)b * T * T + (wave * 16 + q) * T + 2 * lane);
-  if (b + 1 < nt) {
-#pragma unroll
-    for (int q = 0; q < 16; ++q)
-      blk[q] = *reinterpret_cast<const double2*>(L + ((long)(nt - 1) * T + wave * 16 + q) * ld + col0);
-  }
-  __syncthreads();
-  for (int j = nt - 1; j > b; --j) {
-    if (wave == 0) {
-      const int dist = j - b;
-      GhSpin spin(fail);
-      bool ok = true;
-      if (dist > 2) {
-        while (!chain_ready(__hip_atomic_load(x + (long)j * T, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-          for (int q = dist > 64 ? 16 : dist >> 2; q > 0; --q) __builtin_amdgcn_s_sleep(8);
-          if (!spin.keep_waiting(63u)) { ok = false; break; }
-        }
-      }
-      double2 xj = ld_coherent2(x + (long)j * T + 2 * lane);
-      while (ok && !__all(chain_ready(xj.x) && chain_ready(xj.y))) {
-        if (!spin.keep_waiting(1023u)) { ok = false; break; }
-        xj = ld_coherent2(x + (long)j * T + 2 * lane);
-      }
-      if (!ok && lane == 0) gave_up = 1;
-      *reinterpret_cast<double2*>(&xs[j & 1][2 * lane]) = xj;
-    }
-    __syncthreads();
-    if (gave_up) break;
-    const double* xw = &xs[j & 1][wave * 16];              // x_j[16 wave + q]: LDS broadcast reads
-#pragma unroll
-    for (int q = 0; q < 16; ++q) { const double xr = xw[q]; acc.x += blk[q].x * xr; acc.y += blk[q].y * xr; }
-    if (j - 1 > b) {
-#pragma unroll
-      for (int q = 0; q < 16; ++q)
-        blk[q] = *reinterpret_cast<const double2*>(L + ((long)(j - 1) * T + wave * 16 + q) * ld + col0);
-    }
-  }
-  red[wave][2 * lane] = acc.x;
-  red[wave][2 * lane + 1] = acc.y;
-  __syncthreads();
-  if (tid < T) {
-    double v = 0.0;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) v += red[q][tid];
-    wv[tid] = zv - v;
-  }
-  __syncthreads();
-  acc = make_double2(0.0, 0.0);                         // x_b[c] = sum_r dinv_b[r][c] w[r]
-#pragma unroll
-  for (int q = 0; q < 16; ++q) { const double wr = wv[wave * 16 + q]; acc.x += dv[q].x * wr; acc.y += dv[q].y * wr; }
-  __syncthreads();
-  red[wave][2 * lane] = acc.x;
-  red[wave][2 * lane + 1] = acc.y;
-  __syncthreads();
-  if (tid < T) {
-    double v = 0.0;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) v += red[q][tid];
-    if (!chain_ready(v)) v = __longlong_as_double(0x7FF8000000000000LL);
-    __hip_atomic_store(x + (long)b * T + tid, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-// ========================================================= predict reductions
-// partial[s][c] = sum over the s-th row chunk of V[r][c] * z[r]  and of V[r][c]^2
-__global__ __launch_bounds__(256) void colreduce_kernel(const double* V, long ldv, long nrows, long rows_per,
-                                                        const double* z, double* pmu, double* pvar, long ncols_p) {
-  const long c = (long)blockIdx.x * 256 + threadIdx.x;
-  if (c >= ncols_p) return;
-  const long r0 = (long)blockIdx.y * rows_per;
-  const long r1 = r0 + rows_per < nrows ? r0 + rows_per : nrows;
-  double am = 0.0, av = 0.0;
-  for (long r = r0; r < r1; ++r) {
-    const double v = V[r * ldv + c];
-    am += v * z[r];
-    av += v * v;
-  }
-  pmu[(long)blockIdx.y * ncols_p + c] = am;
-  pvar[(long)blockIdx.y * ncols_p + c] = av;
-}
-__global__ void colfinal_kernel(const double* pmu, const double* pvar, long nchunks, long ncols_p, long m,
-                                double* mu, double* var /* in: k(xs,xs) diag; may be NULL */) {
-  const long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= m) return;
-  double am = 0.0, av = 0.0;
-  for (long s = 0; s < nchunks; ++s) { am += pmu[s * ncols_p + c]; av += pvar[s * ncols_p + c]; }
-  mu[c] = am;
-  if (var) var[c] -= av;
-}
-__global__ void fill_kernel(double* p, long n, double v) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) p[i] = v;
-}
-__global__ void eye_kernel(double* p, long n, long ld) {   // p must be pre-zeroed
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i * ld + i] = 1.0;
-}
-// mirror the lower triangle of an n x n matrix into the upper one (out may be != in)
-__global__ void symmetrize_kernel(const double* in, long ldi, double* out, long ldo, long n) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= n * n) return;
-  const long i = idx / n, j = idx % n;
-  out[i * ldo + j] = (j <= i) ? in[i * ldi + j] : in[j * ldi + i];
-}
-__global__ void copy2d_kernel(const double* in, long ldi, double* out, long ldo, long rows, long cols) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= rows * cols) return;
-  const long i = idx / cols, j = idx % cols;
-  out[i * ldo + j] = in[i * ldi + j];
-}
-
-// ================================================= leave-one-out cross-validation
-#define LT 64                 // tile edge of the leave-one-out kernels
-// Column sums of squares of a LOWER-triangular row-major matrix (L^-1): part[s][c] = sum over the rows r >= c of the s-th row
-// chunk of V[r][c]^2.  A workgroup takes 64 columns of one chunk, a wavefront every fourth row: each load instruction reads
-// 512 contiguous bytes, four rows are in flight per trip.  Rows above the tile's first column hold zeros and are not read.
-// The four wavefronts' sums meet in LDS in a fixed order; colsumsq_final_kernel adds the chunks in index order: no atomics,
-// bitwise reproducible.
-__global__ __launch_bounds__(256) void colsumsq_kernel(const double* V, long ld, long np, long rows_per, double* part) {
-  __shared__ double sh[4][LT];
-  const int lc = threadIdx.x & 63, lr = threadIdx.x >> 6;
-  const long c0 = (long)blockIdx.x * LT, c = c0 + lc;
-  long r0 = (long)blockIdx.y * rows_per;
-  const long r1 = r0 + rows_per < np ? r0 + rows_per : np;
-  if (r0 < c0) r0 = c0;
-  double acc = 0.0;
-  long r = r0 + lr;
-  for (; r + 12 < r1; r += 16) {
-    double a[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) a[q] = V[(r + 4 * q) * ld + c];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) acc += (r + 4 * q >= c) ? a[q] * a[q] : 0.0;
-  }
-  for (; r < r1; r += 4) {
-    const double a = V[r * ld + c];
-    acc += (r >= c) ? a * a : 0.0;
-  }
-  sh[lr][lc] = acc;
-  __syncthreads();
-  if (lr == 0) part[(long)blockIdx.y * np + c] = (sh[0][lc] + sh[1][lc]) + (sh[2][lc] + sh[3][lc]);
-}
-__global__ void colsumsq_final_kernel(const double* part, long nchunks, long np, double* c) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= np) return;
-  double v = 0.0;
-  for (long s = 0; s < nchunks; ++s) v += part[s * np + i];
-  c[i] = v;
-}
-// The per-point quantities from alpha and c_i = (K^-1)_ii (c[i * cstride]: a vector, or the diagonal of a matrix):
-//   resid = u = alpha / c,  var = 1 / c,  lpd = 1/2 log c - 1/2 alpha^2 / c - 1/2 log 2 pi,  sw = sqrt(w),  w = 1/2 (1 + alpha^2 / c) / c.
-// Padded rows i >= n get zeros everywhere: nothing of them reaches the sum of lpd or S = K^-1 diag(sqrt(w)).
-// `u` is a second copy of resid that the solve for v = K^-1 u consumes.
-__global__ void loo_point_kernel(const double* alpha, const double* c, long cstride, long n, long np,
-                                 double* resid, double* u, double* var, double* lpd, double* sw) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= np) return;
-  double ui = 0.0, vi = 0.0, li = 0.0, si = 0.0;
-  if (i < n) {
-    const double ci = c[i * cstride], a = alpha[i];
-    ui = a / ci;
-    vi = 1.0 / ci;
-    const double q = a * ui;
-    li = 0.5 * log(ci) - 0.5 * q - 0.91893853320467274178;
-    si = sqrt(0.5 * (1.0 + q) / ci);
-  }
-  resid[i] = ui;
-  if (u) u[i] = ui;
-  var[i] = vi;
-  lpd[i] = li;
-  sw[i] = si;
-}
-// S = Kinv diag(sw) as a FULL matrix from the lower triangle of Kinv, one pass: a workgroup reads the 64 x 64 tile (ti, tj),
-// tj <= ti, into LDS and writes tile (ti, tj) of S as it lies and tile (tj, ti) transposed, column k scaled by sw[k].  Reads and
-// both writes are coalesced (a row of 64 doubles per wavefront); the transposed LDS reads walk a pitch of 65: no bank conflicts.
-__global__ __launch_bounds__(256) void loo_mirror_scale_kernel(const double* W, long ld, const double* sw, double* S) {
-  __shared__ double t[LT][LT + 1];
-  int ti, tj;
-  tri_index(blockIdx.x, ti, tj);
-  const long r0 = (long)ti * LT, c0 = (long)tj * LT;
-  const int lc = threadIdx.x & 63, lr = threadIdx.x >> 6;
-#pragma unroll 4
-  for (int rr = lr; rr < LT; rr += 4) t[rr][lc] = W[(r0 + rr) * ld + c0 + lc];
-  __syncthreads();
-  const double sc = sw[c0 + lc];
-  if (ti != tj) {
-    const double sr = sw[r0 + lc];
-#pragma unroll 4
-    for (int rr = lr; rr < LT; rr += 4) {
-      S[(r0 + rr) * ld + c0 + lc] = t[rr][lc] * sc;
-      S[(c0 + rr) * ld + r0 + lc] = t[lc][rr] * sr;
-    }
-  } else {
-#pragma unroll 4
-    for (int rr = lr; rr < LT; rr += 4) S[(r0 + rr) * ld + c0 + lc] = (lc <= rr ? t[rr][lc] : t[lc][rr]) * sc;
-  }
-}
-// out[0] = sum_{i < n} a[i]: one workgroup, or slices added in index order (launch_sum, as launch_dot)
-__global__ __launch_bounds__(256) void sum_part_kernel(const double* a, long n, double* part) {
-  __shared__ double sh[4];
-  const long per = (n + gridDim.x - 1) / gridDim.x;
-  const long lo = (long)blockIdx.x * per, hi = lo + per < n ? lo + per : n;
-  double v = 0.0;
-  for (long i = lo + threadIdx.x; i < hi; i += 256) v += a[i];
-  v = block_sum_256(v, sh);
-  if (threadIdx.x == 0) part[blockIdx.x] = v;
-}
-static int launch_sum(const double* a, long n, double* out, double* part, hipStream_t st) {
-  const int g = (int)std::max<long>(1, std::min<long>(RED_SLICES, (n + 4095) / 4096));
-  hipLaunchKernelGGL(sum_part_kernel, dim3(g), dim3(256), 0, st, a, n, part);
-  hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(64), 0, st, part, g, 1.0, out, 0, (const int*)nullptr);
-  GH_HIP(hipGetLastError());
-  return GH_OK;
-}
-// *acc = 1 when one of the chained sweeps just enqueued gave up waiting: several deferred pairs of sweeps share the flag words,
-// which every launch clears
-__global__ void chain_fail_note_kernel(const int* ff, const int* fb, double* acc) {
-  if (threadIdx.x == 0 && blockIdx.x == 0 && (*ff != 0 || *fb != 0)) *acc = 1.0;
-}
-
-// ================================================================= the solver
-struct EvPair { hipEvent_t a, b; };
-
-struct gh_chol {
-  gh_chol_opts opts;
-  hipStream_t st = nullptr;
-  hipStream_t st2 = nullptr;             // high-priority panel stream (look-ahead)
-  hipStream_t st3 = nullptr;             // second panel stream: rows-below TRSM beside the potf2 chain
-  bool shared_streams = false;           // st, st2, st3, st4, st_mask belong to the process (gh_shared_streams): not destroyed here
-  hipStream_t st4 = nullptr;             // third panel stream: in-panel rows >= j+2 (everything off the potf2 chain)
-  hipEvent_t ev_diag[32] = {};             // one per 128-column step of a panel (panels of up to 4096 columns)
-  hipEvent_t ev_aux = nullptr, ev_aux2 = nullptr;
-  std::vector<hipEvent_t> ev_p, ev_w, ev_nf;   // deep look-ahead: panel j factored / W(j) done / U(j, j+2) done
-  GhCholPlan plan;                         // two-level driver: the launch list (rebuilt only when Np, the panel starts or the group maximum change)
-  std::vector<hipEvent_t> ev_plan;         // ... and its events, owned by index in the list
-  hipStream_t st_mask = nullptr;         // main-stream stand-in that leaves CUs to the panel chain (small N)
-  hipStream_t tail = nullptr;            // where the last factor() ended: the stream on which its results are complete in stream order
-
-
-  int mask_reserved = -1;                // CUs st_mask leaves out (-1: not created yet, 0: creation failed)
-  hipEvent_t ev_xfer = nullptr;
-  hipEvent_t ev_sync[3] = {nullptr, nullptr, nullptr};
-  int64_t n = 0, np = 0;
-  int ndim = 0;
-  bool have_yerr = false;                // yerr holds the n error bars of compute() / append() (import_factor brings none: gh_chol_set_yerr)
-  hipEvent_t ev_lay[2] = {nullptr, nullptr};   // profile: the relayout of the last append()
-  bool computed = false;
-  int64_t info = 0;
-  double logdet = 0.0;
-  GhBuf A, dinv, x, yerr, v0, v1, v2, scal, rhs, work, work2, scratch, chain;
-  GhBuf A_spare;                         // the buffer the factor left when append / truncate last moved it: where the next move goes (freed by trim)
-  GhBuf samp;                            // gh_chol_sample_conditional: prior diagonal, threshold and the factor / draw work arrays (freed by trim)
-  GhBuf fish;                            // gh_chol_fisher's planes (freed by trim)
-  GhBuf lv;                              // gh_chol_loo's N-vectors: resid, var, lpd, sqrt(w), c, alpha, v (7 Np doubles)
-  long long* d_info = nullptr;           // = (long long*)(scal + 2): the failure word lives beside the scalars (set in compute_enqueue)
-  bool build_on_chain = false;           // this compute(): inputs + kernel-matrix build were enqueued on the chain stream (st2)
-  GhBatchBufs* batch = nullptr;          // gh_chol_objective_batch's buffers (gh_batch.hip), grown once and re-used
-  gh_chol_profile prof;
-  std::vector<EvPair> ev_pool;
-  size_t ev_used = 0;
-  std::vector<size_t> ev_trailing, ev_panel, ev_update;   // ev_update: EVERY trailing-update launch (wide SYRKs and block-column GEMMs)
-  std::vector<double> ev_update_flops;                    // algorithmic flops of each ev_update launch
-  std::vector<double> upd_intervals;                      // last compute(): (start ms, end ms, flops) per trailing-update launch
-  // returns an index into ev_pool (the vector may grow, so never keep pointers), or -1
-  long next_ev() {
-    if (ev_used == ev_pool.size()) {
-      EvPair p;
-      if (hipEventCreate(&p.a) != hipSuccess || hipEventCreate(&p.b) != hipSuccess) return -1;
-      ev_pool.push_back(p);
-    }
-    return (long)ev_used++;
-  }
-  ~gh_chol() {
-    for (auto& p : ev_pool) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
-    for (auto& e : ev_sync) if (e) (void)hipEventDestroy(e);
-    for (auto& e : ev_lay) if (e) (void)hipEventDestroy(e);
-    if (ev_xfer) (void)hipEventDestroy(ev_xfer);
-    if (ev_aux) (void)hipEventDestroy(ev_aux);
-    if (ev_aux2) (void)hipEventDestroy(ev_aux2);
-    for (auto* v : {&ev_p, &ev_w, &ev_nf, &ev_plan}) for (auto e : *v) (void)hipEventDestroy(e);
-    for (auto& e : ev_diag) if (e) (void)hipEventDestroy(e);
-    if (st4 && !shared_streams) (void)hipStreamDestroy(st4);
-    if (st3 && !shared_streams) (void)hipStreamDestroy(st3);
-    if (st_mask && !shared_streams) (void)hipStreamDestroy(st_mask);
-
-
-    if (st2 && !shared_streams) (void)hipStreamDestroy(st2);
-    if (st && !shared_streams) (void)hipStreamDestroy(st);
-    gh_batch_free(batch);
-  }
-};
 
 // ---- the process-wide streams (see gh_common.h)
 #include <map>
@@ -897,7 +192,7 @@ hipStream_t gh_shared_masked_stream(int device, int reserve_cus) {
   return st;
 }
 
-static int set_device(gh_chol* s) {
+int gh_chol_set_device(gh_chol* s) {
   if (gh_device_count() <= 0) { gh_set_error("no HIP device available: the george_amd solver needs an MI355X"); return GH_ERR_HIP; }
   GH_HIP(hipSetDevice(s->opts.device));
   return GH_OK;
@@ -911,7 +206,7 @@ extern "C" int gh_chol_create(const gh_chol_opts* opts, gh_chol** out) {
   if (opts) s->opts = *opts;
   if (s->opts.nb < 0) s->opts.nb = 0;       // 0 = choose per problem size (panel_width())
   if (s->opts.nb % T) { delete s; gh_set_error("nb must be a multiple of 128"); return GH_ERR_BAD_ARG; }
-  int rc = set_device(s);
+  int rc = gh_chol_set_device(s);
   if (rc != GH_OK) { delete s; return rc; }
   hipStream_t shq[4] = {nullptr, nullptr, nullptr, nullptr};
   if (gh_shared_streams(s->opts.device, shq)) {
@@ -955,7 +250,7 @@ __global__ void spin_kernel(long long ticks) {
 }
 extern "C" int gh_debug_stream_overlap(gh_chol* s, double* out, int n) {
   if (!s || !out || n < 36) { gh_set_error("bad argument"); return GH_ERR_BAD_ARG; }
-  int rc = set_device(s);
+  int rc = gh_chol_set_device(s);
   if (rc != GH_OK) return rc;
   hipStream_t q[6] = {nullptr, s->st, s->st2, s->st3, s->st4, s->st_mask};
   for (int i = 0; i < 36; ++i) out[i] = 0.0;
@@ -978,7 +273,7 @@ extern "C" int gh_debug_stream_overlap(gh_chol* s, double* out, int n) {
 // small kernel has to wait for the big one's dispatch to end.  Streams as in gh_debug_stream_overlap.
 extern "C" int gh_debug_stream_dispatch(gh_chol* s, double* out, int n) {
   if (!s || !out || n < 36) { gh_set_error("bad argument"); return GH_ERR_BAD_ARG; }
-  int rc = set_device(s);
+  int rc = gh_chol_set_device(s);
   if (rc != GH_OK) return rc;
   hipStream_t q[6] = {nullptr, s->st, s->st2, s->st3, s->st4, s->st_mask};
   for (int i = 0; i < 36; ++i) out[i] = 0.0;
@@ -1014,7 +309,7 @@ extern "C" int64_t gh_chol_device_bytes(const gh_chol* s) {
   return (int64_t)(tot + gh_batch_bytes(s->batch));
 }
 int gh_chol_batch_begin(gh_chol* s, hipStream_t* st, GhBatchBufs** bufs) {
-  GH_CHECK(set_device(s));
+  GH_CHECK(gh_chol_set_device(s));
   s->computed = false;
   s->info = 0;
   if (!s->batch) s->batch = gh_batch_new();
@@ -1038,24 +333,24 @@ extern "C" int gh_chol_get_profile(const gh_chol* s, gh_chol_profile* out) {
 
 static inline double* blk(double* A, int64_t ld, int64_t r, int64_t c) { return A + r * ld + c; }
 
-// C = A * B^T (alpha=1,beta=0) or C -= A * B^T helpers on k-major operands
+// C = alpha A B^T + beta C on k-major operands
 // (set by factor(): the K = 128 GEMMs of the chain hold 128-144 KiB of LDS per workgroup -- a whole CU.  Below
 //  Np = 24576 the trailing SYRK leaves 32 CUs out and they run there; above it every CU carries two SYRK
 //  workgroups and a chain workgroup that needs a CU to itself waits for one to drain while the dispatcher
 //  holds it empty: N = 65536 went from 1.407 to 1.433 s.  There they keep the 32-KiB K-loop kernel.)
 static thread_local bool t_gemm_small_lds = false;
-static int gemm_nt(hipStream_t st, double* C, int64_t ldc, const double* A, int64_t lda, const double* B, int64_t ldb,
-                   int64_t M, int64_t N, int64_t K, double alpha, double beta, bool lower) {
-  GhGemm g{};
+// t_gemm_small_lds for a scope
+struct SmallLdsGuard { bool prev; explicit SmallLdsGuard(bool v) : prev(t_gemm_small_lds) { t_gemm_small_lds = v; } ~SmallLdsGuard() { t_gemm_small_lds = prev; } };
+int gh_gemm_nt(hipStream_t st, double* C, int64_t ldc, const double* A, int64_t lda, const double* B, int64_t ldb,
+               int64_t M, int64_t N, int64_t K, double alpha, double beta, bool lower) {
+  GhGemm g = gemm_desc(C, ldc, A, lda, true, B, ldb, true, M, N, K, alpha, beta);
   g.small_lds = t_gemm_small_lds;
-  g.C = C; g.ldc = ldc; g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.M = M; g.N = N; g.K = K;
-  g.alpha = alpha; g.beta = beta; g.a_km = true; g.b_km = true; g.lower = lower;
+  g.lower = lower;
   return gh_launch_gemm(g, st);
 }
 
 // gh_potf2.hip: MFMA-blocked 128x128 Cholesky + inverse (the default); GEORGE_AMD_POTF2=simple
 // selects the first scalar version above for A/B validation
-int gh_launch_potf2_mfma(double* A, int64_t lda, double* dinv, long long* info, long long base, hipStream_t st);
 static bool use_simple_potf2() {
   static int v = -1;
   if (v < 0) { const char* e = getenv("GEORGE_AMD_POTF2"); v = (e && e[0] == 's') ? 1 : 0; }
@@ -1063,7 +358,7 @@ static bool use_simple_potf2() {
 }
 
 // in-place lower Cholesky of the n x n block at A (n multiple of 128) + diagonal-block inverses
-static int potrf_block(hipStream_t st, double* A, int64_t ld, int64_t n, double* dinv, long long* d_info, long long base) {
+int gh_chol_potrf_block(hipStream_t st, double* A, int64_t ld, int64_t n, double* dinv, long long* d_info, long long base) {
   for (int64_t j0 = 0; j0 < n; j0 += T) {
     double* dj = dinv + (j0 / T) * T * T;
     if (use_simple_potf2()) {
@@ -1075,8 +370,8 @@ static int potrf_block(hipStream_t st, double* A, int64_t ld, int64_t n, double*
     const int64_t rem = n - (j0 + T);
     if (rem > 0) {
       double* P = blk(A, ld, j0 + T, j0);
-      GH_CHECK(gemm_nt(st, P, ld, P, ld, dj, T, rem, T, T, 1.0, 0.0, false));          // P <- P L_jj^-T (in place)
-      GH_CHECK(gemm_nt(st, blk(A, ld, j0 + T, j0 + T), ld, P, ld, P, ld, rem, rem, T, -1.0, 1.0, true));
+      GH_CHECK(gh_gemm_nt(st, P, ld, P, ld, dj, T, rem, T, T, 1.0, 0.0, false));          // P <- P L_jj^-T (in place)
+      GH_CHECK(gh_gemm_nt(st, blk(A, ld, j0 + T, j0 + T), ld, P, ld, P, ld, rem, rem, T, -1.0, 1.0, true));
     }
   }
   return GH_OK;
@@ -1086,40 +381,21 @@ static int trsm_right(hipStream_t st, const double* L11, int64_t ld11, const dou
   for (int64_t j0 = 0; j0 < n; j0 += T) {
     double* Xj = A21 + j0;
     if (j0 > 0)
-      GH_CHECK(gemm_nt(st, Xj, lda, A21, lda, L11 + j0 * ld11, ld11, m, T, j0, -1.0, 1.0, false));
-    GH_CHECK(gemm_nt(st, Xj, lda, Xj, lda, dinv + (j0 / T) * T * T, T, m, T, T, 1.0, 0.0, false));
+      GH_CHECK(gh_gemm_nt(st, Xj, lda, A21, lda, L11 + j0 * ld11, ld11, m, T, j0, -1.0, 1.0, false));
+    GH_CHECK(gh_gemm_nt(st, Xj, lda, Xj, lda, dinv + (j0 / T) * T * T, T, m, T, T, 1.0, 0.0, false));
   }
   return GH_OK;
 }
 
-// z = L^-1 w as one chained launch; flags[nt] = the time-out flag (cleared here; the words before it are no longer
-// used: the flag-per-block-row kernels are retired, scripts/dev/arms/trsv_chain_flags.hip.inc).  w is read only and
-// must not be z (z is pre-filled with the sentinel).
-static int launch_trsv_fwd_chain(const double* L, long ld, const double* dinv, int64_t nt, const double* w, double* z,
-                                 unsigned* flags, hipStream_t st) {
-  GH_HIP(hipMemsetAsync(flags + nt, 0, sizeof(unsigned), st));
-  GH_HIP(hipMemsetAsync(z, 0xFF, (size_t)nt * T * sizeof(double), st));
-  hipLaunchKernelGGL(trsv_fwd_chain_direct, dim3((unsigned)nt), dim3(CHAIN_THREADS), 0, st, L, ld, dinv, w, z, (int*)(flags + nt));
-  GH_HIP(hipGetLastError());
-  return GH_OK;
-}
-static int launch_trsv_bwd_chain(const double* L, long ld, const double* dinv, int64_t nt, const double* w, double* x,
-                                 unsigned* flags, hipStream_t st) {
-  GH_HIP(hipMemsetAsync(flags + nt, 0, sizeof(unsigned), st));
-  GH_HIP(hipMemsetAsync(x, 0xFF, (size_t)nt * T * sizeof(double), st));
-  hipLaunchKernelGGL(trsv_bwd_chain_direct, dim3((unsigned)nt), dim3(CHAIN_THREADS), 0, st, L, ld, dinv, (int)nt, w, x, (int*)(flags + nt));
-  GH_HIP(hipGetLastError());
-  return GH_OK;
-}
 extern "C" int gh_dev_potrf_block(double* a, int64_t lda, int64_t n, double* dinv, int64_t* info_dev, int64_t base_index, void* stream) {
   if (n % T) { gh_set_error("potrf_block: n must be a multiple of 128"); return GH_ERR_BAD_ARG; }
   // (tile operations of the multi-GPU driver run beside trailing updates that own every CU: small-LDS GEMMs, see t_gemm_small_lds)
-  struct Guard { bool prev; Guard() : prev(t_gemm_small_lds) { t_gemm_small_lds = true; } ~Guard() { t_gemm_small_lds = prev; } } guard;
-  return potrf_block((hipStream_t)stream, a, lda, n, dinv, (long long*)info_dev, base_index);
+  SmallLdsGuard guard(true);
+  return gh_chol_potrf_block((hipStream_t)stream, a, lda, n, dinv, (long long*)info_dev, base_index);
 }
 extern "C" int gh_dev_trsm_right(const double* l11, int64_t ld11, const double* dinv, double* a21, int64_t lda, int64_t m, int64_t n, void* stream) {
   if (n % T || m % T) { gh_set_error("trsm_right: sizes must be multiples of 128"); return GH_ERR_BAD_ARG; }
-  struct Guard { bool prev; Guard() : prev(t_gemm_small_lds) { t_gemm_small_lds = true; } ~Guard() { t_gemm_small_lds = prev; } } guard;
+  SmallLdsGuard guard(true);
   return trsm_right((hipStream_t)stream, l11, ld11, dinv, a21, lda, m, n);
 }
 extern "C" int gh_dev_trsv_lower(const double* l, int64_t ldl, const double* dinv, int64_t n,
@@ -1127,19 +403,17 @@ extern "C" int gh_dev_trsv_lower(const double* l, int64_t ldl, const double* din
   if (n % T || n <= 0 || !scratch) { gh_set_error("trsv_lower: n must be a positive multiple of 128"); return GH_ERR_BAD_ARG; }
   const int64_t nt = n / T;
   if (w == z) { gh_set_error("trsv_lower: w and z must not be the same array"); return GH_ERR_BAD_ARG; }
-  return launch_trsv_fwd_chain(l, (long)ldl, dinv, nt, w, z, (unsigned*)scratch, (hipStream_t)stream);
+  return gh_launch_trsv_fwd_chain(l, (long)ldl, dinv, nt, w, z, (unsigned*)scratch, (hipStream_t)stream);
 }
 extern "C" int gh_dev_trsv_lower_t(const double* l, int64_t ldl, const double* dinv, int64_t n,
                                    const double* w, double* x, void* scratch, void* stream) {
   if (n % T || n <= 0 || !scratch) { gh_set_error("trsv_lower_t: n must be a positive multiple of 128"); return GH_ERR_BAD_ARG; }
   const int64_t nt = n / T;
   if (w == x) { gh_set_error("trsv_lower_t: w and x must not be the same array"); return GH_ERR_BAD_ARG; }
-  return launch_trsv_bwd_chain(l, (long)ldl, dinv, nt, w, x, (unsigned*)scratch, (hipStream_t)stream);
+  return gh_launch_trsv_bwd_chain(l, (long)ldl, dinv, nt, w, x, (unsigned*)scratch, (hipStream_t)stream);
 }
 extern "C" int gh_dev_logdet_accum(const double* a, int64_t lda, int64_t n, double* out_dev, void* stream) {
-  hipLaunchKernelGGL(logdet_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a, (long)lda, (long)n, out_dev, 1);
-  GH_HIP(hipGetLastError());
-  return GH_OK;
+  return gh_launch_logdet_accum(a, (long)lda, (long)n, out_dev, (hipStream_t)stream);
 }
 
 // Outer panel width.  Wider panels raise the SYRK's arithmetic intensity and K-loop length and
@@ -1196,7 +470,7 @@ static int panel_step(gh_chol* s, hipStream_t st, int64_t k0, int64_t nb) {
   //  other in-panel rows on a third stream; the chain on CUs of its own; only the potf2 launches on reserved CUs; the
   //  whole panel as two persistent flag-driven launches.  DESIGN.md section 4, "Where N < 24k stands".)
   if (!s->st3 || !on_panel_stream || m <= 0 || nb / T > 32 || use_simple_potf2()) {
-    GH_CHECK(potrf_block(st, blk(A, ld, k0, k0), ld, nb, dinv, s->d_info, k0));
+    GH_CHECK(gh_chol_potrf_block(st, blk(A, ld, k0, k0), ld, nb, dinv, s->d_info, k0));
     if (m > 0) {
       GH_CHECK(trsm_right(st, blk(A, ld, k0, k0), ld, dinv, blk(A, ld, k0 + nb, k0), ld, m, nb));
     }
@@ -1216,13 +490,13 @@ static int panel_step(gh_chol* s, hipStream_t st, int64_t k0, int64_t nb) {
     GH_HIP(hipEventRecord(s->ev_diag[j0 / T], st));
     GH_HIP(hipStreamWaitEvent(sa, s->ev_diag[j0 / T], 0));
     double* Xj = B + j0;
-    if (j0 > 0) GH_CHECK(gemm_nt(sa, Xj, ld, B, ld, Ak + j0 * ld, ld, m, T, j0, -1.0, 1.0, false));
-    GH_CHECK(gemm_nt(sa, Xj, ld, Xj, ld, dj, T, m, T, T, 1.0, 0.0, false));
+    if (j0 > 0) GH_CHECK(gh_gemm_nt(sa, Xj, ld, B, ld, Ak + j0 * ld, ld, m, T, j0, -1.0, 1.0, false));
+    GH_CHECK(gh_gemm_nt(sa, Xj, ld, Xj, ld, dj, T, m, T, T, 1.0, 0.0, false));
     const int64_t rem = nb - (j0 + T);
     if (rem > 0) {
       double* P = blk(Ak, ld, j0 + T, j0);
-      GH_CHECK(gemm_nt(st, P, ld, P, ld, dj, T, rem, T, T, 1.0, 0.0, false));
-      GH_CHECK(gemm_nt(st, blk(Ak, ld, j0 + T, j0 + T), ld, P, ld, P, ld, rem, rem, T, -1.0, 1.0, true));
+      GH_CHECK(gh_gemm_nt(st, P, ld, P, ld, dj, T, rem, T, T, 1.0, 0.0, false));
+      GH_CHECK(gh_gemm_nt(st, blk(Ak, ld, j0 + T, j0 + T), ld, P, ld, P, ld, rem, rem, T, -1.0, 1.0, true));
     }
   }
   GH_HIP(hipEventRecord(s->ev_aux, sa));
@@ -1329,7 +603,7 @@ static int factor_lookahead_deep(gh_chol* s, int depth) {
     const double* Pj = blk(A, ld, c0(c), c0(j));
     const long eu = prof ? s->next_ev() : -1;
     if (eu >= 0) { GH_HIP(hipEventRecord(s->ev_pool[eu].a, st)); s->ev_update.push_back((size_t)eu); }
-    GH_CHECK(gemm_nt(st, blk(A, ld, c0(c), c0(c)), ld, Pj, ld, Pj, ld, np - c0(c), nbc(c), nbc(j), -1.0, 1.0, false));
+    GH_CHECK(gh_gemm_nt(st, blk(A, ld, c0(c), c0(c)), ld, Pj, ld, Pj, ld, np - c0(c), nbc(c), nbc(j), -1.0, 1.0, false));
     if (eu >= 0) GH_HIP(hipEventRecord(s->ev_pool[eu].b, st));
     // (algorithmic flops of the block column: its lower part only -- the strictly-upper tiles of the
     //  diagonal block are computed for convenience and never read)
@@ -1386,7 +660,7 @@ static int factor_lookahead_deep(gh_chol* s, int depth) {
         s->ev_update_flops.push_back((double)(m2 / T) * (m2 / T + 1) / 2.0 * 2.0 * T * T * (double)nbc(j));
       }
       const double* P2 = blk(A, ld, kw, c0(j));
-      GH_CHECK(gemm_nt(sw, blk(A, ld, kw, kw), ld, P2, ld, P2, ld, m2, m2, nbc(j), -1.0, 1.0, true));
+      GH_CHECK(gh_gemm_nt(sw, blk(A, ld, kw, kw), ld, P2, ld, P2, ld, m2, m2, nbc(j), -1.0, 1.0, true));
       if (et >= 0) GH_HIP(hipEventRecord(s->ev_pool[et].b, sw));
       const double tiles = (double)(m2 / T) * (m2 / T + 1) / 2.0;
       s->prof.trailing_flops += tiles * 2.0 * T * T * (double)nbc(j);
@@ -1506,7 +780,7 @@ static int factor_two_level(gh_chol* s) {
         s->ev_update.push_back((size_t)eu); s->ev_update_flops.push_back(fl);
         if (o.kind == GH_PLAN_F) s->ev_trailing.push_back((size_t)eu);
       }
-      GH_CHECK(gemm_nt(st, blk(A, ld, o.r0, o.c0), ld, blk(A, ld, o.r0, o.k0), ld, blk(A, ld, o.c0, o.k0), ld, m, n, k, -1.0, 1.0, o.lower != 0));
+      GH_CHECK(gh_gemm_nt(st, blk(A, ld, o.r0, o.c0), ld, blk(A, ld, o.r0, o.k0), ld, blk(A, ld, o.c0, o.k0), ld, m, n, k, -1.0, 1.0, o.lower != 0));
       if (eu >= 0) GH_HIP(hipEventRecord(s->ev_pool[eu].b, st));
       s->prof.update_flops += fl;
       if (o.kind == GH_PLAN_F) { s->prof.trailing_flops += fl; s->prof.n_trailing += 1; }
@@ -1529,8 +803,7 @@ static int lookahead_depth(const gh_chol* s) {
 }
 
 static int factor(gh_chol* s) {
-  struct Guard { bool prev; Guard(bool v) : prev(t_gemm_small_lds) { t_gemm_small_lds = v; } ~Guard() { t_gemm_small_lds = prev; } }
-      guard(s->opts.lookahead && s->st2 && trailing_stream(s) == s->st);       // no CUs kept free of the SYRK
+  SmallLdsGuard guard(s->opts.lookahead && s->st2 && trailing_stream(s) == s->st);       // no CUs kept free of the SYRK
   // (a matrix of ONE panel has nothing to look ahead to: on the main stream it saves the two cross-stream hand-overs,
   //  ~35 us each -- a tenth of the step at N = 1024)
   if (s->opts.lookahead && s->st2 && s->st3 && s->st4 && s->np > panel_width(s)) {      // (panel widths: panel_starts())
@@ -1546,7 +819,7 @@ static int factor(gh_chol* s) {
     const int64_t k0 = pc[pj], nb = pc[pj + 1] - pc[pj];
     const long ep = prof ? s->next_ev() : -1;
     if (ep >= 0) { GH_HIP(hipEventRecord(s->ev_pool[ep].a, st)); s->ev_panel.push_back((size_t)ep); }
-    GH_CHECK(potrf_block(st, blk(A, ld, k0, k0), ld, nb, s->dinv.d() + (k0 / T) * T * T, s->d_info, k0));
+    GH_CHECK(gh_chol_potrf_block(st, blk(A, ld, k0, k0), ld, nb, s->dinv.d() + (k0 / T) * T * T, s->d_info, k0));
     const int64_t m = np - (k0 + nb);
     if (m > 0)
       GH_CHECK(trsm_right(st, blk(A, ld, k0, k0), ld, s->dinv.d() + (k0 / T) * T * T, blk(A, ld, k0 + nb, k0), ld, m, nb));
@@ -1555,7 +828,7 @@ static int factor(gh_chol* s) {
       const long et = prof ? s->next_ev() : -1;
       if (et >= 0) { GH_HIP(hipEventRecord(s->ev_pool[et].a, st)); s->ev_trailing.push_back((size_t)et); }
       const double* P = blk(A, ld, k0 + nb, k0);
-      GH_CHECK(gemm_nt(st, blk(A, ld, k0 + nb, k0 + nb), ld, P, ld, P, ld, m, m, nb, -1.0, 1.0, true));
+      GH_CHECK(gh_gemm_nt(st, blk(A, ld, k0 + nb, k0 + nb), ld, P, ld, P, ld, m, m, nb, -1.0, 1.0, true));
       if (et >= 0) GH_HIP(hipEventRecord(s->ev_pool[et].b, st));
       const double tiles = (double)(m / T) * (m / T + 1) / 2.0;
       s->prof.trailing_flops += tiles * 2.0 * T * T * (double)nb;
@@ -1575,12 +848,11 @@ __global__ void prep_inputs_kernel(const double* xs, long nx, const double* es, 
 }
 
 // Everything of compute() up to and including the log-det launch, enqueued on s->st without a
-// host synchronisation; compute_finish() reads the scalars back.
-struct ComputeCtx { long e_all = -1, e_build = -1; };
-static int compute_enqueue(gh_chol* s, gh_kernel* k, const double* x, int64_t n, int32_t ndim, const double* yerr, ComputeCtx& c) {
+// host synchronisation; gh_chol_compute_finish() takes the scalars read back.
+int gh_chol_compute_enqueue(gh_chol* s, gh_kernel* k, const double* x, int64_t n, int32_t ndim, const double* yerr, ComputeCtx& c) {
   if (!s || !k || !x || !yerr || n <= 0) { gh_set_error("bad argument to compute"); return GH_ERR_BAD_ARG; }
   if (ndim != k->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
-  GH_CHECK(set_device(s));
+  GH_CHECK(gh_chol_set_device(s));
   GH_CHECK(k->upload());
   s->computed = false;
   s->info = 0;
@@ -1618,12 +890,12 @@ static int compute_enqueue(gh_chol* s, gh_kernel* k, const double* x, int64_t n,
   if (c.e_build >= 0) GH_HIP(hipEventRecord(s->ev_pool[c.e_build].b, st));
   s->tail = s->st;
   GH_CHECK(factor(s));                                  // (may move s->tail to the chain stream)
-  GH_CHECK(launch_logdet(s->A.d(), np, np, s->scal.d(), s->scal.d() + 8, s->tail));
+  GH_CHECK(gh_launch_logdet(s->A.d(), np, np, s->scal.d(), s->scal.d() + 8, s->tail));
   if (c.e_all >= 0) GH_HIP(hipEventRecord(s->ev_pool[c.e_all].b, s->tail));
   return GH_OK;
 }
 // after the stream has been synchronised and logdet / info copied to the host
-static int compute_finish(gh_chol* s, const ComputeCtx& c, double ld_host, long long info_host, double* logdet_out) {
+int gh_chol_compute_finish(gh_chol* s, const ComputeCtx& c, double ld_host, long long info_host, double* logdet_out) {
   if (s->opts.profile && c.e_all >= 0 && c.e_build >= 0) {
     float ms = 0;
     GH_HIP(hipEventElapsedTime(&ms, s->ev_pool[c.e_all].a, s->ev_pool[c.e_all].b)); s->prof.ms_total = ms;
@@ -1669,806 +941,20 @@ static int compute_finish(gh_chol* s, const ComputeCtx& c, double ld_host, long 
 extern "C" int gh_chol_compute(gh_chol* s, gh_kernel* k, const double* x, int64_t n, int32_t ndim,
                                const double* yerr, double* logdet_out) {
   ComputeCtx c;
-  GH_CHECK(compute_enqueue(s, k, x, n, ndim, yerr, c));
-  hipStream_t st = s->tail;                             // (the stream the factorisation ended on: compute_enqueue)
+  GH_CHECK(gh_chol_compute_enqueue(s, k, x, n, ndim, yerr, c));
+  hipStream_t st = s->tail;                             // (the stream the factorisation ended on: gh_chol_compute_enqueue)
   double back[3] = {0.0, 0.0, 0.0};                     // [0] log-det, [1] (quadratic form), [2] the failure word's bits
-  GH_HIP(hipMemcpyAsync(back, s->scal.d(), 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+  GH_CHECK(read_scalars(s, back, 3, st));
   GH_HIP(hipStreamSynchronize(st));
-  long long info_host = 0;
-  memcpy(&info_host, &back[2], sizeof(long long));
-  return compute_finish(s, c, back[0], info_host, logdet_out);
+  return gh_chol_compute_finish(s, c, back[0], info_from_bits(back[2]), logdet_out);
 }
 
-static int need_computed(gh_chol* s) {
+int gh_chol_need_computed(gh_chol* s) {
   if (!s) { gh_set_error("null solver"); return GH_ERR_BAD_ARG; }
   if (!s->computed) { gh_set_error("you must call 'compute' first"); return GH_ERR_NOT_COMPUTED; }
-  return set_device(s);
+  return gh_chol_set_device(s);
 }
 
-// load a length-n vector (host or device) into a zero-padded device vector of length np
-static int load_vec(gh_chol* s, GhBuf& buf, const double* src) {
-  GH_CHECK(buf.ensure((size_t)s->np * sizeof(double)));
-  if (s->np > s->n) GH_HIP(hipMemsetAsync(buf.d() + s->n, 0, (size_t)(s->np - s->n) * sizeof(double), s->st));
-  return gh_to_device(buf.d(), src, (size_t)s->n, s->st);
-}
-// z = L^-1 w  (w is destroyed)
-// (defer: enqueue only; the caller reads the time-out flag back itself, chain_fail_flag())
-static int trsv_forward(gh_chol* s, double* w, double* z, bool defer = false) {
-  const int64_t nt = s->np / T;
-  static const bool stepwise = getenv("GEORGE_AMD_TRSV_STEPS") != nullptr;       // A/B arm: one launch per block row
-  if (!stepwise) {
-    // forward and backward sweeps keep separate flag sets, [0, nt] and [nt + 1, 2 nt + 1]
-    GH_CHECK(s->chain.ensure((size_t)(2 * nt + 2) * sizeof(unsigned)));
-    unsigned* flags = (unsigned*)s->chain.p;
-    GH_CHECK(launch_trsv_fwd_chain(s->A.d(), (long)s->np, s->dinv.d(), nt, w, z, flags, s->st));
-    if (defer) return GH_OK;
-    int failed = 0;
-    GH_HIP(hipMemcpyAsync(&failed, flags + nt, sizeof(int), hipMemcpyDeviceToHost, s->st));
-    GH_HIP(hipStreamSynchronize(s->st));
-    if (failed) { gh_set_error("forward solve: a workgroup waited more than 2 s for its predecessor"); return GH_ERR_HIP; }
-    return GH_OK;
-  }
-  for (int64_t j = 0; j < nt; ++j) {
-    hipLaunchKernelGGL(trsv_fwd_step, dim3((unsigned)(nt - j)), dim3(256), 0, s->st,
-                       s->A.d(), (long)s->np, s->dinv.d() + j * T * T, (long)(j * T), w, z);
-  }
-  GH_HIP(hipGetLastError());
-  return GH_OK;
-}
-// x = L^-T w  (w is destroyed)
-static int trsv_backward(gh_chol* s, double* w, double* x, bool defer = false) {
-  const int64_t nt = s->np / T;
-  static const bool stepwise = getenv("GEORGE_AMD_TRSV_STEPS") != nullptr;
-  if (!stepwise) {
-    GH_CHECK(s->chain.ensure((size_t)(2 * nt + 2) * sizeof(unsigned)));
-    unsigned* flags = (unsigned*)s->chain.p + (nt + 1);
-    GH_CHECK(launch_trsv_bwd_chain(s->A.d(), (long)s->np, s->dinv.d(), nt, w, x, flags, s->st));
-    if (defer) return GH_OK;
-    int failed = 0;
-    GH_HIP(hipMemcpyAsync(&failed, flags + nt, sizeof(int), hipMemcpyDeviceToHost, s->st));
-    GH_HIP(hipStreamSynchronize(s->st));
-    if (failed) { gh_set_error("backward solve: a workgroup waited more than 2 s for its predecessor"); return GH_ERR_HIP; }
-    return GH_OK;
-  }
-  for (int64_t j = nt - 1; j >= 0; --j) {
-    hipLaunchKernelGGL(trsv_bwd_step, dim3((unsigned)(j + 1)), dim3(256), 0, s->st,
-                       s->A.d(), (long)s->np, s->dinv.d() + j * T * T, (long)(j * T), w, x);
-  }
-  GH_HIP(hipGetLastError());
-  return GH_OK;
-}
-
-extern "C" int gh_chol_dot_solve(gh_chol* s, const double* y, double* out) {
-  GH_CHECK(need_computed(s));
-  if (!y || !out) { gh_set_error("null argument"); return GH_ERR_BAD_ARG; }
-  // y^T K^-1 y = || L^-1 y ||^2 : one forward sweep (the reference does both, basic.py:102)
-  static const bool stepwise = getenv("GEORGE_AMD_TRSV_STEPS") != nullptr;
-  // (the chained kernel only READS its right-hand side: a device-resident y of full padded length is used where it lies)
-  const bool direct = !stepwise && s->np == s->n && gh_is_device_ptr(y);
-  if (!direct) GH_CHECK(load_vec(s, s->v0, y));
-  GH_CHECK(s->v1.ensure((size_t)s->np * sizeof(double)));
-  const long e = s->opts.profile ? s->next_ev() : -1;
-  if (e >= 0) GH_HIP(hipEventRecord(s->ev_pool[e].a, s->st));
-  GH_CHECK(trsv_forward(s, direct ? const_cast<double*>(y) : s->v0.d(), s->v1.d(), !stepwise));
-  const int* fail = stepwise ? nullptr : (const int*)((unsigned*)s->chain.p + s->np / T);
-  GH_CHECK(launch_dot(s->v1.d(), s->v1.d(), (long)s->np, s->scal.d() + 1, s->scal.d() + 72, s->st, fail));
-  if (e >= 0) GH_HIP(hipEventRecord(s->ev_pool[e].b, s->st));
-  double back[3] = {0.0, 0.0, 0.0};                     // [0] quadratic form, [1] (failure word of compute()), [2] the chain's time-out flag
-  GH_HIP(hipMemcpyAsync(back, s->scal.d() + 1, 3 * sizeof(double), hipMemcpyDeviceToHost, s->st));
-  GH_HIP(hipStreamSynchronize(s->st));
-  if (e >= 0) { float ms = 0; GH_HIP(hipEventElapsedTime(&ms, s->ev_pool[e].a, s->ev_pool[e].b)); s->prof.ms_solve = ms; }
-  if (!stepwise && back[2] != 0.0) { gh_set_error("forward solve: a workgroup waited more than 2 s for its predecessor"); return GH_ERR_HIP; }
-  *out = back[0];
-  return GH_OK;
-}
-
-// B (np x rp, row-major, zero padded) <- L^-1 B  (forward) and optionally L^-T (backward)
-// Two-level blocking: 128-row steps (multiplication by the stored diagonal inverse + a small
-// update) inside super-blocks of SB = 8 tiles, then ONE K = 128*SB update of everything below (above)
-// the super-block -- the right-hand side is swept N/(128*SB) times instead of N/128 times.
-// `tri`: B is the identity being overwritten by L^-1 (forward only): block row j is non-zero in
-// columns [0, (j+1)*128) only, so every product is clipped to those columns.
-static int trsm_multi(gh_chol* s, double* B, int64_t rp, bool forward, bool backward, bool tri = false) {
-  // (tiles per super-block; measured at N = 32768 with 4096 right-hand sides, both sweeps: 2 -> 167 ms, 4 -> 158.5,
-  //  8 -> 151.6, 16 -> 149.5; no difference at N = 8192; the switch that overrode it went in round 4)
-  const int64_t SB = 8;
-  const int64_t np = s->np, nt = np / T;
-  const double* L = s->A.d();
-  auto mm = [&](double* Cp, const double* Ap, int64_t lda, bool a_km, const double* Bp, int64_t M, int64_t N, int64_t K,
-                double alpha, double beta) -> int {
-    if (M <= 0 || N <= 0) return GH_OK;
-    GhGemm g{};
-    g.C = Cp; g.ldc = rp; g.A = Ap; g.lda = lda; g.B = Bp; g.ldb = rp;
-    g.M = M; g.N = N; g.K = K; g.alpha = alpha; g.beta = beta; g.a_km = a_km; g.b_km = false;
-    return gh_launch_gemm(g, s->st);
-  };
-  if (forward) {
-    for (int64_t J = 0; J < nt; J += SB) {
-      const int64_t Je = std::min<int64_t>(J + SB, nt);
-      for (int64_t j = J; j < Je; ++j) {
-        double* Bj = B + j * T * rp;
-        const int64_t nc = tri ? (j + 1) * T : rp;
-        GH_CHECK(mm(Bj, s->dinv.d() + j * T * T, T, true, Bj, T, nc, T, 1.0, 0.0));               // B_j <- L_jj^-1 B_j
-        GH_CHECK(mm(B + (j + 1) * T * rp, L + (j + 1) * T * np + j * T, np, true, Bj,
-                    (Je - j - 1) * T, nc, T, -1.0, 1.0));                                           // rows of the super-block
-      }
-      const int64_t nc = tri ? Je * T : rp;
-      GH_CHECK(mm(B + Je * T * rp, L + Je * T * np + J * T, np, true, B + J * T * rp,
-                  (nt - Je) * T, nc, (Je - J) * T, -1.0, 1.0));                                     // everything below
-    }
-  }
-  if (backward) {
-    for (int64_t Je = nt; Je > 0; Je -= SB) {
-      const int64_t J = std::max<int64_t>(Je - SB, 0);
-      for (int64_t j = Je - 1; j >= J; --j) {
-        double* Bj = B + j * T * rp;
-        GH_CHECK(mm(Bj, s->dinv.d() + j * T * T, T, false, Bj, T, rp, T, 1.0, 0.0));              // B_j <- L_jj^-T B_j
-        GH_CHECK(mm(B + J * T * rp, L + j * T * np + J * T, np, false, Bj, (j - J) * T, rp, T, -1.0, 1.0));
-      }
-      GH_CHECK(mm(B, L + J * T * np, np, false, B + J * T * rp, J * T, rp, (Je - J) * T, -1.0, 1.0));   // everything above
-    }
-  }
-  return GH_OK;
-}
-
-extern "C" int gh_chol_solve(gh_chol* s, const double* b, int64_t nrhs, double* out) {
-  GH_CHECK(need_computed(s));
-  if (!b || !out || nrhs <= 0) { gh_set_error("bad argument to solve"); return GH_ERR_BAD_ARG; }
-  const int64_t n = s->n, np = s->np;
-  if (nrhs == 1) {
-    GH_CHECK(load_vec(s, s->v0, b));
-    GH_CHECK(s->v1.ensure((size_t)np * sizeof(double)));
-    GH_CHECK(s->v2.ensure((size_t)np * sizeof(double)));
-    GH_CHECK(trsv_forward(s, s->v0.d(), s->v1.d()));
-    GH_CHECK(trsv_backward(s, s->v1.d(), s->v2.d()));
-    return gh_from_device(out, s->v2.d(), (size_t)n, s->st);
-  }
-  const int64_t rp = gh_round_up(nrhs, T);
-  GH_CHECK(s->rhs.ensure((size_t)np * rp * sizeof(double)));
-  GH_HIP(hipMemsetAsync(s->rhs.d(), 0, (size_t)np * rp * sizeof(double), s->st));
-  GH_HIP(hipMemcpy2DAsync(s->rhs.d(), rp * sizeof(double), b, nrhs * sizeof(double), nrhs * sizeof(double), n,
-                          gh_is_device_ptr(b) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->st));
-  GH_CHECK(trsm_multi(s, s->rhs.d(), rp, true, true));
-  GH_HIP(hipMemcpy2DAsync(out, nrhs * sizeof(double), s->rhs.d(), rp * sizeof(double), nrhs * sizeof(double), n,
-                          gh_is_device_ptr(out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s->st));
-  GH_HIP(hipStreamSynchronize(s->st));
-  return GH_OK;
-}
-
-extern "C" int gh_chol_apply_sqrt(gh_chol* s, const double* r, int64_t nrows, double* out) {
-  GH_CHECK(need_computed(s));
-  if (!r || !out || nrows <= 0) { gh_set_error("bad argument to apply_sqrt"); return GH_ERR_BAD_ARG; }
-  // out = r @ U with U = L^T (basic.py:114):  out[s][j] = sum_{k <= j} r[s][k] L[j][k]
-  const int64_t n = s->n, np = s->np, rr = gh_round_up(nrows, T);
-  GH_CHECK(s->rhs.ensure((size_t)rr * np * sizeof(double)));
-  GH_CHECK(s->work.ensure((size_t)rr * np * sizeof(double)));
-  GH_HIP(hipMemsetAsync(s->rhs.d(), 0, (size_t)rr * np * sizeof(double), s->st));
-  GH_HIP(hipMemcpy2DAsync(s->rhs.d(), np * sizeof(double), r, n * sizeof(double), n * sizeof(double), nrows,
-                          gh_is_device_ptr(r) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->st));
-  GhGemm g{};
-  g.C = s->work.d(); g.ldc = np; g.A = s->rhs.d(); g.lda = np; g.B = s->A.d(); g.ldb = np;
-  g.M = rr; g.N = np; g.K = np; g.alpha = 1.0; g.beta = 0.0; g.a_km = true; g.b_km = true; g.khi_col = true;
-  GH_CHECK(gh_launch_gemm(g, s->st));
-  GH_HIP(hipMemcpy2DAsync(out, n * sizeof(double), s->work.d(), np * sizeof(double), n * sizeof(double), nrows,
-                          gh_is_device_ptr(out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s->st));
-  GH_HIP(hipStreamSynchronize(s->st));
-  return GH_OK;
-}
-
-// Linv (np x np) <- L^-1: forward substitution on the identity, exploiting the lower-triangular right-hand side (tri = true)
-static int linv_into(gh_chol* s, double* Linv) {
-  const int64_t np = s->np;
-  GH_HIP(hipMemsetAsync(Linv, 0, (size_t)np * np * sizeof(double), s->st));
-  hipLaunchKernelGGL(eye_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s->st, Linv, (long)np, (long)np);
-  GH_HIP(hipGetLastError());
-  return trsm_multi(s, Linv, np, true, false, true);
-}
-// W (np x np) <- K^-1, lower triangle valid.  Uses K^-1 = L^-T L^-1:
-//   Linv = L^-1 (forward substitution on the identity), K^-1 = Linv^T Linv (k >= max(i, j)).
-static int inverse_lower(gh_chol* s, double* W /* np*np */, double* Linv /* np*np scratch */) {
-  const int64_t np = s->np;
-  GH_CHECK(linv_into(s, Linv));
-  GhGemm q{};
-  q.C = W; q.ldc = np; q.A = Linv; q.lda = np; q.B = Linv; q.ldb = np;
-  q.M = np; q.N = np; q.K = np; q.alpha = 1.0; q.beta = 0.0; q.a_km = false; q.b_km = false;
-  q.lower = true; q.klo_max = true;
-  return gh_launch_gemm(q, s->st);
-}
-
-extern "C" int gh_chol_get_inverse(gh_chol* s, double* out) {
-  GH_CHECK(need_computed(s));
-  if (!out) { gh_set_error("null output"); return GH_ERR_BAD_ARG; }
-  const int64_t n = s->n, np = s->np;
-  GH_CHECK(s->work.ensure((size_t)np * np * sizeof(double)));
-  GH_CHECK(s->work2.ensure((size_t)np * np * sizeof(double)));
-  GH_CHECK(inverse_lower(s, s->work.d(), s->work2.d()));
-  // full symmetric n x n result (work2 is free again)
-  double* full = s->work2.d();
-  const long tot = (long)n * n;
-  hipLaunchKernelGGL(symmetrize_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s->st, s->work.d(), (long)np, full, (long)n, (long)n);
-  GH_HIP(hipGetLastError());
-  return gh_from_device(out, full, (size_t)tot, s->st);
-}
-
-// Everything of gh_chol_predict but its synchronisation, enqueued on the main stream.  keep_cov: the covariance is formed in
-// s->work (mp x mp, pitch mp; the caller's cov may then be NULL) for a caller that goes on with it on the device
-// (gh_chol_sample_conditional); *dmu_out: the mean on the device (in s->scratch), *xs_dev_out: the test points there (xsd owns
-// them when they came from the host).  mu may be NULL with keep_cov.
-static int predict_enqueue(gh_chol* s, gh_kernel* k, const double* r, const double* xs, int64_t m,
-                           double* mu, double* var, double* cov, bool keep_cov, GhBuf& xsd, double** dmu_out,
-                           const double** xs_dev_out) {
-  const int64_t n = s->n, np = s->np, mp = gh_round_up(m, T);
-  hipStream_t st = s->st;
-  // z = L^-1 r
-  GH_CHECK(load_vec(s, s->v0, r));
-  GH_CHECK(s->v1.ensure((size_t)np * sizeof(double)));
-  GH_CHECK(trsv_forward(s, s->v0.d(), s->v1.d()));
-  // V = L^-1 K(x, xs)   (np x mp): built on the device, forward substitution only, because
-  // K*s K^-1 K*s^T = V^T V and K*s K^-1 r = V^T z  (gp.py:532-545 does both sweeps on the host)
-  const double* xs_dev = xs;
-  if (!gh_is_device_ptr(xs)) {
-    GH_CHECK(xsd.ensure((size_t)m * s->ndim * sizeof(double)));
-    GH_CHECK(gh_to_device(xsd.d(), xs, (size_t)m * s->ndim, st));
-    xs_dev = xsd.d();
-  }
-  GH_CHECK(s->rhs.ensure((size_t)np * mp * sizeof(double)));
-  GH_CHECK(gh_launch_kmat(k, s->x.d(), n, xs_dev, m, nullptr, s->rhs.d(), mp, np, mp, 0, 0, false, false, st));
-  GH_CHECK(trsm_multi(s, s->rhs.d(), mp, true, false));
-  // column reductions
-  const int64_t nchunks = std::min<int64_t>(64, np / T);
-  const int64_t rows_per = gh_round_up((np + nchunks - 1) / nchunks, 1);
-  GH_CHECK(s->scratch.ensure((size_t)(2 * nchunks * mp + 2 * mp) * sizeof(double)));
-  double* pmu = s->scratch.d();
-  double* pvar = pmu + nchunks * mp;
-  double* dmu = pvar + nchunks * mp;
-  double* dvar = dmu + mp;
-  hipLaunchKernelGGL(colreduce_kernel, dim3((unsigned)((mp + 255) / 256), (unsigned)nchunks), dim3(256), 0, st,
-                     s->rhs.d(), (long)mp, (long)np, (long)rows_per, s->v1.d(), pmu, pvar, (long)mp);
-  GH_HIP(hipGetLastError());
-  if (var) GH_CHECK(gh_launch_kdiag(k, xs_dev, xs_dev, m, dvar, st));           // gp.py:539
-  hipLaunchKernelGGL(colfinal_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
-                     pmu, pvar, (long)nchunks, (long)mp, (long)m, dmu, var ? dvar : nullptr);
-  GH_HIP(hipGetLastError());
-  if (mu) GH_CHECK(gh_from_device(mu, dmu, (size_t)m, st));
-  if (var) GH_CHECK(gh_from_device(var, dvar, (size_t)m, st));
-  if (cov || keep_cov) {
-    // cov = K(xs, xs) - V^T V      (gp.py:543-545)
-    GH_CHECK(s->work.ensure((size_t)mp * mp * sizeof(double)));
-    GH_CHECK(gh_launch_kmat(k, xs_dev, m, xs_dev, m, nullptr, s->work.d(), mp, mp, mp, 0, 0, true, false, st));
-    GhGemm g{};
-    g.C = s->work.d(); g.ldc = mp; g.A = s->rhs.d(); g.lda = mp; g.B = s->rhs.d(); g.ldb = mp;
-    g.M = mp; g.N = mp; g.K = np; g.alpha = -1.0; g.beta = 1.0; g.a_km = false; g.b_km = false;
-    GH_CHECK(gh_launch_gemm(g, st));
-    if (cov)
-      GH_HIP(hipMemcpy2DAsync(cov, m * sizeof(double), s->work.d(), mp * sizeof(double), m * sizeof(double), m,
-                              gh_is_device_ptr(cov) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
-  }
-  if (dmu_out) *dmu_out = dmu;
-  if (xs_dev_out) *xs_dev_out = xs_dev;
-  return GH_OK;
-}
-
-extern "C" int gh_chol_predict(gh_chol* s, gh_kernel* k, const double* r, const double* xs, int64_t m,
-                               double* mu, double* var, double* cov) {
-  GH_CHECK(need_computed(s));
-  if (!k || !r || !xs || !mu || m <= 0) { gh_set_error("bad argument to predict"); return GH_ERR_BAD_ARG; }
-  if (k->ndim != s->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
-  GH_CHECK(k->upload());
-  GhBuf xsd;
-  GH_CHECK(predict_enqueue(s, k, r, xs, m, mu, var, cov, false, xsd, nullptr, nullptr));
-  GH_HIP(hipStreamSynchronize(s->st));
-  return GH_OK;
-}
-
-// Input derivatives of the prediction on a computed handle (no reference counterpart; the formulas are in the header).  mu and var
-// come out of predict_enqueue's own launches, bit for bit gh_chol_predict's.  Then alpha = L^-T z by the backward sweep and, only
-// for dvar, W = L^-T V by trsm_multi backward IN PLACE in s->rhs -- predict's column reductions, the last readers of V, are ahead
-// of it on the stream, so no second np x mp buffer exists -- and the fused evaluate-and-reduce kernel of gh_predgrad.hip.  The
-// results gather in s->work and leave in one batch of copies before the only synchronisation this function adds to predict's.
-// With dmu alone (mu, var and dvar all NULL) nothing needs V: the two sweeps for alpha, the kernel, one synchronisation.
-extern "C" int gh_chol_predict_grad(gh_chol* s, gh_kernel* k, const double* r, const double* xs, int64_t m,
-                                    double* mu, double* var, double* dmu, double* dvar) {
-  GH_CHECK(need_computed(s));
-  if (!k || !r || !xs || !dmu || m <= 0) { gh_set_error("bad argument to predict_grad"); return GH_ERR_BAD_ARG; }
-  if (k->ndim != s->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
-  GH_CHECK(k->upload());
-  hipStream_t st = s->st;
-  const int64_t n = s->n, np = s->np, mp = gh_round_up(m, T), nd = s->ndim, nt = np / T;
-  // [var (mp) | dmu (m nd) | dvar (m nd) | partial rows]; the mean stays where predict_enqueue leaves it (s->scratch)
-  const size_t head = (size_t)(mp + 2 * m * nd);
-  GH_CHECK(s->work.ensure((head + gh_predgrad_work_doubles(n, m, (int)nd, dvar != nullptr)) * sizeof(double)));
-  double* var_dev = s->work.d();
-  double* dmu_dev = var_dev + mp;
-  double* dvar_dev = dmu_dev + m * nd;
-  double* partial = dvar_dev + m * nd;
-  GhBuf xsd;
-  double* mu_dev = nullptr;
-  const double* xs_dev = nullptr;
-  static const bool stepwise = getenv("GEORGE_AMD_TRSV_STEPS") != nullptr;
-  const bool values = mu || var || dvar;                 // anything that needs V = L^-1 K(x, xs)
-  if (values) {
-    GH_CHECK(predict_enqueue(s, k, r, xs, m, nullptr, var ? var_dev : nullptr, nullptr, false, xsd, &mu_dev, &xs_dev));
-  } else {
-    // dmu alone needs alpha only: the forward sweep of predict_enqueue (the same launch: the same z, alpha and dmu bits) and
-    // neither K(x, xs) nor a substitution with mp right-hand sides -- 0.3 instead of 2 ms at N = 4096, 7 instead of 38 at 65 536
-    GH_CHECK(load_vec(s, s->v0, r));
-    GH_CHECK(s->v1.ensure((size_t)np * sizeof(double)));
-    GH_CHECK(trsv_forward(s, s->v0.d(), s->v1.d(), true));
-    xs_dev = xs;
-    if (!gh_is_device_ptr(xs)) {
-      GH_CHECK(xsd.ensure((size_t)m * nd * sizeof(double)));
-      GH_CHECK(gh_to_device(xsd.d(), xs, (size_t)m * nd, st));
-      xs_dev = xsd.d();
-    }
-  }
-  GH_CHECK(s->v2.ensure((size_t)np * sizeof(double)));
-  GH_CHECK(trsv_backward(s, s->v1.d(), s->v2.d(), true));                       // alpha = L^-T z
-  if (dvar) GH_CHECK(trsm_multi(s, s->rhs.d(), mp, false, true));               // W = L^-T V
-  GH_CHECK(gh_launch_predgrad(k, s->x.d(), n, xs_dev, m, s->v2.d(), dvar ? s->rhs.d() : nullptr, mp, dmu_dev,
-                              dvar ? dvar_dev : nullptr, partial, st));
-  auto out = [&](double* dst, const double* src, size_t count) -> int {
-    GH_HIP(hipMemcpyAsync(dst, src, count * sizeof(double), gh_is_device_ptr(dst) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
-    return GH_OK;
-  };
-  if (mu) GH_CHECK(out(mu, mu_dev, (size_t)m));
-  if (var) GH_CHECK(out(var, var_dev, (size_t)m));
-  GH_CHECK(out(dmu, dmu_dev, (size_t)(m * nd)));
-  if (dvar) GH_CHECK(out(dvar, dvar_dev, (size_t)(m * nd)));
-  int failed = 0, failed_fwd = 0;                        // the sweeps' time-out flags (the forward one: only where it was deferred)
-  if (!stepwise) GH_HIP(hipMemcpyAsync(&failed, (unsigned*)s->chain.p + (nt + 1) + nt, sizeof(int), hipMemcpyDeviceToHost, st));
-  if (!stepwise && !values) GH_HIP(hipMemcpyAsync(&failed_fwd, (unsigned*)s->chain.p + nt, sizeof(int), hipMemcpyDeviceToHost, st));
-  GH_HIP(hipStreamSynchronize(st));
-  if (failed_fwd) { gh_set_error("forward solve: a workgroup waited more than 2 s for its predecessor"); return GH_ERR_HIP; }
-  if (failed) { gh_set_error("backward solve: a workgroup waited more than 2 s for its predecessor"); return GH_ERR_HIP; }
-  return GH_OK;
-}
-
-// Posterior draws on a computed handle: mu and cov exactly as gh_chol_predict forms them (the same launches), cov left on the
-// device and factored there by the pivoted Cholesky of gh_pstrf.hip, draws = mu + z L^T as one GEMM.  The default threshold
-// is on the PRIOR's scale, m eps max diag K(xs, xs): the rounding error of cov = K** - V^T V is that of its two terms, however
-// small the posterior variances are.  DESIGN.md section 4, "Sampling".
-extern "C" int gh_chol_sample_conditional(gh_chol* s, gh_kernel* k, const double* r, const double* xs, int64_t m,
-                                          const double* z, int64_t nz, double tol, double* mu, double* draws, double* fac,
-                                          int64_t* rank) {
-  GH_CHECK(need_computed(s));
-  if (!k || !r || !xs || !z || !draws || !rank || m <= 0 || nz <= 0) { gh_set_error("bad argument to sample_conditional"); return GH_ERR_BAD_ARG; }
-  if (k->ndim != s->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
-  GH_CHECK(k->upload());
-  hipStream_t st = s->st;
-  const int64_t mp = gh_round_up(m, T);
-  GhBuf xsd;
-  double* dmu = nullptr;
-  const double* xs_dev = nullptr;
-  GH_CHECK(predict_enqueue(s, k, r, xs, m, mu, nullptr, nullptr, true, xsd, &dmu, &xs_dev));
-  // [prior diagonal (mp) | tol (1, padded to 32 doubles) | the work arrays of gh_sample_enqueue]
-  const size_t head = (size_t)(mp + 32) * sizeof(double), wb = gh_sample_work_bytes(m, nz, 1);
-  GH_CHECK(s->samp.ensure(head + wb));
-  double* diag = s->samp.d();
-  double* tol_dev = diag + mp;
-  if (tol < 0.0) {
-    GH_CHECK(gh_launch_kdiag(k, xs_dev, xs_dev, m, diag, st));
-    GH_CHECK(gh_launch_prior_tol(diag, m, tol_dev, st));
-  }
-  GhSample q{};
-  q.cov = s->work.d(); q.lda = mp; q.stride = mp * mp; q.m = m; q.nbatch = 1;
-  q.tol = tol; q.tol_dev = tol < 0.0 ? tol_dev : nullptr; q.mu = dmu;
-  q.z = z; q.nz = nz; q.draws = draws; q.fac = fac; q.rank = rank;
-  q.work = (char*)s->samp.p + head; q.work_bytes = s->samp.bytes - head;
-  const int rc = gh_sample_enqueue(q, st);
-  GH_HIP(hipStreamSynchronize(st));
-  return rc;
-}
-
-extern "C" int gh_chol_grad(gh_chol* s, gh_kernel* k, const uint32_t* which, const double* r,
-                            double* grad, double* alpha, double* diagA) {
-  GH_CHECK(need_computed(s));
-  if (!k || !which || !r || !grad) { gh_set_error("bad argument to grad"); return GH_ERR_BAD_ARG; }
-  if (k->ndim != s->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
-  GH_CHECK(k->upload());
-  const int64_t n = s->n, np = s->np;
-  hipStream_t st = s->st;
-  // alpha = K^-1 r                       (gp.py:429)
-  GH_CHECK(load_vec(s, s->v0, r));
-  GH_CHECK(s->v1.ensure((size_t)np * sizeof(double)));
-  GH_CHECK(s->v2.ensure((size_t)np * sizeof(double)));
-  GH_CHECK(trsv_forward(s, s->v0.d(), s->v1.d()));
-  GH_CHECK(trsv_backward(s, s->v1.d(), s->v2.d()));
-  // K^-1 (lower)                         (gp.py:436)
-  GH_CHECK(s->work.ensure((size_t)np * np * sizeof(double)));
-  GH_CHECK(s->work2.ensure((size_t)np * np * sizeof(double)));
-  GH_CHECK(inverse_lower(s, s->work.d(), s->work2.d()));
-  // 1/2 sum_ij A_ij dK_ij/dtheta, A = alpha alpha^T - K^-1   (gp.py:437,465-466), fused
-  GH_CHECK(s->v0.ensure((size_t)std::max<int64_t>(np, GH_MAX_GRAD) * sizeof(double)));
-  double* dgrad = s->v0.d();                       // v0 is free again
-  double* ddiag = s->v1.d();                       // so is v1
-  GH_CHECK(gh_launch_kgrad_reduce(k, which, s->x.d(), n, s->v2.d(), s->work.d(), np, dgrad, ddiag, s->scratch, st));
-  if (k->size > 0) GH_CHECK(gh_from_device(grad, dgrad, (size_t)k->size, st));
-  if (alpha) GH_CHECK(gh_from_device(alpha, s->v2.d(), (size_t)n, st));
-  if (diagA) GH_CHECK(gh_from_device(diagA, ddiag, (size_t)n, st));
-  GH_HIP(hipStreamSynchronize(st));
-  return GH_OK;
-}
-
-// ============================================================ information of the hyper-parameters
-// (no reference counterpart.)  F_ab = 1/2 tr(K^-1 D_a K^-1 D_b) in its symmetric form: with W_a = L^-1 D_a L^-T,
-// F_ab = 1/2 sum_ij W_a[i,j] W_b[i,j].  K^-1 is never formed; work2 = L^-1, work = the intermediate T_a = L^-1 D_a (lower
-// tiles), and a plane first holds D_a, then W_a (lower tiles).  Both products are triangular in k: N^3 / 3 + N^3 / 6
-// multiply-adds per kernel parameter, N^3 / 6 per diagonal one (its T_a is a column scaling of L^-1).  Resident when every
-// plane fits, else in blocks: one block resident, every later plane formed into one scratch plane and contracted against
-// the block -- a pair's per-tile sums and their final tree are the same launches' arithmetic either way, so the bits do
-// not depend on the blocking.  DESIGN.md section 4, "Information of the hyper-parameters".
-// plane <- W of one parameter.  A kernel parameter's plane holds D already when have_d (a resident call evaluates all of them
-// in one launch: one gh_eval_grad per pair of points); a diagonal parameter (kernel_param < 0) has drow, np entries.
-static int fisher_form_plane(gh_chol* s, gh_kernel* k, int kernel_param, bool have_d, const double* drow, double* plane) {
-  const int64_t np = s->np;
-  hipStream_t st = s->st;
-  double* Linv = s->work2.d();
-  double* Tm = s->work.d();
-  if (kernel_param >= 0) {
-    if (!have_d) {
-      GhFisherSel sel{};
-      sel.n = 1; sel.idx[0] = (short)kernel_param;
-      GH_CHECK(gh_launch_fisher_planes(k, sel, s->x.d(), s->n, np, plane, st));
-    }
-    GhGemm g{};                                        // T = L^-1 D (lower tiles; L^-1 lower-triangular: k <= row)
-    g.C = Tm; g.ldc = np; g.A = Linv; g.lda = np; g.B = plane; g.ldb = np;
-    g.M = np; g.N = np; g.K = np; g.alpha = 1.0; g.beta = 0.0; g.a_km = true; g.b_km = false; g.lower = true; g.khi_row = true;
-    GH_CHECK(gh_launch_gemm(g, st));
-  } else {
-    GH_CHECK(gh_launch_fisher_scale(Linv, np, drow, Tm, st));
-  }
-  GhGemm g{};                                          // W = T L^-T (lower tiles; k <= column)
-  g.C = plane; g.ldc = np; g.A = Tm; g.lda = np; g.B = Linv; g.ldb = np;
-  g.M = np; g.N = np; g.K = np; g.alpha = 1.0; g.beta = 0.0; g.a_km = true; g.b_km = true; g.lower = true; g.khi_col = true;
-  return gh_launch_gemm(g, st);
-}
-
-extern "C" int gh_chol_fisher(gh_chol* s, gh_kernel* k, const uint32_t* which, const double* diag_rows, int32_t n_diag,
-                              int64_t max_bytes, double* fisher) {
-  GH_CHECK(need_computed(s));
-  if (!k || !fisher || n_diag < 0 || n_diag > GH_FISHER_MAX_DIAG || (n_diag > 0 && !diag_rows) || (k->size > 0 && !which)) {
-    gh_set_error("bad argument to fisher"); return GH_ERR_BAD_ARG;
-  }
-  if (k->ndim != s->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
-  GH_CHECK(k->upload());
-  const int64_t n = s->n, np = s->np;
-  hipStream_t st = s->st;
-  const int ptot = n_diag + k->size;
-  if (ptot == 0) return GH_OK;
-  // the active planes: the diagonal ones, then the selected kernel parameters
-  GhFisherMap map{};
-  int kpar[GH_MAX_GRAD + GH_FISHER_MAX_DIAG];          // kernel parameter of an active plane, -1 - p for diagonal row p
-  int Q = 0;
-  for (int p = 0; p < n_diag; ++p) { kpar[Q] = -1 - p; map.out[Q++] = (short)p; }
-  for (int p = 0; p < k->size; ++p) if (which[p]) { kpar[Q] = p; map.out[Q++] = (short)(n_diag + p); }
-  map.q = Q; map.ptot = ptot;
-  if (Q == 0) {                                        // everything masked: zeros
-    GH_CHECK(s->scratch.ensure((size_t)ptot * ptot * sizeof(double)));
-    GH_HIP(hipMemsetAsync(s->scratch.d(), 0, (size_t)ptot * ptot * sizeof(double), st));
-    GH_CHECK(gh_from_device(fisher, s->scratch.d(), (size_t)ptot * ptot, st));
-    GH_HIP(hipStreamSynchronize(st));
-    return GH_OK;
-  }
-  // how many planes beside L^-1 and T: the caller's budget and what the device can give (what the handle's own work
-  // buffers hold now is re-used)
-  const size_t pb = (size_t)np * np * sizeof(double);
-  int64_t fit = Q;
-  if (max_bytes > 0) fit = std::min<int64_t>(fit, max_bytes / (int64_t)pb - 2);
-  size_t mfree = 0, mtot = 0;
-  GH_HIP(hipMemGetInfo(&mfree, &mtot));
-  const size_t have = mfree + s->work.bytes + s->work2.bytes + s->fish.bytes + gh_pool_parked_bytes();
-  fit = std::min<int64_t>(fit, (int64_t)(have / pb) - 2);
-  if (Q > 1 && fit < 2) {
-    gh_set_error("fisher: not even two planes of %zu bytes fit beside L^-1 and the intermediate (max_bytes %lld, device %zu)",
-                 pb, (long long)max_bytes, have);
-    return GH_ERR_NOMEM;
-  }
-  if (fit < 1) { gh_set_error("fisher: no room for a plane of %zu bytes", pb); return GH_ERR_NOMEM; }
-  const bool resident = fit >= Q;
-  const int blk = resident ? Q : (int)fit - 1;         // planes of a block; blocked: one more plane is the scratch
-  const int nslots = resident ? Q : blk + 1;
-  GH_CHECK(s->work.ensure(pb));
-  GH_CHECK(s->work2.ensure(pb));
-  GH_CHECK(s->fish.ensure((size_t)nslots * pb));
-  const int64_t tm = np / T, nblk = tm * (tm + 1) / 2;
-  const int64_t npairs = (int64_t)Q * (Q + 1) / 2;
-  // scratch: [diagonal rows (n_diag np) | partial (nblk npairs) | pair sums | F (ptot^2)]
-  const size_t n_rows = (size_t)n_diag * np, n_part = (size_t)(nblk * npairs);
-  GH_CHECK(s->scratch.ensure((n_rows + n_part + (size_t)npairs + (size_t)ptot * ptot) * sizeof(double)));
-  double* drows = s->scratch.d();
-  double* partial = drows + n_rows;
-  double* pairsum = partial + n_part;
-  double* F = pairsum + npairs;
-  GH_HIP(hipMemsetAsync(F, 0, (size_t)ptot * ptot * sizeof(double), st));
-  if (n_diag > 0) {
-    GH_HIP(hipMemsetAsync(drows, 0, n_rows * sizeof(double), st));
-    GH_HIP(hipMemcpy2DAsync(drows, np * sizeof(double), diag_rows, n * sizeof(double), n * sizeof(double), n_diag,
-                            gh_is_device_ptr(diag_rows) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-  }
-  GH_CHECK(linv_into(s, s->work2.d()));
-  auto slot = [&](int i) { return s->fish.d() + (size_t)i * np * np; };
-  auto form = [&](int a, double* plane) -> int {
-    return fisher_form_plane(s, k, kpar[a], resident, kpar[a] < 0 ? drows + (size_t)(-1 - kpar[a]) * np : nullptr, plane);
-  };
-  if (resident && Q > n_diag) {                        // every kernel plane's D in one launch: the slots behind the diagonal ones
-    GhFisherSel sel{};
-    for (int a = n_diag; a < Q; ++a) sel.idx[sel.n++] = (short)kpar[a];
-    GH_CHECK(gh_launch_fisher_planes(k, sel, s->x.d(), n, np, slot(n_diag), st));
-  }
-  const double* pa[GH_MAX_GRAD + GH_FISHER_MAX_DIAG];
-  int ia[GH_MAX_GRAD + GH_FISHER_MAX_DIAG];
-  for (int b0 = 0; b0 < Q; b0 += blk) {
-    const int b1 = std::min(b0 + blk, Q);
-    for (int a = b0; a < b1; ++a) {
-      GH_CHECK(form(a, slot(a - b0)));
-      pa[a - b0] = slot(a - b0); ia[a - b0] = a;
-    }
-    GH_CHECK(gh_launch_fisher_pairs(pa, ia, b1 - b0, nullptr, nullptr, 0, Q, np, partial, st));
-    for (int c = b1; c < Q; ++c) {                     // (blocked only: a resident call has one block)
-      const double* pc = slot(blk);
-      GH_CHECK(form(c, slot(blk)));
-      GH_CHECK(gh_launch_fisher_pairs(pa, ia, b1 - b0, &pc, &c, 1, Q, np, partial, st));
-    }
-  }
-  GH_CHECK(gh_launch_kgrad_final(partial, nblk, (int)npairs, pairsum, st));
-  GH_CHECK(gh_launch_fisher_mirror(pairsum, map, F, st));
-  GH_CHECK(gh_from_device(fisher, F, (size_t)ptot * ptot, st));
-  GH_HIP(hipStreamSynchronize(st));
-  return GH_OK;
-}
-
-// ============================================================ fused objective
-// nll and its gradient (gp.py:470-480; the optimiser loop of docs/tutorials/hyper.rst:131-152) as
-// ONE call: build K -> factor -> log-det -> z = L^-1 r (used for r^T K^-1 r = |z|^2 AND, through
-// the backward sweep, for alpha) -> K^-1 -> 1/2 sum A_ij dK_ij/dtheta.  Nothing is synchronised
-// until the very end; only scalars and N-vectors reach the host.  `grad == NULL`: the
-// log-likelihood pieces only (compute + dot_solve without the second sweep and the inverse).
-extern "C" int gh_chol_objective(gh_chol* s, gh_kernel* k, const double* x, int64_t n, int32_t ndim,
-                                 const double* yerr, const double* r, const uint32_t* which,
-                                 double* logdet, double* quad, double* grad, double* alpha, double* diagA) {
-  if (!r || !logdet || !quad) { gh_set_error("bad argument to objective"); return GH_ERR_BAD_ARG; }
-  if (grad && !which) { gh_set_error("objective: gradient requested without a parameter mask"); return GH_ERR_BAD_ARG; }
-  ComputeCtx c;
-  GH_CHECK(compute_enqueue(s, k, x, n, ndim, yerr, c));
-  hipStream_t st = s->st;
-  if (s->tail && s->tail != st && s->ev_sync[1]) {      // (the solves and the gradient run on the main stream: it joins here)
-    GH_HIP(hipEventRecord(s->ev_sync[1], s->tail));
-    GH_HIP(hipStreamWaitEvent(st, s->ev_sync[1], 0));
-  }
-  const int64_t np = s->np, nt = np / T;
-  const bool want_alpha = grad || alpha || diagA;
-  GH_CHECK(load_vec(s, s->v0, r));
-  GH_CHECK(s->v1.ensure((size_t)np * sizeof(double)));
-  static const bool stepwise = getenv("GEORGE_AMD_TRSV_STEPS") != nullptr;
-  GH_CHECK(trsv_forward(s, s->v0.d(), s->v1.d(), true));
-  GH_CHECK(launch_dot(s->v1.d(), s->v1.d(), (long)np, s->scal.d() + 1, s->scal.d() + 72, st,
-                      stepwise ? nullptr : (const int*)((const unsigned*)s->chain.p + nt)));           // -> scal[3]
-  double* dgrad = nullptr;
-  double* ddiag = nullptr;
-  if (want_alpha) {
-    GH_CHECK(s->v2.ensure((size_t)np * sizeof(double)));
-    GH_CHECK(trsv_backward(s, s->v1.d(), s->v2.d(), true));                          // alpha (v1 is consumed)
-  }
-  if (grad || diagA) {
-    GH_CHECK(s->work.ensure((size_t)np * np * sizeof(double)));
-    GH_CHECK(s->work2.ensure((size_t)np * np * sizeof(double)));
-    GH_CHECK(inverse_lower(s, s->work.d(), s->work2.d()));
-    GH_CHECK(s->v0.ensure((size_t)std::max<int64_t>(np, GH_MAX_GRAD) * sizeof(double)));
-    dgrad = s->v0.d();
-    ddiag = s->v1.d();
-    static const uint32_t none[GH_MAX_GRAD] = {0};
-    GH_CHECK(gh_launch_kgrad_reduce(k, grad ? which : none, s->x.d(), n, s->v2.d(), s->work.d(), np, dgrad, ddiag, s->scratch, st));
-  }
-  double host[4] = {0.0, 0.0, 0.0, 0.0};                // log-det, quadratic form, failure word (bits), forward chain's time-out flag
-  int fail_b = 0;
-  GH_HIP(hipMemcpyAsync(host, s->scal.d(), 4 * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (!stepwise && want_alpha)
-    GH_HIP(hipMemcpyAsync(&fail_b, (const unsigned*)s->chain.p + (nt + 1) + nt, sizeof(int), hipMemcpyDeviceToHost, st));
-  if (grad && k->size > 0) GH_CHECK(gh_from_device(grad, dgrad, (size_t)k->size, st));
-  if (alpha) GH_CHECK(gh_from_device(alpha, s->v2.d(), (size_t)n, st));
-  if (diagA) GH_CHECK(gh_from_device(diagA, ddiag, (size_t)n, st));
-  GH_HIP(hipStreamSynchronize(st));
-  long long info_host = 0;
-  memcpy(&info_host, &host[2], sizeof(long long));
-  GH_CHECK(compute_finish(s, c, host[0], info_host, logdet));
-  if ((!stepwise && host[3] != 0.0) || fail_b) { gh_set_error("objective: a chained solve waited more than 2 s for its predecessor"); return GH_ERR_HIP; }
-  *quad = host[1];
-  return GH_OK;
-}
-
-// ============================================================ leave-one-out cross-validation
-// (no reference counterpart: src/george/gp.py has no cross-validation.)  With c_i = (K^-1)_ii and alpha = K^-1 r the prediction of
-// y_i from all other points has residual alpha_i / c_i and variance 1 / c_i (GPML 5.4.2), and the gradient of the log
-// pseudo-likelihood is sum_ij B_ij dK_ij/dtheta with B = 1/2 (v alpha^T + alpha v^T) - S S^T, S = K^-1 diag(sqrt(w)), v = K^-1 u:
-// ONE triangular N^3 product for any number of parameters ("Leave-one-out cross-validation").
-//   value path:    alpha -> work = L^-1 -> c = column sums of squares -> per-point kernel -> sum of lpd.   K^-1 is never formed.
-//   gradient path: alpha -> work = K^-1 (work2 = L^-1) -> c = diag -> per-point kernel -> v -> work2 = S -> work = S S^T (lower)
-//                  -> the contraction (gh_launch_kgrad_reduce_loo).
-// Everything is enqueued on s->st; results stay on the device (s->lv, s->v0 = grad, s->v1 = diagB, s->scal[1] = sum of lpd,
-// s->scal[3] != 0: a chained sweep timed out) until loo_fetch().
-enum { LV_RESID = 0, LV_VAR, LV_LPD, LV_SW, LV_C, LV_ALPHA, LV_V, LV_COUNT };     // (alpha and v adjacent: gh_launch_kgrad_reduce_loo)
-static int loo_note_fail(gh_chol* s) {
-  static const bool stepwise = getenv("GEORGE_AMD_TRSV_STEPS") != nullptr;
-  if (stepwise) return GH_OK;
-  const int64_t nt = s->np / T;
-  const int* flags = (const int*)s->chain.p;
-  hipLaunchKernelGGL(chain_fail_note_kernel, dim3(1), dim3(64), 0, s->st, flags + nt, flags + (nt + 1) + nt, s->scal.d() + 3);
-  GH_HIP(hipGetLastError());
-  return GH_OK;
-}
-static int loo_enqueue(gh_chol* s, gh_kernel* k, const uint32_t* which, const double* r, bool grad_path) {
-  const int64_t n = s->n, np = s->np;
-  hipStream_t st = s->st;
-  GH_CHECK(s->lv.ensure((size_t)LV_COUNT * np * sizeof(double)));
-  GH_CHECK(s->v0.ensure((size_t)std::max<int64_t>(np, GH_MAX_GRAD) * sizeof(double)));
-  GH_CHECK(s->v1.ensure((size_t)np * sizeof(double)));
-  double* lv = s->lv.d();
-  GH_HIP(hipMemsetAsync(s->scal.d() + 3, 0, sizeof(double), st));
-  // alpha = K^-1 r
-  double* alpha = lv + LV_ALPHA * np;
-  GH_CHECK(load_vec(s, s->v0, r));
-  GH_CHECK(trsv_forward(s, s->v0.d(), s->v1.d(), true));
-  GH_CHECK(trsv_backward(s, s->v1.d(), alpha, true));
-  GH_CHECK(loo_note_fail(s));
-  const unsigned gv = (unsigned)((np + 255) / 256);
-  if (!grad_path) {
-    // c_i = sum_{k >= i} (L^-1)_ki^2: the diagonal of K^-1 = L^-T L^-1 without the product
-    GH_CHECK(s->work.ensure((size_t)np * np * sizeof(double)));
-    double* Linv = s->work.d();
-    GH_CHECK(linv_into(s, Linv));
-    const int64_t nchunks = std::min<int64_t>(64, np / T);
-    const int64_t rows_per = (np + nchunks - 1) / nchunks;
-    GH_CHECK(s->scratch.ensure((size_t)nchunks * np * sizeof(double)));
-    hipLaunchKernelGGL(colsumsq_kernel, dim3((unsigned)(np / LT), (unsigned)nchunks), dim3(256), 0, st,
-                       Linv, (long)np, (long)np, (long)rows_per, s->scratch.d());
-    hipLaunchKernelGGL(colsumsq_final_kernel, dim3(gv), dim3(256), 0, st, s->scratch.d(), (long)nchunks, (long)np, lv + LV_C * np);
-    hipLaunchKernelGGL(loo_point_kernel, dim3(gv), dim3(256), 0, st, alpha, lv + LV_C * np, 1L, (long)n, (long)np,
-                       lv + LV_RESID * np, (double*)nullptr, lv + LV_VAR * np, lv + LV_LPD * np, lv + LV_SW * np);
-    GH_HIP(hipGetLastError());
-  } else {
-    GH_CHECK(s->work.ensure((size_t)np * np * sizeof(double)));
-    GH_CHECK(s->work2.ensure((size_t)np * np * sizeof(double)));
-    GH_CHECK(inverse_lower(s, s->work.d(), s->work2.d()));
-    hipLaunchKernelGGL(loo_point_kernel, dim3(gv), dim3(256), 0, st, alpha, s->work.d(), (long)np + 1, (long)n, (long)np,
-                       lv + LV_RESID * np, s->v0.d(), lv + LV_VAR * np, lv + LV_LPD * np, lv + LV_SW * np);
-    GH_HIP(hipGetLastError());
-    // v = K^-1 u
-    GH_CHECK(trsv_forward(s, s->v0.d(), s->v1.d(), true));
-    GH_CHECK(trsv_backward(s, s->v1.d(), lv + LV_V * np, true));
-    GH_CHECK(loo_note_fail(s));
-    // work2 <- S = K^-1 diag(sqrt(w)), then work <- M = S S^T (lower tiles)
-    const long tm = (long)(np / LT);
-    hipLaunchKernelGGL(loo_mirror_scale_kernel, dim3((unsigned)(tm * (tm + 1) / 2)), dim3(256), 0, st,
-                       s->work.d(), (long)np, lv + LV_SW * np, s->work2.d());
-    GH_HIP(hipGetLastError());
-    GhGemm g{};
-    g.C = s->work.d(); g.ldc = np; g.A = s->work2.d(); g.lda = np; g.B = s->work2.d(); g.ldb = np;
-    g.M = np; g.N = np; g.K = np; g.alpha = 1.0; g.beta = 0.0; g.a_km = true; g.b_km = true; g.lower = true;
-    GH_CHECK(gh_launch_gemm(g, st));
-    static const uint32_t none[GH_MAX_GRAD] = {0};
-    static_assert(LV_V == LV_ALPHA + 1, "gh_launch_kgrad_reduce_loo reads v one leading dimension (np) behind alpha");
-    GH_CHECK(gh_launch_kgrad_reduce_loo(k, which ? which : none, s->x.d(), n, alpha, s->work.d(), np,
-                                        s->v0.d(), s->v1.d(), s->scratch, st));       // (v0, v1 are free again)
-  }
-  return launch_sum(lv + LV_LPD * np, (long)n, s->scal.d() + 1, s->scal.d() + 72, st);
-}
-// the copies out (host or device destinations), enqueued on s->st
-static int loo_fetch(gh_chol* s, gh_kernel* k, double* resid, double* var, double* lpd, double* grad, double* v, double* diagB) {
-  const int64_t n = s->n, np = s->np;
-  hipStream_t st = s->st;
-  const double* lv = s->lv.d();
-  GH_CHECK(gh_from_device(resid, lv + LV_RESID * np, (size_t)n, st));
-  GH_CHECK(gh_from_device(var, lv + LV_VAR * np, (size_t)n, st));
-  if (lpd) GH_CHECK(gh_from_device(lpd, lv + LV_LPD * np, (size_t)n, st));
-  if (grad && k->size > 0) GH_CHECK(gh_from_device(grad, s->v0.d(), (size_t)k->size, st));
-  if (v) GH_CHECK(gh_from_device(v, lv + LV_V * np, (size_t)n, st));
-  if (diagB) GH_CHECK(gh_from_device(diagB, s->v1.d(), (size_t)n, st));
-  return GH_OK;
-}
-
-extern "C" int gh_chol_loo(gh_chol* s, gh_kernel* k, const uint32_t* which, const double* r, double* lpd_sum, double* resid,
-                           double* var, double* lpd, double* grad, double* v, double* diagB) {
-  GH_CHECK(need_computed(s));
-  if (!k || !r || !lpd_sum || !resid || !var) { gh_set_error("bad argument to loo"); return GH_ERR_BAD_ARG; }
-  if (grad && !which) { gh_set_error("loo: gradient requested without a parameter mask"); return GH_ERR_BAD_ARG; }
-  if (k->ndim != s->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
-  GH_CHECK(k->upload());
-  GH_CHECK(loo_enqueue(s, k, grad ? which : nullptr, r, grad || v || diagB));
-  double host[4] = {0.0, 0.0, 0.0, 0.0};                // (log-det), sum of lpd, (failure word), the chains' time-out flag
-  GH_HIP(hipMemcpyAsync(host, s->scal.d(), 4 * sizeof(double), hipMemcpyDeviceToHost, s->st));
-  GH_CHECK(loo_fetch(s, k, resid, var, lpd, grad, v, diagB));
-  GH_HIP(hipStreamSynchronize(s->st));
-  if (host[3] != 0.0) { gh_set_error("loo: a chained solve waited more than 2 s for its predecessor"); return GH_ERR_HIP; }
-  *lpd_sum = host[1];
-  return GH_OK;
-}
-
-// build K -> factor -> log-det -> the sequence of gh_chol_loo, ONE synchronisation: the analogue of gh_chol_objective for the
-// leave-one-out objective.  The same launches as gh_chol_compute followed by gh_chol_loo: the same bits.
-extern "C" int gh_chol_loo_objective(gh_chol* s, gh_kernel* k, const double* x, int64_t n, int32_t ndim, const double* yerr,
-                                     const double* r, const uint32_t* which, double* logdet, double* lpd_sum,
-                                     double* resid, double* var, double* grad, double* v, double* diagB) {
-  if (!r || !logdet || !lpd_sum || !resid || !var) { gh_set_error("bad argument to loo_objective"); return GH_ERR_BAD_ARG; }
-  if (grad && !which) { gh_set_error("loo_objective: gradient requested without a parameter mask"); return GH_ERR_BAD_ARG; }
-  ComputeCtx c;
-  GH_CHECK(compute_enqueue(s, k, x, n, ndim, yerr, c));
-  hipStream_t st = s->st;
-  if (s->tail && s->tail != st && s->ev_sync[1]) {      // (the solves and the products run on the main stream: it joins here)
-    GH_HIP(hipEventRecord(s->ev_sync[1], s->tail));
-    GH_HIP(hipStreamWaitEvent(st, s->ev_sync[1], 0));
-  }
-  GH_CHECK(loo_enqueue(s, k, grad ? which : nullptr, r, grad || v || diagB));
-  double host[4] = {0.0, 0.0, 0.0, 0.0};                // log-det, sum of lpd, failure word (bits), the chains' time-out flag
-  GH_HIP(hipMemcpyAsync(host, s->scal.d(), 4 * sizeof(double), hipMemcpyDeviceToHost, st));
-  GH_CHECK(loo_fetch(s, k, resid, var, nullptr, grad, v, diagB));
-  GH_HIP(hipStreamSynchronize(st));
-  long long info_host = 0;
-  memcpy(&info_host, &host[2], sizeof(long long));
-  GH_CHECK(compute_finish(s, c, host[0], info_host, logdet));
-  if (host[3] != 0.0) { gh_set_error("loo_objective: a chained solve waited more than 2 s for its predecessor"); return GH_ERR_HIP; }
-  *lpd_sum = host[1];
-  return GH_OK;
-}
-
-// ============================================================ factor export / import
-// The reference's BasicSolver survives pickling COMPUTED (tests/test_pickle.py:21-36: its factor is a
-// NumPy array).  Here the factor lives in HBM, so it is packed on the device -- row i of the lower
-// triangle at offset i (i + 1) / 2, N (N + 1) / 2 doubles -- and copied out, together with the
-// inverses of the 128 x 128 diagonal blocks (Np / 128 x 128 x 128) that every solve multiplies by.
-__global__ void pack_lower_kernel(const double* A, long ld, long n, double* out) {
-  const long i = blockIdx.x;
-  const double* row = A + i * ld;
-  double* o = out + i * (i + 1) / 2;
-  for (long j = threadIdx.x; j <= i; j += blockDim.x) o[j] = row[j];
-}
-__global__ void unpack_lower_kernel(const double* in, long n, double* A, long ld, long np) {
-  const long i = blockIdx.x;                     // row of the padded matrix
-  double* row = A + i * ld;
-  if (i < n) {
-    const double* src = in + i * (i + 1) / 2;
-    for (long j = threadIdx.x; j < np; j += blockDim.x) row[j] = (j <= i) ? src[j] : 0.0;
-  } else {
-    for (long j = threadIdx.x; j < np; j += blockDim.x) row[j] = (j == i) ? 1.0 : 0.0;      // identity padding
-  }
-}
-extern "C" int64_t gh_chol_factor_size(const gh_chol* s) { return s ? s->n * (s->n + 1) / 2 : 0; }
-extern "C" int64_t gh_chol_dinv_size(const gh_chol* s) { return s ? (s->np / T) * T * T : 0; }
-extern "C" int gh_chol_export_factor(gh_chol* s, double* packed_lower, double* dinv_out) {
-  GH_CHECK(need_computed(s));
-  if (!packed_lower || !dinv_out) { gh_set_error("null output"); return GH_ERR_BAD_ARG; }
-  const int64_t n = s->n, np = s->np;
-  const size_t cnt = (size_t)n * (n + 1) / 2;
-  GH_CHECK(s->work.ensure(cnt * sizeof(double)));
-  hipLaunchKernelGGL(pack_lower_kernel, dim3((unsigned)n), dim3(256), 0, s->st, s->A.d(), (long)np, (long)n, s->work.d());
-  GH_HIP(hipGetLastError());
-  GH_CHECK(gh_from_device(packed_lower, s->work.d(), cnt, s->st));
-  GH_CHECK(gh_from_device(dinv_out, s->dinv.d(), (size_t)(np / T) * T * T, s->st));
-  GH_HIP(hipStreamSynchronize(s->st));
-  return GH_OK;
-}
-extern "C" int gh_chol_import_factor(gh_chol* s, int64_t n, int32_t ndim, const double* x, const double* packed_lower,
-                                     const double* dinv_in, double logdet) {
-  if (!s || n <= 0 || ndim <= 0 || !x || !packed_lower || !dinv_in) { gh_set_error("bad argument to import_factor"); return GH_ERR_BAD_ARG; }
-  GH_CHECK(set_device(s));
-  s->computed = false;
-  const int64_t np = gh_round_up(n, T);
-  s->n = n; s->np = np; s->ndim = ndim; s->info = 0; s->have_yerr = false;
-  const size_t cnt = (size_t)n * (n + 1) / 2;
-  GH_CHECK(s->A.ensure((size_t)np * np * sizeof(double)));
-  GH_CHECK(s->dinv.ensure((size_t)(np / T) * T * T * sizeof(double)));
-  GH_CHECK(s->x.ensure((size_t)n * ndim * sizeof(double)));
-  GH_CHECK(s->scal.ensure(256 * sizeof(double)));
-  GH_CHECK(s->work.ensure(cnt * sizeof(double)));
-  GH_CHECK(gh_to_device(s->x.d(), x, (size_t)n * ndim, s->st));
-  GH_CHECK(gh_to_device(s->work.d(), packed_lower, cnt, s->st));
-  GH_CHECK(gh_to_device(s->dinv.d(), dinv_in, (size_t)(np / T) * T * T, s->st));
-  hipLaunchKernelGGL(unpack_lower_kernel, dim3((unsigned)np), dim3(256), 0, s->st, s->work.d(), (long)n, s->A.d(), (long)np, (long)np);
-  GH_HIP(hipGetLastError());
-  GH_HIP(hipStreamSynchronize(s->st));
-  s->logdet = logdet;
-  s->computed = true;
-  return GH_OK;
-}
 extern "C" void gh_chol_release_buffers(gh_chol* s) {
   // frees everything but the handle itself (streams, events); the next compute() re-allocates
   if (!s) return;
@@ -2489,541 +975,3 @@ extern "C" void gh_chol_trim(gh_chol* s) {
   s->batch = nullptr;
 }
 
-// ============================================================ append / truncate
-// Sequential use: the data set gains (or loses) a few trailing points and the factor is kept.  With n = n0 + t, n0 = 128 * (n / 128):
-//   * a Cholesky factor's leading rows do not depend on later rows: the n0 x n0 part of L and its diagonal-block inverses stay as they
-//     are -- in place while the new points fit into the last partial tile, re-laid into buffers of the new Np (leading dimension = Np
-//     throughout the solver) when the tile count grows;
-//   * the new rows against the full tiles, X = K(x_new, x[:n0]) L00^-T: a row of X is the result of one forward sweep over L00 with
-//     a row of the cross-covariance as its right-hand side -- contiguous, where the chained sweep kernels write it;
-//   * the tail block, rows and columns [n0, n + m) padded to 128: S = K(tail, tail) + diag(yerr^2) - L_tail,0 L_tail,0^T, then
-//     potrf_block.  The product has K = n0 and one or a few output tiles: split over K (tail_syrk_splitk_kernel), summed in a fixed
-//     order.  The t old tail rows of the diagonal tile are formed again (last bits may differ from what compute() left there).
-// DESIGN.md, "Appending points".
-static int g_append_path = 0;
-extern "C" int gh_debug_set_append_path(int path) {
-  const int prev = g_append_path;
-  g_append_path = (path >= 1 && path <= 3) ? path : 0;
-  return prev;
-}
-// new rows up to which the chained sweeps (4 rows per pass over the factor) are taken; above, the blocked substitution, whose time does
-// not depend on m up to 128.  Measured (profiles/append/append_paths.json) at n = 4032 / 16320: the substitution 0.75 / 3.3 ms; the
-// sweeps 0.48 / 1.5 ms at m = 4 and 1.36 / 5.1 ms at m = 16, so about 0.77 / 2.7 ms at 8 and 1.07 / 3.9 ms at 12 (interpolated).
-#define GH_APPEND_MULTI_MAX 8
-
-static void swap_bufs(GhBuf& a, GhBuf& b) { std::swap(a.p, b.p); std::swap(a.bytes, b.bytes); std::swap(a.pooled, b.pooled); }
-
-// Where a factor of np2 rows moves to.  Allocating it per call is what a move costs: hipMalloc + hipFree of 34 GB took 960 ms of a 971-ms
-// append at N = 65536 (profiles/append/append_paths.json), the copy 6.5 ms.  So the handle keeps the buffer the factor left at its last
-// move (A_spare) and the next move goes there; when that is too small the new one gets room for np2 / 32 (at least 1024) more rows, which
-// the next 8 or more tile crossings find large enough.  A buffer of more rows holds a matrix of fewer: the leading dimension is Np.
-static int take_factor_buffer(gh_chol* s, GhBuf& out, int64_t np2) {
-  const size_t need = (size_t)np2 * np2 * sizeof(double);
-  if (s->A_spare.p && s->A_spare.bytes >= need) { swap_bufs(out, s->A_spare); return GH_OK; }
-  const int64_t cap = np2 + std::max<int64_t>(1024, gh_round_up(np2 / 32, T));
-  if (out.ensure((size_t)cap * cap * sizeof(double)) == GH_OK) return GH_OK;
-  return out.ensure(need);
-}
-// the lower 128-tiles of dst (nn x nn, nn a multiple of 128): src where row and column are below nvalid, identity elsewhere
-__global__ __launch_bounds__(256) void relayout_lower_kernel(const double* src, long lds, long nvalid, double* dst, long ldd) {
-  const long i = blockIdx.x, jend = (i / T + 1) * T;
-  const double* sr = src + i * lds;
-  double* dr = dst + i * ldd;
-  if (i < nvalid) {
-    for (long j = threadIdx.x; j < jend; j += 256) dr[j] = (j < nvalid) ? sr[j] : 0.0;
-  } else {
-    for (long j = threadIdx.x; j < jend; j += 256) dr[j] = (j == i) ? 1.0 : 0.0;
-  }
-}
-// The last tile row of A (rows [t0, t0 + 128), one per workgroup) cut to n_keep points: rows from n_keep on become identity padding
-// (columns up to the end of the diagonal tile), and the kept rows lose columns n_keep .. of the diagonal tile (zeros already, as
-// potf2 leaves the strict upper triangle: written all the same, so that the tile is what compute() at n_keep builds).
-__global__ __launch_bounds__(256) void pad_rows_kernel(double* A, long ld, long t0, long n_keep) {
-  const long i = t0 + blockIdx.x, jend = t0 + T;
-  double* r = A + i * ld;
-  if (i >= n_keep) { for (long j = threadIdx.x; j < jend; j += 256) r[j] = (j == i) ? 1.0 : 0.0; }
-  else { for (long j = n_keep + threadIdx.x; j < jend; j += 256) r[j] = 0.0; }
-}
-// a 128 x 128 diagonal-block inverse cut to its leading keep x keep part, identity behind it
-__global__ __launch_bounds__(256) void dinv_clip_kernel(double* d, int keep) {
-  for (int idx = threadIdx.x; idx < T * T; idx += 256) {
-    const int i = idx >> 7, j = idx & 127;
-    if (i >= keep || j >= keep) d[idx] = (i == j) ? 1.0 : 0.0;
-  }
-}
-// Split-K stage 1 of Lt Lt^T (Lt: 128 * tiles rows, k contiguous, K = ktot): workgroup (p, sl) forms the 128 x 128 tile p of the
-// lower triangle over the k-slice sl -- the dense solver's tile function -- into part[sl][p].  Stage 2 adds the slices in index order
-// and subtracts the total from S: bitwise reproducible, like the log-det and the dot product.
-__global__ __launch_bounds__(256, 2) void tail_syrk_splitk_kernel(const double* Lt, long ld, long kslice, long ktot, double* part) {
-  __shared__ __attribute__((aligned(1024))) double sm[4 * BM * BK];
-  int ti = 0;
-  while ((ti + 1) * (ti + 2) / 2 <= (int)blockIdx.x) ++ti;
-  const int tj = (int)blockIdx.x - ti * (ti + 1) / 2;
-  const long k0 = (long)blockIdx.y * kslice;
-  const long K = kslice < ktot - k0 ? kslice : ktot - k0;
-  double* C = part + ((long)blockIdx.y * gridDim.x + blockIdx.x) * T * T;
-  gh_tile128_nt_sp<false>(sm, C, T, Lt + (long)ti * T * ld + k0, ld, Lt + (long)tj * T * ld + k0, ld, K);
-}
-__global__ __launch_bounds__(256) void tail_syrk_reduce_kernel(double* S, long ld, const double* part, int nslice) {
-  int ti = 0;
-  while ((ti + 1) * (ti + 2) / 2 <= (int)blockIdx.x) ++ti;
-  const int tj = (int)blockIdx.x - ti * (ti + 1) / 2;
-  const long npairs = gridDim.x;
-  for (int idx = blockIdx.y * 256 + threadIdx.x; idx < T * T; idx += gridDim.y * 256) {
-    double acc = 0.0;
-    for (int sl = 0; sl < nslice; ++sl) acc += part[((long)sl * npairs + blockIdx.x) * T * T + idx];
-    S[((long)ti * T + (idx >> 7)) * ld + (long)tj * T + (idx & 127)] -= acc;
-  }
-}
-
-// X (mr x n0, ld = ldx, mr a multiple of 128) <- X L00^-T, right-looking in row form on the matrix pipe: X_j <- X_j L_jj^-T with the
-// stored inverse, then X[:, j+1:] -= X_j L[j+1:, j]^T -- inside super-blocks of 8 tiles, and ONE K = 1024 update of everything right
-// of a super-block (as trsm_multi).  Every product has both operands k-major; the update is as wide as what is left of the row.
-static int append_trsm_rows(hipStream_t st, const double* L, int64_t ld, const double* dinv, double* X, int64_t ldx, int64_t mr, int64_t nt0) {
-  const int64_t SB = 8;
-  for (int64_t J = 0; J < nt0; J += SB) {
-    const int64_t Je = std::min<int64_t>(J + SB, nt0);
-    for (int64_t j = J; j < Je; ++j) {
-      double* Xj = X + j * T;
-      GH_CHECK(gemm_nt(st, Xj, ldx, Xj, ldx, dinv + j * T * T, T, mr, T, T, 1.0, 0.0, false));
-      if (j + 1 < Je)
-        GH_CHECK(gemm_nt(st, X + (j + 1) * T, ldx, Xj, ldx, L + (j + 1) * T * ld + j * T, ld, mr, (Je - j - 1) * T, T, -1.0, 1.0, false));
-    }
-    if (Je < nt0)
-      GH_CHECK(gemm_nt(st, X + Je * T, ldx, X + J * T, ldx, L + Je * T * ld + J * T, ld, mr, (nt0 - Je) * T, (Je - J) * T, -1.0, 1.0, false));
-  }
-  return GH_OK;
-}
-
-extern "C" int gh_chol_append(gh_chol* s, gh_kernel* k, const double* x_new, int64_t m, const double* yerr_new, double* logdet_out) {
-  if (!s || !k || !x_new || !yerr_new || m <= 0) { gh_set_error("bad argument to append"); return GH_ERR_BAD_ARG; }
-  GH_CHECK(need_computed(s));
-  if (k->ndim != s->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
-  // (the old rows of the last, partial tile are formed again from the kernel and the error bars)
-  if (!s->have_yerr) { gh_set_error("append: the handle was rebuilt by import_factor and holds no error bars (gh_chol_set_yerr)"); return GH_ERR_BAD_ARG; }
-  GH_CHECK(k->upload());
-  const int64_t n = s->n, np = s->np, ndim = s->ndim, n2 = n + m, np2 = gh_round_up(n2, T);
-  const int64_t n0 = (n / T) * T, nt0 = n0 / T, tailp = np2 - n0, tt = tailp / T;
-  const bool grow = np2 > np;
-  const int path = nt0 == 0 ? 0 : g_append_path ? g_append_path : (m <= GH_APPEND_MULTI_MAX ? 2 : 3);
-  hipStream_t st = s->st;
-  // ---- every allocation first: a failure up to here leaves the handle as it was
-  GhBuf A2, dinv2, x2, yerr2;
-  GhPooledBuf saved, part;
-  if (grow) {
-    GH_CHECK(take_factor_buffer(s, A2, np2));
-    GH_CHECK(dinv2.ensure((size_t)(np2 / T) * T * T * sizeof(double)));
-  } else {
-    GH_CHECK(saved.ensure((size_t)2 * T * T * sizeof(double)));
-  }
-  const bool grow_x = s->x.bytes < (size_t)n2 * ndim * sizeof(double) || s->yerr.bytes < (size_t)n2 * sizeof(double);
-  if (grow_x) {
-    GH_CHECK(x2.ensure((size_t)np2 * ndim * sizeof(double)));
-    GH_CHECK(yerr2.ensure((size_t)np2 * sizeof(double)));
-  }
-  const int64_t mr = path == 3 ? gh_round_up(m, T) : m;
-  if (nt0 > 0) GH_CHECK(s->work.ensure((size_t)mr * n0 * sizeof(double)));
-  const int64_t npairs = tt * (tt + 1) / 2;
-  // k-slices in units of 128: as many workgroups as keep the chip busy, at most 256 slices
-  const int64_t want = std::max<int64_t>(1, std::min<int64_t>(256, 2048 / npairs));
-  const int64_t ktiles = nt0 > 0 ? (nt0 + want - 1) / want : 0, nslice = nt0 > 0 ? (nt0 + ktiles - 1) / ktiles : 0;
-  if (nt0 > 0) GH_CHECK(part.ensure((size_t)nslice * npairs * T * T * sizeof(double)));
-  GH_CHECK(s->chain.ensure((size_t)(2 * (np2 / T) + 2) * sizeof(unsigned)));
-  GH_CHECK(s->scal.ensure(256 * sizeof(double)));
-  int* fail = (int*)s->chain.p;
-  s->d_info = (long long*)(s->scal.d() + 2);
-  // ---- inputs
-  double* xd = grow_x ? x2.d() : s->x.d();
-  double* yd = grow_x ? yerr2.d() : s->yerr.d();
-  if (grow_x) {
-    GH_HIP(hipMemcpyAsync(xd, s->x.d(), (size_t)n * ndim * sizeof(double), hipMemcpyDeviceToDevice, st));
-    GH_HIP(hipMemcpyAsync(yd, s->yerr.d(), (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
-  }
-  GH_CHECK(gh_to_device(xd + n * ndim, x_new, (size_t)m * ndim, st));
-  GH_CHECK(gh_to_device(yd + n, yerr_new, (size_t)m, st));
-  GH_HIP(hipMemsetAsync(s->d_info, 0, sizeof(long long), st));
-  GH_HIP(hipMemsetAsync(fail, 0, sizeof(int), st));
-  // ---- 1. grow (or save what is overwritten in place)
-  double* Ad = grow ? A2.d() : s->A.d();
-  double* dd = grow ? dinv2.d() : s->dinv.d();
-  const int64_t ld = grow ? np2 : np;
-  s->prof.ms_append_relayout = 0.0;
-  // From here on the in-place case writes into the handle's own factor.  GH_ERR_NOT_PD and a sweep time-out put the old bits back; any
-  // other error return (a failed HIP call) leaves the tail tile half written, and the handle NOT computed.
-  struct Dirty { gh_chol* s; bool armed; ~Dirty() { if (armed) s->computed = false; } } dirty{s, false};
-  long e_lay = -1;                                        // (profile: the relayout's share, gh_chol_profile.ms_append_relayout)
-  if (grow && s->opts.profile) {                          // (events of its own: the pool belongs to the last compute()'s profile)
-    for (auto& e : s->ev_lay) if (!e) GH_HIP(hipEventCreate(&e));
-    e_lay = 0;
-  }
-  if (e_lay >= 0) GH_HIP(hipEventRecord(s->ev_lay[0], st));
-  if (grow) {
-    hipLaunchKernelGGL(relayout_lower_kernel, dim3((unsigned)np2), dim3(256), 0, st, s->A.d(), (long)np, (long)np, Ad, (long)ld);
-    GH_HIP(hipGetLastError());
-    GH_HIP(hipMemcpyAsync(dd, s->dinv.d(), (size_t)(np / T) * T * T * sizeof(double), hipMemcpyDeviceToDevice, st));
-    if (e_lay >= 0) GH_HIP(hipEventRecord(s->ev_lay[1], st));
-  } else {
-    dirty.armed = true;
-    GH_HIP(hipMemcpy2DAsync(saved.d(), T * sizeof(double), Ad + n0 * ld + n0, ld * sizeof(double), T * sizeof(double), T, hipMemcpyDeviceToDevice, st));
-    GH_HIP(hipMemcpyAsync(saved.d() + T * T, dd + nt0 * T * T, (size_t)T * T * sizeof(double), hipMemcpyDeviceToDevice, st));
-  }
-  // ---- 2. the new rows against the full tiles
-  if (nt0 > 0) {
-    double* Kc = s->work.d();
-    GH_CHECK(gh_launch_kmat(k, xd + n * ndim, m, xd, n0, nullptr, Kc, n0, mr, n0, n, 0, true, false, st));
-    if (path == 3) {
-      GH_CHECK(append_trsm_rows(st, Ad, ld, dd, Kc, n0, mr, nt0));
-      GH_HIP(hipMemcpy2DAsync(Ad + n * ld, ld * sizeof(double), Kc, n0 * sizeof(double), n0 * sizeof(double), m, hipMemcpyDeviceToDevice, st));
-    } else {
-      GH_HIP(hipMemset2DAsync(Ad + n * ld, ld * sizeof(double), 0xFF, n0 * sizeof(double), m, st));
-      const dim3 grid((unsigned)nt0), block(CHAIN_THREADS);
-      int64_t i = 0;
-      if (path == 2) {
-        for (; m - i >= 4; i += 4)
-          hipLaunchKernelGGL(trsv_fwd_chain_multi<4>, grid, block, 0, st, Ad, (long)ld, dd, Kc + i * n0, (long)n0, Ad + (n + i) * ld, (long)ld, fail);
-        for (; m - i >= 2; i += 2)
-          hipLaunchKernelGGL(trsv_fwd_chain_multi<2>, grid, block, 0, st, Ad, (long)ld, dd, Kc + i * n0, (long)n0, Ad + (n + i) * ld, (long)ld, fail);
-      }
-      for (; i < m; ++i)
-        hipLaunchKernelGGL(trsv_fwd_chain_direct, grid, block, 0, st, Ad, (long)ld, dd, Kc + i * n0, Ad + (n + i) * ld, fail);
-      GH_HIP(hipGetLastError());
-    }
-  }
-  // ---- 3. the tail block
-  double* S = Ad + n0 * ld + n0;
-  GH_CHECK(gh_launch_kmat(k, xd + n0 * ndim, n2 - n0, xd + n0 * ndim, n2 - n0, yd + n0, S, ld, tailp, tailp, n0, n0, true, true, st));
-  if (nt0 > 0) {
-    hipLaunchKernelGGL(tail_syrk_splitk_kernel, dim3((unsigned)npairs, (unsigned)nslice), dim3(256), 0, st,
-                       Ad + n0 * ld, (long)ld, (long)(ktiles * T), (long)n0, part.d());
-    hipLaunchKernelGGL(tail_syrk_reduce_kernel, dim3((unsigned)npairs, 16), dim3(256), 0, st, S, (long)ld, part.d(), (int)nslice);
-    GH_HIP(hipGetLastError());
-  }
-  GH_CHECK(potrf_block(st, S, ld, tailp, dd + nt0 * T * T, s->d_info, n0));
-  // ---- 4. log-det over the whole diagonal; one synchronisation brings it back with the failure word and the sweeps' time-out flag
-  GH_CHECK(launch_logdet(Ad, (long)ld, (long)np2, s->scal.d(), s->scal.d() + 8, st));
-  double back[3] = {0.0, 0.0, 0.0};
-  int failed = 0;
-  GH_HIP(hipMemcpyAsync(back, s->scal.d(), 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-  GH_HIP(hipMemcpyAsync(&failed, fail, sizeof(int), hipMemcpyDeviceToHost, st));
-  GH_HIP(hipStreamSynchronize(st));
-  long long info_host = 0;
-  memcpy(&info_host, &back[2], sizeof(long long));
-  if (e_lay >= 0) { float ms = 0; GH_HIP(hipEventElapsedTime(&ms, s->ev_lay[0], s->ev_lay[1])); s->prof.ms_append_relayout = ms; }
-  if (info_host != 0 || failed) {
-    if (!grow) {                                          // put back what was overwritten in place: the old bits
-      GH_HIP(hipMemcpy2DAsync(S, ld * sizeof(double), saved.d(), T * sizeof(double), T * sizeof(double), T, hipMemcpyDeviceToDevice, st));
-      GH_HIP(hipMemcpyAsync(dd + nt0 * T * T, saved.d() + T * T, (size_t)T * T * sizeof(double), hipMemcpyDeviceToDevice, st));
-      if (nt0 > 0) GH_HIP(hipMemset2DAsync(Ad + n * ld, ld * sizeof(double), 0, n0 * sizeof(double), m, st));
-    }
-    GH_HIP(hipStreamSynchronize(st));                     // (the buffers of this call go back to the allocator on return)
-    if (grow && !s->A_spare.p) swap_bufs(s->A_spare, A2);  // (... but not the large one)
-    dirty.armed = false;
-    if (failed) { gh_set_error("append: a workgroup of the forward sweep waited more than 2 s for its predecessor"); return GH_ERR_HIP; }
-    s->info = info_host;
-    gh_set_error("%lld-th leading minor of the array is not positive definite", info_host);
-    return GH_ERR_NOT_PD;
-  }
-  dirty.armed = false;
-  if (grow) { swap_bufs(s->A, A2); swap_bufs(s->A_spare, A2); swap_bufs(s->dinv, dinv2); }   // (the old factor buffer is the spare now)
-  if (grow_x) { swap_bufs(s->x, x2); swap_bufs(s->yerr, yerr2); }
-  s->n = n2; s->np = np2; s->info = 0;
-  s->logdet = back[0];
-  if (logdet_out) *logdet_out = back[0];
-  return GH_OK;
-}
-
-extern "C" int gh_chol_set_yerr(gh_chol* s, const double* yerr) {
-  if (!s || !yerr) { gh_set_error("null argument"); return GH_ERR_BAD_ARG; }
-  GH_CHECK(need_computed(s));
-  GH_CHECK(s->yerr.ensure((size_t)s->np * sizeof(double)));
-  GH_CHECK(gh_to_device(s->yerr.d(), yerr, (size_t)s->n, s->st));
-  GH_HIP(hipStreamSynchronize(s->st));
-  s->have_yerr = true;
-  return GH_OK;
-}
-
-extern "C" int gh_chol_truncate(gh_chol* s, int64_t n_keep, double* logdet_out) {
-  if (!s) { gh_set_error("null solver"); return GH_ERR_BAD_ARG; }
-  GH_CHECK(need_computed(s));
-  if (n_keep <= 0 || n_keep > s->n) { gh_set_error("truncate: n_keep must be in 1 .. %lld", (long long)s->n); return GH_ERR_BAD_ARG; }
-  if (n_keep == s->n) { if (logdet_out) *logdet_out = s->logdet; return GH_OK; }
-  const int64_t np = s->np, np2 = gh_round_up(n_keep, T);
-  hipStream_t st = s->st;
-  GhBuf A2, dinv2, x2, yerr2;
-  GH_CHECK(s->scal.ensure(256 * sizeof(double)));
-  if (np2 < np) {
-    // fewer tiles: the leading dimension is Np, so the lower tiles move into a buffer of the new size -- and dinv, x and yerr with
-    // them: the handle holds what it holds after an append that ended at this size
-    const int64_t ndim = s->ndim;
-    GH_CHECK(take_factor_buffer(s, A2, np2));
-    GH_CHECK(dinv2.ensure((size_t)(np2 / T) * T * T * sizeof(double)));
-    GH_CHECK(x2.ensure((size_t)np2 * ndim * sizeof(double)));
-    if (s->have_yerr) GH_CHECK(yerr2.ensure((size_t)np2 * sizeof(double)));
-    GH_HIP(hipMemcpyAsync(dinv2.d(), s->dinv.d(), (size_t)(np2 / T) * T * T * sizeof(double), hipMemcpyDeviceToDevice, st));
-    GH_HIP(hipMemcpyAsync(x2.d(), s->x.d(), (size_t)n_keep * ndim * sizeof(double), hipMemcpyDeviceToDevice, st));
-    if (s->have_yerr) GH_HIP(hipMemcpyAsync(yerr2.d(), s->yerr.d(), (size_t)n_keep * sizeof(double), hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(relayout_lower_kernel, dim3((unsigned)np2), dim3(256), 0, st, s->A.d(), (long)np, (long)n_keep, A2.d(), (long)np2);
-  } else if (np2 > n_keep) {
-    // dropped rows in the same tile row: a leading principal block of L is the factor of that block of K
-    hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)T), dim3(256), 0, st, s->A.d(), (long)np, (long)(np2 - T), (long)n_keep);
-  }
-  GH_HIP(hipGetLastError());
-  if (n_keep % T) {                                       // ... and of a diagonal block's inverse the inverse of that block
-    hipLaunchKernelGGL(dinv_clip_kernel, dim3(1), dim3(256), 0, st, (np2 < np ? dinv2.d() : s->dinv.d()) + (np2 / T - 1) * T * T, (int)(n_keep % T));
-    GH_HIP(hipGetLastError());
-  }
-  const double* Ad = np2 < np ? A2.d() : s->A.d();
-  GH_CHECK(launch_logdet(Ad, (long)np2, (long)np2, s->scal.d(), s->scal.d() + 8, st));
-  double ldv = 0.0;
-  GH_HIP(hipMemcpyAsync(&ldv, s->scal.d(), sizeof(double), hipMemcpyDeviceToHost, st));
-  GH_HIP(hipStreamSynchronize(st));
-  if (np2 < np) {
-    swap_bufs(s->A, A2); swap_bufs(s->A_spare, A2); swap_bufs(s->dinv, dinv2); swap_bufs(s->x, x2);
-    if (s->have_yerr) swap_bufs(s->yerr, yerr2);
-  }
-  s->n = n_keep; s->np = np2; s->info = 0;
-  s->logdet = ldv;
-  if (logdet_out) *logdet_out = ldv;
-  return GH_OK;
-}
-
-// ============================================================ removing points
-// K[keep, keep] = L[keep, :] L[keep, :]^T = Lk Lk^T + W W^T with Lk = L[keep, keep] (lower triangular, positive diagonal) and
-// W = L[keep, rem] (zero where keep[p] < rem[j]): taking points out is a rank-m Cholesky UPDATE of the gathered factor -- it adds a
-// positive semi-definite term, so it cannot lose positive definiteness -- and rows before the first removed index do not change.
-// Per pass of at most 128 columns of W and per diagonal tile j from the first affected one, with Wj the tile's rows of W:
-//   V = Ljj^-1 Wj;   L' = chol(Ljj Ljj^T + Wj Wj^T) and L'^-1;   C C^T = I + V^T V and C^-1   (Ri = C^-T)
-//   Q = [[Ljj^T L'^-T, -V Ri], [Wj^T L'^-T, Ri]]   (orthogonal);   [Lij' | Wi'] = [Lij | Wi] Q for every tile row i below j.
-// The gathered tile has no stored inverse (it is a principal submatrix of old tiles), so V comes from a substitution.  Everything is
-// written into buffers the handle does not use yet; they are swapped in after the one synchronisation has reported success.
-// DESIGN.md section 4, "Removing points".
-static int g_remove_path = 0;
-extern "C" int gh_debug_set_remove_path(int path) {
-  const int prev = g_remove_path;
-  g_remove_path = (path == 1 || path == 2) ? path : 0;
-  return prev;
-}
-// the argument rule of gh_chol_remove for a factor of n points: host code, no handle and no device needed
-extern "C" int gh_debug_check_remove_args(int64_t n, const int64_t* idx, int64_t m) {
-  if (!idx) { gh_set_error("remove: null index array"); return GH_ERR_BAD_ARG; }
-  if (m <= 0 || m >= n) { gh_set_error("remove: the number of removed points must be in 1 .. %lld", (long long)(n - 1)); return GH_ERR_BAD_ARG; }
-  for (int64_t i = 0; i < m; ++i) {
-    if (idx[i] < 0 || idx[i] >= n) { gh_set_error("remove: index %lld is out of range for %lld points", (long long)idx[i], (long long)n); return GH_ERR_BAD_ARG; }
-    if (i > 0 && idx[i] <= idx[i - 1]) { gh_set_error("remove: indices must be strictly increasing"); return GH_ERR_BAD_ARG; }
-  }
-  return GH_OK;
-}
-
-// dst (np2 x np2, lower 128-tiles) = src[keep, keep] with identity padding; one row per workgroup.  keep is increasing, so a column
-// at or left of the diagonal stays there; the rest of the diagonal tile is written as zero (what potf2 leaves there).
-__global__ __launch_bounds__(256) void remove_gather_lower_kernel(const double* src, long lds, const int* keep, long n2, double* dst, long ldd) {
-  const long p = blockIdx.x, qend = (p / T + 1) * T;
-  double* dr = dst + p * ldd;
-  if (p < n2) {
-    const double* sr = src + (long)keep[p] * lds;
-    for (long q = threadIdx.x; q < qend; q += 256) dr[q] = (q <= p) ? sr[keep[q]] : 0.0;
-  } else {
-    for (long q = threadIdx.x; q < qend; q += 256) dr[q] = (q == p) ? 1.0 : 0.0;
-  }
-}
-// W (rows [row0, np2) x 128, ld 128): W[p, c] = src[keep[p], rem[c]] where c < kc and rem[c] < keep[p], else 0
-__global__ __launch_bounds__(128) void remove_gather_w_kernel(const double* src, long lds, const int* keep, long n2, const int* rem, int kc,
-                                                             double* W, long row0) {
-  const long p = row0 + blockIdx.x;
-  const int c = threadIdx.x;
-  double v = 0.0;
-  if (p < n2 && c < kc) {
-    const long kp = keep[p], rc = rem[c];
-    if (rc < kp) v = src[kp * lds + rc];
-  }
-  W[p * T + c] = v;
-}
-__global__ void remove_gather_vec_kernel(const double* x, const double* yerr, const int* keep, long n2, int ndim, double* x2, double* yerr2) {
-  const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= n2) return;
-  const long kp = keep[p];
-  for (int d = 0; d < ndim; ++d) x2[p * ndim + d] = x[kp * ndim + d];
-  if (yerr2) yerr2[p] = yerr[kp];
-}
-// The small step's substitution, two workgroups (64 columns of Wj each, one column per lane of the first wavefront, its solution in
-// LDS): V = Ljj^-1 Wj.  The other wavefronts save the tile (Lold = Ljj: the tile itself receives Ljj Ljj^T + Wj Wj^T next) and set
-// G = I (it receives V^T V).  Columns from kc on are zero columns of Wj.
-__global__ __launch_bounds__(256) void remove_tile_solve_kernel(const double* __restrict__ Ljj, long ld, const double* __restrict__ Wj, int kc,
-                                                               double* __restrict__ V, double* __restrict__ Lold, double* __restrict__ G) {
-  __shared__ double X[T * 64];
-  const int tid = threadIdx.x, half = blockIdx.x;
-  if (tid >= 64) {
-    for (int idx = tid - 64; idx < 64 * T; idx += 192) {
-      const int i = half * 64 + idx / T, j = idx % T;
-      Lold[i * T + j] = Ljj[(long)i * ld + j];
-      G[i * T + j] = (i == j) ? 1.0 : 0.0;
-    }
-    return;
-  }
-  const int c = half * 64 + tid;
-  if (half * 64 >= kc) {
-    for (int i = 0; i < T; ++i) V[i * T + c] = 0.0;
-    return;
-  }
-  for (int i = 0; i < T; ++i) {
-    const double* Li = Ljj + (long)i * ld;
-    double a0 = Wj[i * T + c], a1 = 0.0, a2 = 0.0, a3 = 0.0;
-    int k = 0;
-    for (; k + 4 <= i; k += 4) {
-      a0 -= Li[k] * X[k * 64 + tid];
-      a1 -= Li[k + 1] * X[(k + 1) * 64 + tid];
-      a2 -= Li[k + 2] * X[(k + 2) * 64 + tid];
-      a3 -= Li[k + 3] * X[(k + 3) * 64 + tid];
-    }
-    for (; k < i; ++k) a0 -= Li[k] * X[k * 64 + tid];
-    const double x = ((a0 + a1) + (a2 + a3)) / Li[i];
-    X[i * 64 + tid] = x;
-    V[i * T + c] = x;
-  }
-}
-// The hot path: [Lij' | Wi'] = [Lij | Wi] Q for the 128 rows of one tile row i below j per workgroup, on the fp64 matrix pipe.  The
-// two halves of the slab live in two buffers (the factor, leading dimension ld; W, 128 wide); Q arrives as four k-major blocks,
-//   B11 = (Ljj^T L'^-T)^T,  nB21 = -(Wj^T L'^-T)^T,  nB12 = (V Ri)^T,  B22 = Ri^T   (128 x 128 each, ld 128),
-// streamed through LDS in 16-deep slabs by the tile function of gh_gemm_tile.h.  The workgroup owns its rows, and no product reads
-// what the launch has written: W' goes to the OTHER W buffer (Wn), the accumulating products read their C through the thread that
-// wrote it, and L' = L B11^T is written in place only after every slab of L has been read (gh_tile128_nt_sp's contract).  Only the
-// first kc (a multiple of 32) columns of W are summed over; the columns of W' from kc on come out as zeros.
-__global__ __launch_bounds__(256, 2) void remove_apply_q_kernel(double* A, long ld, long row0, long col0, const double* Wo, double* Wn,
-                                                               const double* B11, const double* nB21, const double* nB12,
-                                                               const double* B22, long kc) {
-  __shared__ __attribute__((aligned(1024))) double sm[4 * BM * BK];
-  const long r = row0 + (long)blockIdx.x * T;
-  double* Lt = A + r * ld + col0;
-  const double* wo = Wo + r * T;
-  double* wn = Wn + r * T;
-  // (one inlined copy of each form of the tile function, not four: the kernel must fit its registers -- check_kernels.py)
-#pragma unroll 1
-  for (int step = 0; step < 2; ++step) {
-    double* const C = step ? Lt : wn;
-    const long ldc = step ? ld : (long)T;
-    const double* const A0 = step ? (const double*)Lt : wo;      // W' = W Ri               | L' = L Ljj^T L'^-T
-    const double* const A1 = step ? wo : (const double*)Lt;      // W' -= L (V Ri)          | L' += W Wj^T L'^-T
-    const long lda0 = step ? ld : (long)T, lda1 = step ? (long)T : ld;
-    gh_tile128_nt_sp<false>(sm, C, ldc, A0, lda0, step ? B11 : B22, T, step ? (long)T : kc);
-    gh_tile128_nt_sp<true>(sm, C, ldc, A1, lda1, step ? nB21 : nB12, T, step ? kc : (long)T);
-  }
-}
-
-static int gemm_any(hipStream_t st, double* C, int64_t ldc, const double* A, int64_t lda, bool a_km, const double* B, int64_t ldb, bool b_km,
-                    double alpha, double beta) {
-  GhGemm g{};
-  g.C = C; g.ldc = ldc; g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.M = T; g.N = T; g.K = T;
-  g.alpha = alpha; g.beta = beta; g.a_km = a_km; g.b_km = b_km;
-  return gh_launch_gemm(g, st);
-}
-
-extern "C" int gh_chol_remove(gh_chol* s, const int64_t* idx, int64_t m, double* logdet_out) {
-  if (!s) { gh_set_error("null solver"); return GH_ERR_BAD_ARG; }
-  GH_CHECK(need_computed(s));
-  GH_CHECK(gh_debug_check_remove_args(s->n, idx, m));
-  const int64_t n = s->n, np = s->np, ndim = s->ndim, n2 = n - m, np2 = gh_round_up(n2, T), nt2 = np2 / T;
-  if (idx[0] == n - m) return gh_chol_truncate(s, n2, logdet_out);          // (strictly increasing below n: the trailing run)
-  if (g_remove_path == 2) { gh_set_error("remove: compute afresh on the kept points"); return GH_REFACTORIZE; }
-  if (n >= (1LL << 31)) { gh_set_error("remove: too many points"); return GH_ERR_BAD_ARG; }
-  hipStream_t st = s->st;
-  // ---- the index maps (host)
-  std::vector<int> maps((size_t)(n2 + m));
-  {
-    int64_t r = 0, p = 0;
-    for (int64_t i = 0; i < n; ++i) {
-      if (r < m && idx[r] == i) { maps[(size_t)(n2 + r)] = (int)i; ++r; }
-      else maps[(size_t)p++] = (int)i;
-    }
-  }
-  const int64_t j0t = idx[0] / T;                          // first affected tile: idx[0] points are kept in front of the first removed one
-  // ---- every allocation first: a failure up to here leaves the handle as it was (and so does every failure after it)
-  GhBuf A2, dinv2, x2, yerr2;
-  GhPooledBuf wb, qs, ib;
-  GH_CHECK(take_factor_buffer(s, A2, np2));
-  GH_CHECK(dinv2.ensure((size_t)nt2 * T * T * sizeof(double)));
-  GH_CHECK(x2.ensure((size_t)np2 * ndim * sizeof(double)));
-  if (s->have_yerr) GH_CHECK(yerr2.ensure((size_t)np2 * sizeof(double)));
-  GH_CHECK(wb.ensure((size_t)2 * np2 * T * sizeof(double)));
-  GH_CHECK(qs.ensure((size_t)7 * T * T * sizeof(double)));
-  GH_CHECK(ib.ensure(maps.size() * sizeof(int)));
-  GH_CHECK(s->scal.ensure(256 * sizeof(double)));
-  s->d_info = (long long*)(s->scal.d() + 2);
-  // (on an early error return the factor buffer goes back to the handle as its spare, not to the allocator)
-  struct Spare { gh_chol* s; GhBuf& b; bool armed; ~Spare() { if (armed && b.p && !s->A_spare.p) { (void)hipStreamSynchronize(s->st); swap_bufs(s->A_spare, b); } } }
-      spare{s, A2, true};
-  const int* keepd = (const int*)ib.p;
-  const int* remd = keepd + n2;
-  double* const Ad = A2.d();
-  double* const W0 = wb.d();
-  double* const W1 = W0 + np2 * T;
-  double* const V = qs.d();
-  double* const Lold = V + T * T, * const G = Lold + T * T, * const dG = G + T * T, * const B11 = dG + T * T, * const nB21 = B11 + T * T,
-        * const nB12 = nB21 + T * T;
-  GH_HIP(hipMemcpyAsync(ib.p, maps.data(), maps.size() * sizeof(int), hipMemcpyHostToDevice, st));
-  GH_HIP(hipMemsetAsync(s->d_info, 0, sizeof(long long), st));
-  // ---- 1. gather
-  long e_lay = -1;
-  if (s->opts.profile) {
-    for (auto& e : s->ev_lay) if (!e) GH_HIP(hipEventCreate(&e));
-    e_lay = 0;
-    GH_HIP(hipEventRecord(s->ev_lay[0], st));
-  }
-  hipLaunchKernelGGL(remove_gather_lower_kernel, dim3((unsigned)np2), dim3(256), 0, st, s->A.d(), (long)np, keepd, (long)n2, Ad, (long)np2);
-  hipLaunchKernelGGL(remove_gather_vec_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, st, s->x.d(),
-                     s->have_yerr ? s->yerr.d() : (const double*)nullptr, keepd, (long)n2, (int)ndim, x2.d(), s->have_yerr ? yerr2.d() : (double*)nullptr);
-  GH_HIP(hipGetLastError());
-  if (j0t > 0) GH_HIP(hipMemcpyAsync(dinv2.d(), s->dinv.d(), (size_t)j0t * T * T * sizeof(double), hipMemcpyDeviceToDevice, st));
-  if (e_lay >= 0) GH_HIP(hipEventRecord(s->ev_lay[1], st));
-  // ---- 2. the passes: at most 128 columns of W each, read from the OLD factor
-  for (int64_t c0 = 0; c0 < m; c0 += T) {
-    const int64_t kc = std::min<int64_t>(T, m - c0), kcp = gh_round_up(kc, 32);
-    const int64_t pc0 = idx[c0] - c0;                      // kept points in front of this pass's first column: rows of W before it are zero
-    if (pc0 >= n2) break;                                  // (the rest of rem lies behind every kept point)
-    const int64_t jt0 = pc0 / T;
-    hipLaunchKernelGGL(remove_gather_w_kernel, dim3((unsigned)(np2 - jt0 * T)), dim3(128), 0, st, s->A.d(), (long)np, keepd, (long)n2,
-                       remd + c0, (int)kc, W0, (long)(jt0 * T));
-    GH_HIP(hipGetLastError());
-    double* cur = W0;
-    double* oth = W1;
-    for (int64_t j = jt0; j < nt2; ++j) {
-      double* Ljj = Ad + j * T * np2 + j * T;
-      double* Wj = cur + j * T * T;
-      double* dS = dinv2.d() + j * T * T;
-      hipLaunchKernelGGL(remove_tile_solve_kernel, dim3(2), dim3(256), 0, st, Ljj, (long)np2, Wj, (int)kc, V, Lold, G);
-      GH_HIP(hipGetLastError());
-      GH_CHECK(gemm_any(st, Ljj, np2, Lold, T, true, Lold, T, true, 1.0, 0.0));        // S = Ljj Ljj^T
-      GH_CHECK(gemm_any(st, Ljj, np2, Wj, T, true, Wj, T, true, 1.0, 1.0));            //   + Wj Wj^T
-      GH_CHECK(gh_launch_potf2_mfma(Ljj, np2, dS, s->d_info, j * T, st));              // L', L'^-1
-      if (j + 1 == nt2) break;
-      GH_CHECK(gemm_any(st, G, T, V, T, false, V, T, false, 1.0, 1.0));                // G = I + V^T V
-      GH_CHECK(gh_launch_potf2_mfma(G, T, dG, s->d_info, j * T, st));                  // C, C^-1 = Ri^T
-      GH_CHECK(gemm_any(st, B11, T, dS, T, true, Lold, T, false, 1.0, 0.0));           // L'^-1 Ljj
-      GH_CHECK(gemm_any(st, nB21, T, dS, T, true, Wj, T, false, -1.0, 0.0));           // -L'^-1 Wj
-      GH_CHECK(gemm_any(st, nB12, T, dG, T, true, V, T, true, 1.0, 0.0));              // Ri^T V^T
-      hipLaunchKernelGGL(remove_apply_q_kernel, dim3((unsigned)(nt2 - j - 1)), dim3(256), 0, st, Ad, (long)np2, (long)((j + 1) * T), (long)(j * T),
-                         cur, oth, B11, nB21, nB12, dG, (long)kcp);
-      GH_HIP(hipGetLastError());
-      std::swap(cur, oth);
-    }
-  }
-  // ---- 3. log-det over the new diagonal; one synchronisation brings it back with the failure word
-  GH_CHECK(launch_logdet(Ad, (long)np2, (long)np2, s->scal.d(), s->scal.d() + 8, st));
-  double back[3] = {0.0, 0.0, 0.0};
-  GH_HIP(hipMemcpyAsync(back, s->scal.d(), 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-  GH_HIP(hipStreamSynchronize(st));
-  long long info_host = 0;
-  memcpy(&info_host, &back[2], sizeof(long long));
-  if (e_lay >= 0) { float ms = 0; GH_HIP(hipEventElapsedTime(&ms, s->ev_lay[0], s->ev_lay[1])); s->prof.reserved[0] = ms; }
-  if (info_host != 0 || !std::isfinite(back[0])) {
-    gh_set_error("remove: the update met a pivot that is not positive and finite (tile row of index %lld); the factor is unchanged", info_host);
-    return GH_ERR_NOT_PD;
-  }
-  spare.armed = false;
-  swap_bufs(s->A, A2); swap_bufs(s->A_spare, A2);          // (the old factor buffer is the spare now)
-  swap_bufs(s->dinv, dinv2); swap_bufs(s->x, x2);
-  if (s->have_yerr) swap_bufs(s->yerr, yerr2);
-  s->n = n2; s->np = np2; s->info = 0;
-  s->logdet = back[0];
-  if (logdet_out) *logdet_out = back[0];
-  return GH_OK;
-}

@@ -1,4 +1,4 @@
-// gh_device_util.h -- small device helpers with ONE definition for the one-problem kernels (gh_kmat.hip, gh_chol.hip) and
+// gh_device_util.h -- small device helpers with ONE definition for the one-problem kernels (gh_kmat.hip, gh_chol_solve.hip) and
 // their batched forms (gh_batch.hip), which claim the same bits
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,4 +1,4 @@
-// gh_fisher.hip -- the device pieces of gh_chol_fisher (gh_chol.hip): F_ab = 1/2 tr(K^-1 D_a K^-1 D_b) in its symmetric form,
+// gh_fisher.hip -- the device pieces of gh_chol_fisher (gh_chol_solve.hip): F_ab = 1/2 tr(K^-1 D_a K^-1 D_b) in its symmetric form,
 // W_a = L^-1 D_a L^-T (lower 128-tiles, by the GEMM family) and F_ab = sum_{i>j} W_a[i,j] W_b[i,j] + 1/2 sum_i W_a[i,i] W_b[i,i].
 //   fisher_planes_kernel   D_a = dK/dtheta_a for the selected kernel parameters as dense np x np planes, plane-major
 //   fisher_scale_kernel    L^-1 diag(d): what the first product of a DIAGONAL parameter would give, elementwise

@@ -1,4 +1,4 @@
-"""NumPy restatement of the blocked rank-k Cholesky update behind ``gh_chol_remove`` (george_amd/csrc/gh_chol.hip, "removing
+"""NumPy restatement of the blocked rank-k Cholesky update behind ``gh_chol_remove`` (george_amd/csrc/gh_chol_update.hip, "removing
 points"), tile edge ``T`` a parameter.  Not a test: imported by tests/test_remove_host.py and tests/test_gpu_remove.py.
 
 With ``keep`` / ``rem`` the kept / removed indices (both increasing) and L the current factor,

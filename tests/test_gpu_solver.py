@@ -445,22 +445,57 @@ def test_handle_pool_is_budgeted_and_releasable():
         BasicSolver._POOL_MAX_BYTES = old
 
 
-def test_stepwise_trsv_arm_still_works():
+def test_stepwise_trsv_arm_still_works(tmp_path):
     """GEORGE_AMD_TRSV_STEPS selects the one-launch-per-block-row solves (the fallback should the
-    chained kernels' in-order dispatch assumption ever fail): keep it exercised."""
+    chained kernels' in-order dispatch assumption ever fail): keep it exercised.  The switch is read once per process,
+    hence the children.  Beside the log-likelihood and the solve at N = 1500, every entry point with a sweep arm of its own
+    -- the fused objective, predict_gradient, the leave-one-out value and gradient paths -- runs at N = 300 (three tiles,
+    the last one ragged) and EACH arm is held to the NumPy references of tests/grad_ref.py, predgrad_ref.py and loo_ref.py
+    under their tolerance rule, as test_gpu_grad_reference.py, test_gpu_predict_gradient.py and test_gpu_loo.py do."""
     import subprocess, sys, os
+    import grad_ref, predgrad_ref, loo_ref
+    from george_amd.gp import TINY
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     code = ("import sys; sys.path.insert(0, %r); sys.path.insert(0, %r + '/tests'); import numpy as np, zoo\n"
             "from george_amd import GP, kernels\n"
             "x, yerr, y = zoo.bench_data(1500)\n"
             "gp = GP(np.var(y) * kernels.Matern32Kernel(1.0)); gp.compute(x, yerr)\n"
-            "print(repr(float(gp.log_likelihood(y))), repr(float(y @ gp.apply_inverse(y))))\n") % (root, root)
+            "print(repr(float(gp.log_likelihood(y))), repr(float(y @ gp.apply_inverse(y))))\n"
+            "x, yerr, y = zoo.bench_data(300)\n"
+            "t = x[[3, 70, 150, 222, 298]] + np.array([0.01, -0.02, 0.03, 0.015, -0.01])\n"
+            "gp = GP(np.var(y) * kernels.Matern32Kernel(1.0)); gp.compute(x, yerr)\n"
+            "gp.kernel.dirty = True                              # refactorise through the fused objective\n"
+            "nll, g = gp.nll_and_grad(gp.get_parameter_vector(), y)\n"
+            "mu, var, dmu, dvar = gp.predict_gradient(y, t, return_var=True, return_value=True)\n"
+            "np.savez(sys.argv[1], nll=nll, g=g, mu=mu, var=var, dmu=dmu, dvar=dvar,\n"
+            "         L=gp.loo_log_likelihood(y), gL=gp.grad_loo_log_likelihood(y))\n") % (root, root)
+    x, yerr, y = zoo.bench_data(300)
+    n = len(x)
+    kernel = np.var(y) * kernels.Matern32Kernel(1.0)
+    sigma = np.sqrt(yerr ** 2 + TINY)
+    t = x[[3, 70, 150, 222, 298]] + np.array([0.01, -0.02, 0.03, 0.015, -0.01])      # (the child's test points)
+    gref = grad_ref.reference(kernel, x, sigma, y)
+    lref = loo_ref.reference(kernel, x[:, None], sigma, y)
+    pref = predgrad_ref.reference(kernel, x[:, None], sigma, y, t[:, None])
+    assert gref.kappa <= 1e6
     outs = []
-    for env in ({}, {"GEORGE_AMD_TRSV_STEPS": "1"}):
+    for arm, env in enumerate(({}, {"GEORGE_AMD_TRSV_STEPS": "1"})):
         e = dict(os.environ); e.update(env)
-        r = subprocess.run([sys.executable, "-c", code], env=e, capture_output=True, text=True, timeout=600)
+        npz = str(tmp_path / ("arm%d.npz" % arm))
+        r = subprocess.run([sys.executable, "-c", code, npz], env=e, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         outs.append([float(v) for v in r.stdout.split()[-2:]])
+        d = np.load(npz)
+        ratios = dict(
+            nll=abs(-float(d["nll"]) + 0.5 * (gref.quad + gref.logdet + n * np.log(2 * np.pi))) / (0.5 * (gref.tol_quad() + gref.tol_logdet())),
+            grad=gref._ratio(-d["g"] - gref.g, gref.tol_grad()),
+            mu=pref.pred.ratio_mu(d["mu"]), var=pref.pred.ratio_var(d["var"]),
+            dmu=pref.ratio_dmu(d["dmu"].reshape(-1, 1)), dvar=pref.ratio_dvar(d["dvar"].reshape(-1, 1)),
+            L=lref.ratio("L", float(d["L"])), gL=loo_ref.Ref._ratio(d["gL"] - lref.g, lref.tol("g")))
+        print("%s arm: kappa %.3g, error / tolerance %s" % ("stepwise" if env else "chained", gref.kappa,
+                                                             ", ".join("%s %.3g" % kv for kv in sorted(ratios.items()))))
+        assert d["g"].shape == d["gL"].shape == (2,) and d["dmu"].size == d["dvar"].size == 5
+        assert max(ratios.values()) <= 1.0, (env, ratios)
     assert abs(outs[0][0] - outs[1][0]) <= 1e-11 * abs(outs[0][0])
     assert abs(outs[0][1] - outs[1][1]) <= 1e-9 * abs(outs[0][1])
 
@@ -655,7 +690,7 @@ def test_full_size_c3_properties():
 @pytest.mark.parametrize("n", [130, 1000, 5000, 20000])
 def test_chained_forward_solve_repeatable(n):
     """The forward sweep is ONE launch whose workgroups hand z blocks to each other through HBM
-    (gh_chol.hip, trsv_fwd_chain_direct): hammer it -- 25 sweeps per size must give the same bits, and
+    (gh_chol_solve.hip, trsv_fwd_chain_direct): hammer it -- 25 sweeps per size must give the same bits, and
     r^T K^-1 r must agree with the full solve r . apply_inverse(r) (forward + backward sweeps)."""
     x, yerr, y = zoo.bench_data(n)
     s = BasicSolver(np.var(y) * kernels.Matern32Kernel(1.0))
