@@ -138,7 +138,7 @@ int gh_launch_kgrad_reduce_loo(const gh_kernel* k, const uint32_t* which_host, c
                                double* diagB /* n or NULL */, GhBuf& scratch, hipStream_t st);
 
 // grad_dev[p] = sum over the nblk rows of partial (nblk x P) in a fixed-order tree: bitwise reproducible (the second stage of
-// gh_launch_kgrad_reduce, and of the strip form in gh_hodlr.hip)
+// gh_launch_kgrad_reduce, and of the strip form in gh_hodlr_predict.hip)
 int gh_launch_kgrad_final(const double* partial, int64_t nblk, int P, double* grad_dev, hipStream_t st);
 
 // Input derivatives of the prediction (gh_predgrad.hip): dmu[c][d] = sum_i G_cid alpha_i and, when dvar != NULL,

@@ -61,7 +61,7 @@ int gh_launch_potf2_mfma(double* A, int64_t lda, double* dinv, long long* info, 
 // (ti >= tj), is 480 matrix instructions shared by the four wavefronts (~4 us); log|K_b| = -2 sum_i log Linv(i, i).
 // KERN: the block is not read from A but evaluated from the leaf's points (GhPotf2Kern): the HODLR leaf build -- a launch that wrote
 // 268 MB for the next one to read back -- disappears for kernels of the a + b F(r^2) form.
-struct GhLeafRange { int start, size; long off; };       // (= LeafDesc of gh_hodlr.hip)
+struct GhLeafRange { int start, size; long off; };       // (= LeafDesc of gh_hodlr_impl.h)
 template <bool KERN>
 __global__ __launch_bounds__(256, 2) void potf2_kinv_kernel(double* A, long lda, long stride_a, double* logdet, long long* info,
                                                             GhFast fast, const double* x, const double* yerr, int nd, const GhLeafRange* leaves) {

@@ -1,5 +1,5 @@
 // gh_spin.h -- the ONE implementation of "a spin-wait that gives up": every device-side wait of this library (the chained
-// triangular sweeps of gh_chol_solve.hip, the ACA cluster barrier of gh_hodlr.hip) polls through a GhSpin, so that the time-out
+// triangular sweeps of gh_chol_solve.hip, the ACA cluster barrier of gh_hodlr_aca.hip) polls through a GhSpin, so that the time-out
 // (GH_SPIN_TIMEOUT_TICKS of the 100 MHz wall clock = 2 s) and the abort word's protocol have one definition:
 //
 //   * the abort word is an `int` in device memory, 0 while all is well; whoever times out sets it (atomicExch) and every

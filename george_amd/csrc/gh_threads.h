@@ -1,5 +1,5 @@
 // gh_threads.h -- host-thread plumbing shared by the two several-devices-in-one-process solvers
-// (gh_mgpu.hip: dense, gh_hodlr.hip: HODLR sub-tree split): the "ranks" are threads of the caller's
+// (gh_mgpu.hip: dense, gh_hodlr_mgpu.hip: HODLR sub-tree split): the "ranks" are threads of the caller's
 // process, one per device.
 #pragma once
 #include <atomic>

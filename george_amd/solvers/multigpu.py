@@ -213,7 +213,7 @@ class MultiGPUSolver(object):
 
 class MultiGPUHODLRSolver(MultiGPUSolver):
     """The HODLR solver with its tree split over several MI355X of one process (``gh_hodlr_mgpu_*``,
-    george_amd/csrc/gh_hodlr.hip): the top log2(len(devices)) levels are shared, each device owns one
+    george_amd/csrc/gh_hodlr_mgpu.hip): the top log2(len(devices)) levels are shared, each device owns one
     sub-tree.  Same keywords as ``HODLRSolver`` (reference ``src/george/solvers/hodlr.py:13-76``:
     ``min_size=100, tol=0.1, seed=42``) plus ``devices``; same node-by-node random streams as the
     single-GPU solver, so ranks and answers agree with it to rounding.  ``len(devices)`` must be a power

@@ -395,7 +395,7 @@ int  gh_hodlr_dot_solve(gh_hodlr* h, const double* y, double* out);
 int  gh_hodlr_get_inverse(gh_hodlr* h, double* out /* n*n */);
 int  gh_hodlr_ranks(const gh_hodlr* h, int32_t* ranks_out, int32_t max_out, int32_t* n_out);
 /* Fused device-resident forms of the GP glue on a computed handle, the HODLR counterparts of gh_chol_predict / gh_chol_grad.
- * Both work over column strips of n x Ct doubles (Ct a multiple of 64 chosen from a byte budget, gh_hodlr.hip), leave the factor,
+ * Both work over column strips of n x Ct doubles (Ct a multiple of 64 chosen from a byte budget, gh_hodlr_predict.hip), leave the factor,
  * log|K| and the computed state untouched, synchronise once at the end, and refuse a sub-tree handle of the multi-device split. */
 /* mu = K(xs,x) K^-1 r ; var = diag K(xs,xs) - diag(K(xs,x) K^-1 K(x,xs)) ; cov = K(xs,xs) - K(xs,x) K^-1 K(x,xs)
  * (gp.py:482-545 with apply_inverse = hodlr.h:107-114).  k may differ from the kernel of compute() (GP.predict(kernel=...)).

@@ -75,8 +75,8 @@ int gh_debug_set_hodlr_passes(int mask);
 /* 1: HODLR leaves of 129 .. 256 rows through the in-place pivoted Gauss-Jordan (what leaves of more than 256 rows take) instead of
  * the 2 x 2 blocked Cholesky; returns the previous setting (validation arm) */
 int gh_debug_set_hodlr_leaf_gj(int on);
-/* 1 (default): the ACA of tree levels whose blocks have at most 128 rows and columns runs with one wavefront per node
- * (hodlr_aca_wave_kernel); 0: every level with one workgroup per node.  Same ranks and factors, bit for bit; returns the
+/* 1 (default): the ACA of tree levels whose blocks have at most 256 rows and columns -- 128 for a kernel off the a + b F(r^2)
+ * fast form -- runs with one wavefront per node (hodlr_aca_wave_kernel); 0: every level with one workgroup per node.  Same ranks and factors, bit for bit; returns the
  * previous setting. */
 int gh_debug_set_hodlr_wave_aca(int on);
 /* workgroups the cooperative ACA launch of the top tree levels may use (32 .. 256, default 256: one per CU); returns the previous

@@ -1,9 +1,13 @@
 #!/bin/bash
-# A/B of a compile-time variant of gh_hodlr.hip on one box: VARIANT="-DGH_ACA_BATCH_ONES=0" bash scripts/gpu_hodlr_variant_ab.sh
+# A/B of a compile-time variant of the HODLR units on one box: VARIANT="-DGH_ACA_BATCH_ONES=0" bash scripts/gpu_hodlr_variant_ab.sh
+# UNITS: the units that read the flag (default gh_hodlr_aca: GH_ACA_BATCH_ONES and the ACA_* knobs; GH_ACA_TIMES needs "gh_hodlr_aca gh_hodlr").
+# Every other object comes from build/ (make -C george_amd/csrc first).
 cd /root/repo; export TMPDIR=/tmp
 cp george_amd/csrc/libgeorge_amd.so /tmp/lib_default.so
-( cd george_amd/csrc && hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result $VARIANT -c gh_hodlr.hip -o /tmp/gh_hodlr_var.o 2>/dev/null && \
-  hipcc --offload-arch=gfx950 -shared -fPIC build/gh_kmat.o build/gh_gemm.o build/gh_potf2.o build/gh_chol.o /tmp/gh_hodlr_var.o build/gh_mgpu.o -ldl -lpthread -o /tmp/lib_variant.so )
+( cd george_amd/csrc && objs="" && \
+  for u in ${UNITS:-gh_hodlr_aca}; do hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result $VARIANT -c $u.hip -o /tmp/${u}_var.o 2>/dev/null || exit 1; objs="$objs /tmp/${u}_var.o"; done && \
+  for o in build/gh_*.o; do case "$o" in *-hip-*) continue;; esac; u=$(basename $o .o); [ -e /tmp/${u}_var.o ] || objs="$objs $o"; done && \
+  hipcc --offload-arch=gfx950 -shared -fPIC $objs -ldl -lpthread -o /tmp/lib_variant.so )
 cat > /tmp/t.py <<'PY'
 import sys, time; sys.path.insert(0, "/root/repo")
 import numpy as np, bench, torch

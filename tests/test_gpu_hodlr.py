@@ -415,7 +415,7 @@ def test_wave_per_node_aca_gives_the_same_bits(case):
 def test_leaf_product_from_the_level_major_copy_gives_the_same_bits(n, tol):
     """Round 6: the compaction writes the level-major copy V only; the factorisation's leaf product reads a leaf's rows from it
     (a contiguous piece per level) and writes the row-major U for the first time (gh_debug_set_hodlr_u_from_v; LeafSrc in
-    gh_hodlr.hip).  The LDS image the product multiplies from holds the same doubles: identical ranks, log-determinant and solves.
+    gh_hodlr_impl.h).  The LDS image the product multiplies from holds the same doubles: identical ranks, log-determinant and solves.
     n = 5000: ragged leaves (rows past a leaf's end are zeros in the image); tol = 1e-3: few columns, levels of rank zero."""
     x, yerr, y = zoo.bench_data(n)
     kernel = np.var(y) * kernels.ExpSquaredKernel(1.0)

@@ -78,7 +78,7 @@ def _scratch_bytes(tu):
 def test_new_kernels_use_no_scratch_memory():
     """The column reduction, the identity strip and the PMAX = 4 / 16 forms of the strip gradient reduction use no scratch (the
     evaluator's runtime-indexed arrays live in LDS there); the GH_MAX_GRAD form may use what the dense kernel of that width uses."""
-    hod, kmat = _scratch_bytes("gh_hodlr"), _scratch_bytes("gh_kmat")
+    hod, kmat = {**_scratch_bytes("gh_hodlr_predict"), **_scratch_bytes("gh_hodlr_apply")}, _scratch_bytes("gh_kmat")
 
     def one(table, *parts):
         hits = [v for k, v in table.items() if all(p in k for p in parts)]
