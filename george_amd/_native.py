@@ -164,6 +164,7 @@ SIGNATURES = {
                                     _dp, _dp, _dp]),
     "gh_chol_loo": (C.c_int, [_vp, _vp, _dp, _dp, C.POINTER(C.c_double), _dp, _dp, _dp, _dp, _dp, _dp]),
     "gh_chol_fisher": (C.c_int, [_vp, _vp, _dp, _dp, _i32, _i64, _dp]),
+    "gh_chol_lgo": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _dp, _i64, C.POINTER(C.c_double), _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "gh_chol_loo_objective": (C.c_int, [_vp, _vp, _dp, _i64, _i32, _dp, _dp, _dp, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                         _dp, _dp, _dp, _dp, _dp]),
     "gh_chol_objective_batch": (C.c_int, [_vp, _vp, _dp, _i32, _dp, _i64, _i32, _dp, _dp, _dp, _dp, _dp]),

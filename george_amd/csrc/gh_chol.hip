@@ -305,7 +305,7 @@ extern "C" int64_t gh_chol_device_bytes(const gh_chol* s) {
   if (!s) return 0;
   size_t tot = 0;
   for (const GhBuf* b : {&s->A, &s->A_spare, &s->dinv, &s->x, &s->yerr, &s->v0, &s->v1, &s->v2, &s->scal, &s->rhs, &s->work, &s->work2,
-                         &s->scratch, &s->chain, &s->lv, &s->samp, &s->fish}) tot += b->p ? b->bytes : 0;
+                         &s->scratch, &s->chain, &s->lv, &s->samp, &s->fish, &s->lgo}) tot += b->p ? b->bytes : 0;
   return (int64_t)(tot + gh_batch_bytes(s->batch));
 }
 int gh_chol_batch_begin(gh_chol* s, hipStream_t* st, GhBatchBufs** bufs) {
@@ -961,7 +961,7 @@ extern "C" void gh_chol_release_buffers(gh_chol* s) {
   (void)hipSetDevice(s->opts.device);
   if (s->st) (void)hipStreamSynchronize(s->st);
   s->computed = false;
-  for (GhBuf* b : {&s->A, &s->A_spare, &s->dinv, &s->x, &s->yerr, &s->v0, &s->v1, &s->v2, &s->rhs, &s->work, &s->work2, &s->scratch, &s->chain, &s->lv, &s->samp, &s->fish}) b->release();
+  for (GhBuf* b : {&s->A, &s->A_spare, &s->dinv, &s->x, &s->yerr, &s->v0, &s->v1, &s->v2, &s->rhs, &s->work, &s->work2, &s->scratch, &s->chain, &s->lv, &s->samp, &s->fish, &s->lgo}) b->release();
   gh_batch_free(s->batch);
   s->batch = nullptr;
 }
@@ -970,7 +970,7 @@ extern "C" void gh_chol_trim(gh_chol* s) {
   if (!s) return;
   (void)hipSetDevice(s->opts.device);
   if (s->st) (void)hipStreamSynchronize(s->st);
-  for (GhBuf* b : {&s->rhs, &s->work, &s->work2, &s->scratch, &s->A_spare, &s->samp, &s->fish}) b->release();
+  for (GhBuf* b : {&s->rhs, &s->work, &s->work2, &s->scratch, &s->A_spare, &s->samp, &s->fish, &s->lgo}) b->release();
   gh_batch_free(s->batch);
   s->batch = nullptr;
 }

@@ -1,6 +1,6 @@
 // gh_chol_impl.h -- what the three units of the dense solver share (host side, private to them):
 //   gh_chol.hip         the factorisation: handle, streams, tile operations, panel schedules, compute
-//   gh_chol_solve.hip   work on a computed factor: reductions, sweeps, solve .. loo_objective
+//   gh_chol_solve.hip   work on a computed factor: reductions, sweeps, solve .. loo_objective, lgo
 //   gh_chol_update.hip  moving and editing a factor: export / import, append / truncate / set_yerr, remove
 // A kernel is launched only from the unit that defines it; what another unit needs of it is a launcher declared here.
 #pragma once
@@ -44,6 +44,7 @@ struct gh_chol {
   GhBuf A_spare;                         // the buffer the factor left when append / truncate last moved it: where the next move goes (freed by trim)
   GhBuf samp;                            // gh_chol_sample_conditional: prior diagonal, threshold and the factor / draw work arrays (freed by trim)
   GhBuf fish;                            // gh_chol_fisher's planes (freed by trim)
+  GhBuf lgo;                             // gh_chol_lgo's slot matrices, their inverses, partial sums and tables (freed by trim)
   GhBuf lv;                              // gh_chol_loo's N-vectors: resid, var, lpd, sqrt(w), c, alpha, v (7 Np doubles)
   long long* d_info = nullptr;           // = (long long*)(scal + 2): the failure word lives beside the scalars (set in compute_enqueue)
   bool build_on_chain = false;           // this compute(): inputs + kernel-matrix build were enqueued on the chain stream (st2)

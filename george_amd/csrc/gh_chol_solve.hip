@@ -1379,3 +1379,155 @@ extern "C" int gh_chol_loo_objective(gh_chol* s, gh_kernel* k, const double* x, 
   return GH_OK;
 }
 
+
+// ============================================================ leave-group-out cross-validation
+// (no reference counterpart.)  gh_chol_loo with every diagonal entry c_i of K^-1 replaced by the diagonal BLOCK C_gg of a group
+// (include/george_amd.h has the formulas; DESIGN.md section 4, "Leave-group-out cross-validation").  The groups are packed into
+// slots of 128 permuted positions, every slot one block-diagonal, identity-padded 128 x 128 matrix for the batched Cholesky.
+//   value path:    alpha -> work = L^-1 -> slot Gram matrices -> R = chol, R^-1 -> slot kernel -> sum of lpd.   K^-1 is never formed.
+//   gradient path: alpha -> work = K^-1 (work2 = L^-1) -> slot matrices gathered -> R, R^-1 -> slot kernel (+ W) -> v -> T = chol(W)
+//                  -> work2 = S = K^-1[:, J] T -> work = S S^T (lower) -> the contraction of gh_chol_loo.
+// s->lgo, in doubles: Cs | Ri | X (the Gram partials, or W) | cov | the failure word | the tables.  Results stay in s->lv (resid and
+// var by point, lpd by group, alpha, v), s->v0 = grad, s->v1 = diagB, as gh_chol_loo leaves them.
+struct LgoPlan {
+  std::vector<int> idx, grp, minj, pos0;
+  std::vector<long long> start, covoff;
+  int nslots = 0;
+};
+// nullptr, or what is wrong with the grouping
+static const char* lgo_check_groups(int64_t n, const int64_t* order, const int64_t* start, int64_t ngroups) {
+  if (ngroups < 1 || ngroups > n) return "lgo: the number of groups must be between 1 and n";
+  if (start[0] != 0 || start[ngroups] != n) return "lgo: start must rise from 0 to n";
+  for (int64_t g = 0; g < ngroups; ++g) {
+    if (start[g + 1] < start[g] || start[g + 1] > n) return "lgo: start must rise from 0 to n";
+    if (start[g + 1] == start[g]) return "lgo: a group is empty";
+    if (start[g + 1] - start[g] > GH_LGO_SLOT) return "lgo: a group has more than 128 points";
+  }
+  std::vector<char> seen((size_t)n, 0);
+  for (int64_t p = 0; p < n; ++p) {
+    if (order[p] < 0 || order[p] >= n || seen[(size_t)order[p]]) return "lgo: order is not a permutation of 0 .. n-1";
+    seen[(size_t)order[p]] = 1;
+  }
+  return nullptr;
+}
+// consecutive groups share a slot while they fit: at most 2 ceil(n / 128) + 1 slots
+static void lgo_plan(int64_t n, const int64_t* order, const int64_t* start, int64_t ngroups, LgoPlan& p) {
+  p.start.assign(start, start + ngroups + 1);
+  p.covoff.assign((size_t)ngroups + 1, 0);
+  int64_t used = GH_LGO_SLOT;                      // of the current slot (none yet)
+  for (int64_t g = 0; g < ngroups; ++g) {
+    const int64_t m = start[g + 1] - start[g];
+    p.covoff[(size_t)g + 1] = p.covoff[(size_t)g] + m * m;
+    if (used + m > GH_LGO_SLOT) {
+      p.idx.resize(p.idx.size() + GH_LGO_SLOT, -1);
+      p.grp.resize(p.grp.size() + GH_LGO_SLOT, -1);
+      p.pos0.push_back((int)start[g]);
+      p.minj.push_back((int)n);
+      used = 0;
+    }
+    const size_t at = p.idx.size() - GH_LGO_SLOT + (size_t)used;
+    for (int64_t q = 0; q < m; ++q) {
+      p.idx[at + (size_t)q] = (int)order[start[g] + q];
+      p.grp[at + (size_t)q] = (int)g;
+      p.minj.back() = std::min(p.minj.back(), (int)order[start[g] + q]);
+    }
+    used += m;
+  }
+  p.nslots = (int)p.pos0.size();
+}
+
+extern "C" int gh_chol_lgo(gh_chol* s, gh_kernel* k, const uint32_t* which, const double* r, const int64_t* order, const int64_t* start,
+                           int64_t ngroups, double* lpd_sum, double* resid, double* var, double* lpd, double* cov, double* grad,
+                           double* v, double* diagB) {
+  const bool have_args = k && r && order && start && lpd_sum && resid && var;
+  const char* bad = !have_args ? "bad argument to lgo" : (grad && !which) ? "lgo: gradient requested without a parameter mask" : nullptr;
+  if (!bad && s && s->computed) bad = lgo_check_groups(s->n, order, start, ngroups);
+  GH_CHECK(enter_computed(s, k, !bad, bad ? bad : ""));
+  const int64_t n = s->n, np = s->np, SS = (int64_t)GH_LGO_SLOT * GH_LGO_SLOT;
+  const bool grad_path = grad || v || diagB;
+  hipStream_t st = s->st;
+  LgoPlan plan;
+  lgo_plan(n, order, start, ngroups, plan);
+  const int64_t ns = plan.nslots, ncov = cov ? plan.covoff[(size_t)ngroups] : 0;
+  int64_t rows_per = 0;
+  const int64_t nx = grad_path ? 1 : gh_lgo_gram_chunks(n, plan.nslots, &rows_per);
+  // the layout of s->lgo
+  const int64_t o_cs = 0, o_ri = o_cs + ns * SS, o_x = o_ri + ns * SS, o_cov = o_x + nx * ns * SS, o_info = o_cov + gh_round_up(ncov, 2);
+  const int64_t o_ll = o_info + 2, o_int = o_ll + 2 * (ngroups + 1);
+  const size_t n_int = (size_t)(2 * ns * GH_LGO_SLOT + 2 * ns);
+  GH_CHECK(s->lgo.ensure((size_t)o_int * sizeof(double) + n_int * sizeof(int)));
+  double* base = s->lgo.d();
+  long long* d_info = (long long*)(base + o_info);
+  long long* d_ll = (long long*)(base + o_ll);
+  int* d_int = (int*)(base + o_int);
+  GH_HIP(hipMemsetAsync(d_info, 0, sizeof(long long), st));
+  GH_HIP(hipMemcpyAsync(d_ll, plan.start.data(), (size_t)(ngroups + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+  GH_HIP(hipMemcpyAsync(d_ll + ngroups + 1, plan.covoff.data(), (size_t)(ngroups + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+  GH_HIP(hipMemcpyAsync(d_int, plan.idx.data(), (size_t)ns * GH_LGO_SLOT * sizeof(int), hipMemcpyHostToDevice, st));
+  GH_HIP(hipMemcpyAsync(d_int + ns * GH_LGO_SLOT, plan.grp.data(), (size_t)ns * GH_LGO_SLOT * sizeof(int), hipMemcpyHostToDevice, st));
+  GH_HIP(hipMemcpyAsync(d_int + 2 * ns * GH_LGO_SLOT, plan.minj.data(), (size_t)ns * sizeof(int), hipMemcpyHostToDevice, st));
+  GH_HIP(hipMemcpyAsync(d_int + 2 * ns * GH_LGO_SLOT + ns, plan.pos0.data(), (size_t)ns * sizeof(int), hipMemcpyHostToDevice, st));
+  GhLgoSlots t;
+  t.idx = d_int; t.grp = d_int + ns * GH_LGO_SLOT; t.minj = d_int + 2 * ns * GH_LGO_SLOT; t.pos0 = t.minj + ns;
+  t.start = d_ll; t.covoff = d_ll + ngroups + 1; t.nslots = plan.nslots;
+  double* Cs = base + o_cs;
+  double* Ri = base + o_ri;
+  double* X = base + o_x;
+  double* dcov = cov ? base + o_cov : nullptr;
+
+  GH_CHECK(s->lv.ensure((size_t)LV_COUNT * np * sizeof(double)));
+  GH_CHECK(s->v0.ensure((size_t)std::max<int64_t>(np, GH_MAX_GRAD) * sizeof(double)));
+  GH_CHECK(s->v1.ensure((size_t)np * sizeof(double)));
+  double* lv = s->lv.d();
+  GH_HIP(hipMemsetAsync(s->scal.d() + 3, 0, sizeof(double), st));
+  // alpha = K^-1 r
+  double* alpha = lv + LV_ALPHA * np;
+  GH_CHECK(load_vec(s, s->v0, r));
+  GH_CHECK(trsv_forward(s, s->v0.d(), s->v1.d(), true));
+  GH_CHECK(trsv_backward(s, s->v1.d(), alpha, true));
+  GH_CHECK(loo_note_fail(s));
+  GH_CHECK(s->work.ensure((size_t)np * np * sizeof(double)));
+  if (!grad_path) {
+    GH_CHECK(linv_into(s, s->work.d()));
+    GH_CHECK(gh_launch_lgo_gram(s->work.d(), np, n, t, X, Cs, st));
+  } else {
+    GH_CHECK(s->work2.ensure((size_t)np * np * sizeof(double)));
+    GH_CHECK(inverse_lower(s, s->work.d(), s->work2.d()));
+    GH_CHECK(gh_launch_lgo_gather(s->work.d(), np, t, Cs, st));
+    GH_HIP(hipMemsetAsync(s->v0.d(), 0, (size_t)np * sizeof(double), st));       // u by point, zero in the padding
+  }
+  GH_CHECK(gh_launch_potf2_batched(Cs, GH_LGO_SLOT, SS, Ri, SS, d_info, plan.nslots, st));
+  GH_CHECK(gh_launch_lgo_slots(Cs, Ri, t, alpha, lv + LV_RESID * np, lv + LV_VAR * np, grad_path ? s->v0.d() : nullptr, lv + LV_LPD * np,
+                               dcov, grad_path ? X : nullptr, st));
+  if (grad_path) {
+    // v = K^-1 u
+    GH_CHECK(trsv_forward(s, s->v0.d(), s->v1.d(), true));
+    GH_CHECK(trsv_backward(s, s->v1.d(), lv + LV_V * np, true));
+    GH_CHECK(loo_note_fail(s));
+    // X <- T = chol(W) (its inverse, into Ri, is not used); work2 <- S = K^-1[:, J] T; work <- M = S S^T (lower tiles)
+    GH_CHECK(gh_launch_potf2_batched(X, GH_LGO_SLOT, SS, Ri, SS, d_info, plan.nslots, st));
+    GH_CHECK(gh_launch_lgo_block_scale(s->work.d(), np, n, t, X, s->work2.d(), st));
+    GhGemm g = gemm_desc(s->work.d(), np, s->work2.d(), np, true, s->work2.d(), np, true, np, np, np, 1.0, 0.0);
+    g.lower = true;
+    GH_CHECK(gh_launch_gemm(g, st));
+    static const uint32_t none[GH_MAX_GRAD] = {0};
+    GH_CHECK(gh_launch_kgrad_reduce_loo(k, grad ? which : none, s->x.d(), n, alpha, s->work.d(), np, s->v0.d(), s->v1.d(), s->scratch, st));
+  }
+  GH_CHECK(launch_sum(lv + LV_LPD * np, (long)ngroups, s->scal.d() + 1, s->scal.d() + 72, st));
+  double host[4] = {0.0, 0.0, 0.0, 0.0};                // (log-det), sum of lpd, (failure word), the chains' time-out flag
+  long long slot_info = 0;
+  GH_CHECK(read_scalars(s, host, 4, st));
+  GH_HIP(hipMemcpyAsync(&slot_info, d_info, sizeof(long long), hipMemcpyDeviceToHost, st));
+  GH_CHECK(gh_from_device(resid, lv + LV_RESID * np, (size_t)n, st));
+  GH_CHECK(gh_from_device(var, lv + LV_VAR * np, (size_t)n, st));
+  if (lpd) GH_CHECK(gh_from_device(lpd, lv + LV_LPD * np, (size_t)ngroups, st));
+  if (cov) GH_CHECK(gh_from_device(cov, dcov, (size_t)ncov, st));
+  if (grad && k->size > 0) GH_CHECK(gh_from_device(grad, s->v0.d(), (size_t)k->size, st));
+  if (v) GH_CHECK(gh_from_device(v, lv + LV_V * np, (size_t)n, st));
+  if (diagB) GH_CHECK(gh_from_device(diagB, s->v1.d(), (size_t)n, st));
+  GH_HIP(hipStreamSynchronize(st));
+  GH_CHECK(gh_chain_timeout("lgo", host[3] != 0.0, false));
+  if (slot_info != 0) { gh_set_error("lgo: a group's block of K^-1 is not positive definite"); return GH_ERR_NOT_PD; }
+  *lpd_sum = host[1];
+  return GH_OK;
+}

@@ -177,6 +177,37 @@ int gh_launch_fisher_pairs(const double* const* a, const int* a_idx, int na, con
 // F (ptot x ptot, zeroed by the caller) <- the pair sums, mirrored
 int gh_launch_fisher_mirror(const double* pairsum, const GhFisherMap& m, double* F, hipStream_t st);
 
+// The pieces of gh_chol_lgo (gh_lgo.hip).  A slot is GH_LGO_SLOT consecutive entries of the tables: whole groups, in group-sorted
+// ("permuted") order, then padding.  All pointers are device memory.
+#define GH_LGO_SLOT 128
+struct GhLgoSlots {
+  const int* idx;            // (nslots * 128) the point at a slot position, -1: padding
+  const int* grp;            // (nslots * 128) its group, -1: padding
+  const int* minj;           // (nslots) the slot's smallest point index
+  const int* pos0;           // (nslots) the permuted position of the slot's first entry
+  const long long* start;    // (ngroups + 1) the groups' offsets in permuted order
+  const long long* covoff;   // (ngroups + 1) ... and in the packed covariance blocks: sum of m_g^2 before the group
+  int nslots;
+};
+// row chunks of the Gram step (their partial sums are added in index order); part holds chunks * nslots * 128 * 128 doubles
+int gh_lgo_gram_chunks(int64_t n, int nslots, int64_t* rows_per);
+// Cs[slot] = the slot's block-diagonal, identity-padded matrix of K^-1 entries: from L^-1 (np x np, lower; rows >= n are not
+// read) as the Gram matrix of its gathered columns, or gathered from the lower triangle of K^-1
+int gh_launch_lgo_gram(const double* Linv, int64_t np, int64_t n, const GhLgoSlots& t, double* part, double* Cs, hipStream_t st);
+int gh_launch_lgo_gather(const double* Kinv, int64_t np, const GhLgoSlots& t, double* Cs, hipStream_t st);
+// from R = chol(Cs[slot]) and Rinv = R^-1 (gh_launch_potf2_batched): resid, var, u_pt (or NULL) by point, lpd by group, and when
+// not NULL cov (packed group blocks) and Ws[slot] = 1/2 (Cs^-1 + u u^T) inside the groups, the identity elsewhere
+int gh_launch_lgo_slots(const double* R, const double* Rinv, const GhLgoSlots& t, const double* alpha, double* resid, double* var,
+                        double* u_pt, double* lpd, double* cov, double* Ws, hipStream_t st);
+// S (np x np) = K^-1[:, J] blockdiag(Tm) from the lower triangle of K^-1: n columns in permuted order, zero from column n and row n on
+int gh_launch_lgo_block_scale(const double* Kinv, int64_t np, int64_t n, const GhLgoSlots& t, const double* Tm, double* S,
+                              hipStream_t st);
+
+// gh_potf2.hip: batched 128x128 Cholesky + inverse of the factor (block b at A + b*stride_a: the factor in place, zeros above the
+// diagonal; its inverse at dinv + b*stride_d, pitch 128).  A block that is not positive definite sets *info; the blocks after it stop.
+int gh_launch_potf2_batched(double* A, int64_t lda, int64_t stride_a, double* dinv, int64_t stride_d, long long* info,
+                            int nbatch, hipStream_t st);
+
 // fp64 GEMM family on the MFMA pipe: C = beta*C + alpha * op(A) * op(B)^T-ish.  See gh_gemm.hip.
 struct GhGemm {
   double* C; int64_t ldc;

@@ -148,10 +148,7 @@ static int upload(GhBuf& buf, const std::vector<Tv>& v, hipStream_t st) {
   return GH_OK;
 }
 
-// ---- gh_potf2.hip: batched 128x128 Cholesky + inverse of the factor (block b at A + b*stride_a)
-int gh_launch_potf2_batched(double* A, int64_t lda, int64_t stride_a, double* dinv, int64_t stride_d, long long* info,
-                            int nbatch, hipStream_t st);
-// ... and the leaf form: block b -> K_b^-1 (full symmetric, in place) and logdet[b] = log|K_b|, nothing else written
+// ---- gh_potf2.hip: the batched 128x128 Cholesky + inverse of the factor (gh_launch_potf2_batched, gh_common.h) in its leaf form: block b -> K_b^-1 (full symmetric, in place) and logdet[b] = log|K_b|, nothing else written
 int gh_launch_potf2_kinv_batched(double* A, int64_t lda, int64_t stride_a, double* logdet, long long* info, int nbatch, hipStream_t st);
 int gh_launch_potf2_kinv_kernel_batched(double* A, int64_t lda, int64_t stride_a, double* logdet, long long* info, int nbatch,
                                         const GhFast& fast, const double* x, const double* yerr, int nd, const void* leaves, hipStream_t st);

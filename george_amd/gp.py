@@ -601,6 +601,144 @@ class GP(ModelSet):
             return bad
         return -L, -self._assemble_loo_grad(v, diagB, kgrad, quiet)
 
+    # -- leave-group-out cross-validation (no reference counterpart) -------------------------------
+    # The groups I_1 .. I_G partition the points; with C = K^-1, alpha = C r and C_gg the block of C on group g the joint
+    # prediction of the group from all OTHER groups has residual u_g = C_gg^-1 alpha_g and covariance C_gg^-1, and
+    # L = sum_g 1/2 log|C_gg| - 1/2 alpha_g^T u_g - m_g/2 log 2 pi.  Its gradient is sum_ij B_ij dK_ij/dtheta with
+    # B = 1/2 (v alpha^T + alpha v^T) - C W C, v = C u, W = blockdiag_g 1/2 (C_gg^-1 + u_g u_g^T): leave-one-out is the case of
+    # one-point groups.  A solver that offers ``lgo`` (the HIP BasicSolver) keeps all of it on the
+    # device for groups of up to ``LGO_MAX_GROUP`` points; any other one, or a larger group, takes the NumPy branch on
+    # ``apply_inverse`` and ``get_inverse``, formula for formula.
+    def _lgo_groups(self, groups):
+        """``(order, start)`` of a ``groups`` argument: an (n,) integer array of labels -- any integers, groups numbered by
+        sorted unique label -- or a positive int b, windows of b consecutive points.  ``order`` lists the points sorted by
+        group (within a group as they appear in the data), ``start`` the G + 1 offsets of the groups in it."""
+        if not hasattr(self, "_x"):
+            raise RuntimeError("You need to compute the model first")
+        n = len(self._x)
+        if isinstance(groups, (int, np.integer)) and not isinstance(groups, (bool, np.bool_)):
+            if groups < 1:
+                raise ValueError("a window must have at least one point")
+            labels = np.arange(n) // int(groups)
+        else:
+            labels = np.asarray(groups)
+            if labels.dtype.kind not in "iu":
+                raise ValueError("groups must be an int or an array of integer labels")
+            if labels.shape != (n,):
+                raise ValueError("groups must have one label per point: shape ({0},)".format(n))
+        order = np.argsort(labels, kind="stable").astype(np.int64)
+        _, counts = np.unique(labels, return_counts=True)
+        start = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        return order, start
+
+    def _lgo_parts(self, r, order, start, want_grad, want_cov=False):
+        """``(L, resid, var, lpd, cov_blocks | None, kgrad | None, v | None, diagB | None)`` for the residual ``r`` on the
+        computed solver; ``kgrad`` over the unfrozen kernel parameters."""
+        n_k = len(self.kernel)
+        G = len(start) - 1
+        device = callable(getattr(self.solver, "lgo", None))
+        if device and np.max(np.diff(start)) <= getattr(self.solver, "LGO_MAX_GROUP", 0):
+            which = self.kernel.unfrozen_mask.astype(np.uint32) if want_grad else None
+            L, resid, var, lpd, cov, kg_full, v, diagB = self.solver.lgo(r, order, start, which, want_cov)
+            kgrad = kg_full[self.kernel.unfrozen_mask] if (want_grad and n_k) else None
+            return L, resid, var, lpd, cov, kgrad, v, diagB
+        alpha = np.asarray(self.solver.apply_inverse(np.array(r, dtype=np.float64))).flatten()
+        Kinv = np.asarray(self.solver.get_inverse())
+        n = len(alpha)
+        resid, var, lpd = np.empty(n), np.empty(n), np.empty(G)
+        covs = []
+        with np.errstate(divide="ignore", invalid="ignore"):
+            for g in range(G):
+                I = order[start[g]:start[g + 1]]
+                Cgg = Kinv[np.ix_(I, I)]
+                try:
+                    R = np.linalg.cholesky(0.5 * (Cgg + Cgg.T))
+                    Ri = np.linalg.inv(R)
+                except np.linalg.LinAlgError:               # (not positive definite, or not finite: the terms come out NaN)
+                    R = Ri = np.full(Cgg.shape, np.nan)
+                cov = np.dot(Ri.T, Ri)
+                resid[I] = np.dot(cov, alpha[I])
+                var[I] = np.diag(cov)
+                lpd[g] = np.sum(np.log(np.diag(R))) - 0.5 * np.dot(alpha[I], resid[I]) - 0.5 * len(I) * np.log(2 * np.pi)
+                covs.append(cov)
+            L = float(np.sum(lpd))
+            if not want_grad:
+                return L, resid, var, lpd, (covs if want_cov else None), None, None, None
+            v = np.asarray(self.solver.apply_inverse(np.array(resid, dtype=np.float64))).flatten()
+            M = np.zeros((n, n))
+            for g in range(G):
+                I = order[start[g]:start[g + 1]]
+                W = 0.5 * (covs[g] + np.einsum("i,j", resid[I], resid[I]))
+                M += np.dot(np.dot(Kinv[:, I], W), Kinv[I, :])
+            B = 0.5 * (np.einsum("i,j", v, alpha) + np.einsum("i,j", alpha, v)) - M
+        kgrad = np.einsum("ijk,ij", self.kernel.get_gradient(self._x), B) if n_k else None
+        return L, resid, var, lpd, (covs if want_cov else None), kgrad, v, np.array(np.diag(B))
+
+    def lgo_predict(self, y, groups, return_var=True, return_cov=False):
+        """Leave-group-out predictions: ``mu[i]`` (and ``var[i]``) of ``y[i]`` from all points OUTSIDE its group, mean model
+        and white noise included, without G refits.  ``groups``: an (n,) integer array of labels or a positive int b (windows
+        of b consecutive points).  With ``return_cov`` also the list of the G joint predictive covariances, groups in the
+        order of their sorted labels, rows in the order the group's points appear in the data."""
+        order, start = self._lgo_groups(groups)
+        self.recompute()
+        y = self._check_dimensions(y)
+        _, resid, var, _, cov, _, _, _ = self._lgo_parts(self._residual(y), order, start, False, return_cov)
+        out = (np.asarray(y, dtype=np.float64) - resid,)
+        if return_var:
+            out += (var,)
+        if return_cov:
+            out += (cov,)
+        return out if len(out) > 1 else out[0]
+
+    def lgo_log_likelihood(self, y, groups, quiet=False, pointwise=False):
+        """The leave-group-out log pseudo-likelihood ``sum_g log p(y_g | y_-g)``, or its G terms with ``pointwise=True``."""
+        order, start = self._lgo_groups(groups)
+        bad = np.full(len(start) - 1, -np.inf) if pointwise else -np.inf
+        if not self.recompute(quiet=quiet):
+            return bad
+        r = self._residual_quiet(y, quiet)
+        if r is None:
+            return bad
+        L, _, _, lpd, _, _, _, _ = self._lgo_parts(r, order, start, False)
+        if not np.isfinite(L):
+            return bad
+        return lpd if pointwise else L
+
+    def grad_lgo_log_likelihood(self, y, groups, quiet=False):
+        """Gradient of :meth:`lgo_log_likelihood` wrt the unfrozen parameters, ordered mean | white_noise | kernel."""
+        order, start = self._lgo_groups(groups)
+        if not self.recompute(quiet=quiet):
+            return np.zeros(len(self), dtype=np.float64)
+        r = self._residual_quiet(y, quiet)
+        if r is None:
+            return np.zeros(len(self), dtype=np.float64)
+        _, _, _, _, _, kgrad, v, diagB = self._lgo_parts(r, order, start, True)
+        return self._assemble_loo_grad(v, diagB, kgrad, quiet)
+
+    def lgo_nll_and_grad(self, vector, y, groups, quiet=True):
+        """``(-lgo_log_likelihood, -grad_lgo_log_likelihood)`` at ``vector`` for ``scipy.optimize.minimize(..., jac=True)``:
+        ``set_parameter_vector``, ``recompute`` and one leave-group-out call per iterate; ``(inf, zeros)`` outside the prior or
+        on a matrix that is not positive definite."""
+        order, start = self._lgo_groups(groups)
+        self.set_parameter_vector(vector)
+        if not np.isfinite(self.log_prior()):
+            return np.inf, np.zeros(len(vector))
+        bad = (np.inf, np.zeros(len(self)))
+        if not self.recompute(quiet=quiet):
+            return bad
+        r = self._residual_quiet(y, quiet)
+        if r is None:
+            return bad
+        try:
+            L, _, _, _, _, kgrad, v, diagB = self._lgo_parts(r, order, start, True)
+        except np.linalg.LinAlgError:
+            if quiet:
+                return bad
+            raise
+        if not np.isfinite(L):
+            return bad
+        return -L, -self._assemble_loo_grad(v, diagB, kgrad, quiet)
+
     # -- expected information of the hyper-parameters ---------------------------------------------
     # (no reference counterpart.)  For the Gaussian likelihood the expected (Fisher) information is
     #   F_ab = 1/2 tr(K^-1 dK/dtheta_a K^-1 dK/dtheta_b)      white-noise and kernel parameters

@@ -703,6 +703,54 @@ class BasicSolver(object):
         self.computed = True
         return logdet.value, total.value, resid, var, (g[:self._dk.size] if g is not None else None), v, diagB
 
+    # -- leave-group-out cross-validation (no reference counterpart)
+    LGO_MAX_GROUP = 128      # points of one group in the device form: one tile of the batched Cholesky
+
+    def lgo(self, r, order, start, which=None, want_cov=False):
+        """Leave-group-out quantities of the computed factor for residual ``r = y - mean`` (gh_chol_lgo).  ``order`` (n)
+        lists the point indices sorted by group, ``start`` (G + 1) the groups' offsets into it; a group has at most
+        ``LGO_MAX_GROUP`` points.  Returns ``(lpd_sum, resid, var, lpd, cov_blocks | None, grad_full | None, v | None,
+        diagB | None)``: ``resid = y - mu`` of every point predicted jointly with its group from all other groups and ``var``
+        its variance, both in the caller's point order, ``lpd`` the G joint log predictive densities, ``cov_blocks`` (with
+        ``want_cov``) the G predictive covariances, rows in the order of ``order``.  ``which=None``: values only -- K^-1 is not
+        formed.  With a parameter mask also ``grad_full`` = d lpd_sum / d theta over ALL kernel parameters (masked ones
+        exactly 0), ``v`` = d lpd_sum / d mean_i and ``diagB`` = d lpd_sum / d K_ii."""
+        h = self._need()
+        r = N.as_f64(r).reshape(-1)
+        n = self._n
+        if len(r) != n:
+            raise ValueError("dimension mismatch")
+        order = np.ascontiguousarray(order, dtype=np.int64).reshape(-1)
+        start = np.ascontiguousarray(start, dtype=np.int64).reshape(-1)
+        if len(order) != n or len(start) < 2:
+            raise ValueError("order must have one entry per point and start one more than there are groups")
+        G = len(start) - 1
+        total = C.c_double(0.0)
+        resid, var, lpd = np.empty(n), np.empty(n), np.empty(G)
+        sizes = np.diff(start)
+        cov = None
+        if want_cov:
+            if G > n or np.any(sizes < 0) or np.any(sizes > self.LGO_MAX_GROUP):
+                raise ValueError("a group is empty or has more than {0} points".format(self.LGO_MAX_GROUP))
+            cov = np.empty(int(np.sum(sizes ** 2)))
+        g = v = diagB = wh = None
+        if which is not None:
+            wh = np.zeros(max(self._dk.size, 1), dtype=np.uint32)
+            which = np.asarray(which)
+            if which.shape != (self._dk.size,):
+                raise ValueError("which must have shape ({0},)".format(self._dk.size))
+            wh[:self._dk.size] = which != 0
+            g = np.zeros(max(self._dk.size, 1))
+            v, diagB = np.empty(n), np.empty(n)
+        self._retry_without_parked_memory(lambda hh: N.check(N.lib.gh_chol_lgo(
+            hh, self._dk.handle, N.ptr(wh), N.ptr(r), N.ptr(order), N.ptr(start), G, C.byref(total), N.ptr(resid), N.ptr(var),
+            N.ptr(lpd), N.ptr(cov), N.ptr(g), N.ptr(v), N.ptr(diagB))))
+        blocks = None
+        if want_cov:
+            at = np.concatenate([[0], np.cumsum(sizes ** 2)])
+            blocks = [cov[at[i]:at[i + 1]].reshape(sizes[i], sizes[i]) for i in range(G)]
+        return total.value, resid, var, lpd, blocks, (g[:self._dk.size] if g is not None else None), v, diagB
+
     # -- expected information of the hyper-parameters (no reference counterpart)
     # The default budget of fisher().  Nobody has measured a good value: it stands on what _POOL_MAX_BYTES already assumes
     # about the card -- that solver handles may hold that much of it, work arrays included.  The planes belong to the handle

@@ -256,6 +256,7 @@ class HODLRSolver(BasicSolver):
     objective = None
     loo = None
     loo_objective = None
+    lgo = None                        # (GP.lgo_* take their NumPy branch on apply_inverse / get_inverse)
     fisher = None                     # (GP.fisher_information takes its NumPy branch on get_inverse)
     remove = None                     # (GP.remove computes afresh on the kept points)
     predict_gradient = None           # (GP.predict_gradient takes its NumPy branch on apply_inverse)

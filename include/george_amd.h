@@ -268,6 +268,26 @@ int  gh_chol_loo(gh_chol* s, gh_kernel* k, const uint32_t* which /* NULL: no gra
 int  gh_chol_loo_objective(gh_chol* s, gh_kernel* k, const double* x, int64_t n, int32_t ndim, const double* yerr,
                            const double* r, const uint32_t* which, double* logdet, double* lpd_sum,
                            double* resid, double* var, double* grad, double* v, double* diagB);
+/* Leave-group-out cross-validation on a computed handle (no reference lines correspond: src/george/gp.py has no cross-validation).
+ * The groups I_1 .. I_G partition the points: order (n) lists the point indices sorted by group, start (ngroups + 1) the groups'
+ * offsets into it; both are HOST arrays.  With C = K^-1, alpha = C r and C_gg the block of C on group g (m_g points):
+ *   resid_g = C_gg^-1 alpha_g = y_g - mu_g   (mu_g: the joint prediction of the group from all other points)
+ *   cov_g   = C_gg^-1,  var = its diagonal
+ *   lpd[g]  = 1/2 log|C_gg| - 1/2 alpha_g^T C_gg^-1 alpha_g - m_g/2 log 2 pi;      *lpd_sum = sum_g lpd[g]
+ * and, with u = resid, v = C u, W = blockdiag_g 1/2 (C_gg^-1 + u_g u_g^T), B = 1/2 (v alpha^T + alpha v^T) - C W C:
+ *   grad[p]  = sum_ij B_ij dK_ij/dtheta_p  for the parameters selected by `which` (others exactly 0)
+ *   v (n)    : d lpd_sum / d mean_i;      diagB (n) = diag(B): d lpd_sum / d K_ii.
+ * Groups of one point each give gh_chol_loo.  resid, var, v, diagB are in the caller's point order; cov holds the G blocks one after
+ * the other, each m_g x m_g row-major with its rows in the order of `order`.  A group has at most 128 points.  GH_ERR_BAD_ARG, before
+ * any device work, when order is not a permutation of 0 .. n-1, start does not rise from 0 to n, a group is empty or has more than
+ * 128 points, or grad is given without which.  grad, v and diagB all NULL: K^-1 is not formed (one N x N work buffer); otherwise two,
+ * as gh_chol_grad.  The slot buffers are counted by gh_chol_device_bytes and freed by gh_chol_trim.  Data pointers may be host or
+ * device memory.  Two calls give the same bits. */
+int  gh_chol_lgo(gh_chol* s, gh_kernel* k, const uint32_t* which /* NULL: no gradient */, const double* r,
+                 const int64_t* order /* n, host */, const int64_t* start /* ngroups+1, host */, int64_t ngroups,
+                 double* lpd_sum, double* resid /* n, caller's point order */, double* var /* n */,
+                 double* lpd /* ngroups or NULL */, double* cov /* sum m_g^2, group-major, row-major blocks, or NULL */,
+                 double* grad /* size or NULL */, double* v /* n or NULL */, double* diagB /* n or NULL */);
 /* Expected (Fisher) information of the hyper-parameters on a computed handle (no reference lines correspond: src/george/gp.py
  * stops at the gradient; GPML eq. 5.9 differentiated once more and averaged over y ~ N(0, K)):
  *   fisher[a][b] = 1/2 tr(K^-1 D_a K^-1 D_b),    (n_diag + size)^2 doubles, row-major, symmetric bit for bit.
