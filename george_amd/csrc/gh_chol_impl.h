@@ -1,6 +1,7 @@
 // gh_chol_impl.h -- what the three units of the dense solver share (host side, private to them):
 //   gh_chol.hip         the factorisation: handle, streams, tile operations, panel schedules, compute
-//   gh_chol_solve.hip   work on a computed factor: reductions, sweeps, solve .. loo_objective, lgo
+//   gh_chol_solve.hip   work on a computed factor: reductions, sweeps, solve .. fisher, objective, and the cross-validation
+//                       driver (loo, loo_objective, lgo; its kernels: gh_cv.hip)
 //   gh_chol_update.hip  moving and editing a factor: export / import, append / truncate / set_yerr, remove
 // A kernel is launched only from the unit that defines it; what another unit needs of it is a launcher declared here.
 #pragma once

@@ -2,7 +2,7 @@
 //
 // Solves are blocked substitutions that multiply by the stored 128x128 diagonal inverses: TRSV kernels for one right-hand side
 // (one chained launch per sweep), the MFMA GEMM for many.  On top of them: dot_solve, solve, apply_sqrt, get_inverse, predict,
-// predict_grad, sample_conditional, grad, fisher, objective, loo, loo_objective.  The reductions live here too (the log-det's
+// predict_grad, sample_conditional, grad, fisher, objective, loo, loo_objective, lgo.  The reductions live here too (the log-det's
 // launcher is what the other two units call).
 #include <math.h>
 #include "gh_chol_impl.h"
@@ -529,92 +529,7 @@ __global__ void copy2d_kernel(const double* in, long ldi, double* out, long ldo,
   out[i * ldo + j] = in[i * ldi + j];
 }
 
-// ================================================= leave-one-out cross-validation
-#define LT 64                 // tile edge of the leave-one-out kernels
-// Column sums of squares of a LOWER-triangular row-major matrix (L^-1): part[s][c] = sum over the rows r >= c of the s-th row
-// chunk of V[r][c]^2.  A workgroup takes 64 columns of one chunk, a wavefront every fourth row: each load instruction reads
-// 512 contiguous bytes, four rows are in flight per trip.  Rows above the tile's first column hold zeros and are not read.
-// The four wavefronts' sums meet in LDS in a fixed order; colsumsq_final_kernel adds the chunks in index order: no atomics,
-// bitwise reproducible.
-__global__ __launch_bounds__(256) void colsumsq_kernel(const double* V, long ld, long np, long rows_per, double* part) {
-  __shared__ double sh[4][LT];
-  const int lc = threadIdx.x & 63, lr = threadIdx.x >> 6;
-  const long c0 = (long)blockIdx.x * LT, c = c0 + lc;
-  long r0 = (long)blockIdx.y * rows_per;
-  const long r1 = r0 + rows_per < np ? r0 + rows_per : np;
-  if (r0 < c0) r0 = c0;
-  double acc = 0.0;
-  long r = r0 + lr;
-  for (; r + 12 < r1; r += 16) {
-    double a[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) a[q] = V[(r + 4 * q) * ld + c];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) acc += (r + 4 * q >= c) ? a[q] * a[q] : 0.0;
-  }
-  for (; r < r1; r += 4) {
-    const double a = V[r * ld + c];
-    acc += (r >= c) ? a * a : 0.0;
-  }
-  sh[lr][lc] = acc;
-  __syncthreads();
-  if (lr == 0) part[(long)blockIdx.y * np + c] = (sh[0][lc] + sh[1][lc]) + (sh[2][lc] + sh[3][lc]);
-}
-__global__ void colsumsq_final_kernel(const double* part, long nchunks, long np, double* c) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= np) return;
-  double v = 0.0;
-  for (long s = 0; s < nchunks; ++s) v += part[s * np + i];
-  c[i] = v;
-}
-// The per-point quantities from alpha and c_i = (K^-1)_ii (c[i * cstride]: a vector, or the diagonal of a matrix):
-//   resid = u = alpha / c,  var = 1 / c,  lpd = 1/2 log c - 1/2 alpha^2 / c - 1/2 log 2 pi,  sw = sqrt(w),  w = 1/2 (1 + alpha^2 / c) / c.
-// Padded rows i >= n get zeros everywhere: nothing of them reaches the sum of lpd or S = K^-1 diag(sqrt(w)).
-// `u` is a second copy of resid that the solve for v = K^-1 u consumes.
-__global__ void loo_point_kernel(const double* alpha, const double* c, long cstride, long n, long np,
-                                 double* resid, double* u, double* var, double* lpd, double* sw) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= np) return;
-  double ui = 0.0, vi = 0.0, li = 0.0, si = 0.0;
-  if (i < n) {
-    const double ci = c[i * cstride], a = alpha[i];
-    ui = a / ci;
-    vi = 1.0 / ci;
-    const double q = a * ui;
-    li = 0.5 * log(ci) - 0.5 * q - 0.91893853320467274178;
-    si = sqrt(0.5 * (1.0 + q) / ci);
-  }
-  resid[i] = ui;
-  if (u) u[i] = ui;
-  var[i] = vi;
-  lpd[i] = li;
-  sw[i] = si;
-}
-// S = Kinv diag(sw) as a FULL matrix from the lower triangle of Kinv, one pass: a workgroup reads the 64 x 64 tile (ti, tj),
-// tj <= ti, into LDS and writes tile (ti, tj) of S as it lies and tile (tj, ti) transposed, column k scaled by sw[k].  Reads and
-// both writes are coalesced (a row of 64 doubles per wavefront); the transposed LDS reads walk a pitch of 65: no bank conflicts.
-__global__ __launch_bounds__(256) void loo_mirror_scale_kernel(const double* W, long ld, const double* sw, double* S) {
-  __shared__ double t[LT][LT + 1];
-  int ti, tj;
-  tri_index(blockIdx.x, ti, tj);
-  const long r0 = (long)ti * LT, c0 = (long)tj * LT;
-  const int lc = threadIdx.x & 63, lr = threadIdx.x >> 6;
-#pragma unroll 4
-  for (int rr = lr; rr < LT; rr += 4) t[rr][lc] = W[(r0 + rr) * ld + c0 + lc];
-  __syncthreads();
-  const double sc = sw[c0 + lc];
-  if (ti != tj) {
-    const double sr = sw[r0 + lc];
-#pragma unroll 4
-    for (int rr = lr; rr < LT; rr += 4) {
-      S[(r0 + rr) * ld + c0 + lc] = t[rr][lc] * sc;
-      S[(c0 + rr) * ld + r0 + lc] = t[lc][rr] * sr;
-    }
-  } else {
-#pragma unroll 4
-    for (int rr = lr; rr < LT; rr += 4) S[(r0 + rr) * ld + c0 + lc] = (lc <= rr ? t[rr][lc] : t[lc][rr]) * sc;
-  }
-}
+// ================================================= cross-validation: the sum of lpd, the sweeps' time-out note
 // out[0] = sum_{i < n} a[i]: one workgroup, or slices added in index order (launch_sum, as launch_dot)
 __global__ __launch_bounds__(256) void sum_part_kernel(const double* a, long n, double* part) {
   __shared__ double sh[4];
@@ -1256,90 +1171,101 @@ extern "C" int gh_chol_objective(gh_chol* s, gh_kernel* k, const double* x, int6
   return GH_OK;
 }
 
-// ============================================================ leave-one-out cross-validation
+// ============================================================ cross-validation: leave-one-out, leave-group-out
 // (no reference counterpart: src/george/gp.py has no cross-validation.)  With c_i = (K^-1)_ii and alpha = K^-1 r the prediction of
 // y_i from all other points has residual alpha_i / c_i and variance 1 / c_i (GPML 5.4.2), and the gradient of the log
 // pseudo-likelihood is sum_ij B_ij dK_ij/dtheta with B = 1/2 (v alpha^T + alpha v^T) - S S^T, S = K^-1 diag(sqrt(w)), v = K^-1 u:
-// ONE triangular N^3 product for any number of parameters ("Leave-one-out cross-validation").
-//   value path:    alpha -> work = L^-1 -> c = column sums of squares -> per-point kernel -> sum of lpd.   K^-1 is never formed.
-//   gradient path: alpha -> work = K^-1 (work2 = L^-1) -> c = diag -> per-point kernel -> v -> work2 = S -> work = S S^T (lower)
-//                  -> the contraction (gh_launch_kgrad_reduce_loo).
+// ONE triangular N^3 product for any number of parameters ("Leave-one-out cross-validation").  Leave-group-out replaces
+// every c_i by the diagonal BLOCK C_gg of a group (include/george_amd.h has the formulas; DESIGN.md section 4, "Leave-group-out
+// cross-validation").  Both are one sequence of steps with their own middle (loo_enqueue, lgo_enqueue; kernels: gh_cv.hip):
+//   value path:    cv_alpha -> work = L^-1 -> the middle: c or C_gg, per point or per slot -> cv_fetch -> cv_finish.   K^-1 is never formed.
+//   gradient path: cv_alpha -> work = K^-1 (work2 = L^-1) -> the middle, u -> cv_solve (v) -> the middle: work2 = S -> cv_contract
+//                  -> cv_fetch -> cv_finish.
 // Everything is enqueued on s->st; results stay on the device (s->lv, s->v0 = grad, s->v1 = diagB, s->scal[1] = sum of lpd,
-// s->scal[3] != 0: a chained sweep timed out) until loo_fetch().
-enum { LV_RESID = 0, LV_VAR, LV_LPD, LV_SW, LV_C, LV_ALPHA, LV_V, LV_COUNT };     // (alpha and v adjacent: gh_launch_kgrad_reduce_loo)
+// s->scal[3] != 0: a chained sweep timed out) until cv_fetch().
+enum { LV_RESID = 0, LV_VAR, LV_LPD, LV_SW, LV_C, LV_ALPHA, LV_V, LV_COUNT };
 static int loo_note_fail(gh_chol* s) {
   if (gh_trsv_stepwise()) return GH_OK;
   hipLaunchKernelGGL(chain_fail_note_kernel, dim3(1), dim3(64), 0, s->st, (const int*)fwd_fail(s), (const int*)bwd_fail(s), s->scal.d() + 3);
   GH_HIP(hipGetLastError());
   return GH_OK;
 }
-static int loo_enqueue(gh_chol* s, gh_kernel* k, const uint32_t* which, const double* r, bool grad_path) {
-  const int64_t n = s->n, np = s->np;
-  hipStream_t st = s->st;
+// lv[to] = K^-1 v0 (v0 and v1 are consumed): two deferred sweeps, their time-outs noted in scal[3]
+static int cv_solve(gh_chol* s, int to) {
+  GH_CHECK(trsv_forward(s, s->v0.d(), s->v1.d(), true));
+  GH_CHECK(trsv_backward(s, s->v1.d(), s->lv.d() + to * s->np, true));
+  return loo_note_fail(s);
+}
+// the buffers of the sequence, scal[3] cleared, alpha = K^-1 r
+static int cv_alpha(gh_chol* s, const double* r) {
+  const int64_t np = s->np;
   GH_CHECK(s->lv.ensure((size_t)LV_COUNT * np * sizeof(double)));
   GH_CHECK(s->v0.ensure((size_t)std::max<int64_t>(np, GH_MAX_GRAD) * sizeof(double)));
   GH_CHECK(s->v1.ensure((size_t)np * sizeof(double)));
-  double* lv = s->lv.d();
-  GH_HIP(hipMemsetAsync(s->scal.d() + 3, 0, sizeof(double), st));
-  // alpha = K^-1 r
-  double* alpha = lv + LV_ALPHA * np;
+  GH_HIP(hipMemsetAsync(s->scal.d() + 3, 0, sizeof(double), s->st));
   GH_CHECK(load_vec(s, s->v0, r));
-  GH_CHECK(trsv_forward(s, s->v0.d(), s->v1.d(), true));
-  GH_CHECK(trsv_backward(s, s->v1.d(), alpha, true));
-  GH_CHECK(loo_note_fail(s));
-  const unsigned gv = (unsigned)((np + 255) / 256);
-  if (!grad_path) {
-    // c_i = sum_{k >= i} (L^-1)_ki^2: the diagonal of K^-1 = L^-T L^-1 without the product
-    GH_CHECK(s->work.ensure((size_t)np * np * sizeof(double)));
-    double* Linv = s->work.d();
-    GH_CHECK(linv_into(s, Linv));
-    const int64_t nchunks = std::min<int64_t>(64, np / T);
-    const int64_t rows_per = (np + nchunks - 1) / nchunks;
-    GH_CHECK(s->scratch.ensure((size_t)nchunks * np * sizeof(double)));
-    hipLaunchKernelGGL(colsumsq_kernel, dim3((unsigned)(np / LT), (unsigned)nchunks), dim3(256), 0, st,
-                       Linv, (long)np, (long)np, (long)rows_per, s->scratch.d());
-    hipLaunchKernelGGL(colsumsq_final_kernel, dim3(gv), dim3(256), 0, st, s->scratch.d(), (long)nchunks, (long)np, lv + LV_C * np);
-    hipLaunchKernelGGL(loo_point_kernel, dim3(gv), dim3(256), 0, st, alpha, lv + LV_C * np, 1L, (long)n, (long)np,
-                       lv + LV_RESID * np, (double*)nullptr, lv + LV_VAR * np, lv + LV_LPD * np, lv + LV_SW * np);
-    GH_HIP(hipGetLastError());
-  } else {
-    GH_CHECK(s->work.ensure((size_t)np * np * sizeof(double)));
-    GH_CHECK(s->work2.ensure((size_t)np * np * sizeof(double)));
-    GH_CHECK(inverse_lower(s, s->work.d(), s->work2.d()));
-    hipLaunchKernelGGL(loo_point_kernel, dim3(gv), dim3(256), 0, st, alpha, s->work.d(), (long)np + 1, (long)n, (long)np,
-                       lv + LV_RESID * np, s->v0.d(), lv + LV_VAR * np, lv + LV_LPD * np, lv + LV_SW * np);
-    GH_HIP(hipGetLastError());
-    // v = K^-1 u
-    GH_CHECK(trsv_forward(s, s->v0.d(), s->v1.d(), true));
-    GH_CHECK(trsv_backward(s, s->v1.d(), lv + LV_V * np, true));
-    GH_CHECK(loo_note_fail(s));
-    // work2 <- S = K^-1 diag(sqrt(w)), then work <- M = S S^T (lower tiles)
-    const long tm = (long)(np / LT);
-    hipLaunchKernelGGL(loo_mirror_scale_kernel, dim3((unsigned)(tm * (tm + 1) / 2)), dim3(256), 0, st,
-                       s->work.d(), (long)np, lv + LV_SW * np, s->work2.d());
-    GH_HIP(hipGetLastError());
-    GhGemm g = gemm_desc(s->work.d(), np, s->work2.d(), np, true, s->work2.d(), np, true, np, np, np, 1.0, 0.0);
-    g.lower = true;
-    GH_CHECK(gh_launch_gemm(g, st));
-    static const uint32_t none[GH_MAX_GRAD] = {0};
-    static_assert(LV_V == LV_ALPHA + 1, "gh_launch_kgrad_reduce_loo reads v one leading dimension (np) behind alpha");
-    GH_CHECK(gh_launch_kgrad_reduce_loo(k, which ? which : none, s->x.d(), n, alpha, s->work.d(), np,
-                                        s->v0.d(), s->v1.d(), s->scratch, st));       // (v0, v1 are free again)
-  }
-  return launch_sum(lv + LV_LPD * np, (long)n, s->scal.d() + 1, s->scal.d() + 72, st);
+  return cv_solve(s, LV_ALPHA);
 }
-// the copies out (host or device destinations), enqueued on s->st
-static int loo_fetch(gh_chol* s, gh_kernel* k, double* resid, double* var, double* lpd, double* grad, double* v, double* diagB) {
+// work <- M = S S^T (lower tiles), S in work2; then the contraction: v0 = grad over `which` (NULL: no parameter), v1 = diagB
+static int cv_contract(gh_chol* s, gh_kernel* k, const uint32_t* which) {
+  const int64_t np = s->np;
+  GhGemm g = gemm_desc(s->work.d(), np, s->work2.d(), np, true, s->work2.d(), np, true, np, np, np, 1.0, 0.0);
+  g.lower = true;
+  GH_CHECK(gh_launch_gemm(g, s->st));
+  static const uint32_t none[GH_MAX_GRAD] = {0};
+  static_assert(LV_V == LV_ALPHA + 1, "gh_launch_kgrad_reduce_loo reads v one leading dimension (np) behind alpha");
+  return gh_launch_kgrad_reduce_loo(k, which ? which : none, s->x.d(), s->n, s->lv.d() + LV_ALPHA * np, s->work.d(), np,
+                                    s->v0.d(), s->v1.d(), s->scratch, s->st);       // (v0, v1 are free again)
+}
+// the sum of the n_lpd terms of lpd, then the read-back: host <- (log-det), sum of lpd, (failure word), the chains' time-out flag, and
+// the copies out (host or device destinations; lpd, grad, v, diagB may be NULL).  `host` must live until cv_finish().
+static int cv_fetch(gh_chol* s, gh_kernel* k, int64_t n_lpd, double* host, double* resid, double* var, double* lpd, double* grad,
+                    double* v, double* diagB) {
   const int64_t n = s->n, np = s->np;
   hipStream_t st = s->st;
   const double* lv = s->lv.d();
+  GH_CHECK(launch_sum(lv + LV_LPD * np, (long)n_lpd, s->scal.d() + 1, s->scal.d() + 72, st));
+  GH_CHECK(read_scalars(s, host, 4, st));
   GH_CHECK(gh_from_device(resid, lv + LV_RESID * np, (size_t)n, st));
   GH_CHECK(gh_from_device(var, lv + LV_VAR * np, (size_t)n, st));
-  if (lpd) GH_CHECK(gh_from_device(lpd, lv + LV_LPD * np, (size_t)n, st));
+  if (lpd) GH_CHECK(gh_from_device(lpd, lv + LV_LPD * np, (size_t)n_lpd, st));
   if (grad && k->size > 0) GH_CHECK(gh_from_device(grad, s->v0.d(), (size_t)k->size, st));
   if (v) GH_CHECK(gh_from_device(v, lv + LV_V * np, (size_t)n, st));
   if (diagB) GH_CHECK(gh_from_device(diagB, s->v1.d(), (size_t)n, st));
   return GH_OK;
+}
+// the call's ONE synchronisation; with `c`, the end of the compute that the call began with
+static int cv_finish(gh_chol* s, const char* who, const double* host, double* lpd_sum, const ComputeCtx* c = nullptr, double* logdet = nullptr) {
+  GH_HIP(hipStreamSynchronize(s->st));
+  if (c) GH_CHECK(gh_chol_compute_finish(s, *c, host[0], info_from_bits(host[2]), logdet));
+  GH_CHECK(gh_chain_timeout(who, host[3] != 0.0, false));
+  *lpd_sum = host[1];
+  return GH_OK;
+}
+
+// leave-one-out up to the contraction: c_i as the column sums of squares of L^-1, or as the diagonal of K^-1
+static int loo_enqueue(gh_chol* s, gh_kernel* k, const uint32_t* which, const double* r, bool grad_path) {
+  const int64_t n = s->n, np = s->np;
+  hipStream_t st = s->st;
+  GH_CHECK(cv_alpha(s, r));
+  double* lv = s->lv.d();
+  GH_CHECK(s->work.ensure((size_t)np * np * sizeof(double)));
+  if (!grad_path) {
+    // c_i = sum_{k >= i} (L^-1)_ki^2: the diagonal of K^-1 = L^-T L^-1 without the product
+    GH_CHECK(linv_into(s, s->work.d()));
+    const int64_t nchunks = std::min<int64_t>(64, np / T);
+    GH_CHECK(s->scratch.ensure((size_t)nchunks * np * sizeof(double)));
+    GH_CHECK(gh_launch_loo_colsumsq(s->work.d(), np, nchunks, s->scratch.d(), lv + LV_C * np, st));
+    return gh_launch_loo_point(lv + LV_ALPHA * np, lv + LV_C * np, 1, n, np, lv + LV_RESID * np, nullptr, lv + LV_VAR * np,
+                               lv + LV_LPD * np, lv + LV_SW * np, st);
+  }
+  GH_CHECK(s->work2.ensure((size_t)np * np * sizeof(double)));
+  GH_CHECK(inverse_lower(s, s->work.d(), s->work2.d()));
+  GH_CHECK(gh_launch_loo_point(lv + LV_ALPHA * np, s->work.d(), np + 1, n, np, lv + LV_RESID * np, s->v0.d(), lv + LV_VAR * np,
+                               lv + LV_LPD * np, lv + LV_SW * np, st));
+  GH_CHECK(cv_solve(s, LV_V));                                                                  // v = K^-1 u, u in v0
+  GH_CHECK(gh_launch_loo_mirror_scale(s->work.d(), np, lv + LV_SW * np, s->work2.d(), st));     // work2 <- S = K^-1 diag(sqrt(w))
+  return cv_contract(s, k, which);
 }
 
 extern "C" int gh_chol_loo(gh_chol* s, gh_kernel* k, const uint32_t* which, const double* r, double* lpd_sum, double* resid,
@@ -1348,13 +1274,9 @@ extern "C" int gh_chol_loo(gh_chol* s, gh_kernel* k, const uint32_t* which, cons
   GH_CHECK(enter_computed(s, k, have_args && !(grad && !which),
                           have_args ? "loo: gradient requested without a parameter mask" : "bad argument to loo"));
   GH_CHECK(loo_enqueue(s, k, grad ? which : nullptr, r, grad || v || diagB));
-  double host[4] = {0.0, 0.0, 0.0, 0.0};                // (log-det), sum of lpd, (failure word), the chains' time-out flag
-  GH_CHECK(read_scalars(s, host, 4, s->st));
-  GH_CHECK(loo_fetch(s, k, resid, var, lpd, grad, v, diagB));
-  GH_HIP(hipStreamSynchronize(s->st));
-  GH_CHECK(gh_chain_timeout("loo", host[3] != 0.0, false));
-  *lpd_sum = host[1];
-  return GH_OK;
+  double host[4] = {0.0, 0.0, 0.0, 0.0};
+  GH_CHECK(cv_fetch(s, k, s->n, host, resid, var, lpd, grad, v, diagB));
+  return cv_finish(s, "loo", host, lpd_sum);
 }
 
 // build K -> factor -> log-det -> the sequence of gh_chol_loo, ONE synchronisation: the analogue of gh_chol_objective for the
@@ -1366,29 +1288,19 @@ extern "C" int gh_chol_loo_objective(gh_chol* s, gh_kernel* k, const double* x, 
   if (grad && !which) { gh_set_error("loo_objective: gradient requested without a parameter mask"); return GH_ERR_BAD_ARG; }
   ComputeCtx c;
   GH_CHECK(gh_chol_compute_enqueue(s, k, x, n, ndim, yerr, c));
-  hipStream_t st = s->st;
   GH_CHECK(join_tail(s));
   GH_CHECK(loo_enqueue(s, k, grad ? which : nullptr, r, grad || v || diagB));
-  double host[4] = {0.0, 0.0, 0.0, 0.0};                // log-det, sum of lpd, failure word (bits), the chains' time-out flag
-  GH_CHECK(read_scalars(s, host, 4, st));
-  GH_CHECK(loo_fetch(s, k, resid, var, nullptr, grad, v, diagB));
-  GH_HIP(hipStreamSynchronize(st));
-  GH_CHECK(gh_chol_compute_finish(s, c, host[0], info_from_bits(host[2]), logdet));
-  GH_CHECK(gh_chain_timeout("loo_objective", host[3] != 0.0, false));
-  *lpd_sum = host[1];
-  return GH_OK;
+  double host[4] = {0.0, 0.0, 0.0, 0.0};
+  GH_CHECK(cv_fetch(s, k, s->n, host, resid, var, nullptr, grad, v, diagB));
+  return cv_finish(s, "loo_objective", host, lpd_sum, &c, logdet);
 }
 
-
-// ============================================================ leave-group-out cross-validation
-// (no reference counterpart.)  gh_chol_loo with every diagonal entry c_i of K^-1 replaced by the diagonal BLOCK C_gg of a group
-// (include/george_amd.h has the formulas; DESIGN.md section 4, "Leave-group-out cross-validation").  The groups are packed into
-// slots of 128 permuted positions, every slot one block-diagonal, identity-padded 128 x 128 matrix for the batched Cholesky.
-//   value path:    alpha -> work = L^-1 -> slot Gram matrices -> R = chol, R^-1 -> slot kernel -> sum of lpd.   K^-1 is never formed.
-//   gradient path: alpha -> work = K^-1 (work2 = L^-1) -> slot matrices gathered -> R, R^-1 -> slot kernel (+ W) -> v -> T = chol(W)
-//                  -> work2 = S = K^-1[:, J] T -> work = S S^T (lower) -> the contraction of gh_chol_loo.
-// s->lgo, in doubles: Cs | Ri | X (the Gram partials, or W) | cov | the failure word | the tables.  Results stay in s->lv (resid and
-// var by point, lpd by group, alpha, v), s->v0 = grad, s->v1 = diagB, as gh_chol_loo leaves them.
+// ---- leave-group-out: the groups are packed into slots of 128 permuted positions, every slot one block-diagonal, identity-padded
+// 128 x 128 matrix for the batched Cholesky.
+//   value path:    the slots' Gram matrices of L^-1 -> R = chol, R^-1 -> slot kernel.
+//   gradient path: the slots' matrices gathered from K^-1 -> R, R^-1 -> slot kernel (+ W) -> v -> T = chol(W) -> S = K^-1[:, J] T.
+// s->lgo, in doubles: Cs | Ri | X (the Gram partials, or W) | cov | the failure word | the tables.  s->lv holds resid and var by
+// point, lpd by group.
 struct LgoPlan {
   std::vector<int> idx, grp, minj, pos0;
   std::vector<long long> start, covoff;
@@ -1436,19 +1348,16 @@ static void lgo_plan(int64_t n, const int64_t* order, const int64_t* start, int6
   p.nslots = (int)p.pos0.size();
 }
 
-extern "C" int gh_chol_lgo(gh_chol* s, gh_kernel* k, const uint32_t* which, const double* r, const int64_t* order, const int64_t* start,
-                           int64_t ngroups, double* lpd_sum, double* resid, double* var, double* lpd, double* cov, double* grad,
-                           double* v, double* diagB) {
-  const bool have_args = k && r && order && start && lpd_sum && resid && var;
-  const char* bad = !have_args ? "bad argument to lgo" : (grad && !which) ? "lgo: gradient requested without a parameter mask" : nullptr;
-  if (!bad && s && s->computed) bad = lgo_check_groups(s->n, order, start, ngroups);
-  GH_CHECK(enter_computed(s, k, !bad, bad ? bad : ""));
+// what gh_chol_lgo reads back beside the outputs of cv_fetch()
+struct LgoOut { const long long* info = nullptr; const double* cov = nullptr; int64_t ncov = 0; };
+// leave-group-out up to the contraction.  The tables go up before anything else.
+static int lgo_enqueue(gh_chol* s, gh_kernel* k, const uint32_t* which, const double* r, const int64_t* order, const int64_t* start,
+                       int64_t ngroups, bool want_cov, bool grad_path, LgoOut& out) {
   const int64_t n = s->n, np = s->np, SS = (int64_t)GH_LGO_SLOT * GH_LGO_SLOT;
-  const bool grad_path = grad || v || diagB;
   hipStream_t st = s->st;
   LgoPlan plan;
   lgo_plan(n, order, start, ngroups, plan);
-  const int64_t ns = plan.nslots, ncov = cov ? plan.covoff[(size_t)ngroups] : 0;
+  const int64_t ns = plan.nslots, ncov = want_cov ? plan.covoff[(size_t)ngroups] : 0;
   int64_t rows_per = 0;
   const int64_t nx = grad_path ? 1 : gh_lgo_gram_chunks(n, plan.nslots, &rows_per);
   // the layout of s->lgo
@@ -1473,19 +1382,11 @@ extern "C" int gh_chol_lgo(gh_chol* s, gh_kernel* k, const uint32_t* which, cons
   double* Cs = base + o_cs;
   double* Ri = base + o_ri;
   double* X = base + o_x;
-  double* dcov = cov ? base + o_cov : nullptr;
+  double* dcov = want_cov ? base + o_cov : nullptr;
+  out.info = d_info; out.cov = dcov; out.ncov = ncov;
 
-  GH_CHECK(s->lv.ensure((size_t)LV_COUNT * np * sizeof(double)));
-  GH_CHECK(s->v0.ensure((size_t)std::max<int64_t>(np, GH_MAX_GRAD) * sizeof(double)));
-  GH_CHECK(s->v1.ensure((size_t)np * sizeof(double)));
+  GH_CHECK(cv_alpha(s, r));
   double* lv = s->lv.d();
-  GH_HIP(hipMemsetAsync(s->scal.d() + 3, 0, sizeof(double), st));
-  // alpha = K^-1 r
-  double* alpha = lv + LV_ALPHA * np;
-  GH_CHECK(load_vec(s, s->v0, r));
-  GH_CHECK(trsv_forward(s, s->v0.d(), s->v1.d(), true));
-  GH_CHECK(trsv_backward(s, s->v1.d(), alpha, true));
-  GH_CHECK(loo_note_fail(s));
   GH_CHECK(s->work.ensure((size_t)np * np * sizeof(double)));
   if (!grad_path) {
     GH_CHECK(linv_into(s, s->work.d()));
@@ -1497,37 +1398,32 @@ extern "C" int gh_chol_lgo(gh_chol* s, gh_kernel* k, const uint32_t* which, cons
     GH_HIP(hipMemsetAsync(s->v0.d(), 0, (size_t)np * sizeof(double), st));       // u by point, zero in the padding
   }
   GH_CHECK(gh_launch_potf2_batched(Cs, GH_LGO_SLOT, SS, Ri, SS, d_info, plan.nslots, st));
-  GH_CHECK(gh_launch_lgo_slots(Cs, Ri, t, alpha, lv + LV_RESID * np, lv + LV_VAR * np, grad_path ? s->v0.d() : nullptr, lv + LV_LPD * np,
-                               dcov, grad_path ? X : nullptr, st));
-  if (grad_path) {
-    // v = K^-1 u
-    GH_CHECK(trsv_forward(s, s->v0.d(), s->v1.d(), true));
-    GH_CHECK(trsv_backward(s, s->v1.d(), lv + LV_V * np, true));
-    GH_CHECK(loo_note_fail(s));
-    // X <- T = chol(W) (its inverse, into Ri, is not used); work2 <- S = K^-1[:, J] T; work <- M = S S^T (lower tiles)
-    GH_CHECK(gh_launch_potf2_batched(X, GH_LGO_SLOT, SS, Ri, SS, d_info, plan.nslots, st));
-    GH_CHECK(gh_launch_lgo_block_scale(s->work.d(), np, n, t, X, s->work2.d(), st));
-    GhGemm g = gemm_desc(s->work.d(), np, s->work2.d(), np, true, s->work2.d(), np, true, np, np, np, 1.0, 0.0);
-    g.lower = true;
-    GH_CHECK(gh_launch_gemm(g, st));
-    static const uint32_t none[GH_MAX_GRAD] = {0};
-    GH_CHECK(gh_launch_kgrad_reduce_loo(k, grad ? which : none, s->x.d(), n, alpha, s->work.d(), np, s->v0.d(), s->v1.d(), s->scratch, st));
-  }
-  GH_CHECK(launch_sum(lv + LV_LPD * np, (long)ngroups, s->scal.d() + 1, s->scal.d() + 72, st));
-  double host[4] = {0.0, 0.0, 0.0, 0.0};                // (log-det), sum of lpd, (failure word), the chains' time-out flag
+  GH_CHECK(gh_launch_lgo_slots(Cs, Ri, t, lv + LV_ALPHA * np, lv + LV_RESID * np, lv + LV_VAR * np, grad_path ? s->v0.d() : nullptr,
+                               lv + LV_LPD * np, dcov, grad_path ? X : nullptr, st));
+  if (!grad_path) return GH_OK;
+  GH_CHECK(cv_solve(s, LV_V));                                                                  // v = K^-1 u, u in v0
+  // X <- T = chol(W) (its inverse, into Ri, is not used); work2 <- S = K^-1[:, J] T
+  GH_CHECK(gh_launch_potf2_batched(X, GH_LGO_SLOT, SS, Ri, SS, d_info, plan.nslots, st));
+  GH_CHECK(gh_launch_lgo_block_scale(s->work.d(), np, n, t, X, s->work2.d(), st));
+  return cv_contract(s, k, which);
+}
+
+extern "C" int gh_chol_lgo(gh_chol* s, gh_kernel* k, const uint32_t* which, const double* r, const int64_t* order, const int64_t* start,
+                           int64_t ngroups, double* lpd_sum, double* resid, double* var, double* lpd, double* cov, double* grad,
+                           double* v, double* diagB) {
+  const bool have_args = k && r && order && start && lpd_sum && resid && var;
+  const char* bad = !have_args ? "bad argument to lgo" : (grad && !which) ? "lgo: gradient requested without a parameter mask" : nullptr;
+  if (!bad && s && s->computed) bad = lgo_check_groups(s->n, order, start, ngroups);
+  GH_CHECK(enter_computed(s, k, !bad, bad ? bad : ""));
+  LgoOut o;
+  GH_CHECK(lgo_enqueue(s, k, grad ? which : nullptr, r, order, start, ngroups, cov != nullptr, grad || v || diagB, o));
+  double host[4] = {0.0, 0.0, 0.0, 0.0}, sum = 0.0;
   long long slot_info = 0;
-  GH_CHECK(read_scalars(s, host, 4, st));
-  GH_HIP(hipMemcpyAsync(&slot_info, d_info, sizeof(long long), hipMemcpyDeviceToHost, st));
-  GH_CHECK(gh_from_device(resid, lv + LV_RESID * np, (size_t)n, st));
-  GH_CHECK(gh_from_device(var, lv + LV_VAR * np, (size_t)n, st));
-  if (lpd) GH_CHECK(gh_from_device(lpd, lv + LV_LPD * np, (size_t)ngroups, st));
-  if (cov) GH_CHECK(gh_from_device(cov, dcov, (size_t)ncov, st));
-  if (grad && k->size > 0) GH_CHECK(gh_from_device(grad, s->v0.d(), (size_t)k->size, st));
-  if (v) GH_CHECK(gh_from_device(v, lv + LV_V * np, (size_t)n, st));
-  if (diagB) GH_CHECK(gh_from_device(diagB, s->v1.d(), (size_t)n, st));
-  GH_HIP(hipStreamSynchronize(st));
-  GH_CHECK(gh_chain_timeout("lgo", host[3] != 0.0, false));
+  GH_CHECK(cv_fetch(s, k, ngroups, host, resid, var, lpd, grad, v, diagB));
+  GH_HIP(hipMemcpyAsync(&slot_info, o.info, sizeof(long long), hipMemcpyDeviceToHost, s->st));
+  if (cov) GH_CHECK(gh_from_device(cov, o.cov, (size_t)o.ncov, s->st));
+  GH_CHECK(cv_finish(s, "lgo", host, &sum));
   if (slot_info != 0) { gh_set_error("lgo: a group's block of K^-1 is not positive definite"); return GH_ERR_NOT_PD; }
-  *lpd_sum = host[1];
+  *lpd_sum = sum;
   return GH_OK;
 }

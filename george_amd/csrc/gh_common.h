@@ -177,8 +177,17 @@ int gh_launch_fisher_pairs(const double* const* a, const int* a_idx, int na, con
 // F (ptot x ptot, zeroed by the caller) <- the pair sums, mirrored
 int gh_launch_fisher_mirror(const double* pairsum, const GhFisherMap& m, double* F, hipStream_t st);
 
-// The pieces of gh_chol_lgo (gh_lgo.hip).  A slot is GH_LGO_SLOT consecutive entries of the tables: whole groups, in group-sorted
-// ("permuted") order, then padding.  All pointers are device memory.
+// The pieces of gh_chol_loo and gh_chol_lgo (gh_cv.hip).  All pointers are device memory; np is a multiple of 128.
+// c[i] = sum_k Linv[k][i]^2, the diagonal of K^-1 from L^-1 (lower, row-major): nchunks row chunks in part (nchunks * np doubles),
+// added in index order
+int gh_launch_loo_colsumsq(const double* Linv, int64_t np, int64_t nchunks, double* part, double* c, hipStream_t st);
+// resid, var, lpd, sw = sqrt(w) and u (a second copy of resid, or NULL) per point from alpha and c_i = c[i * cstride]; zeros in rows >= n
+int gh_launch_loo_point(const double* alpha, const double* c, int64_t cstride, int64_t n, int64_t np, double* resid, double* u,
+                        double* var, double* lpd, double* sw, hipStream_t st);
+// S (np x np, full) = W diag(sw) from the lower triangle of the symmetric W
+int gh_launch_loo_mirror_scale(const double* W, int64_t np, const double* sw, double* S, hipStream_t st);
+// Leave-group-out: a slot is GH_LGO_SLOT consecutive entries of the tables: whole groups, in group-sorted ("permuted") order, then
+// padding.
 #define GH_LGO_SLOT 128
 struct GhLgoSlots {
   const int* idx;            // (nslots * 128) the point at a slot position, -1: padding

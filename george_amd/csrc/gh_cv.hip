@@ -1,17 +1,134 @@
-// gh_lgo.hip -- the device pieces of gh_chol_lgo (gh_chol_solve.hip): leave-group-out cross-validation.  The groups are packed into
-// "slots" of at most 128 permuted positions (whole groups only); every slot is one identity-padded, block-diagonal 128 x 128 matrix
-// C_slot of K^-1 entries that the batched Cholesky of gh_potf2.hip factors and inverts.
+// gh_cv.hip -- the device pieces of cross-validation: gh_chol_loo, gh_chol_loo_objective and gh_chol_lgo (gh_chol_solve.hip).
+// Leave-one-out, from c_i = (K^-1)_ii:
+//   colsumsq_kernel         value path: c as the column sums of squares of L^-1, per row chunk
+//   colsumsq_final_kernel   ... the chunks added in index order
+//   loo_point_kernel        resid, var, lpd, sqrt(w) (and u) per point from alpha and c
+//   loo_mirror_scale_kernel gradient path: S = K^-1 diag(sqrt(w)), full, from the lower triangle of K^-1
+// Leave-group-out: every c_i becomes the diagonal block C_gg of a group.  The groups are packed into "slots" of at most 128 permuted
+// positions (whole groups only); every slot is one identity-padded, block-diagonal 128 x 128 matrix C_slot of K^-1 entries that the
+// batched Cholesky of gh_potf2.hip factors and inverts.
 //   lgo_gram_kernel         value path: per slot and row chunk, sum_k L^-1[k][J_a] L^-1[k][J_b] on the fp64 matrix pipe
 //   lgo_gram_final_kernel   ... the chunks added in index order, cross-group entries masked, identity padding
 //   lgo_gather_kernel       gradient path: C_slot read straight from the lower triangle of K^-1
 //   lgo_slot_kernel         one workgroup per slot: u, var, lpd (and cov, W = 1/2 (C^-1 + u u^T)) from R = chol(C_slot), R^-1
 //   lgo_block_scale_kernel  S[:, p] = sum_q K^-1[:, J_q] T[q][p]: loo_mirror_scale_kernel with a block-diagonal right factor
 // No atomics anywhere: two calls give the same bits.  Rows i >= n of the padded matrices are never added to anything.
-// DESIGN.md section 4, "Leave-group-out cross-validation".
+// DESIGN.md section 4, "Leave-one-out cross-validation" and "Leave-group-out cross-validation".
 #include <algorithm>
 #include "gh_common.h"
 #include "gh_device_util.h"
 
+// ================================================= leave-one-out
+#define LT 64                 // tile edge of the leave-one-out kernels
+// Column sums of squares of a LOWER-triangular row-major matrix (L^-1): part[s][c] = sum over the rows r >= c of the s-th row
+// chunk of V[r][c]^2.  A workgroup takes 64 columns of one chunk, a wavefront every fourth row: each load instruction reads
+// 512 contiguous bytes, four rows are in flight per trip.  Rows above the tile's first column hold zeros and are not read.
+// The four wavefronts' sums meet in LDS in a fixed order; colsumsq_final_kernel adds the chunks in index order: no atomics,
+// bitwise reproducible.
+__global__ __launch_bounds__(256) void colsumsq_kernel(const double* V, long ld, long np, long rows_per, double* part) {
+  __shared__ double sh[4][LT];
+  const int lc = threadIdx.x & 63, lr = threadIdx.x >> 6;
+  const long c0 = (long)blockIdx.x * LT, c = c0 + lc;
+  long r0 = (long)blockIdx.y * rows_per;
+  const long r1 = r0 + rows_per < np ? r0 + rows_per : np;
+  if (r0 < c0) r0 = c0;
+  double acc = 0.0;
+  long r = r0 + lr;
+  for (; r + 12 < r1; r += 16) {
+    double a[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) a[q] = V[(r + 4 * q) * ld + c];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc += (r + 4 * q >= c) ? a[q] * a[q] : 0.0;
+  }
+  for (; r < r1; r += 4) {
+    const double a = V[r * ld + c];
+    acc += (r >= c) ? a * a : 0.0;
+  }
+  sh[lr][lc] = acc;
+  __syncthreads();
+  if (lr == 0) part[(long)blockIdx.y * np + c] = (sh[0][lc] + sh[1][lc]) + (sh[2][lc] + sh[3][lc]);
+}
+__global__ void colsumsq_final_kernel(const double* part, long nchunks, long np, double* c) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= np) return;
+  double v = 0.0;
+  for (long s = 0; s < nchunks; ++s) v += part[s * np + i];
+  c[i] = v;
+}
+// The per-point quantities from alpha and c_i = (K^-1)_ii (c[i * cstride]: a vector, or the diagonal of a matrix):
+//   resid = u = alpha / c,  var = 1 / c,  lpd = 1/2 log c - 1/2 alpha^2 / c - 1/2 log 2 pi,  sw = sqrt(w),  w = 1/2 (1 + alpha^2 / c) / c.
+// Padded rows i >= n get zeros everywhere: nothing of them reaches the sum of lpd or S = K^-1 diag(sqrt(w)).
+// `u` is a second copy of resid that the solve for v = K^-1 u consumes.
+__global__ void loo_point_kernel(const double* alpha, const double* c, long cstride, long n, long np,
+                                 double* resid, double* u, double* var, double* lpd, double* sw) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= np) return;
+  double ui = 0.0, vi = 0.0, li = 0.0, si = 0.0;
+  if (i < n) {
+    const double ci = c[i * cstride], a = alpha[i];
+    ui = a / ci;
+    vi = 1.0 / ci;
+    const double q = a * ui;
+    li = 0.5 * log(ci) - 0.5 * q - 0.91893853320467274178;
+    si = sqrt(0.5 * (1.0 + q) / ci);
+  }
+  resid[i] = ui;
+  if (u) u[i] = ui;
+  var[i] = vi;
+  lpd[i] = li;
+  sw[i] = si;
+}
+// S = Kinv diag(sw) as a FULL matrix from the lower triangle of Kinv, one pass: a workgroup reads the 64 x 64 tile (ti, tj),
+// tj <= ti, into LDS and writes tile (ti, tj) of S as it lies and tile (tj, ti) transposed, column k scaled by sw[k].  Reads and
+// both writes are coalesced (a row of 64 doubles per wavefront); the transposed LDS reads walk a pitch of 65: no bank conflicts.
+__global__ __launch_bounds__(256) void loo_mirror_scale_kernel(const double* W, long ld, const double* sw, double* S) {
+  __shared__ double t[LT][LT + 1];
+  int ti, tj;
+  tri_index(blockIdx.x, ti, tj);
+  const long r0 = (long)ti * LT, c0 = (long)tj * LT;
+  const int lc = threadIdx.x & 63, lr = threadIdx.x >> 6;
+#pragma unroll 4
+  for (int rr = lr; rr < LT; rr += 4) t[rr][lc] = W[(r0 + rr) * ld + c0 + lc];
+  __syncthreads();
+  const double sc = sw[c0 + lc];
+  if (ti != tj) {
+    const double sr = sw[r0 + lc];
+#pragma unroll 4
+    for (int rr = lr; rr < LT; rr += 4) {
+      S[(r0 + rr) * ld + c0 + lc] = t[rr][lc] * sc;
+      S[(c0 + rr) * ld + r0 + lc] = t[lc][rr] * sr;
+    }
+  } else {
+#pragma unroll 4
+    for (int rr = lr; rr < LT; rr += 4) S[(r0 + rr) * ld + c0 + lc] = (lc <= rr ? t[rr][lc] : t[lc][rr]) * sc;
+  }
+}
+
+int gh_launch_loo_colsumsq(const double* Linv, int64_t np, int64_t nchunks, double* part, double* c, hipStream_t st) {
+  const int64_t rows_per = (np + nchunks - 1) / nchunks;
+  hipLaunchKernelGGL(colsumsq_kernel, dim3((unsigned)(np / LT), (unsigned)nchunks), dim3(256), 0, st,
+                     Linv, (long)np, (long)np, (long)rows_per, part);
+  hipLaunchKernelGGL(colsumsq_final_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, (const double*)part, (long)nchunks,
+                     (long)np, c);
+  GH_HIP(hipGetLastError());
+  return GH_OK;
+}
+int gh_launch_loo_point(const double* alpha, const double* c, int64_t cstride, int64_t n, int64_t np, double* resid, double* u,
+                        double* var, double* lpd, double* sw, hipStream_t st) {
+  hipLaunchKernelGGL(loo_point_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, alpha, c, (long)cstride, (long)n, (long)np,
+                     resid, u, var, lpd, sw);
+  GH_HIP(hipGetLastError());
+  return GH_OK;
+}
+int gh_launch_loo_mirror_scale(const double* W, int64_t np, const double* sw, double* S, hipStream_t st) {
+  const long tm = (long)(np / LT);
+  hipLaunchKernelGGL(loo_mirror_scale_kernel, dim3((unsigned)(tm * (tm + 1) / 2)), dim3(256), 0, st, W, (long)np, sw, S);
+  GH_HIP(hipGetLastError());
+  return GH_OK;
+}
+
+// ================================================= leave-group-out
 namespace {
 constexpr int LG = GH_LGO_SLOT;                   // slot edge = the tile of the batched Cholesky
 constexpr int GK = 16;                            // rows of L^-1 per step of the Gram kernel

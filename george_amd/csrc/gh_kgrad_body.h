@@ -8,7 +8,7 @@
 // likelihood instances came out with another register allocation and schedule (existing GPU tests pin their results, and the
 // benchmark their time); a `bool LOO` template parameter kept the instructions but changed the mangled name that
 // tests/test_hodlr_predict_grad_host.py looks the kernel's scratch size up by.
-// The caller of the leave-one-out form (gh_chol_solve.hip, loo_enqueue) asserts that its two vectors are adjacent, ld = Np apart.
+// The caller of the leave-one-out form (gh_chol_solve.hip, cv_contract) asserts that its two vectors are adjacent, ld = Np apart.
   __shared__ double xr[KT * GH_MAX_NDIM];
   __shared__ double xc[KT * GH_MAX_NDIM];
   __shared__ double red[4][PMAX];

@@ -152,6 +152,13 @@ class GP(ModelSet):
             raise
         return np.ascontiguousarray(yv - mu, dtype=np.float64)
 
+    def _recomputed_residual(self, y, quiet):
+        """:meth:`recompute`, then :meth:`_residual_quiet`: the residual on a computed model, or None where ``quiet`` silenced
+        a matrix that does not factor or a failing mean function."""
+        if not self.recompute(quiet=quiet):
+            return None
+        return self._residual_quiet(y, quiet)
+
     def _compute_alpha(self, y, cache):
         if not cache:
             return self.solver.apply_inverse(self._residual(y), in_place=True).flatten()
@@ -311,9 +318,7 @@ class GP(ModelSet):
 
     def log_likelihood(self, y, quiet=False):
         """-1/2 r^T K^-1 r - 1/2 log|K| - N/2 log 2 pi   (gp.py:369-397)."""
-        if not self.recompute(quiet=quiet):
-            return -np.inf
-        r = self._residual_quiet(y, quiet)
+        r = self._recomputed_residual(y, quiet)
         if r is None:
             return -np.inf
         ll = self._const - 0.5 * self.solver.dot_solve(r)
@@ -321,9 +326,7 @@ class GP(ModelSet):
 
     def grad_log_likelihood(self, y, quiet=False):
         """Gradient wrt the unfrozen parameters, ordered mean | white_noise | kernel (gp.py:406-468)."""
-        if not self.recompute(quiet=quiet):
-            return np.zeros(len(self), dtype=np.float64)
-        r = self._residual_quiet(y, quiet)
+        r = self._recomputed_residual(y, quiet)
         if r is None:
             return np.zeros(len(self), dtype=np.float64)
 
@@ -344,9 +347,10 @@ class GP(ModelSet):
                     kgrad = 0.5 * np.einsum("ijk,ij", self.kernel.get_gradient(self._x), A)
         return self._assemble_grad(alpha, diagA, kgrad, quiet)
 
-    def _assemble_grad(self, alpha, diagA, kgrad, quiet):
+    def _assemble_grad(self, alpha, diagA, kgrad, quiet, diag_weight=0.5):
         """mean | white_noise | kernel blocks of the gradient from alpha, diag(alpha alpha^T - K^-1) and
-        the kernel block (gp.py:443-466)."""
+        the kernel block (gp.py:443-466).  The cross-validation gradients have the same layout from ``v`` and ``diag(B)``
+        (:meth:`_loo_parts`) with ``diag_weight=1.0``."""
         n_wn, n_k = len(self.white_noise), len(self.kernel)
         grad = np.empty(len(self))
         at = 0
@@ -363,7 +367,7 @@ class GP(ModelSet):
         if n_wn:
             wn = self._call_white_noise(self._x)
             wng = self._call_white_noise_gradient(self._x)
-            grad[at:at + n_wn] = 0.5 * np.sum((np.exp(wn) * diagA)[None, :] * wng, axis=1)
+            grad[at:at + n_wn] = diag_weight * np.sum((np.exp(wn) * diagA)[None, :] * wng, axis=1)
             at += n_wn
         if n_k:
             grad[at:at + n_k] = kgrad
@@ -490,6 +494,7 @@ class GP(ModelSet):
             L, resid, var, lpd, kg_full, v, diagB = self.solver.loo(r, which)
             kgrad = kg_full[self.kernel.unfrozen_mask] if (want_grad and n_k) else None
             return L, resid, var, lpd, kgrad, v, diagB
+        # (vectorised, not _lgo_parts' loop over N one-point groups: that costs N Python iterations and other low bits)
         alpha = np.asarray(self.solver.apply_inverse(np.array(r, dtype=np.float64))).flatten()
         Kinv = np.asarray(self.solver.get_inverse())
         c = np.array(np.diag(Kinv), dtype=np.float64)
@@ -506,29 +511,11 @@ class GP(ModelSet):
         kgrad = np.einsum("ijk,ij", self.kernel.get_gradient(self._x), B) if n_k else None
         return L, resid, var, lpd, kgrad, v, np.array(np.diag(B))
 
-    def _assemble_loo_grad(self, v, diagB, kgrad, quiet):
-        """mean | white_noise | kernel blocks of the leave-one-out gradient (the layout of :meth:`_assemble_grad`)."""
-        n_wn, n_k = len(self.white_noise), len(self.kernel)
-        grad = np.empty(len(self))
-        at = 0
-        n_m = len(self.mean)
-        if n_m:
-            try:
-                mg = self._call_mean_gradient(self._x)
-            except ValueError:
-                if quiet:
-                    return np.zeros(len(self), dtype=np.float64)
-                raise
-            grad[at:at + n_m] = np.dot(mg, v)
-            at += n_m
-        if n_wn:
-            wn = self._call_white_noise(self._x)
-            wng = self._call_white_noise_gradient(self._x)
-            grad[at:at + n_wn] = np.sum((np.exp(wn) * diagB)[None, :] * wng, axis=1)
-            at += n_wn
-        if n_k:
-            grad[at:at + n_k] = kgrad
-        return grad
+    def _neg_cv(self, L, kgrad, v, diagB, quiet):
+        """What ``loo_nll_and_grad`` and ``lgo_nll_and_grad`` return for the value ``L`` and the parts of its gradient."""
+        if not np.isfinite(L):
+            return np.inf, np.zeros(len(self))
+        return -L, -self._assemble_grad(v, diagB, kgrad, quiet, diag_weight=1.0)
 
     def loo_predict(self, y, return_var=True):
         """Leave-one-out predictions: ``mu[i]`` (and ``var[i]``) of ``y[i]`` from all other points, mean model included, without
@@ -542,9 +529,7 @@ class GP(ModelSet):
     def loo_log_likelihood(self, y, quiet=False, pointwise=False):
         """The log pseudo-likelihood ``sum_i log p(y_i | y_-i)`` (GPML eq. 5.11), or its N terms with ``pointwise=True``."""
         bad = np.full(len(np.atleast_1d(y)), -np.inf) if pointwise else -np.inf
-        if not self.recompute(quiet=quiet):
-            return bad
-        r = self._residual_quiet(y, quiet)
+        r = self._recomputed_residual(y, quiet)
         if r is None:
             return bad
         L, _, _, lpd, _, _, _ = self._loo_parts(r, False)
@@ -554,13 +539,11 @@ class GP(ModelSet):
 
     def grad_loo_log_likelihood(self, y, quiet=False):
         """Gradient of :meth:`loo_log_likelihood` wrt the unfrozen parameters, ordered mean | white_noise | kernel."""
-        if not self.recompute(quiet=quiet):
-            return np.zeros(len(self), dtype=np.float64)
-        r = self._residual_quiet(y, quiet)
+        r = self._recomputed_residual(y, quiet)
         if r is None:
             return np.zeros(len(self), dtype=np.float64)
         _, _, _, _, kgrad, v, diagB = self._loo_parts(r, True)
-        return self._assemble_loo_grad(v, diagB, kgrad, quiet)
+        return self._assemble_grad(v, diagB, kgrad, quiet, diag_weight=1.0)
 
     def loo_nll_and_grad(self, vector, y, quiet=True):
         """``(-loo_log_likelihood, -grad_loo_log_likelihood)`` at ``vector`` for ``scipy.optimize.minimize(..., jac=True)``:
@@ -573,9 +556,7 @@ class GP(ModelSet):
         fused = (callable(getattr(self.solver_type, "loo_objective", None))
                  and hasattr(self, "_x") and hasattr(self, "_yerr2"))
         if self.computed or not fused:
-            if not self.recompute(quiet=quiet):
-                return bad
-            r = self._residual_quiet(y, quiet)
+            r = self._recomputed_residual(y, quiet)
             if r is None:
                 return bad
             L, _, _, _, kgrad, v, diagB = self._loo_parts(r, True)
@@ -597,9 +578,7 @@ class GP(ModelSet):
             self.computed = True
             self._alpha = None
             kgrad = kg_full[self.kernel.unfrozen_mask] if len(self.kernel) else None
-        if not np.isfinite(L):
-            return bad
-        return -L, -self._assemble_loo_grad(v, diagB, kgrad, quiet)
+        return self._neg_cv(L, kgrad, v, diagB, quiet)
 
     # -- leave-group-out cross-validation (no reference counterpart) -------------------------------
     # The groups I_1 .. I_G partition the points; with C = K^-1, alpha = C r and C_gg the block of C on group g the joint
@@ -694,9 +673,7 @@ class GP(ModelSet):
         """The leave-group-out log pseudo-likelihood ``sum_g log p(y_g | y_-g)``, or its G terms with ``pointwise=True``."""
         order, start = self._lgo_groups(groups)
         bad = np.full(len(start) - 1, -np.inf) if pointwise else -np.inf
-        if not self.recompute(quiet=quiet):
-            return bad
-        r = self._residual_quiet(y, quiet)
+        r = self._recomputed_residual(y, quiet)
         if r is None:
             return bad
         L, _, _, lpd, _, _, _, _ = self._lgo_parts(r, order, start, False)
@@ -707,13 +684,11 @@ class GP(ModelSet):
     def grad_lgo_log_likelihood(self, y, groups, quiet=False):
         """Gradient of :meth:`lgo_log_likelihood` wrt the unfrozen parameters, ordered mean | white_noise | kernel."""
         order, start = self._lgo_groups(groups)
-        if not self.recompute(quiet=quiet):
-            return np.zeros(len(self), dtype=np.float64)
-        r = self._residual_quiet(y, quiet)
+        r = self._recomputed_residual(y, quiet)
         if r is None:
             return np.zeros(len(self), dtype=np.float64)
         _, _, _, _, _, kgrad, v, diagB = self._lgo_parts(r, order, start, True)
-        return self._assemble_loo_grad(v, diagB, kgrad, quiet)
+        return self._assemble_grad(v, diagB, kgrad, quiet, diag_weight=1.0)
 
     def lgo_nll_and_grad(self, vector, y, groups, quiet=True):
         """``(-lgo_log_likelihood, -grad_lgo_log_likelihood)`` at ``vector`` for ``scipy.optimize.minimize(..., jac=True)``:
@@ -724,9 +699,7 @@ class GP(ModelSet):
         if not np.isfinite(self.log_prior()):
             return np.inf, np.zeros(len(vector))
         bad = (np.inf, np.zeros(len(self)))
-        if not self.recompute(quiet=quiet):
-            return bad
-        r = self._residual_quiet(y, quiet)
+        r = self._recomputed_residual(y, quiet)
         if r is None:
             return bad
         try:
@@ -735,9 +708,7 @@ class GP(ModelSet):
             if quiet:
                 return bad
             raise
-        if not np.isfinite(L):
-            return bad
-        return -L, -self._assemble_loo_grad(v, diagB, kgrad, quiet)
+        return self._neg_cv(L, kgrad, v, diagB, quiet)
 
     # -- expected information of the hyper-parameters ---------------------------------------------
     # (no reference counterpart.)  For the Gaussian likelihood the expected (Fisher) information is

@@ -198,46 +198,50 @@ class BasicSolver(object):
         self._factor_state = None
 
     # -- the solver protocol
-    def compute(self, x, yerr):
-        """basic.py:51-70.  ``yerr`` already contains the white noise (gp.py:330)."""
+    def _begin_compute(self, x, yerr, r=None):
+        """The start of a call that factors: the inputs coerced and checked, the old factor forgotten, a new device kernel.
+        Returns ``(x, yerr, r)``."""
         x = N.as_f64(x)
         if x.ndim != 2:
             raise ValueError("x must be (nsamples, ndim)")
         yerr = N.as_f64(np.zeros(len(x)) + yerr)
+        if r is not None:
+            r = N.as_f64(r).reshape(-1)
+            if len(r) != len(x):
+                raise ValueError("dimension mismatch")
         self._computed = False
+        self._factor_state = None
         self._dk = DeviceKernel(self.kernel)
         if x.shape[1] != self._dk.ndim:
             raise RuntimeError("dimension mismatch")
-        h = self._ensure_handle()
-        logdet = C.c_double(0.0)
-        self._factor_state = None
-        self._retry_without_parked_memory(lambda hh: N.check(N.lib.gh_chol_compute(
-            hh, self._dk.handle, N.ptr(x), len(x), x.shape[1], N.ptr(yerr), C.byref(logdet))))
+        return x, yerr, r
+
+    def _end_compute(self, x, yerr, logdet):
         self._n = len(x)
         self._x_host = x                     # (the inputs travel with a pickled factor: predict / grad need them)
         self._yerr_host = yerr               # (... and append)
-        self.log_determinant = logdet.value
+        self.log_determinant = logdet
         self.computed = True
+
+    def _trim_grad(self, g):
+        """the gradient buffer (at least one entry long) cut to the kernel's parameters"""
+        return None if g is None else g[:self._dk.size]
+
+    def compute(self, x, yerr):
+        """basic.py:51-70.  ``yerr`` already contains the white noise (gp.py:330)."""
+        x, yerr, _ = self._begin_compute(x, yerr)
+        logdet = C.c_double(0.0)
+        self._retry_without_parked_memory(lambda hh: N.check(N.lib.gh_chol_compute(
+            hh, self._dk.handle, N.ptr(x), len(x), x.shape[1], N.ptr(yerr), C.byref(logdet))))
+        self._end_compute(x, yerr, logdet.value)
 
     def objective(self, x, yerr, r, which=None, want_grad=True):
         """``compute(x, yerr)`` + ``r^T K^-1 r`` + (optionally) the kernel part of the gradient of the
         log-likelihood in ONE device call (gh_chol_objective; gp.py:470-480 with :303-337, :369-397,
         :429-466).  Returns ``(log_det, quad, grad_all | None, alpha | None, diagA | None)`` and leaves
         the solver computed."""
-        x = N.as_f64(x)
-        if x.ndim != 2:
-            raise ValueError("x must be (nsamples, ndim)")
+        x, yerr, r = self._begin_compute(x, yerr, r)
         n = len(x)
-        yerr = N.as_f64(np.zeros(n) + yerr)
-        r = N.as_f64(r).reshape(-1)
-        if len(r) != n:
-            raise ValueError("dimension mismatch")
-        self._computed = False
-        self._factor_state = None
-        self._dk = DeviceKernel(self.kernel)
-        if x.shape[1] != self._dk.ndim:
-            raise RuntimeError("dimension mismatch")
-        h = self._ensure_handle()
         logdet, quad = C.c_double(0.0), C.c_double(0.0)
         g = alpha = diagA = wh = None
         if want_grad:
@@ -247,12 +251,8 @@ class BasicSolver(object):
         self._retry_without_parked_memory(lambda hh: N.check(N.lib.gh_chol_objective(
             hh, self._dk.handle, N.ptr(x), n, x.shape[1], N.ptr(yerr), N.ptr(r), N.ptr(wh),
             C.byref(logdet), C.byref(quad), N.ptr(g), N.ptr(alpha), N.ptr(diagA))))
-        self._n = n
-        self._x_host = x
-        self._yerr_host = yerr
-        self.log_determinant = logdet.value
-        self.computed = True
-        return logdet.value, quad.value, (g[:self._dk.size] if g is not None else None), alpha, diagA
+        self._end_compute(x, yerr, logdet.value)
+        return logdet.value, quad.value, self._trim_grad(g), alpha, diagA
 
     # -- many parameter vectors at once (GP.log_likelihood_batch: emcee's ``vectorize=True``)
     # One chunk's bordered blocks, (Np + 128)^2 doubles per member, stay under this many bytes of device memory.
@@ -642,6 +642,19 @@ class BasicSolver(object):
         return g[:self._dk.size], alpha, diagA
 
     # -- leave-one-out cross-validation (no reference counterpart; GPML 5.4.2)
+    def _cv_grad_outputs(self, which):
+        """``(wh, g, v, diagB)`` of :meth:`loo` and :meth:`lgo`: the parameter mask as the device reads it and the buffers of
+        the gradient outputs (:meth:`_trim_grad` cuts ``g``); all ``None`` without a mask."""
+        if which is None:
+            return None, None, None, None
+        size, n = self._dk.size, self._n
+        which = np.asarray(which)
+        if which.shape != (size,):
+            raise ValueError("which must have shape ({0},)".format(size))
+        wh = np.zeros(max(size, 1), dtype=np.uint32)
+        wh[:size] = which != 0
+        return wh, np.zeros(max(size, 1)), np.empty(n), np.empty(n)
+
     def loo(self, r, which=None):
         """Leave-one-out quantities of the computed factor for residual ``r = y - mean`` (gh_chol_loo).  Returns
         ``(lpd_sum, resid, var, lpd, grad_full | None, v | None, diagB | None)``: ``resid = y - mu_loo``, ``var`` the
@@ -655,37 +668,18 @@ class BasicSolver(object):
         n = self._n
         total = C.c_double(0.0)
         resid, var, lpd = np.empty(n), np.empty(n), np.empty(n)
-        g = v = diagB = wh = None
-        if which is not None:
-            wh = np.zeros(max(self._dk.size, 1), dtype=np.uint32)
-            which = np.asarray(which)
-            if which.shape != (self._dk.size,):
-                raise ValueError("which must have shape ({0},)".format(self._dk.size))
-            wh[:self._dk.size] = which != 0
-            g = np.zeros(max(self._dk.size, 1))
-            v, diagB = np.empty(n), np.empty(n)
+        wh, g, v, diagB = self._cv_grad_outputs(which)
         self._retry_without_parked_memory(lambda hh: N.check(N.lib.gh_chol_loo(
             hh, self._dk.handle, N.ptr(wh), N.ptr(r), C.byref(total), N.ptr(resid), N.ptr(var), N.ptr(lpd),
             N.ptr(g), N.ptr(v), N.ptr(diagB))))
-        return total.value, resid, var, lpd, (g[:self._dk.size] if g is not None else None), v, diagB
+        return total.value, resid, var, lpd, self._trim_grad(g), v, diagB
 
     def loo_objective(self, x, yerr, r, which=None, want_grad=True):
         """``compute(x, yerr)`` + :meth:`loo` in ONE device call (gh_chol_loo_objective), the leave-one-out analogue of
         :meth:`objective`.  Returns ``(log_det, lpd_sum, resid, var, grad_full | None, v | None, diagB | None)`` and leaves
         the solver computed."""
-        x = N.as_f64(x)
-        if x.ndim != 2:
-            raise ValueError("x must be (nsamples, ndim)")
+        x, yerr, r = self._begin_compute(x, yerr, r)
         n = len(x)
-        yerr = N.as_f64(np.zeros(n) + yerr)
-        r = N.as_f64(r).reshape(-1)
-        if len(r) != n:
-            raise ValueError("dimension mismatch")
-        self._computed = False
-        self._factor_state = None
-        self._dk = DeviceKernel(self.kernel)
-        if x.shape[1] != self._dk.ndim:
-            raise RuntimeError("dimension mismatch")
         logdet, total = C.c_double(0.0), C.c_double(0.0)
         resid, var = np.empty(n), np.empty(n)
         g = v = diagB = wh = None
@@ -696,12 +690,8 @@ class BasicSolver(object):
         self._retry_without_parked_memory(lambda hh: N.check(N.lib.gh_chol_loo_objective(
             hh, self._dk.handle, N.ptr(x), n, x.shape[1], N.ptr(yerr), N.ptr(r), N.ptr(wh),
             C.byref(logdet), C.byref(total), N.ptr(resid), N.ptr(var), N.ptr(g), N.ptr(v), N.ptr(diagB))))
-        self._n = n
-        self._x_host = x
-        self._yerr_host = yerr
-        self.log_determinant = logdet.value
-        self.computed = True
-        return logdet.value, total.value, resid, var, (g[:self._dk.size] if g is not None else None), v, diagB
+        self._end_compute(x, yerr, logdet.value)
+        return logdet.value, total.value, resid, var, self._trim_grad(g), v, diagB
 
     # -- leave-group-out cross-validation (no reference counterpart)
     LGO_MAX_GROUP = 128      # points of one group in the device form: one tile of the batched Cholesky
@@ -733,15 +723,7 @@ class BasicSolver(object):
             if G > n or np.any(sizes < 0) or np.any(sizes > self.LGO_MAX_GROUP):
                 raise ValueError("a group is empty or has more than {0} points".format(self.LGO_MAX_GROUP))
             cov = np.empty(int(np.sum(sizes ** 2)))
-        g = v = diagB = wh = None
-        if which is not None:
-            wh = np.zeros(max(self._dk.size, 1), dtype=np.uint32)
-            which = np.asarray(which)
-            if which.shape != (self._dk.size,):
-                raise ValueError("which must have shape ({0},)".format(self._dk.size))
-            wh[:self._dk.size] = which != 0
-            g = np.zeros(max(self._dk.size, 1))
-            v, diagB = np.empty(n), np.empty(n)
+        wh, g, v, diagB = self._cv_grad_outputs(which)
         self._retry_without_parked_memory(lambda hh: N.check(N.lib.gh_chol_lgo(
             hh, self._dk.handle, N.ptr(wh), N.ptr(r), N.ptr(order), N.ptr(start), G, C.byref(total), N.ptr(resid), N.ptr(var),
             N.ptr(lpd), N.ptr(cov), N.ptr(g), N.ptr(v), N.ptr(diagB))))
@@ -749,7 +731,7 @@ class BasicSolver(object):
         if want_cov:
             at = np.concatenate([[0], np.cumsum(sizes ** 2)])
             blocks = [cov[at[i]:at[i + 1]].reshape(sizes[i], sizes[i]) for i in range(G)]
-        return total.value, resid, var, lpd, blocks, (g[:self._dk.size] if g is not None else None), v, diagB
+        return total.value, resid, var, lpd, blocks, self._trim_grad(g), v, diagB
 
     # -- expected information of the hyper-parameters (no reference counterpart)
     # The default budget of fisher().  Nobody has measured a good value: it stands on what _POOL_MAX_BYTES already assumes
