@@ -43,6 +43,8 @@ import os
 
 import numpy as np
 
+from .solvers.protocol import rhs_matrix, rhs_rows, rhs_vector
+
 __all__ = ["grid_shape", "nccl_options", "HipTileOps", "BlockCyclicCholesky", "DistributedBasicSolver", "DistributedDenseJob"]
 
 
@@ -900,7 +902,7 @@ class DistributedBasicSolver(object):
     def dot_solve(self, y):
         chol = self._need()
         ypad = np.zeros(chol.nt * chol.nb)
-        ypad[:self._n] = np.asarray(y, dtype=np.float64).reshape(-1)
+        ypad[:self._n] = rhs_vector(y, self._n)
         return chol.dot_solve(chol.ops.to_device(ypad))
 
     def _padded(self, y2):
@@ -914,11 +916,9 @@ class DistributedBasicSolver(object):
     def apply_inverse(self, y, in_place=False):
         """basic.py:72-87: ``y`` is (n,) or (n, nrhs)."""
         chol = self._need()
-        ya = np.asarray(y, dtype=np.float64)
-        if ya.ndim < 1 or ya.ndim > 2 or ya.shape[0] != self._n:
-            raise ValueError("dimension mismatch")
+        ya, nrhs = rhs_matrix(y, self._n)
         y2 = ya.reshape(self._n, -1)
-        if y2.shape[1] == 0:
+        if nrhs == 0:
             return ya.copy()
         X = chol.solve(self._padded(y2))
         out = X[:self._n, :y2.shape[1]].cpu().numpy().reshape(ya.shape)
@@ -929,16 +929,13 @@ class DistributedBasicSolver(object):
 
     def get_inverse(self):
         """basic.py:116-121."""
+        self._need()
         return self.apply_inverse(np.eye(self._n), in_place=True)
 
     def apply_sqrt(self, r):
         """basic.py:104-114: ``r @ U`` with ``U^T U = K`` (U = L^T)."""
         chol = self._need()
-        r = np.asarray(r, dtype=np.float64)
-        one_d = r.ndim == 1
-        r2 = r.reshape(1, -1) if one_d else r
-        if r2.shape[1] != self._n:
-            raise ValueError("dimension mismatch")
+        r2, one_d = rhs_rows(r, self._n)
         out = chol.apply_sqrt_t(self._padded(np.ascontiguousarray(r2.T)))
         res = np.ascontiguousarray(out[:self._n, :r2.shape[0]].cpu().numpy().T)
         return res[0] if one_d else res

@@ -121,6 +121,11 @@ class GP(ModelSet):
         if v and self.kernel is not None:
             self.kernel.dirty = False
 
+    def _offers(self, name, on_type=False):
+        """Does the solver (``on_type``: the solver class, before an instance is made) define the optional call ``name``?
+        An optional capability is a callable attribute; a class that does not define it takes the generic branch."""
+        return callable(getattr(self.solver_type if on_type else self.solver, name, None))
+
     def parse_samples(self, t):
         t = np.atleast_1d(t)
         if t.ndim == 1:
@@ -226,7 +231,7 @@ class GP(ModelSet):
             return
         x_all = np.ascontiguousarray(np.concatenate([self._x, xn]))
         yerr2_all = np.ascontiguousarray(np.concatenate([self._yerr2, sig ** 2]))
-        if not (self.computed and callable(getattr(self.solver, "append", None)) and getattr(self.solver, "appendable", True)):
+        if not (self.computed and self._offers("append") and getattr(self.solver, "appendable", True)):
             return self._refactorize_or_restore(x_all, yerr2_all, **kwargs)
         sigma_new = np.sqrt(sig ** 2 + np.exp(self._call_white_noise(xn)))
         self.solver.append(xn, sigma_new)                # (raises with the solver as it was)
@@ -246,7 +251,7 @@ class GP(ModelSet):
         if n == len(self._x):
             return
         x_cut, yerr2_cut = np.ascontiguousarray(self._x[:n]), np.ascontiguousarray(self._yerr2[:n])
-        if not (self.computed and callable(getattr(self.solver, "truncate", None))):
+        if not (self.computed and self._offers("truncate")):
             return self._refactorize_or_restore(x_cut, yerr2_cut, **kwargs)
         self.solver.truncate(n)
         self._obj_cache = None
@@ -292,7 +297,7 @@ class GP(ModelSet):
         keep = np.ones(n, dtype=bool)
         keep[rem] = False
         x_keep, yerr2_keep = np.ascontiguousarray(self._x[keep]), np.ascontiguousarray(self._yerr2[keep])
-        if self.computed and callable(getattr(self.solver, "remove", None)):
+        if self.computed and self._offers("remove"):
             try:
                 self.solver.remove(rem)                   # (raises with the solver as it was)
             except RuntimeError:
@@ -331,7 +336,7 @@ class GP(ModelSet):
             return np.zeros(len(self), dtype=np.float64)
 
         n_wn, n_k = len(self.white_noise), len(self.kernel)
-        fused = callable(getattr(self.solver, "grad", None))
+        fused = self._offers("grad")
         kgrad = diagA = None
         if fused and (n_wn or n_k):
             # alpha, diag(A) and 1/2 sum A_ij dK_ij/dtheta in one device-resident call
@@ -390,7 +395,7 @@ class GP(ModelSet):
         super(GP, self).set_parameter_vector(vector, include_frozen=include_frozen)
 
     def _fused_capable(self):
-        return (callable(getattr(self.solver_type, "objective", None))
+        return (self._offers("objective", on_type=True)
                 and hasattr(self, "_x") and hasattr(self, "_yerr2"))
 
     def _objective(self, y, want_grad, quiet):
@@ -489,7 +494,7 @@ class GP(ModelSet):
         """``(L, resid, var, lpd, kgrad | None, v | None, diagB | None)`` for the residual ``r`` on the computed solver;
         ``kgrad`` over the unfrozen kernel parameters."""
         n_k = len(self.kernel)
-        if callable(getattr(self.solver, "loo", None)):
+        if self._offers("loo"):
             which = self.kernel.unfrozen_mask.astype(np.uint32) if want_grad else None
             L, resid, var, lpd, kg_full, v, diagB = self.solver.loo(r, which)
             kgrad = kg_full[self.kernel.unfrozen_mask] if (want_grad and n_k) else None
@@ -553,7 +558,7 @@ class GP(ModelSet):
         if not np.isfinite(self.log_prior()):
             return np.inf, np.zeros(len(vector))
         bad = (np.inf, np.zeros(len(self)))
-        fused = (callable(getattr(self.solver_type, "loo_objective", None))
+        fused = (self._offers("loo_objective", on_type=True)
                  and hasattr(self, "_x") and hasattr(self, "_yerr2"))
         if self.computed or not fused:
             r = self._recomputed_residual(y, quiet)
@@ -615,7 +620,7 @@ class GP(ModelSet):
         computed solver; ``kgrad`` over the unfrozen kernel parameters."""
         n_k = len(self.kernel)
         G = len(start) - 1
-        device = callable(getattr(self.solver, "lgo", None))
+        device = self._offers("lgo")
         if device and np.max(np.diff(start)) <= getattr(self.solver, "LGO_MAX_GROUP", 0):
             which = self.kernel.unfrozen_mask.astype(np.uint32) if want_grad else None
             L, resid, var, lpd, cov, kg_full, v, diagB = self.solver.lgo(r, order, start, which, want_cov)
@@ -737,7 +742,7 @@ class GP(ModelSet):
             wn = self._call_white_noise(self._x)
             wng = np.atleast_2d(self._call_white_noise_gradient(self._x))
             rows = np.ascontiguousarray(np.exp(wn)[None, :] * wng, dtype=np.float64)
-        if callable(getattr(self.solver, "fisher", None)):
+        if self._offers("fisher"):
             mask = self.kernel.unfrozen_mask
             full = self.solver.fisher(mask.astype(np.uint32), rows)
             keep = np.concatenate([np.arange(n_wn), n_wn + np.flatnonzero(mask)]).astype(int)
@@ -1067,7 +1072,7 @@ class GP(ModelSet):
     def _sample_conditional_cholesky(self, y, xs, z):
         """(size, M) draws of ``sample_conditional(factor="cholesky")`` for the normals ``z``, mean model included."""
         self.recompute()
-        if callable(getattr(self.solver, "sample_conditional", None)):
+        if self._offers("sample_conditional"):
             out, _, _ = self.solver.sample_conditional(self.kernel, self._residual(y), xs, z)
             return out + self._call_mean(xs)
         mu, cov = self.predict(y, xs, return_cov=True)
@@ -1193,7 +1198,7 @@ class GP(ModelSet):
         if kernel is None:
             kernel = self.kernel
 
-        if callable(getattr(self.solver, "predict", None)):
+        if self._offers("predict"):
             if cache:
                 self._compute_alpha(y, True)       # keep the reference's alpha-cache semantics (gp.py:260-275)
             want_var = bool(return_var)
@@ -1286,7 +1291,7 @@ class GP(ModelSet):
         want_var, want_value = bool(return_var), bool(return_value)
         mg = self._mean_gradient_at(xs, mean_gradient)
 
-        if callable(getattr(self.solver, "predict_gradient", None)):
+        if self._offers("predict_gradient"):
             if cache:
                 self._compute_alpha(y, True)       # the alpha-cache semantics of predict
             mu, var, dmu, dvar = self.solver.predict_gradient(kernel, self._residual(y), xs, return_var=want_var,
@@ -1349,7 +1354,7 @@ class GP(ModelSet):
         if factor == "cholesky":
             x = np.ascontiguousarray(x, dtype=np.float64)
             z = np.random.standard_normal((size, len(x)))
-            if callable(getattr(self.solver_type, "sample_conditional", None)):
+            if self._offers("sample_conditional", on_type=True):
                 out, _ = self.kernel.kernel.sample(x, z, jitter=TINY)
             else:
                 cov = self.get_matrix(x)

@@ -9,45 +9,26 @@ keep the GP glue of ``gp.py:482-545`` / ``:429-466`` device-resident;
 :class:`george_amd.GP` uses them when present, the reference GP simply ignores
 them.
 """
+import atexit
 import ctypes as C
 
 import numpy as np
 
 from .. import _native as N
 from ..program import DeviceKernel
+from .protocol import NativeSolver, rhs_vector
 
 __all__ = ["BasicSolver"]
 
-import atexit
 
+class BasicSolver(NativeSolver):
 
-class BasicSolver(object):
+    _SOLVE, _DOT_SOLVE, _GET_INVERSE, _APPLY_SQRT = "gh_chol_solve", "gh_chol_dot_solve", "gh_chol_get_inverse", "gh_chol_apply_sqrt"
 
     def __init__(self, kernel, device=0, nb=0, profile=False, lookahead=True):
-        self.kernel = kernel
-        self._computed = False
-        self._log_det = None
+        super(BasicSolver, self).__init__(kernel)
         self._opts = dict(device=int(device), nb=int(nb), profile=bool(profile), lookahead=bool(lookahead))
-        self._handle = None
-        self._dk = None
         self._factor_state = None
-
-    # -- properties (basic.py:25-49)
-    @property
-    def computed(self):
-        return self._computed
-
-    @computed.setter
-    def computed(self, v):
-        self._computed = v
-
-    @property
-    def log_determinant(self):
-        return self._log_det
-
-    @log_determinant.setter
-    def log_determinant(self, v):
-        self._log_det = v
 
     # -- lifetime.  `GP.compute` instantiates a NEW solver on every call (gp.py:327) -- thousands of
     # times inside an optimiser loop -- so native handles (and the N x N device buffers they own)
@@ -72,18 +53,21 @@ class BasicSolver(object):
     def _pool_key(self):
         return tuple(sorted(self._opts.items()))
 
+    def _new_handle(self, key):
+        """a handle parked under ``key``, or a new one"""
+        free = BasicSolver._POOL.get(key)
+        if free:
+            return free.pop()
+        o = N.gh_chol_opts()
+        o.device, o.nb = self._opts["device"], self._opts["nb"]
+        o.profile, o.lookahead = int(self._opts["profile"]), int(self._opts["lookahead"])
+        h = N._vp()
+        N.check(N.lib.gh_chol_create(C.byref(o), C.byref(h)))
+        return h
+
     def _ensure_handle(self):
         if self._handle is None:
-            free = BasicSolver._POOL.get(self._pool_key())
-            if free:
-                self._handle = free.pop()
-                return self._handle
-            o = N.gh_chol_opts()
-            o.device, o.nb = self._opts["device"], self._opts["nb"]
-            o.profile, o.lookahead = int(self._opts["profile"]), int(self._opts["lookahead"])
-            h = N._vp()
-            N.check(N.lib.gh_chol_create(C.byref(o), C.byref(h)))
-            self._handle = h
+            self._handle = self._new_handle(self._pool_key())
         return self._handle
 
     @staticmethod
@@ -97,16 +81,7 @@ class BasicSolver(object):
 
     def _ensure_batch_handle(self):
         if getattr(self, "_bhandle", None) is None:
-            free = BasicSolver._POOL.get(self._batch_pool_key())
-            if free:
-                self._bhandle = free.pop()
-            else:
-                o = N.gh_chol_opts()
-                o.device, o.nb = self._opts["device"], self._opts["nb"]
-                o.profile, o.lookahead = int(self._opts["profile"]), int(self._opts["lookahead"])
-                h = N._vp()
-                N.check(N.lib.gh_chol_create(C.byref(o), C.byref(h)))
-                self._bhandle = h
+            self._bhandle = self._new_handle(self._batch_pool_key())
         return self._bhandle
 
     @staticmethod
@@ -134,19 +109,11 @@ class BasicSolver(object):
                     pass
                 setattr(self, attr, None)
 
-    def _retry_without_parked_memory(self, call, ensure=None):
-        """Run ``call(handle)``; on MemoryError give back what dead solvers left parked on the device -- the handle pool
-        (up to _POOL_MAX_BYTES, work arrays included) and the native block cache (up to 48 GB) -- and try ONCE more: a
-        new pool key, a multi-GPU handle or the application's own allocations must not fail because of memory nobody uses.
-        (``ensure``: where the handle comes from; the solver's own by default.)"""
-        ensure = ensure or self._ensure_handle
-        try:
-            return call(ensure())
-        except MemoryError:
-            type(self).release_pool()
-            BasicSolver.release_pool()
-            N.lib.gh_release_caches(int(self._opts["device"]))
-            return call(ensure())
+    def _release_parked_memory(self):
+        """what ``_retry_without_parked_memory`` gives back: the handle pool (up to _POOL_MAX_BYTES, work arrays included) and
+        the native block cache (up to 48 GB)"""
+        BasicSolver.release_pool()
+        N.lib.gh_release_caches(int(self._opts["device"]))
 
     @classmethod
     def release_pool(cls):
@@ -199,21 +166,9 @@ class BasicSolver(object):
 
     # -- the solver protocol
     def _begin_compute(self, x, yerr, r=None):
-        """The start of a call that factors: the inputs coerced and checked, the old factor forgotten, a new device kernel.
-        Returns ``(x, yerr, r)``."""
-        x = N.as_f64(x)
-        if x.ndim != 2:
-            raise ValueError("x must be (nsamples, ndim)")
-        yerr = N.as_f64(np.zeros(len(x)) + yerr)
-        if r is not None:
-            r = N.as_f64(r).reshape(-1)
-            if len(r) != len(x):
-                raise ValueError("dimension mismatch")
-        self._computed = False
+        """``_check_inputs``, and a pickled factor that was never uploaded forgotten.  Returns ``(x, yerr, r)``."""
+        x, yerr, r = self._check_inputs(x, yerr, r)
         self._factor_state = None
-        self._dk = DeviceKernel(self.kernel)
-        if x.shape[1] != self._dk.ndim:
-            raise RuntimeError("dimension mismatch")
         return x, yerr, r
 
     def _end_compute(self, x, yerr, logdet):
@@ -412,9 +367,7 @@ class BasicSolver(object):
     def _need(self):
         if self._computed and self._handle is None and getattr(self, "_factor_state", None) is not None:
             self._restore()
-        if not self._computed or self._handle is None:
-            raise RuntimeError("you must call 'compute' first")
-        return self._handle
+        return super(BasicSolver, self)._need()
 
     # -- sequential use (no reference counterpart: basic.py:51-70 always refactorises)
     @property
@@ -515,63 +468,21 @@ class BasicSolver(object):
         self.log_determinant = logdet.value
         self.last_remove_path = "truncate" if trailing else "update"
 
-    def apply_inverse(self, y, in_place=False):
-        """basic.py:72-87 (``cho_solve``): ``y`` is (n,) or (n, nrhs)."""
-        h = self._need()
-        yin = y
-        y = np.asarray(y, dtype=np.float64)
-        if y.shape[0] != self._n or y.ndim > 2:
-            raise ValueError("dimension mismatch")
-        yc = np.ascontiguousarray(y)
-        nrhs = 1 if yc.ndim == 1 else yc.shape[1]
-        writable_inplace = (in_place and isinstance(yin, np.ndarray) and yin.dtype == np.float64
-                            and yin.flags.c_contiguous and yin.flags.writeable)
-        out = yin if writable_inplace else np.empty_like(yc)
-        if nrhs > 0:
-            N.check(N.lib.gh_chol_solve(h, N.ptr(yc), nrhs, N.ptr(out)))
-        if in_place and not writable_inplace and isinstance(yin, np.ndarray):
-            try:
-                yin[...] = out                     # honour overwrite_b for non-contiguous callers (gp.py:296-301)
-                return yin
-            except (ValueError, TypeError):
-                pass
-        return out
-
-    def dot_solve(self, y):
-        """basic.py:89-102."""
-        h = self._need()
-        y = N.as_f64(y).reshape(-1)
-        if len(y) != self._n:
-            raise ValueError("dimension mismatch")
-        out = C.c_double(0.0)
-        N.check(N.lib.gh_chol_dot_solve(h, N.ptr(y), C.byref(out)))
-        return out.value
-
-    def apply_sqrt(self, r):
-        """basic.py:104-114: ``r @ U`` with ``U^T U = K``."""
-        h = self._need()
-        r = N.as_f64(r)
-        one_d = r.ndim == 1
-        r2 = r.reshape(1, -1) if one_d else r
-        if r2.shape[1] != self._n:
-            raise ValueError("dimension mismatch")
-        out = np.empty_like(r2)
-        N.check(N.lib.gh_chol_apply_sqrt(h, N.ptr(r2), r2.shape[0], N.ptr(out)))
-        return out[0] if one_d else out
-
-    def get_inverse(self):
-        """basic.py:116-121."""
-        h = self._need()
-        out = np.empty((self._n, self._n), dtype=np.float64)
-        N.check(N.lib.gh_chol_get_inverse(h, N.ptr(out)))
-        return out
+    def _solve_target(self, y, yc, in_place):
+        """``in_place``: the solve writes straight into a writable contiguous float64 ``y``; any other array gets the values
+        copied back"""
+        if not (in_place and isinstance(y, np.ndarray)):
+            return np.empty_like(yc), None
+        if y.dtype == np.float64 and y.flags.c_contiguous and y.flags.writeable:
+            return y, None
+        return np.empty_like(yc), y
 
     # -- fused, device-resident GP glue (optional protocol extensions)
     def predict(self, kernel, r, xs, return_var=False, return_cov=False):
         """mean / variance / covariance terms of gp.py:532-545 for residual ``r = y - mean``:
         returns ``K* K^-1 r`` and (optionally) ``diag`` or full ``K** - K* K^-1 K*^T``."""
         h = self._need()
-        dk = DeviceKernel(kernel) if kernel is not self.kernel else self._dk
+        dk = self._kernel_for(kernel)
         r, xs = N.as_f64(r).reshape(-1), N.as_f64(xs)
         m = len(xs)
         mu = np.empty(m)
@@ -589,10 +500,8 @@ class BasicSolver(object):
         leaves ``mu`` and ``var`` out (``None``); without ``return_var`` too the call needs ``alpha`` only -- two sweeps instead
         of a substitution with M right-hand sides -- and ``dmu`` has the same bits."""
         h = self._need()
-        dk = DeviceKernel(kernel) if kernel is not self.kernel else self._dk
-        r, xs = N.as_f64(r).reshape(-1), N.as_f64(xs)
-        if len(r) != self._n:
-            raise ValueError("dimension mismatch")
+        dk = self._kernel_for(kernel)
+        r, xs = rhs_vector(r, self._n), N.as_f64(xs)
         if xs.ndim != 2 or xs.shape[1] != dk.ndim:
             raise ValueError("xs must be (M, {0})".format(dk.ndim))
         m = len(xs)
@@ -612,10 +521,8 @@ class BasicSolver(object):
         ``(draws (size, M), mu (M,), rank)``, with ``L`` (M, M) before ``rank`` when ``return_factor``; ``mu`` has no mean
         model.  ``tol=None``: ``M * eps * max diag K(xs, xs)``."""
         h = self._need()
-        dk = DeviceKernel(kernel) if kernel is not self.kernel else self._dk
-        r, xs = N.as_f64(r).reshape(-1), N.as_f64(xs)
-        if len(r) != self._n:
-            raise ValueError("dimension mismatch")
+        dk = self._kernel_for(kernel)
+        r, xs = rhs_vector(r, self._n), N.as_f64(xs)
         m = len(xs)
         z = N.as_f64(z)
         if z.ndim != 2 or z.shape[1] != m or z.shape[0] < 1:
@@ -662,9 +569,7 @@ class BasicSolver(object):
         -- K^-1 is not formed.  With a parameter mask also ``grad_full`` = d lpd_sum / d theta over ALL kernel parameters
         (masked ones exactly 0), ``v`` = d lpd_sum / d mean_i and ``diagB`` = d lpd_sum / d K_ii."""
         h = self._need()
-        r = N.as_f64(r).reshape(-1)
-        if len(r) != self._n:
-            raise ValueError("dimension mismatch")
+        r = rhs_vector(r, self._n)
         n = self._n
         total = C.c_double(0.0)
         resid, var, lpd = np.empty(n), np.empty(n), np.empty(n)
@@ -706,10 +611,8 @@ class BasicSolver(object):
         formed.  With a parameter mask also ``grad_full`` = d lpd_sum / d theta over ALL kernel parameters (masked ones
         exactly 0), ``v`` = d lpd_sum / d mean_i and ``diagB`` = d lpd_sum / d K_ii."""
         h = self._need()
-        r = N.as_f64(r).reshape(-1)
         n = self._n
-        if len(r) != n:
-            raise ValueError("dimension mismatch")
+        r = rhs_vector(r, n)
         order = np.ascontiguousarray(order, dtype=np.int64).reshape(-1)
         start = np.ascontiguousarray(start, dtype=np.int64).reshape(-1)
         if len(order) != n or len(start) < 2:

@@ -12,13 +12,15 @@ import warnings
 import numpy as np
 
 from .. import _native as N
-from ..program import DeviceKernel
 from .basic import BasicSolver
+from .protocol import NativeSolver, rhs_vector
 
 __all__ = ["HODLRSolver"]
 
 
-class HODLRSolver(BasicSolver):
+class HODLRSolver(NativeSolver):
+
+    _SOLVE, _DOT_SOLVE, _GET_INVERSE = "gh_hodlr_solve", "gh_hodlr_dot_solve", "gh_hodlr_get_inverse"
 
     # hodlr.h:147 lets a block's rank grow to min(rows, cols); the level-batched ACA here stops at 1024
     # columns.  A block that needs more (3-D inputs at tight tolerances: docs/user/solvers.rst:40-42) is
@@ -37,7 +39,7 @@ class HODLRSolver(BasicSolver):
         self.tol = tol
         self.seed = seed
         self._hopts = dict(device=int(device), max_rank=int(max_rank))
-        super(HODLRSolver, self).__init__(kernel, device=device)
+        super(HODLRSolver, self).__init__(kernel)
 
     # A native handle keeps its tree, its per-level job tables on the device and the measured schedule of its
     # last compute(): inside an optimiser loop (GP makes a NEW solver object per compute, gp.py:327) a fresh handle
@@ -104,75 +106,50 @@ class HODLRSolver(BasicSolver):
                     pass
         cls._HPOOL.clear()
 
+    def _destroy_handle(self):
+        h, self._handle = self._handle, None
+        if h is not None:
+            N.lib.gh_hodlr_destroy(h)
+
+    def _release_parked_memory(self):
+        """this solver's own handle first, then what dead solvers left parked: both handle pools and the native block cache"""
+        self._destroy_handle()
+        HODLRSolver.release_pool()
+        BasicSolver.release_pool()
+        N.lib.gh_release_caches(self._hopts["device"])
+
     def compute(self, x, yerr):
-        x = N.as_f64(x)
-        if x.ndim != 2:
-            raise ValueError("x must be (nsamples, ndim)")
-        yerr = N.as_f64(np.zeros(len(x)) + yerr)
-        self._computed = False
-        self._dk = DeviceKernel(self.kernel)
-        if x.shape[1] != self._dk.ndim:
-            raise RuntimeError("dimension mismatch")
+        x, yerr, _ = self._check_inputs(x, yerr)
         if self._handle is not None and getattr(self, "_handle_key", None) != self._hkey():
             self._park_handle()               # options were changed on the instance
-        h = self._ensure_handle()
         logdet = C.c_double(0.0)
         self.dense_fallback, self._dense = False, None
         try:
-            try:
-                N.check(N.lib.gh_hodlr_compute(h, self._dk.handle, N.ptr(x), len(x), x.shape[1], N.ptr(yerr), C.byref(logdet)))
-            except MemoryError:
-                # memory that dead solvers left parked (dense handle pool, HODLR handle pool, native block cache) goes back
-                # to the device, and the call is tried once more
-                self._handle = None
-                N.lib.gh_hodlr_destroy(h)
-                BasicSolver.release_pool()
-                HODLRSolver.release_pool()
-                N.lib.gh_release_caches(self._hopts["device"])
-                h = self._ensure_handle()
-                N.check(N.lib.gh_hodlr_compute(h, self._dk.handle, N.ptr(x), len(x), x.shape[1], N.ptr(yerr), C.byref(logdet)))
+            self._retry_without_parked_memory(lambda hh: N.check(N.lib.gh_hodlr_compute(
+                hh, self._dk.handle, N.ptr(x), len(x), x.shape[1], N.ptr(yerr), C.byref(logdet))))
         except N.RankCeilingError as e:
             if len(x) > HODLRSolver.DENSE_FALLBACK_MAX_N:
                 raise
             warnings.warn("HODLRSolver: %s -- answering with the dense device solver (exact)" % (e,), RuntimeWarning)
-            N.lib.gh_hodlr_destroy(self._handle)          # (frees the HODLR scratch before the N x N matrix is built)
-            self._handle = None
+            self._destroy_handle()                        # (frees the HODLR scratch before the N x N matrix is built)
             self._dense = BasicSolver(self.kernel, device=self._hopts["device"])
             self._dense.compute(x, yerr)
             self.dense_fallback = True
-            self._n = len(x)
-            self._log_det = self._dense.log_determinant
-            self.computed = True
-            return
         self._n = len(x)
-        self._log_det = logdet.value
+        self._log_det = self._dense.log_determinant if self.dense_fallback else logdet.value
         self.computed = True
 
+    # -- the solver protocol: a dense-fallback solver answers with the dense forms
     def apply_inverse(self, y, in_place=False):
-        # the reference's pybind/Eigen binding always returns a fresh array
+        # the reference's pybind/Eigen binding always returns a fresh array (SURVEY 8a row a19): the base's policy
         if self._computed and self._dense is not None:
             return self._dense.apply_inverse(y, in_place=False)
-        h = self._need()
-        y = np.asarray(y, dtype=np.float64)
-        if y.shape[0] != self._n or y.ndim > 2:
-            raise ValueError("dimension mismatch")
-        yc = np.ascontiguousarray(y)
-        nrhs = 1 if yc.ndim == 1 else yc.shape[1]
-        out = np.empty_like(yc)
-        if nrhs > 0:
-            N.check(N.lib.gh_hodlr_solve(h, N.ptr(yc), nrhs, N.ptr(out)))
-        return out
+        return super(HODLRSolver, self).apply_inverse(y)
 
     def dot_solve(self, y):
         if self._computed and self._dense is not None:
             return self._dense.dot_solve(y)
-        h = self._need()
-        y = N.as_f64(y).reshape(-1)
-        if len(y) != self._n:
-            raise ValueError("dimension mismatch")
-        out = C.c_double(0.0)
-        N.check(N.lib.gh_hodlr_dot_solve(h, N.ptr(y), C.byref(out)))
-        return out.value
+        return super(HODLRSolver, self).dot_solve(y)
 
     def apply_sqrt(self, r):
         raise NotImplementedError("apply_sqrt is not implemented for the HODLRSolver")
@@ -180,10 +157,7 @@ class HODLRSolver(BasicSolver):
     def get_inverse(self):
         if self._computed and self._dense is not None:
             return self._dense.get_inverse()
-        h = self._need()
-        out = np.empty((self._n, self._n), dtype=np.float64)
-        N.check(N.lib.gh_hodlr_get_inverse(h, N.ptr(out)))
-        return out
+        return super(HODLRSolver, self).get_inverse()
 
     def ranks(self):
         if self._computed and self._dense is not None:
@@ -195,22 +169,10 @@ class HODLRSolver(BasicSolver):
 
     # pickling drops the factor and flags the solver un-computed (hodlr.py:69-76)
     def __getstate__(self):
-        state = self.__dict__.copy()
-        state["_handle"] = None
-        state["_dk"] = None
-        state["_factor_state"] = None
-        state["_computed"] = False
+        state = super(HODLRSolver, self).__getstate__()
         state["_dense"] = None
         state["dense_fallback"] = False          # (it described the factor that is not pickled)
         return state
-
-    def __setstate__(self, state):
-        self.__dict__.update(state)
-
-    def _need(self):
-        if not self._computed or self._handle is None:
-            raise RuntimeError("you must call 'compute' first")
-        return self._handle
 
     # -- fused, device-resident GP glue on the factor (gh_hodlr_predict / gh_hodlr_grad: column strips, no M x N or N x N
     #    array on the host); a dense-fallback solver answers with the dense forms
@@ -221,10 +183,8 @@ class HODLRSolver(BasicSolver):
         if self._computed and self._dense is not None:
             return self._dense.predict(kernel, r, xs, return_var=return_var, return_cov=return_cov)
         h = self._need()
-        dk = DeviceKernel(kernel) if kernel is not self.kernel else self._dk
-        r, xs = N.as_f64(r).reshape(-1), N.as_f64(xs)
-        if len(r) != self._n:
-            raise ValueError("dimension mismatch")
+        dk = self._kernel_for(kernel)
+        r, xs = rhs_vector(r, self._n), N.as_f64(xs)
         want_var = bool(return_var)
         want_cov = bool(return_cov) and not want_var
         m = len(xs)
@@ -241,25 +201,12 @@ class HODLRSolver(BasicSolver):
         if self._computed and self._dense is not None:
             return self._dense.grad(r, which)
         h = self._need()
-        r = N.as_f64(r).reshape(-1)
-        if len(r) != self._n:
-            raise ValueError("dimension mismatch")
+        r = rhs_vector(r, self._n)
         which = np.ascontiguousarray(which, dtype=np.uint32)
         g = np.zeros(max(self._dk.size, 1))
         alpha, diagA = np.empty(self._n), np.empty(self._n)
         N.check(N.lib.gh_hodlr_grad(h, self._dk.handle, N.ptr(which), N.ptr(r), N.ptr(g), N.ptr(alpha), N.ptr(diagA)))
         return g[:self._dk.size], alpha, diagA
-
-    # compute + gradient in one call, the dense solver's profile counters and its leave-one-out entry points (they take a
-    # dense handle; GP's NumPy branch serves this solver through apply_inverse / get_inverse) are not offered
-    profile = None
-    objective = None
-    loo = None
-    loo_objective = None
-    lgo = None                        # (GP.lgo_* take their NumPy branch on apply_inverse / get_inverse)
-    fisher = None                     # (GP.fisher_information takes its NumPy branch on get_inverse)
-    remove = None                     # (GP.remove computes afresh on the kept points)
-    predict_gradient = None           # (GP.predict_gradient takes its NumPy branch on apply_inverse)
 
 
 atexit.register(HODLRSolver.release_pool)

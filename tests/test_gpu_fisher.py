@@ -139,7 +139,7 @@ def test_gp_on_the_device_agrees_with_hodlr_through_the_numpy_branch():
         return gp
 
     dense, hod = gp_on(BasicSolver), gp_on(HODLRSolver, tol=1e-14)
-    assert callable(dense.solver.fisher) and not callable(hod.solver.fisher)
+    assert callable(dense.solver.fisher) and not callable(getattr(hod.solver, "fisher", None))
     Fd, Fh = dense.fisher_information(), hod.fisher_information()
     P = len(dense)
     assert Fd.shape == Fh.shape == (P, P) and P == 2 + 2 + 10

@@ -25,9 +25,13 @@ def test_entry_points_are_bound_and_exported():
 
 def test_solver_protocol():
     assert callable(HODLRSolver.predict) and callable(HODLRSolver.grad)
-    assert HODLRSolver.objective is None and HODLRSolver.profile is None
+    # what the class does not define it does not offer: GP routes on callable(getattr(solver, name, None))
+    for name in ("objective", "profile", "loo", "loo_objective", "lgo", "fisher", "remove", "predict_gradient", "truncate",
+                 "append", "sample_conditional"):
+        assert not callable(getattr(HODLRSolver, name, None)), name
     # the tree split over several devices keeps the generic branch of GP.predict and has no fused gradient
-    assert MultiGPUHODLRSolver.predict is None and not callable(getattr(MultiGPUHODLRSolver, "grad", None))
+    for name in ("predict", "grad"):
+        assert not callable(getattr(MultiGPUHODLRSolver, name, None)), name
 
 
 def test_null_handle_is_a_bad_argument():
