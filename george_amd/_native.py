@@ -50,6 +50,10 @@ class gh_hodlr_opts(C.Structure):
                 ("max_rank", C.c_int32), ("tol", C.c_double), ("reserved", C.c_int32 * 4)]
 
 
+class gh_vecchia_opts(C.Structure):
+    _fields_ = [("device", C.c_int32), ("m", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class gh_mgpu_opts(C.Structure):
     _fields_ = [("n_dev", C.c_int32), ("devices", C.c_int32 * 16), ("pr", C.c_int32), ("pc", C.c_int32),
                 ("nb", C.c_int32), ("transport", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 3)]
@@ -191,6 +195,14 @@ SIGNATURES = {
     "gh_hodlr_ranks": (C.c_int, [_vp, C.POINTER(C.c_int32), _i32, C.POINTER(C.c_int32)]),
     "gh_hodlr_predict": (C.c_int, [_vp, _vp, _dp, _dp, _i64, _dp, _dp, _dp]),
     "gh_hodlr_grad": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _dp, _dp]),
+    "gh_vecchia_create": (C.c_int, [C.POINTER(gh_vecchia_opts), C.POINTER(_vp)]),
+    "gh_vecchia_destroy": (None, [_vp]),
+    "gh_vecchia_compute": (C.c_int, [_vp, _vp, _dp, _i64, _i32, _dp, _dp, C.POINTER(C.c_double)]),
+    "gh_vecchia_info": (_i64, [_vp]),
+    "gh_vecchia_solve": (C.c_int, [_vp, _dp, _i64, _dp]),
+    "gh_vecchia_dot_solve": (C.c_int, [_vp, _dp, C.POINTER(C.c_double)]),
+    "gh_vecchia_grad": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _dp, _dp]),
+    "gh_vecchia_predict": (C.c_int, [_vp, _vp, _dp, _dp, _i64, _dp, _dp, _dp]),
     "gh_mgpu_create": (C.c_int, [C.POINTER(gh_mgpu_opts), C.POINTER(_vp)]),
     "gh_mgpu_destroy": (None, [_vp]),
     "gh_mgpu_compute": (C.c_int, [_vp, _vp, _dp, _i64, _i32, _dp, C.POINTER(C.c_double)]),

@@ -252,10 +252,10 @@ GH_HD double gh_axis(const GhNode& nd, double a, double b, double* pg, double& d
 }
 
 // ------------------------------------------------------------------ leaves
-GH_HD double gh_leaf_value(const GhNode& nd, const double* x1, const double* x2) {
+GH_HD double gh_leaf_value(const GhNode& nd, const double* x1, const double* x2, double* ws = nullptr) {
   if (nd.mtype >= 0) {                    // stationary: templates/kernels.h:260-285
     if (gh_out_of_block(nd, x1, x2)) return 0.0;
-    const double r2 = gh_metric<false>(nd, x1, x2, nullptr);
+    const double r2 = gh_metric<false>(nd, x1, x2, nullptr, ws);
     double rg, pg;
     return gh_radial<false>(nd, r2, rg, pg);
   }
@@ -416,13 +416,13 @@ GH_HD void gh_fast_xgrad(const GhFast& f, const double (&x1)[ND], const double* 
 }
 
 // Sum / Product: kernels.h:75-80, 111-116
-GH_HD double gh_eval_value(const GhNode* prog, int n_nodes, const double* x1, const double* x2) {
+GH_HD double gh_eval_value(const GhNode* prog, int n_nodes, const double* x1, const double* x2, double* ws = nullptr) {
   GhStack st;
   st.s0 = st.s1 = st.s2 = st.s3 = st.s4 = st.s5 = st.s6 = st.s7 = 0.0;
   for (int i = 0; i < n_nodes; ++i) {
     const GhNode& nd = prog[i];
     if (nd.op == GH_OP_LEAF) {
-      st.push(gh_leaf_value(nd, x1, x2));
+      st.push(gh_leaf_value(nd, x1, x2, ws));
     } else {
       const double b = st.s0, a = st.s1;
       st.drop();

@@ -1,0 +1,612 @@
+// gh_vecchia.hip -- the Vecchia (nearest-neighbour) solver behind gh_vecchia_* (include/george_amd.h has the definition)
+//
+// p(y) ~ prod_i p(y_i | y_c(i)), c(i) at most m <= 64 predecessors of i.  For every point the block A = K[c + {i}, c + {i}] (i last)
+// is built from the kernel evaluator and factored; with v = L_cc^-1 k_ci:  f_i = k_ii - v^T v (the square of the block factor's last
+// pivot) and b_i = L_cc^-T v.  Q = (I - B)^T F^-1 (I - B).
+//
+// Kernels: one point per 64-thread workgroup (one wavefront), lane s owns conditioning point s.  The point's coordinates, the lower
+// triangle of A (packed by rows) and the evaluator's runtime-indexed temporaries sit in LDS: no kernel here uses scratch memory.
+// Phases are separated by __syncthreads(); values cross lanes only through LDS or wave operations (readlane, shuffles).
+// Every sum has a fixed order (wave trees, per-workgroup partials added by gh_launch_kgrad_final, gathers through the transposed
+// index instead of floating-point atomics): two calls give the same bits.
+#include <limits.h>
+#include <string.h>
+#include <algorithm>
+#include <vector>
+#include "gh_common.h"
+#include "gh_device_util.h"
+
+#define VM_MAX 64                       // lanes of the workgroup = the cap on m
+#define VWS (GH_EVAL_WS + 1)            // the evaluator's work space per lane, an odd pitch in doubles
+#define V_GRAD_WGS 4096                 // workgroups of the gradient kernel (each walks points blockIdx.x, + gridDim.x, ..)
+#define V_GRAD_LDS (96 * 1024)
+#define V_STRIP_COLS 256                // test points per strip of predict (mean / variance) ..
+#define V_STRIP_BYTES (1L << 30)        // .. within this many bytes for K(x, xs_J) and V together
+#define V_COV_BYTES (8L << 30)          // what predict's covariance may keep on the device: K(x, xs), V and the m x m result
+#define V_RED_ROWS 128                  // rows per chunk of the column reduction (at most V_RED_CHUNKS chunks)
+#define V_RED_CHUNKS 2048
+
+struct gh_vecchia {
+  gh_vecchia_opts opts;
+  hipStream_t st = nullptr;
+  bool shared_stream = false;
+  int64_t n = 0;
+  int ndim = 0;
+  bool computed = false;
+  int64_t info = 0;
+  double logdet = 0.0;
+  // x, yerr, the compacted neighbour table (valid entries first) and its row counts, B (n, m), f, and the transposed index: the
+  // entries (row, slot) of B in column j are tptr[j] .. tptr[j + 1], rows ascending.  One stream: st.
+  GhPooledBuf x, yerr, nbr, cnt, B, f, tptr, trow, tslot, w1, scal;
+  // the caller's table of the last compute(): the same table again (an optimiser moves the hyper-parameters, not the points) is
+  // neither checked nor indexed nor uploaded a second time
+  std::vector<int32_t> nbr_seen;
+};
+
+struct VArgs {
+  const double* x; const double* yerr; const int* nbr; const int* cnt;
+  long n; int m, nd, n_nodes;
+};
+// the workgroup's LDS, in doubles from a 16-byte aligned base; gp = doubles per lane of the evaluator's area (0: none)
+struct VLds {
+  double *xs, *ye, *A, *dinv, *uv, *zv, *wl, *gl; int* gi;
+};
+__host__ __device__ static inline int v_tri(int j) { return j * (j + 1) / 2; }
+__host__ __device__ static inline size_t v_lds_doubles(int m, int nd, int gp) {
+  return (size_t)(m + 1) * nd + (m + 1) + v_tri(m + 1) + VM_MAX + 2 * (m + 1) + VM_MAX + (size_t)VM_MAX * gp + (m + 3) / 2;
+}
+__device__ __forceinline__ VLds v_carve(double* base, int m, int nd, int gp) {
+  VLds l;
+  l.xs = base;
+  l.ye = l.xs + (m + 1) * nd;
+  l.A = l.ye + (m + 1);
+  l.dinv = l.A + v_tri(m + 1);
+  l.uv = l.dinv + VM_MAX;
+  l.zv = l.uv + (m + 1);
+  l.wl = l.zv + (m + 1);
+  l.gl = l.wl + VM_MAX;
+  l.gi = (int*)(l.gl + VM_MAX * gp);
+  return l;
+}
+__device__ __forceinline__ double v_bcast(double v, int src_lane) {           // src_lane: wave-uniform
+  const int lo = __builtin_amdgcn_readlane(__double2loint(v), src_lane);
+  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src_lane);
+  return __hiloint2double(hi, lo);
+}
+// lane j < c holds t_j: L_cc^-1 t and L_cc^-T t with the factor of K_cc in A (dinv = 1 / its diagonal); lanes >= c keep t
+__device__ __forceinline__ double v_fwd(const double* A, const double* dinv, int c, int lane, double t) {
+  for (int k = 0; k < c; ++k) {
+    const double vk = v_bcast(t, k) * dinv[k];
+    if (lane == k) t = vk;
+    else if (lane > k && lane < c) t -= A[v_tri(lane) + k] * vk;
+  }
+  return t;
+}
+__device__ __forceinline__ double v_bwd(const double* A, const double* dinv, int c, int lane, double t) {
+  for (int k = c - 1; k >= 0; --k) {
+    const double bk = v_bcast(t, k) * dinv[k];
+    if (lane == k) t = bk;
+    else if (lane < k) t -= A[v_tri(k) + lane] * bk;
+  }
+  return t;
+}
+// the kernel at block slots (j, k): the point with the lower index is the first argument (as gh_kmat.hip's symmetric build)
+template <bool FAST>
+__device__ __forceinline__ double v_value(const GhFast& fast, const GhNode* prog, int n_nodes, const double* x1, const double* x2,
+                                          double* ws) {
+  if (FAST) return gh_fast_value(fast, x1, x2);
+  __builtin_assume(ws != nullptr);                          // (the evaluator then drops its private arrays: no scratch memory)
+  return gh_eval_value(prog, n_nodes, x1, x2, ws);
+}
+
+// Point i: stage its block, build A, factor K_cc (left-looking, lane j owns row j), then v, f and b.  Returns false -- in every
+// lane -- when a pivot of K_cc or f is not positive and finite.  On return: c, this lane's b (lanes < c), f; in LDS the factor
+// of K_cc (rows < c of A), dinv, k_ci and k_ii (row c of A), gi, xs, ye.
+template <bool FAST>
+__device__ __forceinline__ bool v_block(const VArgs& a, const GhFast& fast, const GhNode* prog, long i, const VLds& l, double* ws,
+                                        int lane, int& c_out, double& b_out, double& f_out) {
+  const int c = a.cnt[i], nd = a.nd;
+  c_out = c;
+  __syncthreads();                                          // (the previous point of this workgroup is done with the LDS)
+  for (int s = lane; s <= c; s += VM_MAX) {
+    const int g = s < c ? a.nbr[i * a.m + s] : (int)i;
+    l.gi[s] = g;
+    l.ye[s] = a.yerr[g];
+  }
+  for (int t = lane; t < (c + 1) * nd; t += VM_MAX) {
+    const int s = t / nd;
+    const long g = s < c ? a.nbr[i * a.m + s] : i;
+    l.xs[t] = a.x[g * nd + (t - s * nd)];
+  }
+  __syncthreads();
+  const int T = v_tri(c + 1);
+  for (int t = lane; t < T; t += VM_MAX) {
+    int j, k;
+    tri_index(t, j, k);
+    const bool jlow = l.gi[j] <= l.gi[k];
+    double v = v_value<FAST>(fast, prog, a.n_nodes, &l.xs[(jlow ? j : k) * nd], &l.xs[(jlow ? k : j) * nd], ws);
+    if (j == k) v += l.ye[j] * l.ye[j];
+    l.A[t] = v;
+  }
+  __syncthreads();
+  for (int k = 0; k < c; ++k) {
+    double s = 0.0;
+    if (lane >= k && lane < c) {
+      const double* rj = l.A + v_tri(lane);
+      const double* rk = l.A + v_tri(k);
+      s = rj[k];
+      for (int q = 0; q < k; ++q) s -= rj[q] * rk[q];
+    }
+    const double d = v_bcast(s, k);                         // the pivot, in every lane
+    if (!(d > 0.0) || !isfinite(d)) return false;
+    const double sd = sqrt(d), inv = 1.0 / sd;
+    if (lane == k) { l.A[v_tri(k) + k] = sd; l.dinv[k] = inv; }
+    else if (lane > k && lane < c) l.A[v_tri(lane) + k] = s * inv;
+    __syncthreads();
+  }
+  const double kci = lane < c ? l.A[v_tri(c) + lane] : 0.0;
+  const double v = v_fwd(l.A, l.dinv, c, lane, kci);
+  const double f = l.A[v_tri(c) + c] - v_bcast(wave_sum(lane < c ? v * v : 0.0), 0);
+  f_out = f;
+  if (!(f > 0.0) || !isfinite(f)) return false;
+  b_out = v_bwd(l.A, l.dinv, c, lane, v);
+  return true;
+}
+
+template <bool FAST>
+__global__ __launch_bounds__(VM_MAX) void vecchia_factor_kernel(VArgs a, GhFast fast, const GhNode* __restrict__ prog,
+                                                                double* __restrict__ B, double* __restrict__ f,
+                                                                double* __restrict__ logf, int* fail) {
+  extern __shared__ __attribute__((aligned(16))) double vsm[];
+  const int lane = threadIdx.x;
+  const VLds l = v_carve(vsm, a.m, a.nd, FAST ? 0 : VWS);
+  const long i = blockIdx.x;
+  int c = 0;
+  double b = 0.0, fi = 1.0;
+  const bool ok = v_block<FAST>(a, fast, prog, i, l, FAST ? nullptr : l.gl + lane * VWS, lane, c, b, fi);
+  if (lane < a.m) B[i * a.m + lane] = (ok && lane < c) ? b : 0.0;
+  if (lane == 0) {
+    f[i] = ok ? fi : 1.0;
+    logf[i] = ok ? log(fi) : 0.0;
+    if (!ok) atomicMin(fail, (int)i);                       // the lowest failing point
+  }
+}
+
+// The likelihood gradient, block by block.  With e = r_i - b^T r_c, z = K_cc^-1 r_c, u = [-b; 1], ze = [z; 0]:
+//   W = 1/2 (e^2/f^2 - 1/f) u u^T + 1/2 (e/f) (ze u^T + u ze^T),    d log p(y_i | y_c) / dtheta = sum_jk W_jk dA_jk/dtheta.
+// The lower triangle of the block goes through the evaluator 64 entries at a time (lane t: gradient row into its LDS area,
+// weight into wl); then lane p adds the 64 rows' entry p in order: the sum of a parameter lives in ONE lane, in one register.
+// partial[workgroup][p]; wd[i][s] = 2 W_ss for slot s (slot m: the point itself).
+template <bool FAST>
+__global__ __launch_bounds__(VM_MAX) void vecchia_grad_kernel(VArgs a, GhFast fast, const GhNode* __restrict__ prog, int P, int gp,
+                                                              const uint32_t* __restrict__ which, const double* __restrict__ r,
+                                                              double* __restrict__ partial, double* __restrict__ wd) {
+  extern __shared__ __attribute__((aligned(16))) double vsm[];
+  const int lane = threadIdx.x, nd = a.nd;
+  const VLds l = v_carve(vsm, a.m, nd, gp);
+  double* const g = l.gl + lane * gp;
+  double* const ws = g + P;
+  __builtin_assume(ws != nullptr);
+  double acc = 0.0;
+  for (long i = blockIdx.x; i < a.n; i += gridDim.x) {
+    int c = 0;
+    double b = 0.0, f = 1.0;
+    const bool ok = v_block<FAST>(a, fast, prog, i, l, ws, lane, c, b, f);
+    if (!ok) {                                              // (compute() has refused such a point: only with another kernel)
+      for (int s = lane; s <= a.m; s += VM_MAX) wd[i * (a.m + 1) + s] = 0.0;
+      continue;
+    }
+    const double rc = lane < c ? r[l.gi[lane]] : 0.0;
+    const double e = r[i] - v_bcast(wave_sum(lane < c ? b * rc : 0.0), 0);
+    const double z = v_bwd(l.A, l.dinv, c, lane, v_fwd(l.A, l.dinv, c, lane, rc));
+    const double ca = 0.5 * (e * e / (f * f) - 1.0 / f), cb = 0.5 * e / f;
+    if (lane < c) { l.uv[lane] = -b; l.zv[lane] = z; }
+    if (lane == 0) { l.uv[c] = 1.0; l.zv[c] = 0.0; }
+    if (lane < a.m) wd[i * (a.m + 1) + lane] = lane < c ? 2.0 * (ca * b * b - 2.0 * cb * z * b) : 0.0;
+    if (lane == 0) wd[i * (a.m + 1) + a.m] = 2.0 * ca;
+    __syncthreads();
+    const int T = v_tri(c + 1);
+    for (int t0 = 0; t0 < T && P > 0; t0 += VM_MAX) {
+      const int t = t0 + lane, nact = T - t0 < VM_MAX ? T - t0 : VM_MAX;
+      if (t < T) {
+        int j, k;
+        tri_index(t, j, k);
+        const double uj = l.uv[j], uk = l.uv[k];
+        const double w = ca * uj * uk + cb * (l.zv[j] * uk + uj * l.zv[k]);
+        const bool jlow = l.gi[j] <= l.gi[k];
+        gh_eval_grad(prog, a.n_nodes, &l.xs[(jlow ? j : k) * nd], &l.xs[(jlow ? k : j) * nd], g, ws);
+        l.wl[lane] = j == k ? w : 2.0 * w;
+      }
+      __syncthreads();
+      if (lane < P)
+        for (int q = 0; q < nact; ++q) acc += l.wl[q] * l.gl[q * gp + lane];
+      __syncthreads();
+    }
+  }
+  if (lane < P) partial[(long)blockIdx.x * P + lane] = which[lane] ? acc : 0.0;
+}
+
+// The forward operator as a row gather over the nrhs columns of r (row pitch ldr): with e = r_i - sum_s b_is r_c(i,s)
+//   mode 0: e     1: e / f_i     2: e / sqrt(f_i)     3: e^2 / f_i
+__global__ __launch_bounds__(256) void vecchia_fwd_kernel(const double* __restrict__ B, const double* __restrict__ f,
+                                                          const int* __restrict__ nbr, const int* __restrict__ cnt, long n, int m,
+                                                          const double* __restrict__ r, long nrhs, long ldr,
+                                                          double* __restrict__ out, long ldo, int mode) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= n * nrhs) return;
+  const long i = idx / nrhs, col = idx - i * nrhs;
+  const int c = cnt[i];
+  double s = 0.0;
+  for (int q = 0; q < c; ++q) s += B[i * m + q] * r[(long)nbr[i * m + q] * ldr + col];
+  const double e = r[i * ldr + col] - s;
+  const double fi = f[i];
+  out[i * ldo + col] = mode == 0 ? e : mode == 1 ? e / fi : mode == 2 ? e / sqrt(fi) : e * e / fi;
+}
+// (I - B)^T as a gather through the transposed index: out_j = w_j - sum over the entries (row, slot) of column j of b_row,slot w_row
+__global__ __launch_bounds__(256) void vecchia_bwd_kernel(const double* __restrict__ B, const long long* __restrict__ tptr,
+                                                          const int* __restrict__ trow, const int* __restrict__ tslot, long n, int m,
+                                                          const double* __restrict__ w, long nrhs, double* __restrict__ out) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= n * nrhs) return;
+  const long j = idx / nrhs, col = idx - j * nrhs;
+  double s = 0.0;
+  for (long long q = tptr[j]; q < tptr[j + 1]; ++q) s += B[(long)trow[q] * m + tslot[q]] * w[(long)trow[q] * nrhs + col];
+  out[idx] = w[idx] - s;
+}
+// diagA_j = the point's own slot plus its slots in the blocks of later points
+__global__ __launch_bounds__(256) void vecchia_diag_kernel(const double* __restrict__ wd, const long long* __restrict__ tptr,
+                                                           const int* __restrict__ trow, const int* __restrict__ tslot, long n, int m,
+                                                           double* __restrict__ diagA) {
+  const long j = (long)blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  double s = wd[j * (m + 1) + m];
+  for (long long q = tptr[j]; q < tptr[j + 1]; ++q) s += wd[(long)trow[q] * (m + 1) + tslot[q]];
+  diagA[j] = s;
+}
+// predict: for the cw columns of a strip (row pitch ld) and the rows of chunk blockIdx.y
+//   pmu[chunk][j] = sum_i Kx[i][j] alpha[i],   pvar[chunk][j] = sum_i V[i][j]^2   (V == nullptr: the mean only)
+__global__ __launch_bounds__(64) void vecchia_colred_kernel(const double* __restrict__ Kx, const double* __restrict__ V, long ld, long n,
+                                                            long rows_per, const double* __restrict__ alpha, int cw,
+                                                            double* __restrict__ pmu, double* __restrict__ pvar, long ldp) {
+  const int j = blockIdx.x * 64 + threadIdx.x;
+  if (j >= cw) return;
+  const long r0 = (long)blockIdx.y * rows_per, r1 = r0 + rows_per < n ? r0 + rows_per : n;
+  double smu = 0.0, sv = 0.0;
+  for (long i = r0; i < r1; ++i) smu += Kx[i * ld + j] * alpha[i];
+  pmu[(long)blockIdx.y * ldp + j] = smu;
+  if (V) {
+    for (long i = r0; i < r1; ++i) { const double v = V[i * ld + j]; sv += v * v; }
+    pvar[(long)blockIdx.y * ldp + j] = sv;
+  }
+}
+// the chunk partials added in chunk order: mu[j] = sum, var[j] = var[j] (holding k(xs_j, xs_j)) - sum
+__global__ __launch_bounds__(64) void vecchia_colfinal_kernel(const double* __restrict__ pmu, const double* __restrict__ pvar, long nchunks,
+                                                              long ldp, int cw, double* __restrict__ mu, double* __restrict__ var) {
+  const int j = blockIdx.x * 64 + threadIdx.x;
+  if (j >= cw) return;
+  double smu = 0.0, sv = 0.0;
+  for (long c = 0; c < nchunks; ++c) smu += pmu[c * ldp + j];
+  mu[j] = smu;
+  if (var) {
+    for (long c = 0; c < nchunks; ++c) sv += pvar[c * ldp + j];
+    var[j] = var[j] - sv;
+  }
+}
+
+// ================================================================================ host side
+extern "C" int gh_vecchia_create(const gh_vecchia_opts* opts, gh_vecchia** out) {
+  if (!out || !opts) { gh_set_error("null argument"); return GH_ERR_BAD_ARG; }
+  if (opts->m < 1 || opts->m > VM_MAX) { gh_set_error("the Vecchia solver takes 1 <= m <= %d neighbours, not %d", VM_MAX, (int)opts->m); return GH_ERR_BAD_ARG; }
+  if (gh_device_count() <= 0) { gh_set_error("no HIP device available: the george_amd Vecchia solver needs an MI355X"); return GH_ERR_HIP; }
+  gh_vecchia* h = new gh_vecchia();
+  h->opts = *opts;
+  if (hipSetDevice(h->opts.device) != hipSuccess) { delete h; gh_set_error("cannot initialise HIP device %d", (int)opts->device); return GH_ERR_HIP; }
+  hipStream_t shq[4] = {nullptr, nullptr, nullptr, nullptr};
+  if (gh_shared_streams(h->opts.device, shq) && shq[0]) {
+    h->shared_stream = true;
+    h->st = shq[0];
+  } else if ((gh_prime_device(h->opts.device), hipStreamCreate(&h->st)) != hipSuccess) {
+    delete h; gh_set_error("cannot initialise HIP device %d", (int)opts->device); return GH_ERR_HIP;
+  }
+  *out = h;
+  return GH_OK;
+}
+extern "C" void gh_vecchia_destroy(gh_vecchia* h) {
+  if (!h) return;
+  (void)hipSetDevice(h->opts.device);
+  if (h->st) (void)hipStreamSynchronize(h->st);             // (pooled blocks may be re-acquired by another handle)
+  if (h->st && !h->shared_stream) (void)hipStreamDestroy(h->st);
+  delete h;
+}
+extern "C" int64_t gh_vecchia_info(const gh_vecchia* h) { return h ? h->info : 0; }
+
+static int v_need(gh_vecchia* h) {
+  if (!h) { gh_set_error("null solver"); return GH_ERR_BAD_ARG; }
+  if (!h->computed) { gh_set_error("you must call 'compute' first"); return GH_ERR_NOT_COMPUTED; }
+  GH_HIP(hipSetDevice(h->opts.device));
+  return GH_OK;
+}
+template <typename Tv>
+static int v_upload(GhBuf& buf, const std::vector<Tv>& v, hipStream_t st) {
+  GH_CHECK(buf.ensure(std::max<size_t>(v.size(), 1) * sizeof(Tv)));
+  if (!v.empty()) GH_HIP(hipMemcpyAsync(buf.p, v.data(), v.size() * sizeof(Tv), hipMemcpyHostToDevice, st));
+  return GH_OK;
+}
+// The neighbour table checked and compacted on the host: every entry of row i is -1 or in [0, i), no entry twice in a row.  A bad
+// index would be an out-of-bounds read on the device, so nothing is launched before this has passed.  tab: valid entries first
+// (their order kept), then -1; cnt: per row; and the transposed index by a counting sort (rows ascending inside a column).
+static int v_index(const int32_t* nbr, int64_t n, int m, std::vector<int>& tab, std::vector<int>& cnt, std::vector<long long>& tptr,
+                   std::vector<int>& trow, std::vector<int>& tslot) {
+  tab.assign((size_t)n * m, -1);
+  cnt.assign((size_t)n, 0);
+  tptr.assign((size_t)n + 1, 0);
+  std::vector<int64_t> seen((size_t)n, -1);
+  for (int64_t i = 0; i < n; ++i) {
+    int c = 0;
+    for (int s = 0; s < m; ++s) {
+      const int32_t j = nbr[i * m + s];
+      if (j == -1) continue;
+      if (j < 0 || j >= i) { gh_set_error("neighbour table: row %lld holds %d, which is not one of its predecessors", (long long)i, (int)j); return GH_ERR_BAD_ARG; }
+      if (seen[j] == i) { gh_set_error("neighbour table: row %lld holds %d twice", (long long)i, (int)j); return GH_ERR_BAD_ARG; }
+      seen[j] = i;
+      tab[(size_t)i * m + c++] = j;
+      ++tptr[(size_t)j + 1];
+    }
+    cnt[(size_t)i] = c;
+  }
+  for (int64_t j = 0; j < n; ++j) tptr[(size_t)j + 1] += tptr[(size_t)j];
+  trow.assign((size_t)tptr[(size_t)n], 0);
+  tslot.assign((size_t)tptr[(size_t)n], 0);
+  std::vector<long long> at(tptr.begin(), tptr.end() - 1);
+  for (int64_t i = 0; i < n; ++i)
+    for (int s = 0; s < cnt[(size_t)i]; ++s) {
+      const long long q = at[(size_t)tab[(size_t)i * m + s]]++;
+      trow[(size_t)q] = (int)i;
+      tslot[(size_t)q] = s;
+    }
+  return GH_OK;
+}
+static VArgs v_args(const gh_vecchia* h, const gh_kernel* k) {
+  VArgs a;
+  a.x = h->x.d(); a.yerr = h->yerr.d(); a.nbr = (const int*)h->nbr.p; a.cnt = (const int*)h->cnt.p;
+  a.n = (long)h->n; a.m = h->opts.m; a.nd = h->ndim; a.n_nodes = (int)k->nodes.size();
+  return a;
+}
+static inline unsigned v_blocks(size_t work) { return (unsigned)((work + 255) / 256); }
+// out (n, nrhs) = (I - B)^T F^-1 (I - B) rhs; tmp: n * nrhs doubles; all device memory
+static int v_apply_q(gh_vecchia* h, const double* rhs, long nrhs, double* tmp, double* out) {
+  const size_t tot = (size_t)h->n * nrhs;
+  hipLaunchKernelGGL(vecchia_fwd_kernel, dim3(v_blocks(tot)), dim3(256), 0, h->st, (const double*)h->B.d(), (const double*)h->f.d(),
+                     (const int*)h->nbr.p, (const int*)h->cnt.p, (long)h->n, h->opts.m, rhs, nrhs, nrhs, tmp, nrhs, 1);
+  hipLaunchKernelGGL(vecchia_bwd_kernel, dim3(v_blocks(tot)), dim3(256), 0, h->st, (const double*)h->B.d(), (const long long*)h->tptr.p,
+                     (const int*)h->trow.p, (const int*)h->tslot.p, (long)h->n, h->opts.m, (const double*)tmp, nrhs, out);
+  GH_HIP(hipGetLastError());
+  return GH_OK;
+}
+
+extern "C" int gh_vecchia_compute(gh_vecchia* h, gh_kernel* k, const double* x, int64_t n, int32_t ndim, const double* yerr,
+                                  const int32_t* nbr, double* logdet_out) {
+  if (!h || !k || !x || !yerr || !nbr || n <= 0 || n > 0x7ffffff0L) { gh_set_error("bad argument to compute"); return GH_ERR_BAD_ARG; }
+  h->computed = false;
+  h->info = 0;
+  if (ndim != k->ndim || ndim < 1 || ndim > GH_MAX_NDIM) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
+  const int m = h->opts.m;
+  const bool same_table = h->n == n && h->nbr_seen.size() == (size_t)n * m && memcmp(h->nbr_seen.data(), nbr, (size_t)n * m * sizeof(int32_t)) == 0;
+  std::vector<int> tab, cnt, trow, tslot;
+  std::vector<long long> tptr;
+  if (!same_table) {
+    h->nbr_seen.clear();
+    GH_CHECK(v_index(nbr, n, m, tab, cnt, tptr, trow, tslot));
+  }
+  GH_HIP(hipSetDevice(h->opts.device));
+  GH_CHECK(k->upload());
+  hipStream_t st = h->st;
+  h->n = n;
+  h->ndim = ndim;
+  GH_CHECK(h->x.ensure((size_t)n * ndim * sizeof(double)));
+  GH_CHECK(h->yerr.ensure((size_t)n * sizeof(double)));
+  GH_CHECK(gh_to_device(h->x.d(), x, (size_t)n * ndim, st));
+  GH_CHECK(gh_to_device(h->yerr.d(), yerr, (size_t)n, st));
+  if (!same_table) {
+    GH_CHECK(v_upload(h->nbr, tab, st));
+    GH_CHECK(v_upload(h->cnt, cnt, st));
+    GH_CHECK(v_upload(h->tptr, tptr, st));
+    GH_CHECK(v_upload(h->trow, trow, st));
+    GH_CHECK(v_upload(h->tslot, tslot, st));
+    GH_HIP(hipStreamSynchronize(st));                       // (the host vectors end with this call)
+    h->nbr_seen.assign(nbr, nbr + (size_t)n * m);
+  }
+  GH_CHECK(h->B.ensure((size_t)n * m * sizeof(double)));
+  GH_CHECK(h->f.ensure((size_t)n * sizeof(double)));
+  GH_CHECK(h->w1.ensure((size_t)n * sizeof(double)));
+  GH_CHECK(h->scal.ensure(2 * sizeof(double)));
+  int* fail = (int*)(h->scal.d() + 1);
+  GH_HIP(hipMemsetD32Async((hipDeviceptr_t)fail, INT_MAX, 1, st));
+  const VArgs a = v_args(h, k);
+  const bool fast = k->fast.ok != 0;
+  const size_t lds = v_lds_doubles(m, ndim, fast ? 0 : VWS) * sizeof(double);
+  if (fast) hipLaunchKernelGGL(vecchia_factor_kernel<true>, dim3((unsigned)n), dim3(VM_MAX), lds, st, a, k->fast, (const GhNode*)k->d_nodes,
+                               h->B.d(), h->f.d(), h->w1.d(), fail);
+  else hipLaunchKernelGGL(vecchia_factor_kernel<false>, dim3((unsigned)n), dim3(VM_MAX), lds, st, a, k->fast, (const GhNode*)k->d_nodes,
+                          h->B.d(), h->f.d(), h->w1.d(), fail);
+  GH_HIP(hipGetLastError());
+  GH_CHECK(gh_launch_kgrad_final(h->w1.d(), n, 1, h->scal.d(), st));          // log|K| ~ sum_i log f_i, fixed order
+  double res[2] = {0.0, 0.0};
+  GH_HIP(hipMemcpyAsync(res, h->scal.d(), 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+  GH_HIP(hipStreamSynchronize(st));
+  int failed;
+  memcpy(&failed, &res[1], sizeof(int));
+  if (failed != INT_MAX) {
+    h->info = (int64_t)failed + 1;
+    gh_set_error("the conditional of point %lld is not positive definite", (long long)failed);
+    return GH_ERR_NOT_PD;
+  }
+  h->logdet = res[0];
+  if (logdet_out) *logdet_out = res[0];
+  h->computed = true;
+  return GH_OK;
+}
+
+extern "C" int gh_vecchia_solve(gh_vecchia* h, const double* b, int64_t nrhs, double* out) {
+  GH_CHECK(v_need(h));
+  if (!b || !out || nrhs <= 0) { gh_set_error("bad argument to solve"); return GH_ERR_BAD_ARG; }
+  const size_t tot = (size_t)h->n * nrhs;
+  GhPooledBuf rhs, tmp;
+  GH_CHECK(rhs.ensure(tot * sizeof(double)));
+  GH_CHECK(tmp.ensure(tot * sizeof(double)));
+  GH_CHECK(gh_to_device(rhs.d(), b, tot, h->st));
+  GH_CHECK(v_apply_q(h, rhs.d(), (long)nrhs, tmp.d(), rhs.d()));
+  GH_CHECK(gh_from_device(out, rhs.d(), tot, h->st));
+  GH_HIP(hipStreamSynchronize(h->st));
+  return GH_OK;
+}
+extern "C" int gh_vecchia_dot_solve(gh_vecchia* h, const double* y, double* out) {
+  GH_CHECK(v_need(h));
+  if (!y || !out) { gh_set_error("null argument"); return GH_ERR_BAD_ARG; }
+  const long n = (long)h->n;
+  GhPooledBuf yd;
+  GH_CHECK(yd.ensure((size_t)n * sizeof(double)));
+  GH_CHECK(gh_to_device(yd.d(), y, (size_t)n, h->st));
+  hipLaunchKernelGGL(vecchia_fwd_kernel, dim3(v_blocks((size_t)n)), dim3(256), 0, h->st, (const double*)h->B.d(), (const double*)h->f.d(),
+                     (const int*)h->nbr.p, (const int*)h->cnt.p, n, h->opts.m, (const double*)yd.d(), 1L, 1L, h->w1.d(), 1L, 3);
+  GH_HIP(hipGetLastError());
+  GH_CHECK(gh_launch_kgrad_final(h->w1.d(), n, 1, h->scal.d(), h->st));       // sum_i e_i^2 / f_i, fixed order
+  double v = 0.0;
+  GH_HIP(hipMemcpyAsync(&v, h->scal.d(), sizeof(double), hipMemcpyDeviceToHost, h->st));
+  GH_HIP(hipStreamSynchronize(h->st));
+  *out = v;
+  return GH_OK;
+}
+
+extern "C" int gh_vecchia_grad(gh_vecchia* h, gh_kernel* k, const uint32_t* which, const double* r, double* grad, double* alpha,
+                               double* diagA) {
+  GH_CHECK(v_need(h));
+  if (!k || !which || !r || !grad) { gh_set_error("bad argument to grad"); return GH_ERR_BAD_ARG; }
+  if (k->ndim != h->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
+  if (k->size > GH_MAX_GRAD) { gh_set_error("grad: %d kernel parameters, at most %d", k->size, GH_MAX_GRAD); return GH_ERR_BAD_ARG; }
+  GH_CHECK(k->upload());
+  const long n = (long)h->n;
+  const int m = h->opts.m, P = k->size, Pw = P > 0 ? P : 1;
+  hipStream_t st = h->st;
+  GhPooledBuf rd, tmp, al, part, wd, dg;
+  GH_CHECK(rd.ensure((size_t)n * sizeof(double)));
+  GH_CHECK(tmp.ensure((size_t)n * sizeof(double)));
+  GH_CHECK(al.ensure((size_t)n * sizeof(double)));
+  GH_CHECK(gh_to_device(rd.d(), r, (size_t)n, st));
+  if (alpha) {
+    GH_CHECK(v_apply_q(h, rd.d(), 1L, tmp.d(), al.d()));
+    GH_CHECK(gh_from_device(alpha, al.d(), (size_t)n, st));
+  }
+  const unsigned nwg = (unsigned)std::min<long>(n, V_GRAD_WGS);
+  const size_t which_bytes = ((sizeof(uint32_t) * Pw + 15) / 16) * 16;
+  GH_CHECK(part.ensure(which_bytes + ((size_t)nwg + 1) * Pw * sizeof(double)));
+  GH_CHECK(wd.ensure((size_t)n * (m + 1) * sizeof(double)));
+  GH_CHECK(dg.ensure((size_t)n * sizeof(double)));
+  uint32_t* d_which = (uint32_t*)part.p;
+  double* partial = (double*)((char*)part.p + which_bytes);
+  double* dgrad = partial + (size_t)nwg * Pw;
+  if (P > 0) GH_HIP(hipMemcpyAsync(d_which, which, sizeof(uint32_t) * P, hipMemcpyHostToDevice, st));
+  const VArgs a = v_args(h, k);
+  const int gp = (P + GH_EVAL_WS) | 1;                      // doubles per lane: the gradient row, the evaluator's work space; odd
+  const size_t lds = v_lds_doubles(m, h->ndim, gp) * sizeof(double);
+  if (lds > 64 * 1024) {                                    // (m = 64 with eight or more input dimensions and ~60 parameters: 70 KB at most)
+    GH_HIP(hipFuncSetAttribute((const void*)vecchia_grad_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, V_GRAD_LDS));
+    GH_HIP(hipFuncSetAttribute((const void*)vecchia_grad_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, V_GRAD_LDS));
+  }
+  if (k->fast.ok) hipLaunchKernelGGL(vecchia_grad_kernel<true>, dim3(nwg), dim3(VM_MAX), lds, st, a, k->fast, (const GhNode*)k->d_nodes, P, gp,
+                                     (const uint32_t*)d_which, (const double*)rd.d(), partial, wd.d());
+  else hipLaunchKernelGGL(vecchia_grad_kernel<false>, dim3(nwg), dim3(VM_MAX), lds, st, a, k->fast, (const GhNode*)k->d_nodes, P, gp,
+                          (const uint32_t*)d_which, (const double*)rd.d(), partial, wd.d());
+  GH_HIP(hipGetLastError());
+  if (P > 0) {
+    GH_CHECK(gh_launch_kgrad_final(partial, nwg, P, dgrad, st));
+    GH_CHECK(gh_from_device(grad, dgrad, (size_t)P, st));
+  }
+  if (diagA) {
+    hipLaunchKernelGGL(vecchia_diag_kernel, dim3(v_blocks((size_t)n)), dim3(256), 0, st, (const double*)wd.d(), (const long long*)h->tptr.p,
+                       (const int*)h->trow.p, (const int*)h->tslot.p, n, m, dg.d());
+    GH_HIP(hipGetLastError());
+    GH_CHECK(gh_from_device(diagA, dg.d(), (size_t)n, st));
+  }
+  GH_HIP(hipStreamSynchronize(st));
+  return GH_OK;
+}
+
+extern "C" int gh_vecchia_predict(gh_vecchia* h, gh_kernel* k, const double* r, const double* xs, int64_t m, double* mu, double* var,
+                                  double* cov) {
+  GH_CHECK(v_need(h));
+  if (!k || !r || !xs || !mu || m <= 0 || (var && cov) || m > 0x3fffffffL) { gh_set_error("bad argument to predict"); return GH_ERR_BAD_ARG; }
+  if (k->ndim != h->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
+  GH_CHECK(k->upload());
+  const long n = (long)h->n;
+  hipStream_t st = h->st;
+  GhPooledBuf rd, tmp, al, xsd, sK, sV, part, res, kss;
+  GH_CHECK(rd.ensure((size_t)n * sizeof(double)));
+  GH_CHECK(tmp.ensure((size_t)n * sizeof(double)));
+  GH_CHECK(al.ensure((size_t)n * sizeof(double)));
+  GH_CHECK(gh_to_device(rd.d(), r, (size_t)n, st));
+  GH_CHECK(v_apply_q(h, rd.d(), 1L, tmp.d(), al.d()));
+  const double* xs_dev = xs;
+  if (!gh_is_device_ptr(xs)) {
+    GH_CHECK(xsd.ensure((size_t)m * h->ndim * sizeof(double)));
+    GH_CHECK(gh_to_device(xsd.d(), xs, (size_t)m * h->ndim, st));
+    xs_dev = xsd.d();
+  }
+  // with cov, K(x, xs) and V stay whole for the product: one strip of mp columns over np rows (GhGemm: M, N multiples of 128, K of
+  // 16; the padding is zero).  Without, strips of Ct test points.
+  const bool want_v = var || cov;
+  const long mp = gh_round_up(m, 128), np = cov ? gh_round_up(n, 16) : n;
+  long Ct = mp;
+  if (cov) {
+    const double need = 2.0 * 8.0 * (double)np * (double)mp + 8.0 * (double)mp * (double)mp;
+    if (need > (double)V_COV_BYTES) {
+      gh_set_error("predict: the covariance keeps K(x, xs), V and the m x m result on the device, %.3g bytes for n = %ld, m = %ld, over the "
+                   "budget of %ld; ask for the variance or for fewer test points at a time", need, n, (long)m, (long)V_COV_BYTES);
+      return GH_ERR_NOMEM;
+    }
+  } else {
+    Ct = std::max<long>(1, std::min<long>(V_STRIP_COLS, V_STRIP_BYTES / (16 * n)));
+    Ct = std::min<long>(Ct, m);
+  }
+  const size_t strip_bytes = (size_t)np * Ct * sizeof(double);
+  GH_CHECK(sK.ensure(strip_bytes));
+  if (want_v) GH_CHECK(sV.ensure(strip_bytes));
+  if (cov) GH_CHECK(kss.ensure((size_t)mp * mp * sizeof(double)));
+  const long nchunks = std::min<long>(V_RED_CHUNKS, (n + V_RED_ROWS - 1) / V_RED_ROWS);
+  const long rows_per = (n + nchunks - 1) / nchunks;
+  GH_CHECK(part.ensure((size_t)2 * nchunks * Ct * sizeof(double)));
+  GH_CHECK(res.ensure((size_t)2 * m * sizeof(double)));
+  double* pmu = part.d();
+  double* pvar = pmu + nchunks * Ct;
+  double* dmu = res.d();
+  double* dvar = dmu + m;
+  if (var) GH_CHECK(gh_launch_kdiag(k, xs_dev, xs_dev, m, dvar, st));
+  if (cov) GH_HIP(hipMemsetAsync(sV.p, 0, strip_bytes, st));                  // (rows n .. np of V)
+  for (long j0 = 0; j0 < m; j0 += Ct) {
+    const int cw = (int)std::min<long>(Ct, m - j0);
+    // Kx = K(x, xs_J), np x Ct row-major (columns past cw, rows past n: zero)
+    GH_CHECK(gh_launch_kmat(k, h->x.d(), n, xs_dev + j0 * h->ndim, cw, nullptr, sK.d(), Ct, np, Ct, 0, 0, false, false, st));
+    if (want_v)                                              // V = F^-1/2 (I - B) Kx
+      hipLaunchKernelGGL(vecchia_fwd_kernel, dim3(v_blocks((size_t)n * Ct)), dim3(256), 0, st, (const double*)h->B.d(), (const double*)h->f.d(),
+                         (const int*)h->nbr.p, (const int*)h->cnt.p, n, h->opts.m, (const double*)sK.d(), Ct, Ct, sV.d(), Ct, 2);
+    hipLaunchKernelGGL(vecchia_colred_kernel, dim3((unsigned)((cw + 63) / 64), (unsigned)nchunks), dim3(64), 0, st, (const double*)sK.d(),
+                       var ? (const double*)sV.d() : (const double*)nullptr, Ct, n, rows_per, (const double*)al.d(), cw, pmu, pvar, Ct);
+    hipLaunchKernelGGL(vecchia_colfinal_kernel, dim3((unsigned)((cw + 63) / 64)), dim3(64), 0, st, (const double*)pmu, (const double*)pvar,
+                       nchunks, Ct, cw, dmu + j0, var ? dvar + j0 : (double*)nullptr);
+    GH_HIP(hipGetLastError());
+  }
+  GH_CHECK(gh_from_device(mu, dmu, (size_t)m, st));
+  if (var) GH_CHECK(gh_from_device(var, dvar, (size_t)m, st));
+  if (cov) {
+    // cov = K(xs, xs) - V^T V
+    GH_CHECK(gh_launch_kmat(k, xs_dev, m, xs_dev, m, nullptr, kss.d(), mp, mp, mp, 0, 0, true, false, st));
+    GhGemm g{};
+    g.C = kss.d(); g.ldc = mp; g.A = sV.d(); g.lda = mp; g.B = sV.d(); g.ldb = mp;
+    g.M = mp; g.N = mp; g.K = np; g.alpha = -1.0; g.beta = 1.0; g.a_km = false; g.b_km = false;
+    GH_CHECK(gh_launch_gemm(g, st));
+    GH_HIP(hipMemcpy2DAsync(cov, m * sizeof(double), kss.d(), mp * sizeof(double), m * sizeof(double), m,
+                            gh_is_device_ptr(cov) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+  }
+  GH_HIP(hipStreamSynchronize(st));
+  return GH_OK;
+}

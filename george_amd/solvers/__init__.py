@@ -5,5 +5,6 @@ from .trivial import TrivialSolver
 from .basic import BasicSolver
 from .hodlr import HODLRSolver
 from .multigpu import MultiGPUSolver, MultiGPUHODLRSolver
+from .vecchia import VecchiaSolver
 
-__all__ = ["TrivialSolver", "BasicSolver", "HODLRSolver", "MultiGPUSolver", "MultiGPUHODLRSolver"]
+__all__ = ["TrivialSolver", "BasicSolver", "HODLRSolver", "MultiGPUSolver", "MultiGPUHODLRSolver", "VecchiaSolver"]

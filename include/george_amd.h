@@ -429,6 +429,41 @@ int  gh_hodlr_predict(gh_hodlr* h, gh_kernel* k, const double* r /* n: y - mean 
 int  gh_hodlr_grad(gh_hodlr* h, gh_kernel* k, const uint32_t* which, const double* r,
                    double* grad /* size */, double* alpha /* n or NULL */, double* diagA /* n or NULL */);
 
+/* ------------------------------------------------------------ Vecchia solver
+ * The nearest-neighbour (Vecchia) approximation p(y) ~ prod_i p(y_i | y_c(i)): c(i) holds at most m points among the
+ * predecessors of i in the order the points are given in.  With b_i = K_cc^-1 k_ci and f_i = k_ii - k_ci^T b_i the precision is
+ * Q = (I - B)^T F^-1 (I - B), B strictly lower triangular with the b_i as rows, F = diag(f).  Every predecessor in c(i)
+ * (m >= n - 1) gives the dense answers up to rounding.  O(n m^3) flops, O(n m) memory; no reference counterpart.  Fixed-order
+ * sums throughout: two calls give the same bits.  (george_amd/csrc/gh_vecchia.hip) */
+typedef struct gh_vecchia gh_vecchia;
+typedef struct gh_vecchia_opts {
+  int32_t device;
+  int32_t m;             /* neighbours per point, 1 .. 64 */
+  int32_t reserved[2];
+} gh_vecchia_opts;
+/* GH_ERR_BAD_ARG for m < 1 or m > 64 (host check, before any device is touched) */
+int  gh_vecchia_create(const gh_vecchia_opts* opts, gh_vecchia** out);
+void gh_vecchia_destroy(gh_vecchia* h);
+/* nbr: host array, row i = the neighbours of point i, each -1 (padding, anywhere in the row) or in [0, i), no duplicates in a
+ * row, any order; checked on the host before any launch (GH_ERR_BAD_ARG).  *logdet_out = sum_i log f_i.  A pivot of a K_cc or
+ * an f_i that is not positive and finite: GH_ERR_NOT_PD, gh_vecchia_info() = the lowest such point, and the handle is not
+ * computed. */
+int  gh_vecchia_compute(gh_vecchia* h, gh_kernel* k, const double* x, int64_t n, int32_t ndim, const double* yerr,
+                        const int32_t* nbr /* n*m */, double* logdet_out);
+int64_t gh_vecchia_info(const gh_vecchia* h);     /* 1-based index of the failing point after GH_ERR_NOT_PD, else 0 */
+int  gh_vecchia_solve(gh_vecchia* h, const double* b, int64_t nrhs, double* out);   /* out = Q b; (n, nrhs) row-major */
+int  gh_vecchia_dot_solve(gh_vecchia* h, const double* y, double* out);             /* y^T Q y = sum_i e_i^2 / f_i */
+/* grad[p] = sum_i sum_jk W(i)_jk dk(x_j, x_k)/dtheta_p over the blocks c(i) + {i}, with W(i) the derivative of
+ * log p(y_i | y_c(i)) with respect to the block (parameters not selected by `which`: exactly 0); alpha = Q r;
+ * diagA_j = 2 sum over the blocks that hold j of W_jj.  The layout of gh_chol_grad, and its values when m >= n - 1. */
+int  gh_vecchia_grad(gh_vecchia* h, gh_kernel* k, const uint32_t* which, const double* r,
+                     double* grad /* size */, double* alpha /* n or NULL */, double* diagA /* n or NULL */);
+/* mu = K(xs,x) Q r; var = diag K(xs,xs) - colsumsq(V), cov = K(xs,xs) - V^T V with V = F^-1/2 (I - B) K(x,xs).  var / cov may be
+ * NULL (not both non-NULL); k may differ from the kernel of compute().  Strips of test points sized to a byte budget; cov keeps
+ * K(x,xs), V and the m x m result on the device: GH_ERR_NOMEM when the budget does not hold them. */
+int  gh_vecchia_predict(gh_vecchia* h, gh_kernel* k, const double* r /* n: y - mean */, const double* xs, int64_t m,
+                        double* mu /* m */, double* var /* m or NULL */, double* cov /* m*m or NULL */);
+
 /* --------------------------------------------------- dense solver on several GPUs
  * The BasicSolver protocol of /root/reference/src/george/solvers/basic.py:51-102 (compute, log-determinant,
  * dot_solve, apply_inverse) for ONE process that owns several MI355X: 2-D block-cyclic tiles (tile (I, J)
