@@ -2,7 +2,8 @@
 //
 // p(y) ~ prod_i p(y_i | y_c(i)), c(i) at most m <= 64 predecessors of i.  For every point the block A = K[c + {i}, c + {i}] (i last)
 // is built from the kernel evaluator and factored; with v = L_cc^-1 k_ci:  f_i = k_ii - v^T v (the square of the block factor's last
-// pivot) and b_i = L_cc^-T v.  Q = (I - B)^T F^-1 (I - B).
+// pivot) and b_i = L_cc^-T v.  Q = (I - B)^T F^-1 (I - B).  Local prediction (gh_vecchia_predict_local) puts a test point in the
+// place of point i and its nearest data points in the place of c(i): the same block, mu = v^T L_cc^-1 r_c, var = k** - v^T v.
 //
 // Kernels: one point per 64-thread workgroup (one wavefront), lane s owns conditioning point s.  The point's coordinates, the lower
 // triangle of A (packed by rows) and the evaluator's runtime-indexed temporaries sit in LDS: no kernel here uses scratch memory.
@@ -99,36 +100,38 @@ __device__ __forceinline__ double v_value(const GhFast& fast, const GhNode* prog
   return gh_eval_value(prog, n_nodes, x1, x2, ws);
 }
 
-// Point i: stage its block, build A, factor K_cc (left-looking, lane j owns row j), then v, f and b.  Returns false -- in every
-// lane -- when a pivot of K_cc or f is not positive and finite.  On return: c, this lane's b (lanes < c), f; in LDS the factor
-// of K_cc (rows < c of A), dinv, k_ci and k_ii (row c of A), gi, xs, ye.
-template <bool FAST>
-__device__ __forceinline__ bool v_block(const VArgs& a, const GhFast& fast, const GhNode* prog, long i, const VLds& l, double* ws,
-                                        int lane, int& c_out, double& b_out, double& f_out) {
-  const int c = a.cnt[i], nd = a.nd;
-  c_out = c;
-  __syncthreads();                                          // (the previous point of this workgroup is done with the LDS)
+// The three steps of a block, shared by the likelihood kernels (v_block) and by local prediction (vecchia_local_kernel).
+// Stage: slots s < c take the data points row[s]; slot c -- the block's last row -- takes the point x_last with the error bar
+// ye_last and the index g_last, which only orders the kernel's arguments (the point with the lower index comes first).
+__device__ __forceinline__ void v_stage(const VArgs& a, const int* __restrict__ row, int c, int g_last, const double* __restrict__ x_last,
+                                        double ye_last, const VLds& l, int lane) {
+  const int nd = a.nd;
   for (int s = lane; s <= c; s += VM_MAX) {
-    const int g = s < c ? a.nbr[i * a.m + s] : (int)i;
+    const int g = s < c ? row[s] : g_last;
     l.gi[s] = g;
-    l.ye[s] = a.yerr[g];
+    l.ye[s] = s < c ? a.yerr[g] : ye_last;
   }
   for (int t = lane; t < (c + 1) * nd; t += VM_MAX) {
     const int s = t / nd;
-    const long g = s < c ? a.nbr[i * a.m + s] : i;
-    l.xs[t] = a.x[g * nd + (t - s * nd)];
+    l.xs[t] = s < c ? a.x[(long)row[s] * nd + (t - s * nd)] : x_last[t - s * nd];
   }
-  __syncthreads();
-  const int T = v_tri(c + 1);
-  for (int t = lane; t < T; t += VM_MAX) {
+}
+// Build: the entries t0 <= t < t1 of the packed lower triangle from one kernel, ye^2 added on the diagonal
+template <bool FAST>
+__device__ __forceinline__ void v_build(const GhFast& fast, const GhNode* prog, int n_nodes, const VLds& l, int nd, int t0, int t1,
+                                        double* ws, int lane) {
+  for (int t = t0 + lane; t < t1; t += VM_MAX) {
     int j, k;
     tri_index(t, j, k);
     const bool jlow = l.gi[j] <= l.gi[k];
-    double v = v_value<FAST>(fast, prog, a.n_nodes, &l.xs[(jlow ? j : k) * nd], &l.xs[(jlow ? k : j) * nd], ws);
+    double v = v_value<FAST>(fast, prog, n_nodes, &l.xs[(jlow ? j : k) * nd], &l.xs[(jlow ? k : j) * nd], ws);
     if (j == k) v += l.ye[j] * l.ye[j];
     l.A[t] = v;
   }
-  __syncthreads();
+}
+// Factor: rows < c of A in place, left-looking, lane j owns row j; dinv = 1 / the factor's diagonal.  Returns false -- in every
+// lane -- at a pivot that is not positive and finite.
+__device__ __forceinline__ bool v_factor(const VLds& l, int c, int lane) {
   for (int k = 0; k < c; ++k) {
     double s = 0.0;
     if (lane >= k && lane < c) {
@@ -144,6 +147,23 @@ __device__ __forceinline__ bool v_block(const VArgs& a, const GhFast& fast, cons
     else if (lane > k && lane < c) l.A[v_tri(lane) + k] = s * inv;
     __syncthreads();
   }
+  return true;
+}
+
+// Point i: stage its block, build A, factor K_cc, then v, f and b.  Returns false -- in every lane -- when a pivot of K_cc or f
+// is not positive and finite.  On return: c, this lane's b (lanes < c), f; in LDS the factor of K_cc (rows < c of A), dinv,
+// k_ci and k_ii (row c of A), gi, xs, ye.
+template <bool FAST>
+__device__ __forceinline__ bool v_block(const VArgs& a, const GhFast& fast, const GhNode* prog, long i, const VLds& l, double* ws,
+                                        int lane, int& c_out, double& b_out, double& f_out) {
+  const int c = a.cnt[i];
+  c_out = c;
+  __syncthreads();                                          // (the previous point of this workgroup is done with the LDS)
+  v_stage(a, a.nbr + i * a.m, c, (int)i, a.x + i * a.nd, a.yerr[i], l, lane);
+  __syncthreads();
+  v_build<FAST>(fast, prog, a.n_nodes, l, a.nd, 0, v_tri(c + 1), ws, lane);
+  __syncthreads();
+  if (!v_factor(l, c, lane)) return false;
   const double kci = lane < c ? l.A[v_tri(c) + lane] : 0.0;
   const double v = v_fwd(l.A, l.dinv, c, lane, kci);
   const double f = l.A[v_tri(c) + c] - v_bcast(wave_sum(lane < c ? v * v : 0.0), 0);
@@ -169,6 +189,44 @@ __global__ __launch_bounds__(VM_MAX) void vecchia_factor_kernel(VArgs a, GhFast 
     f[i] = ok ? fi : 1.0;
     logf[i] = ok ? log(fi) : 0.0;
     if (!ok) atomicMin(fail, (int)i);                       // the lowest failing point
+  }
+}
+
+// Local prediction: test point t conditioned on the c data points of its row of the query table (valid entries first), one
+// test point per workgroup.  The test point is the block's last row: rows < c are K_cc + yerr^2 from the data kernel, row c is
+// k_c = k(x_j, t) and k** = k(t, t) from the cross kernel (its index INT_MAX puts the data point first).  With v = L^-1 k_c and
+// w = L^-1 r_c:  mu = v^T w,  var = k** - v^T v.  c == 0: mu = 0, var = k**.  A pivot that is not positive and finite, or a
+// variance that is not finite, records the test point in *fail (the lowest one) and writes zeros.
+template <bool FAST>
+__global__ __launch_bounds__(VM_MAX) void vecchia_local_kernel(VArgs a, GhFast fast_d, const GhNode* __restrict__ prog_d, GhFast fast_c,
+                                                               const GhNode* __restrict__ prog_c, int n_nodes_c,
+                                                               const double* __restrict__ r, const double* __restrict__ xs,
+                                                               const int* __restrict__ qtab, const int* __restrict__ qcnt, int mq,
+                                                               double* __restrict__ mu, double* __restrict__ var, int* fail) {
+  extern __shared__ __attribute__((aligned(16))) double vsm[];
+  const int lane = threadIdx.x, nd = a.nd;
+  const VLds l = v_carve(vsm, mq, nd, FAST ? 0 : VWS);
+  double* const ws = FAST ? nullptr : l.gl + lane * VWS;
+  const long t = blockIdx.x;
+  const int c = qcnt[t];
+  v_stage(a, qtab + t * mq, c, INT_MAX, xs + t * nd, 0.0, l, lane);
+  __syncthreads();
+  v_build<FAST>(fast_d, prog_d, a.n_nodes, l, nd, 0, v_tri(c), ws, lane);
+  v_build<FAST>(fast_c, prog_c, n_nodes_c, l, nd, v_tri(c), v_tri(c + 1), ws, lane);
+  __syncthreads();
+  bool ok = v_factor(l, c, lane);
+  double m_t = 0.0, v_t = 0.0;
+  if (ok) {
+    const double v = v_fwd(l.A, l.dinv, c, lane, lane < c ? l.A[v_tri(c) + lane] : 0.0);
+    const double w = v_fwd(l.A, l.dinv, c, lane, lane < c ? r[l.gi[lane]] : 0.0);
+    m_t = wave_sum(lane < c ? v * w : 0.0);                 // (lane 0 has the sums)
+    v_t = l.A[v_tri(c) + c] - wave_sum(lane < c ? v * v : 0.0);
+  }
+  if (lane == 0) {
+    ok = ok && isfinite(v_t);
+    mu[t] = ok ? m_t : 0.0;
+    if (var) var[t] = ok ? v_t : 0.0;
+    if (!ok) atomicMin(fail, (int)t);
   }
 }
 
@@ -607,6 +665,83 @@ extern "C" int gh_vecchia_predict(gh_vecchia* h, gh_kernel* k, const double* r, 
     GH_HIP(hipMemcpy2DAsync(cov, m * sizeof(double), kss.d(), mp * sizeof(double), m * sizeof(double), m,
                             gh_is_device_ptr(cov) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
   }
+  GH_HIP(hipStreamSynchronize(st));
+  return GH_OK;
+}
+
+// The query table of predict_local checked and compacted on the host, as v_index does with compute's: every entry of a row is -1
+// or in [0, n), no entry twice in a row.  tab: valid entries first (their order kept), then -1; cnt: per row.
+static int v_query_index(const int32_t* qnbr, int64_t M, int mq, int64_t n, std::vector<int>& tab, std::vector<int>& cnt) {
+  tab.assign((size_t)M * mq, -1);
+  cnt.assign((size_t)M, 0);
+  std::vector<int64_t> seen((size_t)n, -1);
+  for (int64_t t = 0; t < M; ++t) {
+    int c = 0;
+    for (int s = 0; s < mq; ++s) {
+      const int32_t j = qnbr[t * mq + s];
+      if (j == -1) continue;
+      if (j < 0 || j >= n) { gh_set_error("query table: row %lld holds %d, which is not one of the %lld data points", (long long)t, (int)j, (long long)n); return GH_ERR_BAD_ARG; }
+      if (seen[j] == t) { gh_set_error("query table: row %lld holds %d twice", (long long)t, (int)j); return GH_ERR_BAD_ARG; }
+      seen[j] = t;
+      tab[(size_t)t * mq + c++] = j;
+    }
+    cnt[(size_t)t] = c;
+  }
+  return GH_OK;
+}
+
+extern "C" int gh_vecchia_predict_local(gh_vecchia* h, gh_kernel* k_data, gh_kernel* k_cross, const double* r, const double* xs, int64_t M,
+                                        const int32_t* qnbr, int32_t mq, double* mu, double* var) {
+  GH_CHECK(v_need(h));
+  if (!k_data || !k_cross || !r || !xs || !qnbr || !mu || M <= 0 || M > 0x3fffffffL) { gh_set_error("bad argument to predict_local"); return GH_ERR_BAD_ARG; }
+  if (mq < 1 || mq > VM_MAX) { gh_set_error("predict_local takes 1 <= mq <= %d neighbours per test point, not %d", VM_MAX, (int)mq); return GH_ERR_BAD_ARG; }
+  if (k_data->ndim != h->ndim || k_cross->ndim != h->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
+  h->info = 0;
+  const long n = (long)h->n;
+  std::vector<int> tab, cnt;
+  GH_CHECK(v_query_index(qnbr, M, mq, n, tab, cnt));        // (before any launch: a bad index would be an out-of-bounds read)
+  GH_CHECK(k_data->upload());
+  if (k_cross != k_data) GH_CHECK(k_cross->upload());
+  hipStream_t st = h->st;
+  GhPooledBuf rd, xsd, qt, qc, res;
+  GH_CHECK(rd.ensure((size_t)n * sizeof(double)));
+  GH_CHECK(gh_to_device(rd.d(), r, (size_t)n, st));
+  const double* xs_dev = xs;
+  if (!gh_is_device_ptr(xs)) {
+    GH_CHECK(xsd.ensure((size_t)M * h->ndim * sizeof(double)));
+    GH_CHECK(gh_to_device(xsd.d(), xs, (size_t)M * h->ndim, st));
+    xs_dev = xsd.d();
+  }
+  GH_CHECK(v_upload(qt, tab, st));
+  GH_CHECK(v_upload(qc, cnt, st));
+  GH_CHECK(res.ensure((size_t)2 * M * sizeof(double)));
+  GH_CHECK(h->scal.ensure(2 * sizeof(double)));
+  double* dmu = res.d();
+  double* dvar = var ? dmu + M : nullptr;
+  int* fail = (int*)(h->scal.d() + 1);
+  GH_HIP(hipMemsetD32Async((hipDeviceptr_t)fail, INT_MAX, 1, st));
+  VArgs a = v_args(h, k_data);
+  a.m = mq;
+  // the interpreter evaluates every kernel, the fast form only some: one instantiation for "both fast", one for the rest
+  const bool fast = k_data->fast.ok != 0 && k_cross->fast.ok != 0;
+  const size_t lds = v_lds_doubles(mq, h->ndim, fast ? 0 : VWS) * sizeof(double);        // (at most 37 KB: mq = 64, 16 dimensions)
+  if (fast) hipLaunchKernelGGL(vecchia_local_kernel<true>, dim3((unsigned)M), dim3(VM_MAX), lds, st, a, k_data->fast, (const GhNode*)k_data->d_nodes,
+                               k_cross->fast, (const GhNode*)k_cross->d_nodes, (int)k_cross->nodes.size(), (const double*)rd.d(), xs_dev,
+                               (const int*)qt.p, (const int*)qc.p, (int)mq, dmu, dvar, fail);
+  else hipLaunchKernelGGL(vecchia_local_kernel<false>, dim3((unsigned)M), dim3(VM_MAX), lds, st, a, k_data->fast, (const GhNode*)k_data->d_nodes,
+                          k_cross->fast, (const GhNode*)k_cross->d_nodes, (int)k_cross->nodes.size(), (const double*)rd.d(), xs_dev,
+                          (const int*)qt.p, (const int*)qc.p, (int)mq, dmu, dvar, fail);
+  GH_HIP(hipGetLastError());
+  int failed = INT_MAX;
+  GH_HIP(hipMemcpyAsync(&failed, fail, sizeof(int), hipMemcpyDeviceToHost, st));
+  GH_HIP(hipStreamSynchronize(st));                         // (the host tables end with this call)
+  if (failed != INT_MAX) {
+    h->info = (int64_t)failed + 1;
+    gh_set_error("the conditional of test point %lld is not positive definite", (long long)failed);
+    return GH_ERR_NOT_PD;
+  }
+  GH_CHECK(gh_from_device(mu, dmu, (size_t)M, st));
+  if (var) GH_CHECK(gh_from_device(var, dvar, (size_t)M, st));
   GH_HIP(hipStreamSynchronize(st));
   return GH_OK;
 }

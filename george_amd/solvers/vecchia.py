@@ -7,7 +7,14 @@ The joint density is replaced by a product of conditionals, ``p(y) ~ prod_i p(y_
 in the conditioning set (``m >= N - 1``) it is the dense likelihood up to rounding; smooth kernels with little noise need a
 larger ``m`` than rough or noisy ones.  No reference counterpart.  The device side is ``george_amd/csrc/gh_vecchia.hip``.
 
-Not built: ordering strategies beyond the three of ``order=`` (max-min and the like), and ``apply_sqrt``.
+Two predictors.  ``predict`` conditions every test point on all N data points through ``Q`` (the default, ``predict="global"``):
+O(N M) kernel values, and a variance ``k** - K* Q K*^T`` that is only as good as ``Q`` -- it goes negative when ``m`` is too
+small for the kernel.  ``predict_local`` (``predict="local"``) conditions each test point on its ``m`` nearest data points
+alone: a proper conditional variance, O(M m^3) whatever N, no joint covariance between test points.  Its neighbour search
+(:func:`vecchia_query_neighbors`) runs on the host and dominates the call at large M.
+
+Not built: ordering strategies beyond the three of ``order=`` (max-min and the like), ``apply_sqrt``, a device-side
+neighbour search, and a joint covariance between the test points of local prediction.
 """
 import atexit
 import ctypes as C
@@ -18,29 +25,37 @@ import numpy as np
 from .. import _native as N
 from .protocol import NativeSolver, rhs_matrix, rhs_vector
 
-__all__ = ["VecchiaSolver", "vecchia_neighbors"]
+__all__ = ["VecchiaSolver", "vecchia_neighbors", "vecchia_query_neighbors"]
 
 M_MAX = 64
 
 
-def _nearest_predecessors(x, rows, cand, m):
-    """For each row ``i`` of ``rows`` the ``min(#, m)`` nearest of its candidates ``cand`` (len(rows), k; entries >= i or
-    >= len(x) do not count) by squared Euclidean distance, ties to the lower index: ``(table (len(rows), m) sorted
-    ascending and padded with -1, the m-th smallest distance or inf)``."""
+def _nearest_candidates(x, q, limit, cand, m):
+    """For each query point ``q[i]`` the ``min(#, m)`` nearest of its candidates ``cand`` (len(q), k; entries >= limit[i] do
+    not count) among the points ``x`` by squared Euclidean distance, ties to the lower index: ``(table (len(q), m) sorted
+    ascending and padded with -1, the m-th smallest distance or inf)``.  ``limit[i] = i`` ranks predecessors, ``len(x)``
+    every point."""
     n = len(x)
-    valid = cand < rows[:, None]
+    valid = cand < limit[:, None]
     safe = np.where(valid, cand, 0)
-    d2 = ((x[safe] - x[rows][:, None, :]) ** 2).sum(axis=-1)
+    d2 = ((x[safe] - q[:, None, :]) ** 2).sum(axis=-1)
     d2 = np.where(valid, d2, np.inf)
     key = np.where(valid, cand, n)
     pick = np.lexsort((key, d2), axis=1)[:, :m]                     # by distance, then by index
     sel = np.take_along_axis(key, pick, axis=1)
     dm = np.take_along_axis(d2, pick, axis=1)
     if sel.shape[1] < m:
-        sel = np.concatenate([sel, np.full((len(rows), m - sel.shape[1]), n)], axis=1)
-        dm = np.concatenate([dm, np.full((len(rows), m - dm.shape[1]), np.inf)], axis=1)
+        sel = np.concatenate([sel, np.full((len(q), m - sel.shape[1]), n)], axis=1)
+        dm = np.concatenate([dm, np.full((len(q), m - dm.shape[1]), np.inf)], axis=1)
     sel = np.sort(sel, axis=1)                                      # (the fill value n sorts last)
     return np.where(sel >= n, -1, sel).astype(np.int32), dm[:, m - 1]
+
+
+def _certain(dm, dist, k, n):
+    """Is the choice among the ``k`` points a tree query returned certain?  Every point the query left out is at least
+    ``dist[:, -1]`` away: yes when the m-th chosen one (squared distance ``dm``) is nearer than that by more than the two
+    routes' rounding, or when the query returned every point."""
+    return (np.sqrt(dm) < dist[:, -1] * (1.0 - 1e-9)) if k < n else np.ones(len(dm), dtype=bool)
 
 
 def vecchia_neighbors(x, m):
@@ -71,7 +86,7 @@ def vecchia_neighbors(x, m):
     # the first rows directly: every predecessor is a candidate
     n0 = min(n, 4 * m + 64)
     rows = np.arange(n0)
-    table[:n0] = _nearest_predecessors(x, rows, np.broadcast_to(np.arange(n0)[None, :], (n0, n0)), m)[0]
+    table[:n0] = _nearest_candidates(x, x[rows], rows, np.broadcast_to(np.arange(n0)[None, :], (n0, n0)), m)[0]
     if n0 == n:
         return table
     from scipy.spatial import cKDTree
@@ -85,14 +100,101 @@ def vecchia_neighbors(x, m):
             dist, cand = tree.query(x[rows], k=k)
             if k == 1:
                 dist, cand = dist[:, None], cand[:, None]
-            tab, dm = _nearest_predecessors(x, rows, cand, m)
-            # every point the query left out is at least dist[:, -1] away: the choice is certain when the m-th chosen one is
-            # nearer than that by more than the two routes' rounding (or when the query returned every point)
-            sure = (np.sqrt(dm) < dist[:, -1] * (1.0 - 1e-9)) if k < n else np.ones(len(rows), dtype=bool)
+            tab, dm = _nearest_candidates(x, x[rows], rows, cand, m)
+            sure = _certain(dm, dist, k, n)
             table[rows[sure]] = tab[sure]
             again.append(rows[~sure])
         todo, k = np.concatenate(again), min(n, 2 * k)
     return table
+
+
+# The tree of a data set is built once and kept, keyed by a digest of the inputs, the way VecchiaSolver._TABLES keeps tables.
+_TREES = []
+_TREES_MAX = 2
+
+
+def _tree(x):
+    key = (x.shape, hashlib.blake2b(memoryview(np.ascontiguousarray(x)).cast("B"), digest_size=16).digest())
+    for k, tree in _TREES:
+        if k == key:
+            return tree
+    from scipy.spatial import cKDTree
+    tree = cKDTree(x)
+    _TREES.append((key, tree))
+    del _TREES[:-_TREES_MAX]
+    return tree
+
+
+def vecchia_query_neighbors(x, t, m):
+    """The conditioning sets of local prediction: row ``c`` holds the ``min(N, m)`` data points ``x`` nearest to the test
+    point ``t[c]`` under the Euclidean distance on the inputs as given, ties going to the lower index, sorted ascending and
+    padded with -1.  (M, m) int32.
+
+    Exact for every input: it equals the brute-force search.  Strictly increasing 1-D ``x`` goes through ``searchsorted``
+    and a window of ``2 m`` points around the test point; everything else goes through ``scipy.spatial.cKDTree`` (built
+    once per data set and kept) with a query size that grows until the ``m`` nearest points are certain, and a direct
+    search when N is small.  The search runs on the host, O(M m log N): for large M it takes longer than the device call
+    it feeds."""
+    x = np.asarray(x, dtype=np.float64)
+    t = np.asarray(t, dtype=np.float64)
+    if x.ndim == 1:
+        x = x[:, None]
+    if t.ndim == 1:
+        t = t[:, None]
+    if x.ndim != 2 or t.ndim != 2 or x.shape[1] != t.shape[1]:
+        raise ValueError("x must be (nsamples, ndim) and t (ntest, ndim)")
+    m = int(m)
+    if m < 1:
+        raise ValueError("m must be at least 1")
+    n, nt = len(x), len(t)
+    table = np.full((nt, m), -1, dtype=np.int32)
+    if n == 0 or nt == 0:
+        return table
+    limit = np.full(nt, n)
+    if x.shape[1] == 1 and np.all(np.diff(x[:, 0]) > 0):
+        # the m nearest points of a sorted line are consecutive and lie among the m before and the m after the test point
+        step = max(1, (1 << 22) // (2 * m))
+        for s in range(0, nt, step):
+            rows = slice(s, s + step)
+            cand = np.searchsorted(x[:, 0], t[rows, 0])[:, None] + np.arange(-m, m)[None, :]
+            cand = np.where((cand >= 0) & (cand < n), cand, n)
+            table[rows] = _nearest_candidates(x, t[rows], limit[rows], cand, m)[0]
+        return table
+    if n <= 4 * m + 64:                                                     # directly: every point is a candidate
+        step = max(1, (1 << 22) // (n * x.shape[1]))
+        for s in range(0, nt, step):
+            rows = slice(s, s + step)
+            table[rows] = _nearest_candidates(x, t[rows], limit[rows], np.broadcast_to(np.arange(n)[None, :], (len(t[rows]), n)), m)[0]
+        return table
+    tree = _tree(x)
+    todo, k = np.arange(nt), min(n, m + 1)
+    while len(todo):
+        again = []
+        step = max(1, (1 << 22) // (k * x.shape[1]))                        # rows per query: the candidates' coordinates in 32 MB
+        for s in range(0, len(todo), step):
+            rows = todo[s:s + step]
+            dist, cand = tree.query(t[rows], k=k)
+            if k == 1:
+                dist, cand = dist[:, None], cand[:, None]
+            tab, dm = _nearest_candidates(x, t[rows], limit[rows], cand, m)
+            sure = _certain(dm, dist, k, n)
+            table[rows[sure]] = tab[sure]
+            again.append(rows[~sure])
+        todo, k = np.concatenate(again), min(n, 2 * k)
+    return table
+
+
+def _check_query_neighbors(nbr, nt, m, n):
+    """the (nt, m) query table as contiguous int32: every entry is -1 or in [0, n), none twice in a row"""
+    nbr = np.asarray(nbr)
+    if nbr.shape != (nt, m) or nbr.dtype.kind not in "iu":
+        raise ValueError("neighbors must be an integer table of shape ({0}, {1})".format(nt, m))
+    if np.any(nbr < -1) or np.any(nbr >= n):
+        raise ValueError("neighbors: every entry must be -1 or one of the data points 0 .. {0}".format(n - 1))
+    s = np.sort(nbr, axis=1)
+    if np.any((s[:, 1:] == s[:, :-1]) & (s[:, 1:] >= 0)):
+        raise ValueError("neighbors: an entry appears twice in a row")
+    return np.ascontiguousarray(nbr, dtype=np.int32)
 
 
 def _check_neighbors(nbr, n, m):
@@ -111,26 +213,32 @@ def _check_neighbors(nbr, n, m):
 
 
 class VecchiaSolver(NativeSolver):
-    """``VecchiaSolver(kernel, m=32, order=None, neighbors=None, device=0)``.
+    """``VecchiaSolver(kernel, m=32, order=None, neighbors=None, device=0, predict="global")``.
 
     ``m``: neighbours per point, 1 .. 64.  ``order``: ``None`` (the caller's order), ``"coordinate"`` (a stable argsort of
     the first input column) or a permutation array (solver position -> caller's index); the solver permutes its inputs on
     the way in and un-permutes ``alpha``, ``diagA`` and solve results on the way out.  ``neighbors``: ``None``
     (:func:`vecchia_neighbors` of the ordered inputs) or an (N, m) integer table IN SOLVER ORDER, padded with -1; entries
-    need not be sorted."""
+    need not be sorted.  ``predict``: what :meth:`predict` -- and with it ``GP.predict`` -- computes: ``"global"``, every
+    test point conditioned on all data points through ``Q``, or ``"local"``, :meth:`predict_local`."""
 
-    def __init__(self, kernel, m=32, order=None, neighbors=None, device=0):
+    def __init__(self, kernel, m=32, order=None, neighbors=None, device=0, predict="global"):
         m = int(m)
         if m < 1 or m > M_MAX:
             raise ValueError("VecchiaSolver: 1 <= m <= {0}, not {1}".format(M_MAX, m))
         if isinstance(order, str) and order != "coordinate":
             raise ValueError("VecchiaSolver: order is None, 'coordinate' or a permutation")
+        if predict not in ("global", "local"):
+            raise ValueError("VecchiaSolver: predict is 'global' or 'local'")
         self.m = m
         self.order = order
         self.neighbors = neighbors
+        self.predict_mode = predict
         self.failed_point = None
+        self.failed_test_point = None
         self._vopts = dict(device=int(device))
         self._perm = None
+        self._xo = None                                     # the ordered host inputs of compute(): what predict_local searches
         super(VecchiaSolver, self).__init__(kernel)
 
     # The default table depends on the ordered inputs and m only, and GP makes a new solver for every compute (one per iterate
@@ -203,6 +311,7 @@ class VecchiaSolver(NativeSolver):
     def __getstate__(self):
         state = super(VecchiaSolver, self).__getstate__()
         state["_perm"] = None
+        state["_xo"] = None
         return state
 
     def _permutation(self, x):
@@ -220,13 +329,13 @@ class VecchiaSolver(NativeSolver):
     def compute(self, x, yerr):
         x, yerr, _ = self._check_inputs(x, yerr)
         n = len(x)
-        self.failed_point = None
+        self.failed_point = self.failed_test_point = None
         perm = self._permutation(x)
         if perm is not None:
             x, yerr = np.ascontiguousarray(x[perm]), np.ascontiguousarray(yerr[perm])
         nbr = self._default_table(x) if self.neighbors is None else _check_neighbors(self.neighbors, n, self.m)
         logdet = C.c_double(0.0)
-        self._perm, self._n = perm, n
+        self._perm, self._n, self._xo = perm, n, x
 
         def run(h):
             rc = N.lib.gh_vecchia_compute(h, self._dk.handle, N.ptr(x), n, x.shape[1], N.ptr(yerr), N.ptr(nbr), C.byref(logdet))
@@ -299,7 +408,16 @@ class VecchiaSolver(NativeSolver):
 
     def predict(self, kernel, r, xs, return_var=False, return_cov=False):
         """``K* Q r`` and (optionally) the diagonal or the whole of ``K** - K* Q K*^T``, in strips of test points.  The
-        covariance keeps two N x M blocks and the M x M result on the device and raises ``MemoryError`` over its budget."""
+        covariance keeps two N x M blocks and the M x M result on the device and raises ``MemoryError`` over its budget.
+
+        With ``predict="local"`` this is :meth:`predict_local` with its defaults; a covariance is then a ``ValueError``
+        (and so is ``GP.sample_conditional``, which asks for one)."""
+        if self.predict_mode == "local":
+            if return_cov and not return_var:
+                raise ValueError("VecchiaSolver(predict='local') has no covariance between test points: they are conditionally "
+                                 "independent given their neighbours; ask for return_var=True or return_cov=False")
+            mu, var = self.predict_local(kernel, r, xs, return_var=return_var)
+            return mu, var, None
         h = self._need()
         dk = self._kernel_for(kernel)
         r, xs = self._in(rhs_vector(r, self._n)), N.as_f64(xs)
@@ -312,6 +430,46 @@ class VecchiaSolver(NativeSolver):
         if m > 0:
             N.check(N.lib.gh_vecchia_predict(h, dk.handle, N.ptr(r), N.ptr(xs), m, N.ptr(mu), N.ptr(var), N.ptr(cov)))
         return mu, var, cov
+
+    def predict_local(self, kernel, r, xs, return_var=False, neighbors=None, m=None):
+        """Nearest-neighbour prediction: test point ``c`` conditioned on the data points of row ``c`` of ``neighbors`` alone,
+        ``mu = k_c^T (K_cc + yerr^2)^-1 r_c`` and ``var = k** - k_c^T (K_cc + yerr^2)^-1 k_c``.  Returns ``(mu, var | None)``.
+
+        ``var`` is a proper conditional variance: positive, never below the dense one, never above ``k**``.  One Cholesky of at
+        most ``m x m`` per test point, O(M m^3) whatever N.  ``K_cc`` comes from the solver's kernel as of ``compute``, ``k_c``
+        and ``k**`` from ``kernel`` (a component of it, for instance).  ``m``: 1 .. 64, the solver's by default.
+        ``neighbors``: ``None`` (:func:`vecchia_query_neighbors` of the solver's ordered inputs, a host search that dominates
+        the call at large M) or an (M, m) integer table in the CALLER's point numbering, padded with -1 anywhere, entries in
+        any order; a row without entries gives ``mu = 0``, ``var = k**``.  A block that is not positive definite raises
+        ``numpy.linalg.LinAlgError`` with ``failed_test_point`` set; the solver stays computed."""
+        m = self.m if m is None else int(m)
+        if m < 1 or m > M_MAX:
+            raise ValueError("predict_local: 1 <= m <= {0}, not {1}".format(M_MAX, m))
+        h = self._need()
+        dk = self._kernel_for(kernel)
+        r, xs = self._in(rhs_vector(r, self._n)), N.as_f64(xs)
+        if xs.ndim == 1:
+            xs = xs[:, None]
+        if xs.ndim != 2 or xs.shape[1] != self._xo.shape[1]:
+            raise ValueError("xs must be (ntest, {0})".format(self._xo.shape[1]))
+        nt = len(xs)
+        if neighbors is None:
+            nbr = vecchia_query_neighbors(self._xo, xs, m)
+        else:
+            nbr = _check_query_neighbors(neighbors, nt, m, self._n)
+            if self._perm is not None:                      # caller's index -> solver position
+                inv = np.empty(self._n, dtype=np.int32)
+                inv[self._perm] = np.arange(self._n, dtype=np.int32)
+                nbr = np.ascontiguousarray(np.where(nbr >= 0, inv[nbr], -1), dtype=np.int32)
+        self.failed_test_point = None
+        mu = np.empty(nt)
+        var = np.empty(nt) if return_var else None
+        if nt > 0:
+            rc = N.lib.gh_vecchia_predict_local(h, self._dk.handle, dk.handle, N.ptr(r), N.ptr(xs), nt, N.ptr(nbr), m, N.ptr(mu), N.ptr(var))
+            if rc == N.GH_ERR_NOT_PD:
+                self.failed_test_point = int(N.lib.gh_vecchia_info(h)) - 1
+            N.check(rc)
+        return mu, var
 
 
 atexit.register(VecchiaSolver.release_pool)

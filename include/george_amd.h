@@ -450,7 +450,7 @@ void gh_vecchia_destroy(gh_vecchia* h);
  * computed. */
 int  gh_vecchia_compute(gh_vecchia* h, gh_kernel* k, const double* x, int64_t n, int32_t ndim, const double* yerr,
                         const int32_t* nbr /* n*m */, double* logdet_out);
-int64_t gh_vecchia_info(const gh_vecchia* h);     /* 1-based index of the failing point after GH_ERR_NOT_PD, else 0 */
+int64_t gh_vecchia_info(const gh_vecchia* h);     /* 1-based index of the failing (test) point after GH_ERR_NOT_PD, else 0 */
 int  gh_vecchia_solve(gh_vecchia* h, const double* b, int64_t nrhs, double* out);   /* out = Q b; (n, nrhs) row-major */
 int  gh_vecchia_dot_solve(gh_vecchia* h, const double* y, double* out);             /* y^T Q y = sum_i e_i^2 / f_i */
 /* grad[p] = sum_i sum_jk W(i)_jk dk(x_j, x_k)/dtheta_p over the blocks c(i) + {i}, with W(i) the derivative of
@@ -463,6 +463,19 @@ int  gh_vecchia_grad(gh_vecchia* h, gh_kernel* k, const uint32_t* which, const d
  * K(x,xs), V and the m x m result on the device: GH_ERR_NOMEM when the budget does not hold them. */
 int  gh_vecchia_predict(gh_vecchia* h, gh_kernel* k, const double* r /* n: y - mean */, const double* xs, int64_t m,
                         double* mu /* m */, double* var /* m or NULL */, double* cov /* m*m or NULL */);
+/* Local (nearest-neighbour) prediction: test point c is conditioned on the data points of row c of qnbr alone,
+ *   mu = k_c^T (K_cc + yerr^2)^-1 r_c,   var = k** - k_c^T (K_cc + yerr^2)^-1 k_c,
+ * a proper conditional variance; one Cholesky of at most 64 x 64 per test point, O(M mq^3) whatever n, no n-sized work space.
+ * x and yerr are the handle's copies from compute().  qnbr: host array, each entry -1 (padding, anywhere in the row) or in
+ * [0, n), no duplicates in a row, any order; checked on the host before any launch (GH_ERR_BAD_ARG).  1 <= mq <= 64,
+ * independent of the handle's m.  A row without a valid entry gives mu = 0, var = k**.  k_data builds K_cc (the lower data
+ * index is the first argument), k_cross builds k_c = k(x_j, t) and k** = k(t, t); they may be the same object; a dimension
+ * mismatch on either is GH_ERR_DIM.  A pivot that is not positive and finite or a variance that is not finite: GH_ERR_NOT_PD,
+ * gh_vecchia_info() = the lowest such test point, the handle stays computed and no output is defined.  A variance that rounds
+ * to a tiny negative value is returned as computed.  A test point's result does not depend on the other test points. */
+int  gh_vecchia_predict_local(gh_vecchia* h, gh_kernel* k_data, gh_kernel* k_cross, const double* r /* n: y - mean */,
+                              const double* xs, int64_t M, const int32_t* qnbr /* M*mq */, int32_t mq,
+                              double* mu /* M */, double* var /* M or NULL */);
 
 /* --------------------------------------------------- dense solver on several GPUs
  * The BasicSolver protocol of /root/reference/src/george/solvers/basic.py:51-102 (compute, log-determinant,
