@@ -204,6 +204,8 @@ SIGNATURES = {
     "gh_vecchia_grad": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _dp, _dp]),
     "gh_vecchia_predict": (C.c_int, [_vp, _vp, _dp, _dp, _i64, _dp, _dp, _dp]),
     "gh_vecchia_predict_local": (C.c_int, [_vp, _vp, _vp, _dp, _dp, _i64, _dp, _i32, _dp, _dp]),
+    "gh_vecchia_search": (C.c_int, [_i32, _dp, _i64, _i32, _dp, _i64, _dp, _i32, _i32, _dp]),
+    "gh_vecchia_predict_local_search": (C.c_int, [_vp, _vp, _vp, _dp, _dp, _i64, _i32, _i32, _dp, _dp, _dp]),
     "gh_mgpu_create": (C.c_int, [C.POINTER(gh_mgpu_opts), C.POINTER(_vp)]),
     "gh_mgpu_destroy": (None, [_vp]),
     "gh_mgpu_compute": (C.c_int, [_vp, _vp, _dp, _i64, _i32, _dp, C.POINTER(C.c_double)]),

@@ -16,8 +16,8 @@
 #include <vector>
 #include "gh_common.h"
 #include "gh_device_util.h"
+#include "gh_vecchia_impl.h"
 
-#define VM_MAX 64                       // lanes of the workgroup = the cap on m
 #define VWS (GH_EVAL_WS + 1)            // the evaluator's work space per lane, an odd pitch in doubles
 #define V_GRAD_WGS 4096                 // workgroups of the gradient kernel (each walks points blockIdx.x, + gridDim.x, ..)
 #define V_GRAD_LDS (96 * 1024)
@@ -27,27 +27,6 @@
 #define V_RED_ROWS 128                  // rows per chunk of the column reduction (at most V_RED_CHUNKS chunks)
 #define V_RED_CHUNKS 2048
 
-struct gh_vecchia {
-  gh_vecchia_opts opts;
-  hipStream_t st = nullptr;
-  bool shared_stream = false;
-  int64_t n = 0;
-  int ndim = 0;
-  bool computed = false;
-  int64_t info = 0;
-  double logdet = 0.0;
-  // x, yerr, the compacted neighbour table (valid entries first) and its row counts, B (n, m), f, and the transposed index: the
-  // entries (row, slot) of B in column j are tptr[j] .. tptr[j + 1], rows ascending.  One stream: st.
-  GhPooledBuf x, yerr, nbr, cnt, B, f, tptr, trow, tslot, w1, scal;
-  // the caller's table of the last compute(): the same table again (an optimiser moves the hyper-parameters, not the points) is
-  // neither checked nor indexed nor uploaded a second time
-  std::vector<int32_t> nbr_seen;
-};
-
-struct VArgs {
-  const double* x; const double* yerr; const int* nbr; const int* cnt;
-  long n; int m, nd, n_nodes;
-};
 // the workgroup's LDS, in doubles from a 16-byte aligned base; gp = doubles per lane of the evaluator's area (0: none)
 struct VLds {
   double *xs, *ye, *A, *dinv, *uv, *zv, *wl, *gl; int* gi;
@@ -449,6 +428,9 @@ extern "C" int gh_vecchia_compute(gh_vecchia* h, gh_kernel* k, const double* x, 
   h->info = 0;
   if (ndim != k->ndim || ndim < 1 || ndim > GH_MAX_NDIM) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
   const int m = h->opts.m;
+  if (h->grid.valid && !(h->n == n && h->ndim == ndim && !gh_is_device_ptr(x) &&
+                         memcmp(h->grid.x_seen.data(), x, (size_t)n * ndim * sizeof(double)) == 0))
+    h->grid.valid = false;                                  // (other points: the next search builds its grid again)
   const bool same_table = h->n == n && h->nbr_seen.size() == (size_t)n * m && memcmp(h->nbr_seen.data(), nbr, (size_t)n * m * sizeof(int32_t)) == 0;
   std::vector<int> tab, cnt, trow, tslot;
   std::vector<long long> tptr;
@@ -690,30 +672,35 @@ static int v_query_index(const int32_t* qnbr, int64_t M, int mq, int64_t n, std:
   return GH_OK;
 }
 
-extern "C" int gh_vecchia_predict_local(gh_vecchia* h, gh_kernel* k_data, gh_kernel* k_cross, const double* r, const double* xs, int64_t M,
-                                        const int32_t* qnbr, int32_t mq, double* mu, double* var) {
+// What the two local predictions share.  Head: the argument checks, and r and xs on the device.
+static int v_local_begin(gh_vecchia* h, gh_kernel* k_data, gh_kernel* k_cross, const double* r, const double* xs, int64_t M, int32_t mq,
+                         const double* mu, const void* table) {
   GH_CHECK(v_need(h));
-  if (!k_data || !k_cross || !r || !xs || !qnbr || !mu || M <= 0 || M > 0x3fffffffL) { gh_set_error("bad argument to predict_local"); return GH_ERR_BAD_ARG; }
+  if (!k_data || !k_cross || !r || !xs || !table || !mu || M <= 0 || M > 0x3fffffffL) { gh_set_error("bad argument to predict_local"); return GH_ERR_BAD_ARG; }
   if (mq < 1 || mq > VM_MAX) { gh_set_error("predict_local takes 1 <= mq <= %d neighbours per test point, not %d", VM_MAX, (int)mq); return GH_ERR_BAD_ARG; }
   if (k_data->ndim != h->ndim || k_cross->ndim != h->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
   h->info = 0;
-  const long n = (long)h->n;
-  std::vector<int> tab, cnt;
-  GH_CHECK(v_query_index(qnbr, M, mq, n, tab, cnt));        // (before any launch: a bad index would be an out-of-bounds read)
+  return GH_OK;
+}
+static int v_local_inputs(gh_vecchia* h, gh_kernel* k_data, gh_kernel* k_cross, const double* r, const double* xs, int64_t M, GhBuf& rd,
+                          GhBuf& xsd, const double** xs_dev) {
   GH_CHECK(k_data->upload());
   if (k_cross != k_data) GH_CHECK(k_cross->upload());
-  hipStream_t st = h->st;
-  GhPooledBuf rd, xsd, qt, qc, res;
-  GH_CHECK(rd.ensure((size_t)n * sizeof(double)));
-  GH_CHECK(gh_to_device(rd.d(), r, (size_t)n, st));
-  const double* xs_dev = xs;
+  GH_CHECK(rd.ensure((size_t)h->n * sizeof(double)));
+  GH_CHECK(gh_to_device(rd.d(), r, (size_t)h->n, h->st));
+  *xs_dev = xs;
   if (!gh_is_device_ptr(xs)) {
     GH_CHECK(xsd.ensure((size_t)M * h->ndim * sizeof(double)));
-    GH_CHECK(gh_to_device(xsd.d(), xs, (size_t)M * h->ndim, st));
-    xs_dev = xsd.d();
+    GH_CHECK(gh_to_device(xsd.d(), xs, (size_t)M * h->ndim, h->st));
+    *xs_dev = xsd.d();
   }
-  GH_CHECK(v_upload(qt, tab, st));
-  GH_CHECK(v_upload(qc, cnt, st));
+  return GH_OK;
+}
+// Tail: the kernel over the device table qt (valid entries first) with the row counts qc, the failure flag, mu and var back.
+static int v_local_run(gh_vecchia* h, gh_kernel* k_data, gh_kernel* k_cross, const double* rd, const double* xs_dev, int64_t M,
+                       const int* qt, const int* qc, int32_t mq, double* mu, double* var) {
+  hipStream_t st = h->st;
+  GhPooledBuf res;
   GH_CHECK(res.ensure((size_t)2 * M * sizeof(double)));
   GH_CHECK(h->scal.ensure(2 * sizeof(double)));
   double* dmu = res.d();
@@ -726,15 +713,15 @@ extern "C" int gh_vecchia_predict_local(gh_vecchia* h, gh_kernel* k_data, gh_ker
   const bool fast = k_data->fast.ok != 0 && k_cross->fast.ok != 0;
   const size_t lds = v_lds_doubles(mq, h->ndim, fast ? 0 : VWS) * sizeof(double);        // (at most 37 KB: mq = 64, 16 dimensions)
   if (fast) hipLaunchKernelGGL(vecchia_local_kernel<true>, dim3((unsigned)M), dim3(VM_MAX), lds, st, a, k_data->fast, (const GhNode*)k_data->d_nodes,
-                               k_cross->fast, (const GhNode*)k_cross->d_nodes, (int)k_cross->nodes.size(), (const double*)rd.d(), xs_dev,
-                               (const int*)qt.p, (const int*)qc.p, (int)mq, dmu, dvar, fail);
+                               k_cross->fast, (const GhNode*)k_cross->d_nodes, (int)k_cross->nodes.size(), rd, xs_dev, qt, qc, (int)mq, dmu, dvar,
+                               fail);
   else hipLaunchKernelGGL(vecchia_local_kernel<false>, dim3((unsigned)M), dim3(VM_MAX), lds, st, a, k_data->fast, (const GhNode*)k_data->d_nodes,
-                          k_cross->fast, (const GhNode*)k_cross->d_nodes, (int)k_cross->nodes.size(), (const double*)rd.d(), xs_dev,
-                          (const int*)qt.p, (const int*)qc.p, (int)mq, dmu, dvar, fail);
+                          k_cross->fast, (const GhNode*)k_cross->d_nodes, (int)k_cross->nodes.size(), rd, xs_dev, qt, qc, (int)mq, dmu, dvar,
+                          fail);
   GH_HIP(hipGetLastError());
   int failed = INT_MAX;
   GH_HIP(hipMemcpyAsync(&failed, fail, sizeof(int), hipMemcpyDeviceToHost, st));
-  GH_HIP(hipStreamSynchronize(st));                         // (the host tables end with this call)
+  GH_HIP(hipStreamSynchronize(st));                         // (the caller's host tables end with this call)
   if (failed != INT_MAX) {
     h->info = (int64_t)failed + 1;
     gh_set_error("the conditional of test point %lld is not positive definite", (long long)failed);
@@ -744,4 +731,42 @@ extern "C" int gh_vecchia_predict_local(gh_vecchia* h, gh_kernel* k_data, gh_ker
   if (var) GH_CHECK(gh_from_device(var, dvar, (size_t)M, st));
   GH_HIP(hipStreamSynchronize(st));
   return GH_OK;
+}
+
+extern "C" int gh_vecchia_predict_local(gh_vecchia* h, gh_kernel* k_data, gh_kernel* k_cross, const double* r, const double* xs, int64_t M,
+                                        const int32_t* qnbr, int32_t mq, double* mu, double* var) {
+  GH_CHECK(v_local_begin(h, k_data, k_cross, r, xs, M, mq, mu, qnbr));
+  std::vector<int> tab, cnt;
+  GH_CHECK(v_query_index(qnbr, M, mq, (long)h->n, tab, cnt));        // (before any launch: a bad index would be an out-of-bounds read)
+  GhPooledBuf rd, xsd, qt, qc;
+  const double* xs_dev = nullptr;
+  GH_CHECK(v_local_inputs(h, k_data, k_cross, r, xs, M, rd, xsd, &xs_dev));
+  GH_CHECK(v_upload(qt, tab, h->st));
+  GH_CHECK(v_upload(qc, cnt, h->st));
+  return v_local_run(h, k_data, k_cross, rd.d(), xs_dev, M, (const int*)qt.p, (const int*)qc.p, mq, mu, var);
+}
+
+// The same with the table made on the device: the grid of the handle's x (built at the first search after a compute() on other
+// points, or with another occupancy), the search, and its table and row counts straight into the kernel -- the search writes
+// valid entries first and nothing but data points, so there is nothing to check, compact or upload.
+extern "C" int gh_vecchia_predict_local_search(gh_vecchia* h, gh_kernel* k_data, gh_kernel* k_cross, const double* r, const double* xs,
+                                               int64_t M, int32_t mq, int32_t occupancy, double* mu, double* var, int32_t* table_out) {
+  GH_CHECK(v_local_begin(h, k_data, k_cross, r, xs, M, mq, mu, /* the table is made here */ mu));
+  if (occupancy < 0) { gh_set_error("bad argument to predict_local"); return GH_ERR_BAD_ARG; }
+  hipStream_t st = h->st;
+  if (!h->grid.valid || h->grid.occupancy != occupancy) {
+    h->grid.valid = false;
+    h->grid.x_seen.resize((size_t)h->n * h->ndim);
+    GH_HIP(hipMemcpyAsync(h->grid.x_seen.data(), h->x.p, h->grid.x_seen.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    GH_HIP(hipStreamSynchronize(st));
+    GH_CHECK(gh_vgrid_build(h->grid, h->grid.x_seen.data(), h->n, h->ndim, occupancy, st));
+  }
+  GhPooledBuf rd, xsd, qt, qc;
+  const double* xs_dev = nullptr;
+  GH_CHECK(v_local_inputs(h, k_data, k_cross, r, xs, M, rd, xsd, &xs_dev));
+  GH_CHECK(qt.ensure((size_t)M * mq * sizeof(int)));
+  GH_CHECK(qc.ensure((size_t)M * sizeof(int)));
+  GH_CHECK(gh_vgrid_query(h->grid, xs_dev, M, nullptr, mq, (int*)qt.p, (int*)qc.p, st));
+  if (table_out) GH_HIP(hipMemcpyAsync(table_out, qt.p, (size_t)M * mq * sizeof(int), hipMemcpyDefault, st));
+  return v_local_run(h, k_data, k_cross, rd.d(), xs_dev, M, (const int*)qt.p, (const int*)qc.p, mq, mu, var);
 }

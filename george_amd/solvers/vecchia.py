@@ -10,11 +10,18 @@ larger ``m`` than rough or noisy ones.  No reference counterpart.  The device si
 Two predictors.  ``predict`` conditions every test point on all N data points through ``Q`` (the default, ``predict="global"``):
 O(N M) kernel values, and a variance ``k** - K* Q K*^T`` that is only as good as ``Q`` -- it goes negative when ``m`` is too
 small for the kernel.  ``predict_local`` (``predict="local"``) conditions each test point on its ``m`` nearest data points
-alone: a proper conditional variance, O(M m^3) whatever N, no joint covariance between test points.  Its neighbour search
-(:func:`vecchia_query_neighbors`) runs on the host and dominates the call at large M.
+alone: a proper conditional variance, O(M m^3) whatever N, no joint covariance between test points.
 
-Not built: ordering strategies beyond the three of ``order=`` (max-min and the like), ``apply_sqrt``, a device-side
-neighbour search, and a joint covariance between the test points of local prediction.
+The neighbour search.  Both tables -- the predecessors of ``compute`` (:func:`vecchia_neighbors`) and the nearest data points
+of local prediction (:func:`vecchia_query_neighbors`) -- are exact and come from the host by default (``search="host"``:
+``scipy.spatial.cKDTree`` on one thread, which dominates ``predict_local`` at large M) or from the device
+(``search="device"``, ``george_amd/csrc/gh_vecchia_search.hip``: a cell grid over the first three coordinates, one query per
+wavefront).  For up to 7 input dimensions the two give the same table, near-ties included, and so the same bits everywhere; from
+8 dimensions on NumPy adds the squared differences in another order than the device, and a device row is a nearest set under the
+device's own distances (the two can differ where two distances agree to rounding).
+
+Not built: ordering strategies beyond the three of ``order=`` (max-min and the like), ``apply_sqrt``, and a joint covariance
+between the test points of local prediction.
 """
 import atexit
 import ctypes as C
@@ -58,14 +65,32 @@ def _certain(dm, dist, k, n):
     return (np.sqrt(dm) < dist[:, -1] * (1.0 - 1e-9)) if k < n else np.ones(len(dm), dtype=bool)
 
 
-def vecchia_neighbors(x, m):
+def _device_search(x, q, limit, m, device, occupancy=0):
+    """``gh_vecchia_search``: the (len(q), m) table of the points ``x`` nearest to the queries ``q`` among those below
+    ``limit`` (None: all)"""
+    table = np.empty((len(q), m), dtype=np.int32)
+    if m > M_MAX:
+        raise ValueError("the device search takes 1 <= m <= {0}, not {1}".format(M_MAX, m))
+    x, q = np.ascontiguousarray(x), np.ascontiguousarray(q)
+    if limit is not None:
+        limit = np.ascontiguousarray(limit, dtype=np.int64)
+    N.check(N.lib.gh_vecchia_search(int(device), N.ptr(x), len(x), x.shape[1], N.ptr(q), len(q), N.ptr(limit), m, int(occupancy),
+                                    N.ptr(table)))
+    return table
+
+
+def vecchia_neighbors(x, m, device=None):
     """The default conditioning sets: row ``i`` holds the ``min(i, m)`` nearest predecessors of point ``i`` under the
     Euclidean distance on ``x`` as given, ties going to the lower index, sorted ascending and padded with -1.  (N, m)
     int32.  The table depends on ``x`` only, so it stays fixed while an optimiser moves the hyper-parameters.
 
     Exact for every N: it equals the brute-force search.  Strictly increasing 1-D input takes the previous ``m`` points;
     everything else goes through ``scipy.spatial.cKDTree`` with a query size that grows until the ``m`` nearest
-    predecessors are certain, and a direct search for the first rows."""
+    predecessors are certain, and a direct search for the first rows.
+
+    ``device``: ``None`` searches on the host as described; an integer runs the exact search on that device
+    (``gh_vecchia_search`` with the limit ``i`` for row ``i``; m <= 64): the same table for up to 7 input dimensions, and
+    from 8 on a nearest set under the device's own distances, which NumPy adds in another order.  No device: RuntimeError."""
     x = np.asarray(x, dtype=np.float64)
     if x.ndim == 1:
         x = x[:, None]
@@ -75,6 +100,8 @@ def vecchia_neighbors(x, m):
     if m < 1:
         raise ValueError("m must be at least 1")
     n = len(x)
+    if device is not None:
+        return _device_search(x, x, np.arange(n, dtype=np.int64), m, device)
     table = np.full((n, m), -1, dtype=np.int32)
     if n == 0:
         return table
@@ -125,7 +152,7 @@ def _tree(x):
     return tree
 
 
-def vecchia_query_neighbors(x, t, m):
+def vecchia_query_neighbors(x, t, m, device=None):
     """The conditioning sets of local prediction: row ``c`` holds the ``min(N, m)`` data points ``x`` nearest to the test
     point ``t[c]`` under the Euclidean distance on the inputs as given, ties going to the lower index, sorted ascending and
     padded with -1.  (M, m) int32.
@@ -134,7 +161,11 @@ def vecchia_query_neighbors(x, t, m):
     and a window of ``2 m`` points around the test point; everything else goes through ``scipy.spatial.cKDTree`` (built
     once per data set and kept) with a query size that grows until the ``m`` nearest points are certain, and a direct
     search when N is small.  The search runs on the host, O(M m log N): for large M it takes longer than the device call
-    it feeds."""
+    it feeds.
+
+    ``device``: ``None`` searches on the host as described; an integer runs the exact search on that device
+    (``gh_vecchia_search``; m <= 64): the same table for up to 7 input dimensions, and from 8 on a nearest set under the
+    device's own distances, which NumPy adds in another order.  No device: RuntimeError."""
     x = np.asarray(x, dtype=np.float64)
     t = np.asarray(t, dtype=np.float64)
     if x.ndim == 1:
@@ -147,6 +178,8 @@ def vecchia_query_neighbors(x, t, m):
     if m < 1:
         raise ValueError("m must be at least 1")
     n, nt = len(x), len(t)
+    if device is not None:
+        return _device_search(x, t, None, m, device)
     table = np.full((nt, m), -1, dtype=np.int32)
     if n == 0 or nt == 0:
         return table
@@ -213,16 +246,18 @@ def _check_neighbors(nbr, n, m):
 
 
 class VecchiaSolver(NativeSolver):
-    """``VecchiaSolver(kernel, m=32, order=None, neighbors=None, device=0, predict="global")``.
+    """``VecchiaSolver(kernel, m=32, order=None, neighbors=None, device=0, predict="global", search="host")``.
 
     ``m``: neighbours per point, 1 .. 64.  ``order``: ``None`` (the caller's order), ``"coordinate"`` (a stable argsort of
     the first input column) or a permutation array (solver position -> caller's index); the solver permutes its inputs on
     the way in and un-permutes ``alpha``, ``diagA`` and solve results on the way out.  ``neighbors``: ``None``
     (:func:`vecchia_neighbors` of the ordered inputs) or an (N, m) integer table IN SOLVER ORDER, padded with -1; entries
     need not be sorted.  ``predict``: what :meth:`predict` -- and with it ``GP.predict`` -- computes: ``"global"``, every
-    test point conditioned on all data points through ``Q``, or ``"local"``, :meth:`predict_local`."""
+    test point conditioned on all data points through ``Q``, or ``"local"``, :meth:`predict_local`.  ``search``: where the
+    default tables of ``compute`` and of ``predict_local`` are made, ``"host"`` or ``"device"`` (the same tables for up to 7
+    input dimensions; see the module's text)."""
 
-    def __init__(self, kernel, m=32, order=None, neighbors=None, device=0, predict="global"):
+    def __init__(self, kernel, m=32, order=None, neighbors=None, device=0, predict="global", search="host"):
         m = int(m)
         if m < 1 or m > M_MAX:
             raise ValueError("VecchiaSolver: 1 <= m <= {0}, not {1}".format(M_MAX, m))
@@ -230,10 +265,13 @@ class VecchiaSolver(NativeSolver):
             raise ValueError("VecchiaSolver: order is None, 'coordinate' or a permutation")
         if predict not in ("global", "local"):
             raise ValueError("VecchiaSolver: predict is 'global' or 'local'")
+        if search not in ("host", "device"):
+            raise ValueError("VecchiaSolver: search is 'host' or 'device'")
         self.m = m
         self.order = order
         self.neighbors = neighbors
         self.predict_mode = predict
+        self.search = search
         self.failed_point = None
         self.failed_test_point = None
         self._vopts = dict(device=int(device))
@@ -251,7 +289,7 @@ class VecchiaSolver(NativeSolver):
         for k, tab in VecchiaSolver._TABLES:
             if k == key:
                 return tab
-        tab = vecchia_neighbors(x, self.m)
+        tab = vecchia_neighbors(x, self.m, device=self._vopts["device"] if self.search == "device" else None)
         VecchiaSolver._TABLES.append((key, tab))
         del VecchiaSolver._TABLES[:-VecchiaSolver._TABLES_MAX]
         return tab
@@ -431,7 +469,7 @@ class VecchiaSolver(NativeSolver):
             N.check(N.lib.gh_vecchia_predict(h, dk.handle, N.ptr(r), N.ptr(xs), m, N.ptr(mu), N.ptr(var), N.ptr(cov)))
         return mu, var, cov
 
-    def predict_local(self, kernel, r, xs, return_var=False, neighbors=None, m=None):
+    def predict_local(self, kernel, r, xs, return_var=False, neighbors=None, m=None, search=None):
         """Nearest-neighbour prediction: test point ``c`` conditioned on the data points of row ``c`` of ``neighbors`` alone,
         ``mu = k_c^T (K_cc + yerr^2)^-1 r_c`` and ``var = k** - k_c^T (K_cc + yerr^2)^-1 k_c``.  Returns ``(mu, var | None)``.
 
@@ -441,7 +479,14 @@ class VecchiaSolver(NativeSolver):
         ``neighbors``: ``None`` (:func:`vecchia_query_neighbors` of the solver's ordered inputs, a host search that dominates
         the call at large M) or an (M, m) integer table in the CALLER's point numbering, padded with -1 anywhere, entries in
         any order; a row without entries gives ``mu = 0``, ``var = k**``.  A block that is not positive definite raises
-        ``numpy.linalg.LinAlgError`` with ``failed_test_point`` set; the solver stays computed."""
+        ``numpy.linalg.LinAlgError`` with ``failed_test_point`` set; the solver stays computed.
+
+        ``search``: ``"host"``, ``"device"`` or ``None`` (the solver's setting), where the table of ``neighbors=None`` is
+        made.  ``"device"`` is one call: the search runs over the solver's points on the device (their grid is built at the
+        first call after a ``compute`` on other points) and its table never leaves it.  An explicit ``neighbors`` ignores it."""
+        search = self.search if search is None else search
+        if search not in ("host", "device"):
+            raise ValueError("predict_local: search is 'host' or 'device'")
         m = self.m if m is None else int(m)
         if m < 1 or m > M_MAX:
             raise ValueError("predict_local: 1 <= m <= {0}, not {1}".format(M_MAX, m))
@@ -453,7 +498,10 @@ class VecchiaSolver(NativeSolver):
         if xs.ndim != 2 or xs.shape[1] != self._xo.shape[1]:
             raise ValueError("xs must be (ntest, {0})".format(self._xo.shape[1]))
         nt = len(xs)
-        if neighbors is None:
+        fused = neighbors is None and search == "device"
+        if fused:
+            nbr = None
+        elif neighbors is None:
             nbr = vecchia_query_neighbors(self._xo, xs, m)
         else:
             nbr = _check_query_neighbors(neighbors, nt, m, self._n)
@@ -465,7 +513,10 @@ class VecchiaSolver(NativeSolver):
         mu = np.empty(nt)
         var = np.empty(nt) if return_var else None
         if nt > 0:
-            rc = N.lib.gh_vecchia_predict_local(h, self._dk.handle, dk.handle, N.ptr(r), N.ptr(xs), nt, N.ptr(nbr), m, N.ptr(mu), N.ptr(var))
+            if fused:
+                rc = N.lib.gh_vecchia_predict_local_search(h, self._dk.handle, dk.handle, N.ptr(r), N.ptr(xs), nt, m, 0, N.ptr(mu), N.ptr(var), None)
+            else:
+                rc = N.lib.gh_vecchia_predict_local(h, self._dk.handle, dk.handle, N.ptr(r), N.ptr(xs), nt, N.ptr(nbr), m, N.ptr(mu), N.ptr(var))
             if rc == N.GH_ERR_NOT_PD:
                 self.failed_test_point = int(N.lib.gh_vecchia_info(h)) - 1
             N.check(rc)

@@ -476,6 +476,25 @@ int  gh_vecchia_predict(gh_vecchia* h, gh_kernel* k, const double* r /* n: y - m
 int  gh_vecchia_predict_local(gh_vecchia* h, gh_kernel* k_data, gh_kernel* k_cross, const double* r /* n: y - mean */,
                               const double* xs, int64_t M, const int32_t* qnbr /* M*mq */, int32_t mq,
                               double* mu /* M */, double* var /* M or NULL */);
+/* The exact nearest-neighbour search on the device (george_amd/csrc/gh_vecchia_search.hip); it needs no solver handle.  Row c of
+ * table_out (host, (nq, m) int32) = the min(#eligible, m) points of x nearest to q[c] by squared Euclidean distance, ties going
+ * to the lower index, ascending by index, then -1.  Point j is eligible for query c when j < limit[c]; limit == NULL: every
+ * point (limit[c] = c with q = x gives the default table of gh_vecchia_compute).  d2 = sum_k (x_k - q_k)^2 from k = 0 on without
+ * fused multiply-adds: for ndim <= 7 the double NumPy's ((x - q)**2).sum(-1) gives; for more dimensions NumPy adds in another
+ * order and the rows are a nearest set under THIS distance.  A cell grid over the first min(ndim, 3) coordinates aimed at
+ * `occupancy` points per cell (0: automatic; >= n: one cell, a brute-force search) prunes exactly.  x, q and limit may be host
+ * or device memory.  Host checks before any device call: GH_ERR_BAD_ARG for m outside 1 .. 64, a null pointer, a negative size
+ * or occupancy; GH_ERR_DIM for ndim outside 1 .. GH_MAX_NDIM; nq == 0 or n == 0 gives a table of -1 and touches no device.  Two
+ * calls give the same bits. */
+int  gh_vecchia_search(int32_t device, const double* x, int64_t n, int32_t ndim, const double* q, int64_t nq,
+                       const int64_t* limit /* nq or NULL */, int32_t m, int32_t occupancy, int32_t* table_out /* nq*m */);
+/* gh_vecchia_predict_local with the table made by that search over the handle's own x: the grid is kept in the handle and built
+ * again at the first search after a compute() on other points (n (8 ndim + 4) bytes and 4 bytes per cell on the device, the
+ * points once more on the host); the table and its row counts stay on the device.  table_out (host, M*mq, or NULL) receives the
+ * table, in the handle's point numbering.  Errors and gh_vecchia_info() as gh_vecchia_predict_local. */
+int  gh_vecchia_predict_local_search(gh_vecchia* h, gh_kernel* k_data, gh_kernel* k_cross, const double* r /* n: y - mean */,
+                                     const double* xs, int64_t M, int32_t mq, int32_t occupancy,
+                                     double* mu /* M */, double* var /* M or NULL */, int32_t* table_out /* M*mq or NULL */);
 
 /* --------------------------------------------------- dense solver on several GPUs
  * The BasicSolver protocol of /root/reference/src/george/solvers/basic.py:51-102 (compute, log-determinant,
