@@ -765,7 +765,9 @@ extern "C" int gh_chol_solve(gh_chol* s, const double* b, int64_t nrhs, double* 
     GH_CHECK(s->v2.ensure((size_t)np * sizeof(double)));
     GH_CHECK(trsv_forward(s, s->v0.d(), s->v1.d()));
     GH_CHECK(trsv_backward(s, s->v1.d(), s->v2.d()));
-    return gh_from_device(out, s->v2.d(), (size_t)n, s->st);
+    GH_CHECK(gh_from_device(out, s->v2.d(), (size_t)n, s->st));
+    GH_HIP(hipStreamSynchronize(s->st));                  // (a device `out` is only enqueued by gh_from_device)
+    return GH_OK;
   }
   const int64_t rp = gh_round_up(nrhs, T);
   GH_CHECK(s->rhs.ensure((size_t)np * rp * sizeof(double)));
@@ -824,7 +826,9 @@ extern "C" int gh_chol_get_inverse(gh_chol* s, double* out) {
   const long tot = (long)n * n;
   hipLaunchKernelGGL(symmetrize_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s->st, s->work.d(), (long)np, full, (long)n, (long)n);
   GH_HIP(hipGetLastError());
-  return gh_from_device(out, full, (size_t)tot, s->st);
+  GH_CHECK(gh_from_device(out, full, (size_t)tot, s->st));
+  GH_HIP(hipStreamSynchronize(s->st));                    // (a device `out` is only enqueued by gh_from_device)
+  return GH_OK;
 }
 
 // Everything of gh_chol_predict but its synchronisation, enqueued on the main stream.  keep_cov: the covariance is formed in

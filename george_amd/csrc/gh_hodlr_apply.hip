@@ -1083,7 +1083,9 @@ extern "C" int gh_hodlr_solve(gh_hodlr* h, const double* b, int64_t nrhs, double
   GH_CHECK(h->rhs.ensure(tot * sizeof(double)));
   GH_CHECK(gh_to_device(h->rhs.d(), b, tot, h->st));
   GH_CHECK(hodlr_solve_all(h, g_hodlr_passes, h->rhs.d(), nrhs, (int)nrhs));
-  return gh_from_device(out, h->rhs.d(), tot, h->st);
+  GH_CHECK(gh_from_device(out, h->rhs.d(), tot, h->st));
+  GH_HIP(hipStreamSynchronize(h->st));                    // (a device `out` is only enqueued by gh_from_device)
+  return GH_OK;
 }
 extern "C" int gh_hodlr_dot_solve(gh_hodlr* h, const double* y, double* out) {
   GH_CHECK(hodlr_need(h));
@@ -1112,5 +1114,7 @@ extern "C" int gh_hodlr_get_inverse(gh_hodlr* h, double* out) {
   GH_HIP(hipMemsetAsync(h->rhs.p, 0, (size_t)n * n * sizeof(double), h->st));
   GH_CHECK(hodlr_launch_eye_strip(h->rhs.d(), n, 0, (int)n, h->st));
   GH_CHECK(hodlr_solve_all(h, g_hodlr_passes, h->rhs.d(), n, (int)n));
-  return gh_from_device(out, h->rhs.d(), (size_t)n * n, h->st);
+  GH_CHECK(gh_from_device(out, h->rhs.d(), (size_t)n * n, h->st));
+  GH_HIP(hipStreamSynchronize(h->st));                    // (a device `out` is only enqueued by gh_from_device)
+  return GH_OK;
 }

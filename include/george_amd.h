@@ -10,14 +10,40 @@
  * Conventions
  *   - all matrices are C-contiguous (row-major) fp64, exactly as the reference
  *     passes them through pybind11 / NumPy;
- *   - every data pointer may be a HOST pointer or a DEVICE (HBM) pointer; the
- *     library detects which (hipPointerGetAttributes) and stages host buffers
- *     itself.  Results are written to the memory space of the `out` pointer;
  *   - every function returns a status code (GH_OK == 0); gh_last_error() gives
  *     a thread-local message.  No exception crosses the boundary;
  *   - handles are opaque, owned by the library, freed by *_destroy, and not
  *     re-entrant (one call at a time per handle);
  *   - calls are synchronous: on return the result is complete.
+ *
+ * Pointer kinds (what tests/test_gpu_device_pointers.py passes, entry by entry)
+ *   - DATA ARRAYS may be host memory or device (HBM) memory, each on its own: the
+ *     points (x, x1, x2, xs, t, q, x_new), error bars and right-hand sides (yerr,
+ *     yerr_new, y, r, b, z, diag_rows, params), packed factors, `limit` of the
+ *     search, and every array result (out, mu, var, cov, dmu, dvar, grad, alpha,
+ *     diagA, resid, lpd, v, diagB, fisher, draws, fac, logdet / quad / info of the
+ *     batch calls).  `rank` of the sample calls too.  The library detects which
+ *     (hipPointerGetAttributes), stages host arrays itself, reads device inputs
+ *     where they lie or copies them, and writes a result into the memory space
+ *     of its pointer;
+ *   - these are always HOST memory, because the library reads or writes them on
+ *     the host: the scalar results logdet_out, `out` of the *_dot_solve entries,
+ *     logdet / quad of gh_chol_objective, logdet / lpd_sum of the cross-validation
+ *     entries; the masks `which` (gh_chol_objective_grad_batch alone takes
+ *     either); the index tables order, start, idx, nbr, qnbr;
+ *     table_out of the two search entries; ranks_out and the like.  So is every
+ *     pointer of the multi-device entries (gh_mgpu_*, gh_hodlr_mgpu_*), and
+ *     every pointer of gh_dev_* is DEVICE memory, as said there;
+ *   - a device array needs the alignment of its element type (8 bytes for
+ *     doubles) and no more: no kernel reads or writes a caller's array with a
+ *     wider access unless it has checked the address;
+ *   - the caller guarantees that device inputs are complete when the call is
+ *     made (the calls run on the library's own streams).  Inputs are never
+ *     modified -- not even transiently -- unless the entry says that two
+ *     arguments may alias;
+ *   - every result, on the host or on the device, is complete when the call
+ *     returns; two calls with the same arguments give the same bits whatever the
+ *     memory spaces of the arguments.
  */
 #ifndef GEORGE_AMD_H_
 #define GEORGE_AMD_H_
@@ -137,8 +163,8 @@ int  gh_kernel_x2_gradient_general(gh_kernel* k, const double* x1, int64_t n1,
                                    const double* x2, int64_t n2, double* out /* n1*n2*ndim */);
 /* Prior draws at t (m, ndim) (replaces GP.sample(t), src/george/gp.py -- get_matrix + TINY on the diagonal -- and utils.py:11-33):
  * K(t, t) + jitter * I is built and factored on the device (gh_dev_pstrf), draws (nz, m) = z[:, :rank] L[:, :rank]^T for the caller's
- * standard normals z (nz, m).  tol < 0: m * eps * max diag (K(t, t) + jitter I).  fac (m, m) or NULL; *rank int64.  Pointers may be
- * host or device memory; the current device and its null stream, as gh_kernel_value_symmetric. */
+ * standard normals z (nz, m).  tol < 0: m * eps * max diag (K(t, t) + jitter I).  fac (m, m) or NULL; *rank int64 (host or device
+ * memory).  The current device and its null stream, as gh_kernel_value_symmetric. */
 int  gh_kernel_sample(gh_kernel* k, const double* t, int64_t m, double jitter, const double* z, int64_t nz, double tol,
                       double* draws /* nz*m */, double* fac /* m*m or NULL */, int64_t* rank);
 
@@ -153,7 +179,9 @@ int  gh_kernel_sample(gh_kernel* k, const double* t, int64_t m, double jitter, c
  * plus fused device-resident forms of the GP glue around it
  *   GP.predict            src/george/gp.py:482-545 -> gh_chol_predict
  *   GP.grad_log_likelihood (kernel part) gp.py:429-466 -> gh_chol_grad
- * K is built on the device from (kernel, x) and never visits the host. */
+ * K is built on the device from (kernel, x) and never visits the host.
+ * Pointer kinds: "Pointer kinds" at the top of this file holds for every entry below; an entry repeats only which of its
+ * pointers are host memory. */
 typedef struct gh_chol_opts {
   int32_t device;        /* HIP device ordinal                                   */
   int32_t nb;            /* outer panel width (multiple of 128); 0 = default      */
@@ -164,14 +192,15 @@ typedef struct gh_chol_opts {
 
 int  gh_chol_create(const gh_chol_opts* opts, gh_chol** out);
 void gh_chol_destroy(gh_chol* s);
-/* yerr: (n,) standard deviations ALREADY including white noise (gp.py:330). */
+/* yerr: (n,) standard deviations ALREADY including white noise (gp.py:330).  x and yerr: host or device memory, each on its own
+ * (both on the device: one launch brings them in, no copy is enqueued); *logdet_out: host. */
 int  gh_chol_compute(gh_chol* s, gh_kernel* k, const double* x, int64_t n, int32_t ndim,
                      const double* yerr, double* logdet_out);
 /* Sequential use (no reference counterpart: gp.py:303-337 always rebuilds).
  * K' = [[K, k(x, xn)], [k(xn, x), k(xn, xn) + diag(yerr_new^2)]]: extend the computed factor by m rows.  The rows of the
  * full 128-row tiles of the factor and their diagonal-block inverses are not touched (bit for bit); the rows of the last,
  * partial tile are formed again.  The kernel must be the one (same parameters) the handle was computed with; that is the
- * caller's contract.  x_new (m, ndim), yerr_new (m): host or device.  On GH_OK the handle is computed at n + m and
+ * caller's contract.  x_new (m, ndim), yerr_new (m).  On GH_OK the handle is computed at n + m and
  * *logdet_out = log|K'|.  On GH_ERR_NOT_PD, gh_chol_info() is the 1-based index in the extended matrix, and the handle is
  * left computed at the OLD n with the old factor bits; so it is after GH_ERR_NOMEM.  Any other error (a failed HIP call) while
  * the last tile is being rewritten in place leaves the handle NOT computed.  A handle rebuilt by gh_chol_import_factor needs
@@ -191,17 +220,21 @@ int  gh_chol_truncate(gh_chol* s, int64_t n_keep, double* logdet_out);
  * -- GH_ERR_BAD_ARG for a bad idx, GH_ERR_NOMEM, a failed HIP call, GH_ERR_NOT_PD for a pivot that is not finite and positive --
  * the handle keeps its factor, size, info and log-determinant bit for bit.  GH_REFACTORIZE: see gh_debug_set_remove_path. */
 int  gh_chol_remove(gh_chol* s, const int64_t* idx, int64_t m, double* logdet_out);
-/* the error bars (n, as given to compute / append) of a computed handle: what gh_chol_import_factor does not bring */
+/* the error bars (n, as given to compute / append; host or device memory) of a computed handle: what gh_chol_import_factor does
+ * not bring */
 int  gh_chol_set_yerr(gh_chol* s, const double* yerr);
 int64_t gh_chol_info(const gh_chol* s);     /* 1-based index of the failing pivot after GH_ERR_NOT_PD, else 0 */
 int64_t gh_chol_size(const gh_chol* s);
 int64_t gh_chol_device_bytes(const gh_chol* s);  /* HBM bytes the handle holds right now (factor + work arrays) */
+/* the protocol's four: b, y, r and the array results are host or device memory; *out of gh_chol_dot_solve is a host double.  A
+ * device y is read where it lies when n is a multiple of 128, and is not modified. */
 int  gh_chol_solve(gh_chol* s, const double* b, int64_t nrhs, double* out);   /* b, out: (n, nrhs) row-major; may alias */
 int  gh_chol_dot_solve(gh_chol* s, const double* y, double* out);
 int  gh_chol_apply_sqrt(gh_chol* s, const double* r, int64_t nrows, double* out); /* r, out: (nrows, n) */
 int  gh_chol_get_inverse(gh_chol* s, double* out /* n*n */);
 /* mu = K(xs,x) K^-1 r ; var = diag(K(xs,xs)) - diag(K(xs,x) K^-1 K(x,xs)) ;
- * cov = K(xs,xs) - K(xs,x) K^-1 K(x,xs).   var / cov may be NULL. */
+ * cov = K(xs,xs) - K(xs,x) K^-1 K(x,xs).   var / cov may be NULL.  r, xs, mu, var, cov: host or device memory (device xs are
+ * read where they lie). */
 int  gh_chol_predict(gh_chol* s, gh_kernel* k, const double* r /* n: y - mean */,
                      const double* xs, int64_t m, double* mu /* m */,
                      double* var /* m or NULL */, double* cov /* m*m or NULL */);
@@ -209,11 +242,11 @@ int  gh_chol_predict(gh_chol* s, gh_kernel* k, const double* r /* n: y - mean */
  * utils.py:11-33 behind it).  mu and cov are formed exactly as gh_chol_predict forms them; cov stays on the device and is factored
  * there by the diagonally pivoted Cholesky with rank truncation of gh_dev_pstrf (a predictive covariance is numerically
  * semidefinite: a plain Cholesky fails on it); then, as one GEMM,
- *   draws (nz, m) = mu + z[:, :rank] L[:, :rank]^T        z (nz, m): standard normals supplied by the caller, host or device.
+ *   draws (nz, m) = mu + z[:, :rank] L[:, :rank]^T        z (nz, m): standard normals supplied by the caller.
  * tol: the factor's absolute stop threshold; tol < 0 means the default m * eps * max diag K(xs, xs) -- the PRIOR's scale, because
  * the rounding error of cov scales with the prior, not with the possibly tiny posterior variances.  mu (m) or NULL (no mean model:
  * the caller adds it); fac (m, m) or NULL receives L (columns >= rank exactly zero; L L^T approximates cov within tol entrywise);
- * *rank (int64): the number of pivots taken.  Pointers may be host or device memory.  The covariance never reaches the host; the
+ * *rank (int64, host or device memory): the number of pivots taken.  The covariance never reaches the host; the
  * work buffers are counted by gh_chol_device_bytes and freed by gh_chol_trim. */
 int  gh_chol_sample_conditional(gh_chol* s, gh_kernel* k, const double* r /* n: y - mean */, const double* xs, int64_t m,
                                 const double* z /* nz*m */, int64_t nz, double tol, double* mu /* m or NULL */,
@@ -226,7 +259,7 @@ int  gh_chol_sample_conditional(gh_chol* s, gh_kernel* k, const double* r /* n: 
  *   dvar[c][d] = D_cd - 2 sum_i G_cid w_ic
  * mu and var are gh_chol_predict's, bit for bit (the same launches).  G is evaluated and reduced in one kernel and never stored;
  * the sums run in a fixed order (no atomics: two calls give the same bits).  mu, var and dvar may be NULL, each on its own (dvar
- * without var is allowed); dmu may not.  Pointers may be host or device memory; the results leave in one batch of copies
+ * without var is allowed); dmu may not.  The results leave in one batch of copies
  * followed by one synchronisation, after the one of predict's forward sweep.  With dmu alone (mu, var and dvar all NULL) neither
  * K(x, xs) nor a substitution with m right-hand sides is formed: two sweeps for alpha, the kernel, one synchronisation; dmu has
  * the same bits either way.  Memory is that of gh_chol_predict with var (W = K^-1 K(x, xs) overwrites V = L^-1 K(x, xs) in
@@ -235,7 +268,7 @@ int  gh_chol_predict_grad(gh_chol* s, gh_kernel* k, const double* r /* n: y - me
                           double* mu /* m or NULL */, double* var /* m or NULL */,
                           double* dmu /* m*ndim */, double* dvar /* m*ndim or NULL */);
 /* alpha = K^-1 r; A = alpha alpha^T - K^-1; grad[p] = 1/2 sum_ij A_ij dK_ij/dtheta_p
- * for the parameters selected by `which` (others 0); diagA (n) = diag(A). */
+ * for the parameters selected by `which` (others 0); diagA (n) = diag(A).  which: host; r, grad, alpha, diagA: host or device. */
 int  gh_chol_grad(gh_chol* s, gh_kernel* k, const uint32_t* which, const double* r,
                   double* grad /* size */, double* alpha /* n or NULL */, double* diagA /* n or NULL */);
 /* Fused hyper-parameter objective: GP.nll + GP.grad_nll (src/george/gp.py:470-480, i.e. compute
@@ -243,7 +276,8 @@ int  gh_chol_grad(gh_chol* s, gh_kernel* k, const uint32_t* which, const double*
  * device-resident call with one synchronisation: build K, factor, *logdet = log|K|,
  * *quad = r^T K^-1 r, and -- when grad != NULL -- alpha = K^-1 r (from the same forward solve),
  * K^-1 and grad[p] = 1/2 sum_ij A_ij dK_ij/dtheta_p for the parameters selected by `which`.
- * grad / alpha / diagA may be NULL; the handle is left computed (solve / predict may follow). */
+ * grad / alpha / diagA may be NULL; the handle is left computed (solve / predict may follow).  *logdet, *quad and which: host;
+ * x, yerr, r, grad, alpha, diagA: host or device memory. */
 int  gh_chol_objective(gh_chol* s, gh_kernel* k, const double* x, int64_t n, int32_t ndim,
                        const double* yerr, const double* r /* n: y - mean */, const uint32_t* which,
                        double* logdet, double* quad, double* grad /* size or NULL */,
@@ -257,14 +291,14 @@ int  gh_chol_objective(gh_chol* s, gh_kernel* k, const double* x, int64_t n, int
  *   grad[p]  = sum_ij B_ij dK_ij/dtheta_p  for the parameters selected by `which` (others exactly 0)
  *   v (n)    : d lpd_sum / d mean_i;      diagB (n) = diag(B): d lpd_sum / d K_ii.
  * grad, v and diagB all NULL: K^-1 is not formed (c from L^-1; one N x N work buffer); otherwise two, as gh_chol_grad.
- * which == NULL: no gradient (grad must be NULL too).  Pointers may be host or device memory.  Two calls give the same bits. */
+ * which == NULL: no gradient (grad must be NULL too).  *lpd_sum and which are host memory.  Two calls give the same bits. */
 int  gh_chol_loo(gh_chol* s, gh_kernel* k, const uint32_t* which /* NULL: no gradient */, const double* r,
                  double* lpd_sum, double* resid /* n: alpha_i / c_i = y_i - mu_i */, double* var /* n */,
                  double* lpd /* n or NULL */, double* grad /* size, or NULL */, double* v /* n or NULL */,
                  double* diagB /* n or NULL */);
 /* Fused leave-one-out objective: gh_chol_compute + gh_chol_loo as ONE device-resident call with one synchronisation (what
  * gh_chol_objective is to compute + dot_solve + grad), bit for bit the results of the two calls; *logdet = log|K|.  The handle
- * is left computed; on GH_ERR_NOT_PD gh_chol_info() is set and it is not. */
+ * is left computed; on GH_ERR_NOT_PD gh_chol_info() is set and it is not.  *logdet, *lpd_sum and which: host. */
 int  gh_chol_loo_objective(gh_chol* s, gh_kernel* k, const double* x, int64_t n, int32_t ndim, const double* yerr,
                            const double* r, const uint32_t* which, double* logdet, double* lpd_sum,
                            double* resid, double* var, double* grad, double* v, double* diagB);
@@ -281,8 +315,8 @@ int  gh_chol_loo_objective(gh_chol* s, gh_kernel* k, const double* x, int64_t n,
  * the other, each m_g x m_g row-major with its rows in the order of `order`.  A group has at most 128 points.  GH_ERR_BAD_ARG, before
  * any device work, when order is not a permutation of 0 .. n-1, start does not rise from 0 to n, a group is empty or has more than
  * 128 points, or grad is given without which.  grad, v and diagB all NULL: K^-1 is not formed (one N x N work buffer); otherwise two,
- * as gh_chol_grad.  The slot buffers are counted by gh_chol_device_bytes and freed by gh_chol_trim.  Data pointers may be host or
- * device memory.  Two calls give the same bits. */
+ * as gh_chol_grad.  The slot buffers are counted by gh_chol_device_bytes and freed by gh_chol_trim.  *lpd_sum and which are host
+ * memory, like order and start.  Two calls give the same bits. */
 int  gh_chol_lgo(gh_chol* s, gh_kernel* k, const uint32_t* which /* NULL: no gradient */, const double* r,
                  const int64_t* order /* n, host */, const int64_t* start /* ngroups+1, host */, int64_t ngroups,
                  double* lpd_sum, double* resid /* n, caller's point order */, double* var /* n */,
@@ -301,8 +335,8 @@ int  gh_chol_lgo(gh_chol* s, gh_kernel* k, const uint32_t* which /* NULL: no gra
  * its own.  When every active plane fits (the budget, and what the device can allocate) they are resident at once; otherwise
  * the call works in blocks -- (planes that fit) - 1 resident, every later plane formed again into the remaining one for every
  * block -- and the result has the same bits for every max_bytes the call accepts.  When not even two planes fit: GH_ERR_NOMEM.
- * The factor is not modified and on any failure the handle keeps its factor, size, info and log-determinant.  Pointers may be
- * host or device memory.  Everything runs on the handle's main stream with one synchronisation at the end; the buffers are
+ * The factor is not modified and on any failure the handle keeps its factor, size, info and log-determinant.  which is host
+ * memory.  Everything runs on the handle's main stream with one synchronisation at the end; the buffers are
  * counted by gh_chol_device_bytes and freed by gh_chol_trim.  For a general (full-matrix) metric the evaluator's
  * parameter-gradient entries are the reference's, and the information inherits them. */
 int  gh_chol_fisher(gh_chol* s, gh_kernel* k, const uint32_t* which /* size */,
@@ -360,7 +394,8 @@ int  gh_chol_objective_grad_batch(gh_chol* s, gh_kernel* k, const double* params
  * tests/test_pickle.py:21-36, because its factor is a NumPy array, basic.py:68): the lower
  * triangle of L packed by rows (gh_chol_factor_size() = n (n + 1) / 2 doubles) and the inverses of
  * its 128 x 128 diagonal blocks (gh_chol_dinv_size() doubles).  import_factor() rebuilds a computed
- * handle from them plus the inputs x (n, ndim) that predict / grad evaluate kernels against. */
+ * handle from them plus the inputs x (n, ndim) that predict / grad evaluate kernels against.  packed_lower, dinv_out / dinv_in
+ * and x: host or device memory. */
 int64_t gh_chol_factor_size(const gh_chol* s);
 int64_t gh_chol_dinv_size(const gh_chol* s);
 int  gh_chol_export_factor(gh_chol* s, double* packed_lower, double* dinv_out);
@@ -396,7 +431,9 @@ int  gh_chol_get_update_intervals(const gh_chol* s, double* out /* 3 * max_launc
 /* ------------------------------------------------------------ HODLR solver
  * Replaces HODLRSolver (src/george/solvers/hodlr.py:13-76), the pybind11
  * `Solver` (src/george/solvers/_hodlr.cpp:38-110) and hodlr::Node
- * (include/george/hodlr.h:13-258). */
+ * (include/george/hodlr.h:13-258).  x, yerr, b, y, r, xs and the array results are host or device memory ("Pointer kinds" at
+ * the top of this file; a device y of gh_hodlr_dot_solve is read where it lies); *logdet_out, *out of gh_hodlr_dot_solve, which
+ * and ranks_out / n_out are host memory. */
 typedef struct gh_hodlr_opts {
   int32_t device;
   int32_t min_size;      /* hodlr.py:43 default 100 */
@@ -419,7 +456,7 @@ int  gh_hodlr_ranks(const gh_hodlr* h, int32_t* ranks_out, int32_t max_out, int3
  * log|K| and the computed state untouched, synchronise once at the end, and refuse a sub-tree handle of the multi-device split. */
 /* mu = K(xs,x) K^-1 r ; var = diag K(xs,xs) - diag(K(xs,x) K^-1 K(x,xs)) ; cov = K(xs,xs) - K(xs,x) K^-1 K(x,xs)
  * (gp.py:482-545 with apply_inverse = hodlr.h:107-114).  k may differ from the kernel of compute() (GP.predict(kernel=...)).
- * var / cov may be NULL (not both non-NULL).  Pointers may be host or device memory.  cov keeps K(x,xs) and K^-1 K(x,xs) whole on
+ * var / cov may be NULL (not both non-NULL).  cov keeps K(x,xs) and K^-1 K(x,xs) whole on
  * the device (2 * 8 * n * m bytes): GH_ERR_NOMEM when they do not fit. */
 int  gh_hodlr_predict(gh_hodlr* h, gh_kernel* k, const double* r /* n: y - mean */, const double* xs, int64_t m,
                       double* mu /* m */, double* var /* m or NULL */, double* cov /* m*m or NULL */);
@@ -434,7 +471,10 @@ int  gh_hodlr_grad(gh_hodlr* h, gh_kernel* k, const uint32_t* which, const doubl
  * predecessors of i in the order the points are given in.  With b_i = K_cc^-1 k_ci and f_i = k_ii - k_ci^T b_i the precision is
  * Q = (I - B)^T F^-1 (I - B), B strictly lower triangular with the b_i as rows, F = diag(f).  Every predecessor in c(i)
  * (m >= n - 1) gives the dense answers up to rounding.  O(n m^3) flops, O(n m) memory; no reference counterpart.  Fixed-order
- * sums throughout: two calls give the same bits.  (george_amd/csrc/gh_vecchia.hip) */
+ * sums throughout: two calls give the same bits.  (george_amd/csrc/gh_vecchia.hip)
+ * x, yerr, b, y, r, xs and the array results mu, var, cov, out, grad, alpha, diagA are host or device memory ("Pointer kinds" at
+ * the top of this file); *logdet_out, *out of gh_vecchia_dot_solve, which, nbr, qnbr and table_out are host memory.  A compute()
+ * on device x always drops a kept search grid (the points cannot be compared on the host). */
 typedef struct gh_vecchia gh_vecchia;
 typedef struct gh_vecchia_opts {
   int32_t device;
