@@ -1,7 +1,8 @@
 // gh_chol_impl.h -- what the three units of the dense solver share (host side, private to them):
 //   gh_chol.hip         the factorisation: handle, streams, tile operations, panel schedules, compute
-//   gh_chol_solve.hip   work on a computed factor: reductions, sweeps, solve .. fisher, objective, and the cross-validation
-//                       driver (loo, loo_objective, lgo; its kernels: gh_cv.hip)
+//   gh_chol_solve.hip   work on a computed factor: sweeps, solve .. fisher, objective, and the cross-validation driver (loo,
+//                       loo_objective, lgo; its kernels: gh_cv.hip).  predict's column reduction, the staging of test points and
+//                       the pitched copy to the caller are shared with the other solvers: gh_predict.hip (gh_common.h)
 //   gh_chol_update.hip  moving and editing a factor: export / import, append / truncate / set_yerr, remove
 // A kernel is launched only from the unit that defines it; what another unit needs of it is a launcher declared here.
 #pragma once

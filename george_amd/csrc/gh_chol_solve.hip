@@ -482,32 +482,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void trsv_bwd_chain_direct(const dou
   }
 }
 
-// ========================================================= predict reductions
-// partial[s][c] = sum over the s-th row chunk of V[r][c] * z[r]  and of V[r][c]^2
-__global__ __launch_bounds__(256) void colreduce_kernel(const double* V, long ldv, long nrows, long rows_per,
-                                                        const double* z, double* pmu, double* pvar, long ncols_p) {
-  const long c = (long)blockIdx.x * 256 + threadIdx.x;
-  if (c >= ncols_p) return;
-  const long r0 = (long)blockIdx.y * rows_per;
-  const long r1 = r0 + rows_per < nrows ? r0 + rows_per : nrows;
-  double am = 0.0, av = 0.0;
-  for (long r = r0; r < r1; ++r) {
-    const double v = V[r * ldv + c];
-    am += v * z[r];
-    av += v * v;
-  }
-  pmu[(long)blockIdx.y * ncols_p + c] = am;
-  pvar[(long)blockIdx.y * ncols_p + c] = av;
-}
-__global__ void colfinal_kernel(const double* pmu, const double* pvar, long nchunks, long ncols_p, long m,
-                                double* mu, double* var /* in: k(xs,xs) diag; may be NULL */) {
-  const long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= m) return;
-  double am = 0.0, av = 0.0;
-  for (long s = 0; s < nchunks; ++s) { am += pmu[s * ncols_p + c]; av += pvar[s * ncols_p + c]; }
-  mu[c] = am;
-  if (var) var[c] -= av;
-}
+// ========================================================= small helpers
 __global__ void fill_kernel(double* p, long n, double v) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) p[i] = v;
 }
@@ -620,25 +595,6 @@ static int join_tail(gh_chol* s) {
   }
   return GH_OK;
 }
-// m test points on the device: where they lie, or copied into xsd
-static int stage_points(gh_chol* s, const double* xs, int64_t m, GhBuf& xsd, const double** xs_dev) {
-  *xs_dev = xs;
-  if (!gh_is_device_ptr(xs)) {
-    GH_CHECK(xsd.ensure((size_t)m * s->ndim * sizeof(double)));
-    GH_CHECK(gh_to_device(xsd.d(), xs, (size_t)m * s->ndim, s->st));
-    *xs_dev = xsd.d();
-  }
-  return GH_OK;
-}
-// rows x cols doubles between row-pitched arrays (pitches in doubles) of which the caller's -- src when from_caller, else dst --
-// may be host or device memory
-static int copy_rows(double* dst, int64_t ldd, const double* src, int64_t lds, int64_t cols, int64_t rows, bool from_caller, hipStream_t st) {
-  const bool dev = gh_is_device_ptr(from_caller ? (const void*)src : (const void*)dst);
-  GH_HIP(hipMemcpy2DAsync(dst, ldd * sizeof(double), src, lds * sizeof(double), cols * sizeof(double), rows,
-                          dev ? hipMemcpyDeviceToDevice : from_caller ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost, st));
-  return GH_OK;
-}
-
 // load a length-n vector (host or device) into a zero-padded device vector of length np
 static int load_vec(gh_chol* s, GhBuf& buf, const double* src) {
   GH_CHECK(buf.ensure((size_t)s->np * sizeof(double)));
@@ -772,9 +728,9 @@ extern "C" int gh_chol_solve(gh_chol* s, const double* b, int64_t nrhs, double* 
   const int64_t rp = gh_round_up(nrhs, T);
   GH_CHECK(s->rhs.ensure((size_t)np * rp * sizeof(double)));
   GH_HIP(hipMemsetAsync(s->rhs.d(), 0, (size_t)np * rp * sizeof(double), s->st));
-  GH_CHECK(copy_rows(s->rhs.d(), rp, b, nrhs, nrhs, n, true, s->st));
+  GH_CHECK(gh_copy_rows(s->rhs.d(), rp, b, nrhs, nrhs, n, true, s->st));
   GH_CHECK(trsm_multi(s, s->rhs.d(), rp, true, true));
-  GH_CHECK(copy_rows(out, nrhs, s->rhs.d(), rp, nrhs, n, false, s->st));
+  GH_CHECK(gh_copy_rows(out, nrhs, s->rhs.d(), rp, nrhs, n, false, s->st));
   GH_HIP(hipStreamSynchronize(s->st));
   return GH_OK;
 }
@@ -787,11 +743,11 @@ extern "C" int gh_chol_apply_sqrt(gh_chol* s, const double* r, int64_t nrows, do
   GH_CHECK(s->rhs.ensure((size_t)rr * np * sizeof(double)));
   GH_CHECK(s->work.ensure((size_t)rr * np * sizeof(double)));
   GH_HIP(hipMemsetAsync(s->rhs.d(), 0, (size_t)rr * np * sizeof(double), s->st));
-  GH_CHECK(copy_rows(s->rhs.d(), np, r, n, n, nrows, true, s->st));
+  GH_CHECK(gh_copy_rows(s->rhs.d(), np, r, n, n, nrows, true, s->st));
   GhGemm g = gemm_desc(s->work.d(), np, s->rhs.d(), np, true, s->A.d(), np, true, rr, np, np, 1.0, 0.0);
   g.khi_col = true;
   GH_CHECK(gh_launch_gemm(g, s->st));
-  GH_CHECK(copy_rows(out, n, s->work.d(), np, n, nrows, false, s->st));
+  GH_CHECK(gh_copy_rows(out, n, s->work.d(), np, n, nrows, false, s->st));
   GH_HIP(hipStreamSynchronize(s->st));
   return GH_OK;
 }
@@ -847,7 +803,7 @@ static int predict_enqueue(gh_chol* s, gh_kernel* k, const double* r, const doub
   // V = L^-1 K(x, xs)   (np x mp): built on the device, forward substitution only, because
   // K*s K^-1 K*s^T = V^T V and K*s K^-1 r = V^T z  (gp.py:532-545 does both sweeps on the host)
   const double* xs_dev = nullptr;
-  GH_CHECK(stage_points(s, xs, m, xsd, &xs_dev));
+  GH_CHECK(gh_stage_points(xs, m, s->ndim, xsd, st, &xs_dev));
   GH_CHECK(s->rhs.ensure((size_t)np * mp * sizeof(double)));
   GH_CHECK(gh_launch_kmat(k, s->x.d(), n, xs_dev, m, nullptr, s->rhs.d(), mp, np, mp, 0, 0, false, false, st));
   GH_CHECK(trsm_multi(s, s->rhs.d(), mp, true, false));
@@ -859,13 +815,10 @@ static int predict_enqueue(gh_chol* s, gh_kernel* k, const double* r, const doub
   double* pvar = pmu + nchunks * mp;
   double* dmu = pvar + nchunks * mp;
   double* dvar = dmu + mp;
-  hipLaunchKernelGGL(colreduce_kernel, dim3((unsigned)((mp + 255) / 256), (unsigned)nchunks), dim3(256), 0, st,
-                     s->rhs.d(), (long)mp, (long)np, (long)rows_per, s->v1.d(), pmu, pvar, (long)mp);
-  GH_HIP(hipGetLastError());
   if (var) GH_CHECK(gh_launch_kdiag(k, xs_dev, xs_dev, m, dvar, st));           // gp.py:539
-  hipLaunchKernelGGL(colfinal_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
-                     pmu, pvar, (long)nchunks, (long)mp, (long)m, dmu, var ? dvar : nullptr);
-  GH_HIP(hipGetLastError());
+  // (the m columns in use start as many 256-thread workgroups as the mp padded ones: mp rounds m up to 128)
+  GH_CHECK(gh_launch_colreduce(s->rhs.d(), s->v1.d(), s->rhs.d(), s->rhs.d(), mp, np, rows_per, nchunks, m, pmu, pvar, mp, dmu,
+                               var ? dvar : nullptr, 256, st));
   if (mu) GH_CHECK(gh_from_device(mu, dmu, (size_t)m, st));
   if (var) GH_CHECK(gh_from_device(var, dvar, (size_t)m, st));
   if (cov || keep_cov) {
@@ -873,7 +826,7 @@ static int predict_enqueue(gh_chol* s, gh_kernel* k, const double* r, const doub
     GH_CHECK(s->work.ensure((size_t)mp * mp * sizeof(double)));
     GH_CHECK(gh_launch_kmat(k, xs_dev, m, xs_dev, m, nullptr, s->work.d(), mp, mp, mp, 0, 0, true, false, st));
     GH_CHECK(gh_launch_gemm(gemm_desc(s->work.d(), mp, s->rhs.d(), mp, false, s->rhs.d(), mp, false, mp, mp, np, -1.0, 1.0), st));
-    if (cov) GH_CHECK(copy_rows(cov, m, s->work.d(), mp, m, m, false, st));
+    if (cov) GH_CHECK(gh_copy_rows(cov, m, s->work.d(), mp, m, m, false, st));
   }
   if (dmu_out) *dmu_out = dmu;
   if (xs_dev_out) *xs_dev_out = xs_dev;
@@ -920,7 +873,7 @@ extern "C" int gh_chol_predict_grad(gh_chol* s, gh_kernel* k, const double* r, c
     GH_CHECK(load_vec(s, s->v0, r));
     GH_CHECK(s->v1.ensure((size_t)np * sizeof(double)));
     GH_CHECK(trsv_forward(s, s->v0.d(), s->v1.d(), true));
-    GH_CHECK(stage_points(s, xs, m, xsd, &xs_dev));
+    GH_CHECK(gh_stage_points(xs, m, s->ndim, xsd, st, &xs_dev));
   }
   GH_CHECK(s->v2.ensure((size_t)np * sizeof(double)));
   GH_CHECK(trsv_backward(s, s->v1.d(), s->v2.d(), true));                       // alpha = L^-T z
@@ -1089,7 +1042,7 @@ extern "C" int gh_chol_fisher(gh_chol* s, gh_kernel* k, const uint32_t* which, c
   GH_HIP(hipMemsetAsync(F, 0, (size_t)ptot * ptot * sizeof(double), st));
   if (n_diag > 0) {
     GH_HIP(hipMemsetAsync(drows, 0, n_rows * sizeof(double), st));
-    GH_CHECK(copy_rows(drows, np, diag_rows, n, n, n_diag, true, st));
+    GH_CHECK(gh_copy_rows(drows, np, diag_rows, n, n, n_diag, true, st));
   }
   GH_CHECK(linv_into(s, s->work2.d()));
   auto slot = [&](int i) { return s->fish.d() + (size_t)i * np * np; };

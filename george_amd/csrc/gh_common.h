@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -238,6 +239,30 @@ struct GhGemm {
 };
 #define GH_GEMM_STAIR_MAX 128
 int gh_launch_gemm(const GhGemm& g, hipStream_t st);
+
+// What the solvers' predict calls share (gh_predict.hip).
+// m test points of ndim coordinates on the device: *xs_dev is xs where that is device memory, else a copy that `own` owns
+int gh_stage_points(const double* xs, int64_t m, int ndim, GhBuf& own, hipStream_t st, const double** xs_dev);
+// rows x cols doubles between row-pitched arrays (pitches in doubles) of which the caller's -- src when from_caller, else dst --
+// may be host or device memory
+int gh_copy_rows(double* dst, int64_t ldd, const double* src, int64_t lds, int64_t cols, int64_t rows, bool from_caller, hipStream_t st);
+// Column reduction over row-major operands of row pitch ld, in nchunks chunks of rows_per rows (partials: nchunks x ldp each):
+//   mu[j] = sum_i A[i][j] z[i],   var[j] = var[j] - sum_i P[i][j] Q[i][j]      for j < cols, i < nrows
+// P == nullptr: the mean only; else P is A or Q (an operand is loaded once per row).  var may be nullptr with P set (the second
+// moment then stays in pvar).  Rows ascending inside a chunk, chunks in ascending order: the same bits whatever `threads` (the
+// workgroup size, 64 .. 256) and whatever the other columns hold.
+int gh_launch_colreduce(const double* A, const double* z, const double* P, const double* Q, int64_t ld, int64_t nrows, int64_t rows_per,
+                        int64_t nchunks, int64_t cols, double* pmu, double* pvar, int64_t ldp, double* mu, double* var, int threads,
+                        hipStream_t st);
+// predict over column strips for a solver without buffers of its own: mu = Kx^T alpha and, with S = make_second(Kx) and
+// F = first_second ? Kx : S, var = diag K(xs, xs) - colsum(F .* S) or cov = K(xs, xs) - F^T S, where Kx = K(x, xs) is built
+// strip_cols columns at a time (with cov: whole, with the padding the product needs).  make_second gets a strip sK (np rows of
+// pitch ld, cw columns in use, strip_bytes in all) and fills sSecond, of the same shape, on st.  x, alpha, xs_dev: device
+// memory; mu, var, cov: the caller's, host or device.  Synchronises st.
+typedef std::function<int(const double* sK, double* sSecond, int64_t ld, int64_t np, int cw, size_t strip_bytes)> GhMakeSecond;
+int gh_predict_strips(gh_kernel* k, const double* x, int64_t n, int ndim, const double* alpha, const double* xs_dev, int64_t m,
+                      int64_t strip_cols, int64_t red_rows, int64_t red_chunks, double* mu, double* var, double* cov, hipStream_t st,
+                      bool first_second, const GhMakeSecond& make_second);
 // Diagonally pivoted Cholesky with rank truncation, batched (gh_pstrf.hip; the definition is at the top of that file).
 // All pointers are device memory.  The launcher enqueues on st; for m > 512 it also synchronises st once per 128 pivots.
 struct GhPstrf {

@@ -1,6 +1,7 @@
 // gh_device_util.h -- small device helpers with ONE definition for the one-problem kernels (gh_kmat.hip, gh_chol_solve.hip) and
 // their batched forms (gh_batch.hip), which claim the same bits; and (hw_*) for the HODLR units whose kernels reduce over a
-// workgroup of any size: gh_hodlr.hip, gh_hodlr_aca.hip, gh_hodlr_apply.hip
+// workgroup of any size: gh_hodlr.hip, gh_hodlr_aca.hip, gh_hodlr_apply.hip.  (The column reduction of predict needs none of
+// them -- a thread per column -- and has its one definition in gh_predict.hip.)
 #pragma once
 #include <hip/hip_runtime.h>
 

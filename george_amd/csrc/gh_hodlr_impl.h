@@ -2,7 +2,8 @@
 //   gh_hodlr.hip          the factorisation: handle, tree, leaf stage, Gauss-Jordan and core kernels, compaction, compute()
 //   gh_hodlr_aca.hip      the ACA kernels (a workgroup or a cluster per node; a wavefront per node) and their launchers
 //   gh_hodlr_apply.hip    applying a factor to right-hand sides: the small dense products, apply / solve, solve .. get_inverse
-//   gh_hodlr_predict.hip  predict and the likelihood gradient on a computed factor, over column strips
+//   gh_hodlr_predict.hip  predict and the likelihood gradient on a computed factor, over column strips (predict's strip loop and
+//                         column reduction are the ones all solvers share: gh_predict.hip, declared in gh_common.h)
 //   gh_hodlr_mgpu.hip     the tree split over several devices (gh_hodlr_mgpu_*)
 // A kernel is launched only from the unit that defines it; what another unit needs of it is a launcher declared here.
 #pragma once

@@ -6,7 +6,8 @@
 // gh_hodlr_predict / gh_hodlr_grad (include/george_amd.h): the GP glue around apply_inverse (gp.py:482-545, :429-466) without
 // the M x N and N x N host arrays of the generic branch.  Both walk over COLUMN STRIPS: an n x Ct row-major block is built on the
 // device (cross-covariances, or columns of the identity), hodlr_solve_all() turns it into K^-1 times itself in place, and one
-// reduction kernel consumes it; only M- or P-vectors reach the host.
+// reduction kernel consumes it; only M- or P-vectors reach the host.  predict's walk is the driver every solver shares
+// (gh_predict_strips, gh_predict.hip): what is its own is alpha, the strip width and how a strip becomes K^-1 times itself.
 //
 // HODLR_STRIP_BYTES is what ONE strip of n x Ct doubles may take: 512 MiB.  predict holds two strips (K(x, xs_J) and K^-1 of
 // it), grad one, so the calls need at most 1 GiB beyond the factor whatever M or n is.  At n = 262 144 it gives Ct = 256 = CPASS
@@ -30,43 +31,6 @@ static long strip_cols(long n, long need) {
   return std::max<long>(ct, 64);
 }
 
-// Two-operand column reduction: for the cw columns of a strip (row pitch ld) and the rows of chunk blockIdx.y,
-//   pmu[chunk][j] = sum_i Kx[i][j] alpha[i],   pvar[chunk][j] = sum_i Kx[i][j] W[i][j]   (W == nullptr: the mean only)
-// A thread per column: a wavefront reads 64 consecutive doubles of a row of each operand, alpha[i] is a uniform load.
-__global__ __launch_bounds__(64) void hodlr_colred2_kernel(const double* __restrict__ Kx, const double* __restrict__ W, long ld, long n,
-                                                           long rows_per, const double* __restrict__ alpha, int cw,
-                                                           double* __restrict__ pmu, double* __restrict__ pvar, long ldp) {
-  const int j = blockIdx.x * 64 + threadIdx.x;
-  if (j >= cw) return;
-  const long r0 = (long)blockIdx.y * rows_per, r1 = r0 + rows_per < n ? r0 + rows_per : n;
-  double smu = 0.0, sv = 0.0;
-  if (W) {
-#pragma unroll 4
-    for (long i = r0; i < r1; ++i) {
-      const double a = Kx[i * ld + j];
-      smu += a * alpha[i];
-      sv += a * W[i * ld + j];
-    }
-    pvar[(long)blockIdx.y * ldp + j] = sv;
-  } else {
-#pragma unroll 4
-    for (long i = r0; i < r1; ++i) smu += Kx[i * ld + j] * alpha[i];
-  }
-  pmu[(long)blockIdx.y * ldp + j] = smu;
-}
-// the chunk partials added in chunk order: mu[j] = sum, var[j] = var[j] (holding k(xs_j, xs_j)) - sum
-__global__ __launch_bounds__(64) void hodlr_colfinal2_kernel(const double* __restrict__ pmu, const double* __restrict__ pvar, long nchunks, long ldp,
-                                                             int cw, double* __restrict__ mu, double* __restrict__ var) {
-  const int j = blockIdx.x * 64 + threadIdx.x;
-  if (j >= cw) return;
-  double smu = 0.0, sv = 0.0;
-  for (long c = 0; c < nchunks; ++c) smu += pmu[c * ldp + j];
-  mu[j] = smu;
-  if (var) {
-    for (long c = 0; c < nchunks; ++c) sv += pvar[c * ldp + j];
-    var[j] = var[j] - sv;
-  }
-}
 // The rectangular strip form of kgrad_reduce_kernel (gh_kmat.hip): W = K^-1 E_J for the columns J = [col0, col0 + cw) (row pitch
 // ld); workgroup (blockIdx.x, blockIdx.y) takes the 64 x 64 tile of rows 64 blockIdx.x .. and strip columns 64 blockIdx.y .. and
 // writes ONE partial row  1/2 sum_{i, j in tile} (alpha_i alpha_j - W[i][j - col0]) dK(x_i, x_j)/dtheta_p.  Every (i, j) of the
@@ -155,64 +119,22 @@ extern "C" int gh_hodlr_predict(gh_hodlr* h, gh_kernel* k, const double* r, cons
   const long n = h->n;
   const int passes = hodlr_passes();
   hipStream_t st = h->st;
-  GhPooledBuf al, xsd, sK, sW, part, res, kss;
+  GhPooledBuf al, xsd;
   GH_CHECK(solve_alpha(h, r, al));
-  const double* xs_dev = xs;
-  if (!gh_is_device_ptr(xs)) {
-    GH_CHECK(xsd.ensure((size_t)m * h->ndim * sizeof(double)));
-    GH_CHECK(gh_to_device(xsd.d(), xs, (size_t)m * h->ndim, st));
-    xs_dev = xsd.d();
-  }
-  // with cov, all of Kx and W stay resident for the product: one strip of mp columns over np rows (GhGemm: M, N multiples of
-  // 128, K of 16; the padding is zero).  Without, strips of Ct columns.
-  const long mp = gh_round_up(m, 128), np = cov ? gh_round_up(n, 16) : n;
-  const long Ct = cov ? mp : strip_cols(n, m);
-  const size_t strip_bytes = (size_t)np * Ct * sizeof(double);
-  const bool want_w = var || cov;
-  if (sK.ensure(strip_bytes) != GH_OK || (want_w && sW.ensure(strip_bytes) != GH_OK) || (cov && kss.ensure((size_t)mp * mp * sizeof(double)) != GH_OK)) {
-    if (cov) gh_set_error("predict: the covariance keeps K(x, xs) and K^-1 K(x, xs) on the device, 2 x %zu bytes for n = %ld, m = %ld, and they do not "
-                          "fit; ask for the variance or for fewer test points at a time", strip_bytes, n, (long)m);
-    return GH_ERR_NOMEM;
-  }
-  const long nchunks = std::min<long>(HODLR_RED_CHUNKS, (n + HODLR_RED_ROWS - 1) / HODLR_RED_ROWS);
-  const long rows_per = (n + nchunks - 1) / nchunks;
-  GH_CHECK(part.ensure((size_t)2 * nchunks * Ct * sizeof(double)));
-  GH_CHECK(res.ensure((size_t)2 * m * sizeof(double)));
-  double* pmu = part.d();
-  double* pvar = pmu + nchunks * Ct;
-  double* dmu = res.d();
-  double* dvar = dmu + m;
-  if (var) GH_CHECK(gh_launch_kdiag(k, xs_dev, xs_dev, m, dvar, st));           // gp.py:539
-  for (long j0 = 0; j0 < m; j0 += Ct) {
-    const int cw = (int)std::min<long>(Ct, m - j0);
-    // Kx = K(x, xs_J), n x Ct row-major (columns past cw, rows past n: zero)
-    GH_CHECK(gh_launch_kmat(k, h->x.d(), n, xs_dev + j0 * h->ndim, cw, nullptr, sK.d(), Ct, np, Ct, 0, 0, false, false, st));
-    if (want_w) {
-      // W = K^-1 Kx on a second copy   (gp.py:541, 544: apply_inverse(Kxs.T))
-      GH_HIP(hipMemcpyAsync(sW.p, sK.p, strip_bytes, hipMemcpyDeviceToDevice, st));
-      GH_CHECK(hodlr_solve_all(h, passes, sW.d(), Ct, cw));
-    }
-    hipLaunchKernelGGL(hodlr_colred2_kernel, dim3((unsigned)((cw + 63) / 64), (unsigned)nchunks), dim3(64), 0, st,
-                       (const double*)sK.d(), var ? (const double*)sW.d() : (const double*)nullptr, Ct, n, rows_per,
-                       (const double*)al.d(), cw, pmu, pvar, Ct);
-    hipLaunchKernelGGL(hodlr_colfinal2_kernel, dim3((unsigned)((cw + 63) / 64)), dim3(64), 0, st, (const double*)pmu, (const double*)pvar,
-                       nchunks, Ct, cw, dmu + j0, var ? dvar + j0 : (double*)nullptr);
-    GH_HIP(hipGetLastError());
-  }
-  GH_CHECK(gh_from_device(mu, dmu, (size_t)m, st));
-  if (var) GH_CHECK(gh_from_device(var, dvar, (size_t)m, st));
-  if (cov) {
-    // cov = K(xs, xs) - Kx^T W      (gp.py:543-545; not a V^T V form: the HODLR inverse is not exactly symmetric)
-    GH_CHECK(gh_launch_kmat(k, xs_dev, m, xs_dev, m, nullptr, kss.d(), mp, mp, mp, 0, 0, true, false, st));
-    GhGemm g{};
-    g.C = kss.d(); g.ldc = mp; g.A = sK.d(); g.lda = mp; g.B = sW.d(); g.ldb = mp;
-    g.M = mp; g.N = mp; g.K = np; g.alpha = -1.0; g.beta = 1.0; g.a_km = false; g.b_km = false;
-    GH_CHECK(gh_launch_gemm(g, st));
-    GH_HIP(hipMemcpy2DAsync(cov, m * sizeof(double), kss.d(), mp * sizeof(double), m * sizeof(double), m,
-                            gh_is_device_ptr(cov) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
-  }
-  GH_HIP(hipStreamSynchronize(st));
-  return GH_OK;
+  const double* xs_dev = nullptr;
+  GH_CHECK(gh_stage_points(xs, m, h->ndim, xsd, st, &xs_dev));
+  // W = K^-1 Kx on a second copy   (gp.py:541, 544: apply_inverse(Kxs.T)); the moments are Kx . W, not a V^T V form: the HODLR
+  // inverse is not exactly symmetric
+  const int rc = gh_predict_strips(k, h->x.d(), n, h->ndim, al.d(), xs_dev, m, strip_cols(n, m), HODLR_RED_ROWS, HODLR_RED_CHUNKS, mu, var, cov,
+                                   st, true, [&](const double* sK, double* sW, int64_t ld, int64_t, int cw, size_t strip_bytes) -> int {
+    GH_HIP(hipMemcpyAsync(sW, sK, strip_bytes, hipMemcpyDeviceToDevice, st));
+    return hodlr_solve_all(h, passes, sW, ld, cw);
+  });
+  if (rc == GH_ERR_NOMEM && cov)
+    gh_set_error("predict: the covariance keeps K(x, xs) and K^-1 K(x, xs) on the device, 2 x %zu bytes for n = %ld, m = %ld, and they do not "
+                 "fit; ask for the variance or for fewer test points at a time",
+                 (size_t)gh_round_up(n, 16) * gh_round_up(m, 128) * sizeof(double), n, (long)m);
+  return rc;
 }
 
 extern "C" int gh_hodlr_grad(gh_hodlr* h, gh_kernel* k, const uint32_t* which, const double* r,

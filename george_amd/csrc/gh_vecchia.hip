@@ -300,35 +300,6 @@ __global__ __launch_bounds__(256) void vecchia_diag_kernel(const double* __restr
   for (long long q = tptr[j]; q < tptr[j + 1]; ++q) s += wd[(long)trow[q] * (m + 1) + tslot[q]];
   diagA[j] = s;
 }
-// predict: for the cw columns of a strip (row pitch ld) and the rows of chunk blockIdx.y
-//   pmu[chunk][j] = sum_i Kx[i][j] alpha[i],   pvar[chunk][j] = sum_i V[i][j]^2   (V == nullptr: the mean only)
-__global__ __launch_bounds__(64) void vecchia_colred_kernel(const double* __restrict__ Kx, const double* __restrict__ V, long ld, long n,
-                                                            long rows_per, const double* __restrict__ alpha, int cw,
-                                                            double* __restrict__ pmu, double* __restrict__ pvar, long ldp) {
-  const int j = blockIdx.x * 64 + threadIdx.x;
-  if (j >= cw) return;
-  const long r0 = (long)blockIdx.y * rows_per, r1 = r0 + rows_per < n ? r0 + rows_per : n;
-  double smu = 0.0, sv = 0.0;
-  for (long i = r0; i < r1; ++i) smu += Kx[i * ld + j] * alpha[i];
-  pmu[(long)blockIdx.y * ldp + j] = smu;
-  if (V) {
-    for (long i = r0; i < r1; ++i) { const double v = V[i * ld + j]; sv += v * v; }
-    pvar[(long)blockIdx.y * ldp + j] = sv;
-  }
-}
-// the chunk partials added in chunk order: mu[j] = sum, var[j] = var[j] (holding k(xs_j, xs_j)) - sum
-__global__ __launch_bounds__(64) void vecchia_colfinal_kernel(const double* __restrict__ pmu, const double* __restrict__ pvar, long nchunks,
-                                                              long ldp, int cw, double* __restrict__ mu, double* __restrict__ var) {
-  const int j = blockIdx.x * 64 + threadIdx.x;
-  if (j >= cw) return;
-  double smu = 0.0, sv = 0.0;
-  for (long c = 0; c < nchunks; ++c) smu += pmu[c * ldp + j];
-  mu[j] = smu;
-  if (var) {
-    for (long c = 0; c < nchunks; ++c) sv += pvar[c * ldp + j];
-    var[j] = var[j] - sv;
-  }
-}
 
 // ================================================================================ host side
 extern "C" int gh_vecchia_create(const gh_vecchia_opts* opts, gh_vecchia** out) {
@@ -580,75 +551,32 @@ extern "C" int gh_vecchia_predict(gh_vecchia* h, gh_kernel* k, const double* r, 
   GH_CHECK(k->upload());
   const long n = (long)h->n;
   hipStream_t st = h->st;
-  GhPooledBuf rd, tmp, al, xsd, sK, sV, part, res, kss;
+  GhPooledBuf rd, tmp, al, xsd;
   GH_CHECK(rd.ensure((size_t)n * sizeof(double)));
   GH_CHECK(tmp.ensure((size_t)n * sizeof(double)));
   GH_CHECK(al.ensure((size_t)n * sizeof(double)));
   GH_CHECK(gh_to_device(rd.d(), r, (size_t)n, st));
   GH_CHECK(v_apply_q(h, rd.d(), 1L, tmp.d(), al.d()));
-  const double* xs_dev = xs;
-  if (!gh_is_device_ptr(xs)) {
-    GH_CHECK(xsd.ensure((size_t)m * h->ndim * sizeof(double)));
-    GH_CHECK(gh_to_device(xsd.d(), xs, (size_t)m * h->ndim, st));
-    xs_dev = xsd.d();
-  }
-  // with cov, K(x, xs) and V stay whole for the product: one strip of mp columns over np rows (GhGemm: M, N multiples of 128, K of
-  // 16; the padding is zero).  Without, strips of Ct test points.
-  const bool want_v = var || cov;
-  const long mp = gh_round_up(m, 128), np = cov ? gh_round_up(n, 16) : n;
-  long Ct = mp;
+  const double* xs_dev = nullptr;
+  GH_CHECK(gh_stage_points(xs, m, h->ndim, xsd, st, &xs_dev));
   if (cov) {
+    const long mp = gh_round_up(m, 128), np = gh_round_up(n, 16);
     const double need = 2.0 * 8.0 * (double)np * (double)mp + 8.0 * (double)mp * (double)mp;
     if (need > (double)V_COV_BYTES) {
       gh_set_error("predict: the covariance keeps K(x, xs), V and the m x m result on the device, %.3g bytes for n = %ld, m = %ld, over the "
                    "budget of %ld; ask for the variance or for fewer test points at a time", need, n, (long)m, (long)V_COV_BYTES);
       return GH_ERR_NOMEM;
     }
-  } else {
-    Ct = std::max<long>(1, std::min<long>(V_STRIP_COLS, V_STRIP_BYTES / (16 * n)));
-    Ct = std::min<long>(Ct, m);
   }
-  const size_t strip_bytes = (size_t)np * Ct * sizeof(double);
-  GH_CHECK(sK.ensure(strip_bytes));
-  if (want_v) GH_CHECK(sV.ensure(strip_bytes));
-  if (cov) GH_CHECK(kss.ensure((size_t)mp * mp * sizeof(double)));
-  const long nchunks = std::min<long>(V_RED_CHUNKS, (n + V_RED_ROWS - 1) / V_RED_ROWS);
-  const long rows_per = (n + nchunks - 1) / nchunks;
-  GH_CHECK(part.ensure((size_t)2 * nchunks * Ct * sizeof(double)));
-  GH_CHECK(res.ensure((size_t)2 * m * sizeof(double)));
-  double* pmu = part.d();
-  double* pvar = pmu + nchunks * Ct;
-  double* dmu = res.d();
-  double* dvar = dmu + m;
-  if (var) GH_CHECK(gh_launch_kdiag(k, xs_dev, xs_dev, m, dvar, st));
-  if (cov) GH_HIP(hipMemsetAsync(sV.p, 0, strip_bytes, st));                  // (rows n .. np of V)
-  for (long j0 = 0; j0 < m; j0 += Ct) {
-    const int cw = (int)std::min<long>(Ct, m - j0);
-    // Kx = K(x, xs_J), np x Ct row-major (columns past cw, rows past n: zero)
-    GH_CHECK(gh_launch_kmat(k, h->x.d(), n, xs_dev + j0 * h->ndim, cw, nullptr, sK.d(), Ct, np, Ct, 0, 0, false, false, st));
-    if (want_v)                                              // V = F^-1/2 (I - B) Kx
-      hipLaunchKernelGGL(vecchia_fwd_kernel, dim3(v_blocks((size_t)n * Ct)), dim3(256), 0, st, (const double*)h->B.d(), (const double*)h->f.d(),
-                         (const int*)h->nbr.p, (const int*)h->cnt.p, n, h->opts.m, (const double*)sK.d(), Ct, Ct, sV.d(), Ct, 2);
-    hipLaunchKernelGGL(vecchia_colred_kernel, dim3((unsigned)((cw + 63) / 64), (unsigned)nchunks), dim3(64), 0, st, (const double*)sK.d(),
-                       var ? (const double*)sV.d() : (const double*)nullptr, Ct, n, rows_per, (const double*)al.d(), cw, pmu, pvar, Ct);
-    hipLaunchKernelGGL(vecchia_colfinal_kernel, dim3((unsigned)((cw + 63) / 64)), dim3(64), 0, st, (const double*)pmu, (const double*)pvar,
-                       nchunks, Ct, cw, dmu + j0, var ? dvar + j0 : (double*)nullptr);
+  const long Ct = std::min<long>(std::max<long>(1, std::min<long>(V_STRIP_COLS, V_STRIP_BYTES / (16 * n))), m);
+  // V = F^-1/2 (I - B) Kx: the moments are V . V
+  return gh_predict_strips(k, h->x.d(), n, h->ndim, al.d(), xs_dev, m, Ct, V_RED_ROWS, V_RED_CHUNKS, mu, var, cov, st, false,
+                           [&](const double* sK, double* sV, int64_t ld, int64_t, int, size_t) -> int {
+    hipLaunchKernelGGL(vecchia_fwd_kernel, dim3(v_blocks((size_t)n * ld)), dim3(256), 0, st, (const double*)h->B.d(), (const double*)h->f.d(),
+                       (const int*)h->nbr.p, (const int*)h->cnt.p, n, h->opts.m, sK, (long)ld, (long)ld, sV, (long)ld, 2);
     GH_HIP(hipGetLastError());
-  }
-  GH_CHECK(gh_from_device(mu, dmu, (size_t)m, st));
-  if (var) GH_CHECK(gh_from_device(var, dvar, (size_t)m, st));
-  if (cov) {
-    // cov = K(xs, xs) - V^T V
-    GH_CHECK(gh_launch_kmat(k, xs_dev, m, xs_dev, m, nullptr, kss.d(), mp, mp, mp, 0, 0, true, false, st));
-    GhGemm g{};
-    g.C = kss.d(); g.ldc = mp; g.A = sV.d(); g.lda = mp; g.B = sV.d(); g.ldb = mp;
-    g.M = mp; g.N = mp; g.K = np; g.alpha = -1.0; g.beta = 1.0; g.a_km = false; g.b_km = false;
-    GH_CHECK(gh_launch_gemm(g, st));
-    GH_HIP(hipMemcpy2DAsync(cov, m * sizeof(double), kss.d(), mp * sizeof(double), m * sizeof(double), m,
-                            gh_is_device_ptr(cov) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
-  }
-  GH_HIP(hipStreamSynchronize(st));
-  return GH_OK;
+    return GH_OK;
+  });
 }
 
 // The query table of predict_local checked and compacted on the host, as v_index does with compute's: every entry of a row is -1
@@ -688,13 +616,7 @@ static int v_local_inputs(gh_vecchia* h, gh_kernel* k_data, gh_kernel* k_cross, 
   if (k_cross != k_data) GH_CHECK(k_cross->upload());
   GH_CHECK(rd.ensure((size_t)h->n * sizeof(double)));
   GH_CHECK(gh_to_device(rd.d(), r, (size_t)h->n, h->st));
-  *xs_dev = xs;
-  if (!gh_is_device_ptr(xs)) {
-    GH_CHECK(xsd.ensure((size_t)M * h->ndim * sizeof(double)));
-    GH_CHECK(gh_to_device(xsd.d(), xs, (size_t)M * h->ndim, h->st));
-    *xs_dev = xsd.d();
-  }
-  return GH_OK;
+  return gh_stage_points(xs, M, h->ndim, xsd, h->st, xs_dev);
 }
 // Tail: the kernel over the device table qt (valid entries first) with the row counts qc, the failure flag, mu and var back.
 static int v_local_run(gh_vecchia* h, gh_kernel* k_data, gh_kernel* k_cross, const double* rd, const double* xs_dev, int64_t M,

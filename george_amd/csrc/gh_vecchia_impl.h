@@ -1,5 +1,6 @@
 // gh_vecchia_impl.h -- what the Vecchia units share: the solver handle (gh_vecchia.hip) and the nearest-neighbour search on a
-// cell grid (gh_vecchia_search.hip).  Private to the library.
+// cell grid (gh_vecchia_search.hip).  Private to the library.  predict through Q runs on the strip driver all solvers share
+// (gh_predict.hip, declared in gh_common.h).
 #pragma once
 #include <vector>
 #include "gh_common.h"

@@ -248,6 +248,27 @@ def test_more_workgroups_than_the_chip_holds():
     _check("grad: diagA", diagA, ref.diagA, tol["diagA"])
 
 
+def test_predict_strips():
+    """N = 700, 3-D, m = 32, 600 test points: without a covariance predict walks them in strips of 256 + 256 + 88, and the column
+    sums over 6 chunks of 117 rows, the last one short.  A column's value depends on no other column -- not in the forward
+    operator, not in the sums -- and a strip only changes the row pitch: every prefix of the test points gives the bits of the full
+    call, mean and variance alike, with or without the variance.  The covariance goes through the GEMM: to tolerance."""
+    kernel, x, yerr, r, _ = _problem("expsq_3d", 700)
+    tol = _tol("expsq_3d", 700)
+    t = np.random.RandomState(600).uniform(0, 2, (600, 3))
+    solver = VecchiaSolver(kernel, m=32)
+    solver.compute(x, yerr)
+    mu, var, _ = solver.predict(kernel, r, t, return_var=True)
+    cov = solver.predict(kernel, r, t, return_cov=True)[2]
+    for k in (1, 255, 256, 257, 512, 513, 600):
+        mu_k, var_k, _ = solver.predict(kernel, r, t[:k], return_var=True)
+        assert np.array_equal(mu_k, mu[:k]) and np.array_equal(var_k, var[:k]), k
+        mu_m, var_m, _ = solver.predict(kernel, r, t[:k])
+        assert np.array_equal(mu_m, mu[:k]) and var_m is None, k
+        if k < 600:
+            _check("predict M=%d: covariance" % k, solver.predict(kernel, r, t[:k], return_cov=True)[2], cov[:k, :k], tol["cov"])
+
+
 def test_two_runs_give_the_same_bits():
     kernel, x, yerr, r, xs = _problem("expsq_3d", 777)
     which = np.ones(len(kernel), dtype=np.uint32)
