@@ -12,11 +12,11 @@ from . import _native                     # noqa: F401  (raises ImportError if t
 from . import kernels
 from .gp import GP
 from .metrics import Metric
-from .solvers import TrivialSolver, BasicSolver, HODLRSolver, MultiGPUSolver, MultiGPUHODLRSolver, VecchiaSolver
+from .solvers import TrivialSolver, BasicSolver, HODLRSolver, MultiGPUSolver, MultiGPUHODLRSolver, VecchiaSolver, InducingSolver
 from .kernel_interface import KernelInterface
 
 __all__ = ["__version__", "kernels", "GP", "Metric", "TrivialSolver", "BasicSolver",
-           "HODLRSolver", "MultiGPUSolver", "MultiGPUHODLRSolver", "VecchiaSolver", "KernelInterface"]
+           "HODLRSolver", "MultiGPUSolver", "MultiGPUHODLRSolver", "VecchiaSolver", "InducingSolver", "KernelInterface"]
 
 
 def device_count():

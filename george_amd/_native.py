@@ -54,6 +54,10 @@ class gh_vecchia_opts(C.Structure):
     _fields_ = [("device", C.c_int32), ("m", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class gh_inducing_opts(C.Structure):
+    _fields_ = [("device", C.c_int32), ("method", C.c_int32), ("strip_points", C.c_int32), ("reserved", C.c_int32)]
+
+
 class gh_mgpu_opts(C.Structure):
     _fields_ = [("n_dev", C.c_int32), ("devices", C.c_int32 * 16), ("pr", C.c_int32), ("pc", C.c_int32),
                 ("nb", C.c_int32), ("transport", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 3)]
@@ -206,6 +210,14 @@ SIGNATURES = {
     "gh_vecchia_predict_local": (C.c_int, [_vp, _vp, _vp, _dp, _dp, _i64, _dp, _i32, _dp, _dp]),
     "gh_vecchia_search": (C.c_int, [_i32, _dp, _i64, _i32, _dp, _i64, _dp, _i32, _i32, _dp]),
     "gh_vecchia_predict_local_search": (C.c_int, [_vp, _vp, _vp, _dp, _dp, _i64, _i32, _i32, _dp, _dp, _dp]),
+    "gh_inducing_create": (C.c_int, [C.POINTER(gh_inducing_opts), C.POINTER(_vp)]),
+    "gh_inducing_destroy": (None, [_vp]),
+    "gh_inducing_info": (_i64, [_vp]),
+    "gh_inducing_compute": (C.c_int, [_vp, _vp, _dp, _i64, _i32, _dp, _dp, _i64, C.c_double, C.POINTER(C.c_double)]),
+    "gh_inducing_solve": (C.c_int, [_vp, _dp, _i64, _dp]),
+    "gh_inducing_dot_solve": (C.c_int, [_vp, _dp, C.POINTER(C.c_double)]),
+    "gh_inducing_grad": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _dp, _dp]),
+    "gh_inducing_predict": (C.c_int, [_vp, _vp, _dp, _dp, _i64, _dp, _dp, _dp]),
     "gh_mgpu_create": (C.c_int, [C.POINTER(gh_mgpu_opts), C.POINTER(_vp)]),
     "gh_mgpu_destroy": (None, [_vp]),
     "gh_mgpu_compute": (C.c_int, [_vp, _vp, _dp, _i64, _i32, _dp, C.POINTER(C.c_double)]),

@@ -131,6 +131,9 @@ int gh_launch_potf2_mfma(double* A, int64_t lda, double* dinv, long long* info, 
 // out[0] (+)= 2 * sum_i log(A[i][i]); part: RED_SLICES doubles.  accumulate: one workgroup, out[0] += (the tile ABI's form)
 int gh_launch_logdet(const double* A, long lda, long n, double* out, double* part, hipStream_t st);
 int gh_launch_logdet_accum(const double* A, long lda, long n, double* out, hipStream_t st);
+// Linv (np x np) <- L^-1 for a factor L of pitch np (np a multiple of 128) with the inverses dinv of its diagonal blocks, as
+// gh_chol_potrf_block leaves them: forward substitution on the identity in GEMMs, no handle (gh_chol's own L^-1, and gh_inducing.hip)
+int gh_chol_linv(hipStream_t st, const double* L, const double* dinv, int64_t np, double* Linv);
 // z = L^-1 w / x = L^-T w as one chained launch; flags[nt] = the time-out flag (cleared here).  w is read only and must not be
 // the output (which is pre-filled with the sentinel).
 int gh_launch_trsv_fwd_chain(const double* L, long ld, const double* dinv, int64_t nt, const double* w, double* z, unsigned* flags, hipStream_t st);

@@ -671,16 +671,17 @@ extern "C" int gh_chol_dot_solve(gh_chol* s, const double* y, double* out) {
 // the super-block -- the right-hand side is swept N/(128*SB) times instead of N/128 times.
 // `tri`: B is the identity being overwritten by L^-1 (forward only): block row j is non-zero in
 // columns [0, (j+1)*128) only, so every product is clipped to those columns.
-static int trsm_multi(gh_chol* s, double* B, int64_t rp, bool forward, bool backward, bool tri = false) {
+// (_on: on any factor L of pitch np with its diagonal-block inverses dinv; trsm_multi below is the handle's own)
+static int trsm_multi_on(hipStream_t st, const double* L, const double* dinv, int64_t np, double* B, int64_t rp, bool forward, bool backward,
+                         bool tri) {
   // (tiles per super-block; measured at N = 32768 with 4096 right-hand sides, both sweeps: 2 -> 167 ms, 4 -> 158.5,
   //  8 -> 151.6, 16 -> 149.5; no difference at N = 8192; the switch that overrode it went in round 4)
   const int64_t SB = 8;
-  const int64_t np = s->np, nt = np / T;
-  const double* L = s->A.d();
+  const int64_t nt = np / T;
   auto mm = [&](double* Cp, const double* Ap, int64_t lda, bool a_km, const double* Bp, int64_t M, int64_t N, int64_t K,
                 double alpha, double beta) -> int {
     if (M <= 0 || N <= 0) return GH_OK;
-    return gh_launch_gemm(gemm_desc(Cp, rp, Ap, lda, a_km, Bp, rp, false, M, N, K, alpha, beta), s->st);
+    return gh_launch_gemm(gemm_desc(Cp, rp, Ap, lda, a_km, Bp, rp, false, M, N, K, alpha, beta), st);
   };
   if (forward) {
     for (int64_t J = 0; J < nt; J += SB) {
@@ -688,7 +689,7 @@ static int trsm_multi(gh_chol* s, double* B, int64_t rp, bool forward, bool back
       for (int64_t j = J; j < Je; ++j) {
         double* Bj = B + j * T * rp;
         const int64_t nc = tri ? (j + 1) * T : rp;
-        GH_CHECK(mm(Bj, s->dinv.d() + j * T * T, T, true, Bj, T, nc, T, 1.0, 0.0));               // B_j <- L_jj^-1 B_j
+        GH_CHECK(mm(Bj, dinv + j * T * T, T, true, Bj, T, nc, T, 1.0, 0.0));                        // B_j <- L_jj^-1 B_j
         GH_CHECK(mm(B + (j + 1) * T * rp, L + (j + 1) * T * np + j * T, np, true, Bj,
                     (Je - j - 1) * T, nc, T, -1.0, 1.0));                                           // rows of the super-block
       }
@@ -702,13 +703,16 @@ static int trsm_multi(gh_chol* s, double* B, int64_t rp, bool forward, bool back
       const int64_t J = std::max<int64_t>(Je - SB, 0);
       for (int64_t j = Je - 1; j >= J; --j) {
         double* Bj = B + j * T * rp;
-        GH_CHECK(mm(Bj, s->dinv.d() + j * T * T, T, false, Bj, T, rp, T, 1.0, 0.0));              // B_j <- L_jj^-T B_j
+        GH_CHECK(mm(Bj, dinv + j * T * T, T, false, Bj, T, rp, T, 1.0, 0.0));                       // B_j <- L_jj^-T B_j
         GH_CHECK(mm(B + J * T * rp, L + j * T * np + J * T, np, false, Bj, (j - J) * T, rp, T, -1.0, 1.0));
       }
       GH_CHECK(mm(B, L + J * T * np, np, false, B + J * T * rp, J * T, rp, (Je - J) * T, -1.0, 1.0));   // everything above
     }
   }
   return GH_OK;
+}
+static int trsm_multi(gh_chol* s, double* B, int64_t rp, bool forward, bool backward, bool tri = false) {
+  return trsm_multi_on(s->st, s->A.d(), s->dinv.d(), s->np, B, rp, forward, backward, tri);
 }
 
 extern "C" int gh_chol_solve(gh_chol* s, const double* b, int64_t nrhs, double* out) {
@@ -752,14 +756,15 @@ extern "C" int gh_chol_apply_sqrt(gh_chol* s, const double* r, int64_t nrows, do
   return GH_OK;
 }
 
-// Linv (np x np) <- L^-1: forward substitution on the identity, exploiting the lower-triangular right-hand side (tri = true)
-static int linv_into(gh_chol* s, double* Linv) {
-  const int64_t np = s->np;
-  GH_HIP(hipMemsetAsync(Linv, 0, (size_t)np * np * sizeof(double), s->st));
-  hipLaunchKernelGGL(eye_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s->st, Linv, (long)np, (long)np);
+// Linv (np x np) <- L^-1: forward substitution on the identity, exploiting the lower-triangular right-hand side (tri = true).
+// Handle-free (declared in gh_chol_impl.h): the inducing-point solver inverts its two m x m factors with it.
+int gh_chol_linv(hipStream_t st, const double* L, const double* dinv, int64_t np, double* Linv) {
+  GH_HIP(hipMemsetAsync(Linv, 0, (size_t)np * np * sizeof(double), st));
+  hipLaunchKernelGGL(eye_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, Linv, (long)np, (long)np);
   GH_HIP(hipGetLastError());
-  return trsm_multi(s, Linv, np, true, false, true);
+  return trsm_multi_on(st, L, dinv, np, Linv, np, true, false, true);
 }
+static int linv_into(gh_chol* s, double* Linv) { return gh_chol_linv(s->st, s->A.d(), s->dinv.d(), s->np, Linv); }
 // W (np x np) <- K^-1, lower triangle valid.  Uses K^-1 = L^-T L^-1:
 //   Linv = L^-1 (forward substitution on the identity), K^-1 = Linv^T Linv (k >= max(i, j)).
 static int inverse_lower(gh_chol* s, double* W /* np*np */, double* Linv /* np*np scratch */) {

@@ -6,5 +6,6 @@ from .basic import BasicSolver
 from .hodlr import HODLRSolver
 from .multigpu import MultiGPUSolver, MultiGPUHODLRSolver
 from .vecchia import VecchiaSolver
+from .inducing import InducingSolver
 
-__all__ = ["TrivialSolver", "BasicSolver", "HODLRSolver", "MultiGPUSolver", "MultiGPUHODLRSolver", "VecchiaSolver"]
+__all__ = ["TrivialSolver", "BasicSolver", "HODLRSolver", "MultiGPUSolver", "MultiGPUHODLRSolver", "VecchiaSolver", "InducingSolver"]

@@ -1,0 +1,262 @@
+"""``InducingSolver`` -- the inducing-point approximations DTC and FITC on one MI355X, for smooth kernels on data sets no
+N x N factor fits: 10^5 - 10^6 points, a few hundred to a few thousand inducing inputs.
+
+The covariance is replaced by a low-rank term through ``m`` inducing inputs ``u`` plus a diagonal,
+``C = K_fu (K_uu + jitter I)^-1 K_uf + diag(lambda)``, with ``lambda_i = yerr_i^2`` (DTC) or ``yerr_i^2`` plus the variance the
+low-rank term leaves at ``x_i`` (FITC).  O(N m^2) flops in GEMM shapes, O(m^2) memory beside the data: the data points pass
+through the device in strips.  It is the complement of :class:`VecchiaSolver`: near-exact where the kernel is smooth (which is
+where the nearest-neighbour likelihood stays percents off), mediocre for rough kernels (where Vecchia converges fast).  Rule of
+thumb: smooth kernel, inducing points; rough kernel, Vecchia; and check one against the other.  With ``u = x`` and no jitter
+both methods are the dense likelihood up to rounding.  No reference counterpart.  The definition is in ``include/george_amd.h``,
+the device side in ``george_amd/csrc/gh_inducing.hip``.
+
+Prediction is the same for both methods, O(M m^2) whatever N.
+
+``jitter`` is relative: the device gets ``jitter * mean_j k(u_j, u_j)`` on the diagonal of ``K_uu``, and the likelihood gradient
+treats that number as a constant.
+
+Not built: the selection of the inducing points on the device (:func:`inducing_points` is O(N m) NumPy on the host),
+``apply_sqrt``, variational (VFE) bounds, optimising the inducing locations, and a multi-device form.
+"""
+import atexit
+import ctypes as C
+import hashlib
+
+import numpy as np
+
+from .. import _native as N
+from .protocol import NativeSolver, rhs_matrix, rhs_vector
+
+__all__ = ["InducingSolver", "inducing_points"]
+
+M_MAX = 8192
+METHODS = {"dtc": 0, "fitc": 1}
+
+
+def inducing_points(x, m):
+    """The indices of ``min(m, N)`` of the points ``x`` chosen by greedy max-min distance: the point nearest the centroid
+    first, then each time the point whose smallest squared Euclidean distance to the chosen ones is largest, ties going to
+    the lower index.  O(N m) on the host.  Returns an int64 array in the order chosen."""
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim == 1:
+        x = x[:, None]
+    if x.ndim != 2:
+        raise ValueError("x must be (nsamples, ndim)")
+    m = int(m)
+    if m < 1:
+        raise ValueError("m must be at least 1")
+    n = len(x)
+    k = min(m, n)
+    idx = np.empty(k, dtype=np.int64)
+    if n == 0:
+        return idx
+    d2 = ((x - x.mean(axis=0)) ** 2).sum(axis=1)
+    idx[0] = np.argmin(d2)                                  # (argmin / argmax return the first of equals: the lower index)
+    dmin = ((x - x[idx[0]]) ** 2).sum(axis=1)
+    for j in range(1, k):
+        idx[j] = np.argmax(dmin)
+        np.minimum(dmin, ((x - x[idx[j]]) ** 2).sum(axis=1), out=dmin)
+    return idx
+
+
+class InducingSolver(NativeSolver):
+    """``InducingSolver(kernel, inducing=512, method="fitc", jitter=1e-10, device=0, strip_points=0)``.
+
+    ``inducing``: an (m, ndim) array of inducing inputs, or an int ``m``: ``min(m, N)`` of the data points chosen by
+    :func:`inducing_points` (kept per data set, so an optimiser pays for the selection once); 1 <= m <= 8192.  ``method``:
+    ``"dtc"`` or ``"fitc"``.  ``jitter``: relative to the mean of ``k(u_j, u_j)``.  ``strip_points``: data points per
+    strip on the device, 0 for a choice by memory budget (results do not depend on it beyond rounding).
+
+    A factorisation that fails raises ``numpy.linalg.LinAlgError`` like the other solvers, naming the factor;
+    ``failed_factor`` is then ``"K_uu"`` or ``"A"`` and ``failed_pivot`` its 0-based pivot."""
+
+    def __init__(self, kernel, inducing=512, method="fitc", jitter=1e-10, device=0, strip_points=0):
+        if method not in METHODS:
+            raise ValueError("InducingSolver: method is 'dtc' or 'fitc'")
+        jitter = float(jitter)
+        if not jitter >= 0.0:
+            raise ValueError("InducingSolver: jitter must not be negative")
+        strip_points = int(strip_points)
+        if strip_points < 0:
+            raise ValueError("InducingSolver: strip_points must not be negative")
+        if np.ndim(inducing) == 0:
+            inducing = int(inducing)
+            if inducing < 1 or inducing > M_MAX:
+                raise ValueError("InducingSolver: 1 <= m <= {0}, not {1}".format(M_MAX, inducing))
+        else:
+            inducing = N.as_f64(inducing)
+            if inducing.ndim == 1:
+                inducing = inducing[:, None]
+            if inducing.ndim != 2 or not 1 <= len(inducing) <= M_MAX:
+                raise ValueError("InducingSolver: inducing must be (m, ndim) with 1 <= m <= {0}".format(M_MAX))
+        self.inducing = inducing
+        self.method = method
+        self.jitter = jitter
+        self.failed_factor = None
+        self.failed_pivot = None
+        self.u = None                                       # the inducing inputs of the last compute()
+        self._iopts = dict(device=int(device), method=METHODS[method], strip_points=strip_points)
+        super(InducingSolver, self).__init__(kernel)
+
+    # The default inducing set depends on the inputs and m only, and GP makes a new solver for every compute (one per iterate
+    # of an optimiser): the last selections are kept, keyed by a digest of the inputs.
+    _TABLES = []
+    _TABLES_MAX = 2
+
+    def _default_points(self, x):
+        key = (x.shape, self.inducing, hashlib.blake2b(memoryview(x).cast("B"), digest_size=16).digest())
+        for k, idx in InducingSolver._TABLES:
+            if k == key:
+                return idx
+        idx = inducing_points(x, self.inducing)
+        InducingSolver._TABLES.append((key, idx))
+        del InducingSolver._TABLES[:-InducingSolver._TABLES_MAX]
+        return idx
+
+    # -- lifetime.  The handle of a dropped solver (its m x m buffers on the device) is parked, at most _HPOOL_MAX per
+    # (device, method, strip_points), and picked up by the next solver with the same options.
+    _HPOOL = {}
+    _HPOOL_MAX = 2
+
+    def _ensure_handle(self):
+        if self._handle is None:
+            self._hkey = (self._iopts["device"], self._iopts["method"], self._iopts["strip_points"])
+            free = InducingSolver._HPOOL.get(self._hkey)
+            if free:
+                self._handle = free.pop()
+                return self._handle
+            o = N.gh_inducing_opts()
+            o.device, o.method, o.strip_points = self._hkey
+            h = N._vp()
+            N.check(N.lib.gh_inducing_create(C.byref(o), C.byref(h)))
+            self._handle = h
+        return self._handle
+
+    def _destroy_handle(self):
+        h, self._handle = getattr(self, "_handle", None), None
+        if h is not None and h.value:
+            N.lib.gh_inducing_destroy(h)
+
+    def __del__(self):
+        try:
+            h, self._handle = getattr(self, "_handle", None), None
+            if h is not None and h.value:
+                free = InducingSolver._HPOOL.setdefault(self._hkey, [])
+                if len(free) < InducingSolver._HPOOL_MAX:
+                    free.append(h)
+                else:
+                    N.lib.gh_inducing_destroy(h)
+        except Exception:
+            pass
+
+    @classmethod
+    def release_pool(cls):
+        """Destroy every parked native handle (frees their device memory)."""
+        for free in cls._HPOOL.values():
+            while free:
+                try:
+                    N.lib.gh_inducing_destroy(free.pop())
+                except Exception:
+                    pass
+        cls._HPOOL.clear()
+
+    def _release_parked_memory(self):
+        self._destroy_handle()
+        InducingSolver.release_pool()
+        N.lib.gh_release_caches(self._iopts["device"])
+
+    def compute(self, x, yerr):
+        x, yerr, _ = self._check_inputs(x, yerr)
+        n = len(x)
+        self.failed_factor = self.failed_pivot = None
+        if isinstance(self.inducing, int):
+            u = np.ascontiguousarray(x[self._default_points(x)])
+        else:
+            u = self.inducing
+            if u.shape[1] != x.shape[1]:
+                raise ValueError("InducingSolver: inducing must be (m, {0})".format(x.shape[1]))
+        m = len(u)
+        kd = np.empty(m)
+        N.check(N.lib.gh_kernel_value_diagonal(self._dk.handle, N.ptr(u), N.ptr(u), m, N.ptr(kd)))
+        jitter = self.jitter * float(np.mean(kd))
+        logdet = C.c_double(0.0)
+        self._n, self.u = n, u
+
+        def run(h):
+            rc = N.lib.gh_inducing_compute(h, self._dk.handle, N.ptr(x), n, x.shape[1], N.ptr(yerr), N.ptr(u), m, jitter, C.byref(logdet))
+            if rc == N.GH_ERR_NOT_PD:
+                info = int(N.lib.gh_inducing_info(h))
+                self.failed_factor, self.failed_pivot = ("K_uu" if info > 0 else "A"), abs(info) - 1
+                raise np.linalg.LinAlgError("InducingSolver: the factorisation of {0} failed at pivot {1} ({2}); raise jitter (now {3:g})"
+                                            .format("K_uu + jitter I" if info > 0 else "A = I + V Lambda^-1 V^T", self.failed_pivot,
+                                                    N.last_error(), self.jitter))
+            N.check(rc)
+
+        self._retry_without_parked_memory(run)
+        self._log_det = logdet.value
+        self.computed = True
+
+    # -- the solver protocol
+    def apply_inverse(self, y, in_place=False):
+        """``C^-1 y`` for ``y`` of shape (n,) or (n, nrhs); ``in_place`` writes the values back into a writable array ``y``."""
+        h = self._need()
+        yc, nrhs = rhs_matrix(y, self._n)
+        out = np.empty_like(yc)
+        if nrhs > 0:
+            N.check(N.lib.gh_inducing_solve(h, N.ptr(yc), nrhs, N.ptr(out)))
+        if in_place and isinstance(y, np.ndarray) and y.flags.writeable:
+            try:
+                y[...] = out
+                return y
+            except (ValueError, TypeError):
+                pass
+        return out
+
+    def dot_solve(self, y):
+        """``y^T C^-1 y = sum_i y_i^2 / lambda_i - |t(y)|^2``."""
+        h = self._need()
+        y = rhs_vector(y, self._n)
+        out = C.c_double(0.0)
+        N.check(N.lib.gh_inducing_dot_solve(h, N.ptr(y), C.byref(out)))
+        return out.value
+
+    def apply_sqrt(self, r):
+        raise NotImplementedError("apply_sqrt is not implemented for the InducingSolver")
+
+    def get_inverse(self):
+        """``C^-1`` as a dense matrix: ``apply_inverse`` of the identity.  N^2 memory: meant for small N."""
+        self._need()
+        return self.apply_inverse(np.eye(self._n))
+
+    # -- device-resident GP glue
+    def grad(self, r, which):
+        """``BasicSolver.grad``'s ``(kgrad_full, alpha, diagA)`` for the DTC / FITC likelihood: the gradient over ALL kernel
+        parameters (masked ones 0), ``alpha = C^-1 r`` and ``diagA_i = alpha_i^2 - (C^-1)_ii``.  With ``u = x`` and no jitter
+        these are the dense values."""
+        h = self._need()
+        r = rhs_vector(r, self._n)
+        which = np.ascontiguousarray(which, dtype=np.uint32)
+        g = np.zeros(max(self._dk.size, 1))
+        alpha, diagA = np.empty(self._n), np.empty(self._n)
+        N.check(N.lib.gh_inducing_grad(h, self._dk.handle, N.ptr(which), N.ptr(r), N.ptr(g), N.ptr(alpha), N.ptr(diagA)))
+        return g[:self._dk.size], alpha, diagA
+
+    def predict(self, kernel, r, xs, return_var=False, return_cov=False):
+        """The predictive mean and (optionally) variance or covariance at ``xs``, the same for DTC and FITC, in strips of
+        test points.  The covariance keeps three M x m blocks and the M x M result on the device and raises ``MemoryError``
+        over its budget."""
+        h = self._need()
+        dk = self._kernel_for(kernel)
+        r, xs = rhs_vector(r, self._n), N.as_f64(xs)
+        want_var = bool(return_var)
+        want_cov = bool(return_cov) and not want_var
+        m = len(xs)
+        mu = np.empty(m)
+        var = np.empty(m) if want_var else None
+        cov = np.empty((m, m)) if want_cov else None
+        if m > 0:
+            N.check(N.lib.gh_inducing_predict(h, dk.handle, N.ptr(r), N.ptr(xs), m, N.ptr(mu), N.ptr(var), N.ptr(cov)))
+        return mu, var, cov
+
+
+atexit.register(InducingSolver.release_pool)

@@ -536,6 +536,51 @@ int  gh_vecchia_predict_local_search(gh_vecchia* h, gh_kernel* k_data, gh_kernel
                                      const double* xs, int64_t M, int32_t mq, int32_t occupancy,
                                      double* mu /* M */, double* var /* M or NULL */, int32_t* table_out /* M*mq or NULL */);
 
+/* ------------------------------------------------------------ inducing-point solver
+ * The low-rank approximations DTC and FITC through m inducing inputs u, the complement of the Vecchia solver: near-exact for
+ * smooth kernels, mediocre for rough ones.  With s_i = yerr_i^2, K_uu the symmetric build over u (the lower index is the first
+ * argument) and K_fu = K(x, u) (the data point is the first argument):
+ *   K_uu + jitter I = L_u L_u^T,   V = L_u^-1 K_uf (m x n),   q_i = |V[:, i]|^2,
+ *   lambda_i = s_i + phi max(k(x_i, x_i) - q_i, 0)      (phi = 0: DTC, 1: FITC),
+ *   C = V^T V + diag(lambda)  -- the model covariance --,   A = I + V Lambda^-1 V^T = L_A L_A^T,   H = L_A^-1 V,
+ *   log|C| = sum_i log lambda_i + 2 sum_j log (L_A)_jj,   t(b) = H Lambda^-1 b,
+ *   C^-1 b = Lambda^-1 b - Lambda^-1 H^T t(b),   b^T C^-1 b = sum_i b_i^2 / lambda_i - |t(b)|^2.
+ * O(n m^2) flops in GEMM shapes; nothing of size n x m is kept: the data points pass in strips, and the handle holds about five
+ * m x m matrices (m padded to a multiple of 128; 2.7 GB at the cap m = 8192).  No reference counterpart.  Sums have a fixed
+ * order (strips ascending on one stream): two calls give the same bits.  (george_amd/csrc/gh_inducing.hip)
+ * x, yerr, u, b, y, r, xs and the array results out, grad, alpha, diagA, mu, var, cov are host or device memory ("Pointer kinds"
+ * at the top of this file); *logdet_out, *out of gh_inducing_dot_solve and which are host memory. */
+typedef struct gh_inducing gh_inducing;
+typedef struct gh_inducing_opts {
+  int32_t device;
+  int32_t method;        /* 0: DTC, 1: FITC */
+  int32_t strip_points;  /* data points per strip: 0 = from a byte budget, else rounded up to a multiple of 128 */
+  int32_t reserved;
+} gh_inducing_opts;
+/* GH_ERR_BAD_ARG for a method other than 0 / 1 or a negative strip_points (host check, before any device is touched) */
+int  gh_inducing_create(const gh_inducing_opts* opts, gh_inducing** out);
+void gh_inducing_destroy(gh_inducing* h);
+/* After GH_ERR_NOT_PD: +p when pivot p (1-based) of K_uu + jitter I failed, -p when pivot p of A failed; else 0. */
+int64_t gh_inducing_info(const gh_inducing* h);
+/* u: (m, ndim), 1 <= m <= 8192 (GH_ERR_BAD_ARG otherwise, a host check); jitter >= 0 is absolute.  A pivot of K_uu + jitter I or
+ * of A that is not positive: GH_ERR_NOT_PD, gh_inducing_info() says which, and the handle is not computed. */
+int  gh_inducing_compute(gh_inducing* h, gh_kernel* k, const double* x, int64_t n, int32_t ndim, const double* yerr,
+                         const double* u, int64_t m, double jitter, double* logdet_out);
+int  gh_inducing_solve(gh_inducing* h, const double* b, int64_t nrhs, double* out);   /* out = C^-1 b; (n, nrhs) row-major */
+int  gh_inducing_dot_solve(gh_inducing* h, const double* y, double* out);             /* y^T C^-1 y */
+/* The likelihood gradient in the layout of gh_chol_grad: alpha = C^-1 r, diagA_i = alpha_i^2 - (C^-1)_ii, and with
+ * P = K_uu^-1 K_uf (K_uu with its jitter), T = (P alpha) alpha^T - P C^-1, Z = T - phi P diag(diagA), W = -1/2 Z P^T:
+ *   grad[p] = sum_ij Z_ji dk(x_i, u_j)/dtheta_p + sum_jj' W_jj' dk(u_j, u_j')/dtheta_p + 1/2 phi sum_i diagA_i dk(x_i, x_i)/dtheta_p
+ * (parameters not selected by `which`: exactly 0; the clamp in lambda counts as inactive).  k: the kernel of compute(). */
+int  gh_inducing_grad(gh_inducing* h, gh_kernel* k, const uint32_t* which, const double* r,
+                      double* grad /* size */, double* alpha /* n or NULL */, double* diagA /* n or NULL */);
+/* The same for DTC and FITC: with V* = L_u^-1 K(u, xs), H* = L_A^-1 V*:  mu = H*^T t(r),
+ * var = diag K(xs,xs) - colsumsq(V*) + colsumsq(H*),  cov = K(xs,xs) - V*^T V* + H*^T H*.  O(M m^2) whatever n, in strips of
+ * test points; var / cov may be NULL (not both non-NULL); cov keeps its operands whole: GH_ERR_NOMEM over the strip budget.  k
+ * may differ from the kernel of compute(). */
+int  gh_inducing_predict(gh_inducing* h, gh_kernel* k, const double* r /* n: y - mean */, const double* xs, int64_t M,
+                         double* mu /* M */, double* var /* M or NULL */, double* cov /* M*M or NULL */);
+
 /* --------------------------------------------------- dense solver on several GPUs
  * The BasicSolver protocol of /root/reference/src/george/solvers/basic.py:51-102 (compute, log-determinant,
  * dot_solve, apply_inverse) for ONE process that owns several MI355X: 2-D block-cyclic tiles (tile (I, J)
