@@ -29,40 +29,10 @@ from george_amd.solvers.inducing import inducing_points
 
 import inducing_ref
 import vecchia_ref
+from inducing_cases import GAP_CAP, GAP_MAX_N, JITTER, _check, _check_grad, _check_predict, _problem, tolerances
 from oracle import solver_np
 
 pytestmark = pytest.mark.gpu
-
-EPS = np.finfo(np.float64).eps
-CAPS = {"logdet": 1e-10, "quad": 1e-9, "ll": 1e-9}
-GAP_CAP = 1e-9
-GAP_MAX_N = 800
-JITTER = {"expsq_1d": 1e-8}
-
-
-def _kernel(name):
-    """(kernel, ndim, amplitude); comp_3d takes the interpreter, has six parameters and one of them frozen"""
-    if name == "m32_3d":
-        return 1.3 * kernels.Matern32Kernel(0.6, ndim=3), 3, np.sqrt(1.3)
-    if name == "m32_1d":
-        return 1.7 * kernels.Matern32Kernel(0.8), 1, np.sqrt(1.7)
-    if name == "expsq_1d":
-        return 0.9 * kernels.ExpSquaredKernel(0.5), 1, np.sqrt(0.9)
-    k = 0.8 * kernels.Matern32Kernel([0.5, 0.7, 0.9], ndim=3) + 0.3 * kernels.ExpSquaredKernel(0.6, ndim=3)
-    k.freeze_parameter(k.get_parameter_names()[2])
-    return k, 3, 1.0
-
-
-@functools.lru_cache(maxsize=None)
-def _problem(name, n):
-    """(kernel, x, yerr, r, xs): error bars 0.1 .. 0.15 of the amplitude, 300 test points"""
-    kernel, ndim, amp = _kernel(name)
-    rng = np.random.RandomState(1000 * ndim + n)
-    x = np.sort(rng.uniform(0, 10, n))[:, None] if ndim == 1 else rng.uniform(0, 2, (n, ndim))
-    yerr = amp * (0.1 + 0.05 * rng.rand(n))
-    r = amp * (np.sin(3.0 * x.sum(axis=1)) + 0.3 * rng.randn(n))
-    xs = rng.uniform(0, 10 if ndim == 1 else 2, (300, ndim))
-    return kernel, x, yerr, r, xs
 
 
 @functools.lru_cache(maxsize=None)
@@ -83,7 +53,7 @@ def _setup(name, n, m, method, inducing="maxmin"):
     g["ll"] = g["quad"]
     print("gaps", name, n, m, method, {key: "%.1e" % v for key, v in g.items()})
     assert max(g.values()) <= GAP_CAP, "the problem is too ill-conditioned for these tests: replace it"
-    tol = {key: min(1000.0 * max(v, 4 * EPS), CAPS.get(key, np.inf)) for key, v in g.items()}
+    tol = tolerances(g)
     return u, rel_jitter, jitter, ref, tol
 
 
@@ -93,37 +63,6 @@ def _solver(name, n, m, method, strip, inducing="maxmin"):
     s = InducingSolver(kernel, inducing=u, method=method, jitter=rel_jitter, strip_points=strip)
     s.compute(x, yerr)
     return s
-
-
-def _check(what, got, want, tol, scale=None):
-    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-    scale = np.max(np.abs(want)) if scale is None else scale
-    err = np.max(np.abs(got - want) / np.maximum(scale, np.finfo(float).tiny))
-    print("%-26s error %.3g  bound %.3g" % (what, err, tol))
-    assert err <= tol, (what, err, tol)
-
-
-def _check_grad(s, kernel, r, ref, tol):
-    mask = kernel.unfrozen_mask
-    g, alpha, diagA = s.grad(r, mask.astype(np.uint32))
-    assert len(g) == len(mask) and np.all(g[~mask] == 0.0)
-    _check("grad: kernel", g[mask], ref.kgrad[mask], tol["kgrad"], scale=ref.S[mask])
-    _check("grad: alpha", alpha, ref.alpha, tol["alpha"])
-    _check("grad: diagA", diagA, ref.diagA, tol["diagA"])
-    return g, alpha, diagA
-
-
-def _check_predict(s, kernel, r, xs, ref, tol, m_list):
-    out = None
-    for mm in m_list:
-        mu0, var0, cov0 = ref.predict(kernel, xs[:mm])
-        mu, var, cov = s.predict(kernel, r, xs[:mm], return_var=True)
-        assert cov is None
-        _check("predict M=%d: mean" % mm, mu, mu0, tol["mu"])
-        _check("  .. variance", var, var0, tol["var"])
-        assert np.array_equal(s.predict(kernel, r, xs[:mm])[0], mu)
-        out = (mu, var)
-    return out
 
 
 CASES = [("m32_3d", 1, "fitc"), ("m32_3d", 127, "fitc"), ("m32_3d", 128, "dtc"), ("m32_3d", 129, "fitc"), ("m32_3d", 129, "dtc"),
@@ -198,7 +137,7 @@ def test_every_point_an_inducing_point_is_the_dense_solver(method):
              kgrad=float(np.max(np.abs(ref.kgrad - d["kgrad"]) / d["S"])), mu=inducing_ref.rel(ref.predict(kernel, xs)[0], d["mu"]),
              var=inducing_ref.rel(ref.predict(kernel, xs)[1], d["var"]))
     print("gaps", g)
-    tol = {key: min(1000.0 * max(v, 4 * EPS), CAPS.get(key, np.inf)) for key, v in g.items()}
+    tol = tolerances(g)
     s = InducingSolver(kernel, inducing=x, method=method, jitter=0.0)
     s.compute(x, yerr)
     b = BasicSolver(kernel)

@@ -1,5 +1,6 @@
 """The inducing-point solver on the host: the NumPy restatement (tests/inducing_ref.py) against LAPACK on the explicit matrix
-``C`` and against central differences of itself, ``u = x`` against the dense GP, the max-min selection against a brute-force
+``C`` and against central differences of itself, its block-wise gradient route against the stacked one, the bound of the device
+tests against deliberately wrong gradients, ``u = x`` against the dense GP, the max-min selection against a brute-force
 loop, the accuracy claim against the Vecchia restatement, the solver protocol before ``compute``, the inputs that are refused,
 and the argument checks of the C ABI.  No device is touched."""
 import ctypes
@@ -18,6 +19,7 @@ from george_amd.solvers.inducing import inducing_points
 from george_amd.solvers.protocol import NativeSolver
 from george_amd.solvers.vecchia import vecchia_neighbors
 
+import inducing_cases
 import inducing_ref
 import vecchia_ref
 from oracle import solver_np
@@ -96,6 +98,68 @@ def test_every_point_an_inducing_point_is_the_dense_gp(name, n, method):
     assert abs(ref.log_likelihood() - ll) <= 1e-11 * abs(ll)
     assert inducing_ref.rel(ref.alpha, d["alpha"]) <= 1e-10 and inducing_ref.rel(ref.diagA, d["diagA"]) <= 1e-10
     assert np.max(np.abs(ref.kgrad - d["kgrad"]) / d["S"]) <= 1e-12
+
+
+@pytest.mark.parametrize("method", ["dtc", "fitc"])
+def test_blockwise_gradient_equals_the_stacked_one(method):
+    """N = 300 (blocks of 256 + 44 points), m = 60, six parameters: the two routes add the same terms in another grouping.
+    Observed: 3e-17 of ``S``; asserted at 4 eps, the least the tolerance rule takes two CPU routes to differ by."""
+    kernel, x, yerr, r = _problem("comp_3d", 300)
+    u = x[inducing_points(x, 60)]
+    jitter = 1e-10 * np.mean(solver_np.kernel_matrix(kernel, u, diag=True))
+    a = inducing_ref.reference(kernel, x, yerr, u, jitter, method, r=r, want_grad=True)
+    b = inducing_ref.reference(kernel, x, yerr, u, jitter, method, r=r, want_grad=True, route="blocks")
+    assert inducing_ref.BLOCK < 300 and a.kgrad.shape == b.kgrad.shape == (6,)
+    assert np.array_equal(a.alpha, b.alpha) and np.array_equal(a.diagA, b.diagA)
+    print(np.abs(a.kgrad - b.kgrad) / a.S, np.abs(a.S - b.S) / a.S)
+    assert np.all(np.abs(a.kgrad - b.kgrad) <= 4 * inducing_cases.EPS * a.S)
+    # S is a sum of 300 * 60 + 60^2 + 300 non-negative terms and only a scale: any order of adding n such terms is within n eps
+    assert np.all(np.abs(a.S - b.S) <= (300 * 60 + 60 * 60 + 300) * inducing_cases.EPS * a.S)
+    with pytest.raises(ValueError):
+        inducing_ref.reference(kernel, x, yerr, u, jitter, method, r=r, want_grad=True, route="tiles")
+    with pytest.raises(ValueError):
+        inducing_ref.reference(kernel, x, yerr, u, jitter, method, r=r, want_grad=True, defect="none")
+
+
+def test_a_kernel_without_parameters():
+    """``gaps`` and both routes on the DotProductKernel: an empty gradient, a gap of 0"""
+    kernel, x, yerr, r, xs, u = inducing_cases.dot_problem()
+    for method in ("dtc", "fitc"):
+        jitter, ref, tol = inducing_cases.bounds("dot", kernel, x, yerr, r, xs, u, 1e-10, method)
+        assert ref.kgrad.shape == ref.S.shape == (0,) and tol["kgrad"] == 4000 * inducing_cases.EPS
+        b = inducing_ref.reference(kernel, x, yerr, u, jitter, method, r=r, want_grad=True, route="blocks")
+        assert b.kgrad.shape == (0,) and np.array_equal(b.diagA, ref.diagA)
+
+
+# Where a defect changes the gradient at all: the FITC ones under FITC, the 4096-point one beyond 4096 points.
+def _applies(defect, method, n):
+    if defect in ("fitc_first_4096", "fitc_weight_one", "z_phi_zero") and method == "dtc":
+        return False
+    return defect != "fitc_first_4096" or n > inducing_ref.DIAG_POINTS
+
+
+@pytest.mark.parametrize("method", ["dtc", "fitc"])
+@pytest.mark.parametrize("case", [4, 64, "N4200"])
+def test_the_bound_of_the_device_tests_rejects_every_defect(case, method):
+    """The problems of tests/test_gpu_inducing_grad.py at P = 4 and P = 64 (N = 300, m = 65) and at N = 4200 (m = 65, 273 000
+    pairs), with the bound those tests put on the gradient -- 1000 x the gap of the two CPU routes, over ``S``: every wrong
+    gradient of ``inducing_ref.DEFECTS`` is further from the restatement than that, the single missing pair included.  A
+    defect that cannot change the gradient of a problem (``_applies``) must leave every bit of it."""
+    if case == "N4200":
+        kernel, x, yerr, r, xs, u = inducing_cases.m32_case(4200, 65)
+        _, jitter, ref, tol = inducing_cases.m32_bounds(4200, 65, method)
+    else:
+        kernel, x, yerr, r, xs, u = inducing_cases.pcase(case)
+        _, jitter, ref, tol = inducing_cases.pcase_bounds(case, method)
+    route = "blocks" if len(x) > inducing_cases.GAP_MAX_N else "stacked"
+    for defect in inducing_ref.DEFECTS:
+        bad = inducing_ref.reference(kernel, x, yerr, u, jitter, method, r=r, want_grad=True, route=route, defect=defect)
+        err = float(np.max(np.abs(bad.kgrad - ref.kgrad) / ref.S))
+        print("%-16s error %.3g  bound %.3g" % (defect, err, tol["kgrad"]))
+        if _applies(defect, method, len(x)):
+            assert err > tol["kgrad"], (defect, err, tol["kgrad"])
+        else:
+            assert np.array_equal(bad.kgrad, ref.kgrad), defect
 
 
 # ------------------------------------------------------------------ the selection of inducing points
