@@ -218,6 +218,7 @@ SIGNATURES = {
     "gh_inducing_dot_solve": (C.c_int, [_vp, _dp, C.POINTER(C.c_double)]),
     "gh_inducing_grad": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _dp, _dp]),
     "gh_inducing_predict": (C.c_int, [_vp, _vp, _dp, _dp, _i64, _dp, _dp, _dp]),
+    "gh_inducing_select": (C.c_int, [_i32, _dp, _i64, _i32, _i64, _i64, _dp, _dp]),
     "gh_mgpu_create": (C.c_int, [C.POINTER(gh_mgpu_opts), C.POINTER(_vp)]),
     "gh_mgpu_destroy": (None, [_vp]),
     "gh_mgpu_compute": (C.c_int, [_vp, _vp, _dp, _i64, _i32, _dp, C.POINTER(C.c_double)]),

@@ -15,8 +15,11 @@ Prediction is the same for both methods, O(M m^2) whatever N.
 ``jitter`` is relative: the device gets ``jitter * mean_j k(u_j, u_j)`` on the diagonal of ``K_uu``, and the likelihood gradient
 treats that number as a constant.
 
-Not built: the selection of the inducing points on the device (:func:`inducing_points` is O(N m) NumPy on the host),
-``apply_sqrt``, variational (VFE) bounds, optimising the inducing locations, and a multi-device form.
+The default inducing set is greedy max-min distance over the data (:func:`inducing_points`): O(N m) NumPy on the host by
+default, or ``select="device"``: one streaming kernel per pick (``george_amd/csrc/gh_inducing_select.hip``) that returns the
+same points for up to 7 input dimensions.
+
+Not built: ``apply_sqrt``, variational (VFE) bounds, optimising the inducing locations, and a multi-device form.
 """
 import atexit
 import ctypes as C
@@ -33,10 +36,17 @@ M_MAX = 8192
 METHODS = {"dtc": 0, "fitc": 1}
 
 
-def inducing_points(x, m):
+def inducing_points(x, m, device=None, return_dmin=False):
     """The indices of ``min(m, N)`` of the points ``x`` chosen by greedy max-min distance: the point nearest the centroid
     first, then each time the point whose smallest squared Euclidean distance to the chosen ones is largest, ties going to
-    the lower index.  O(N m) on the host.  Returns an int64 array in the order chosen."""
+    the lower index.  Returns an int64 array in the order chosen; with ``return_dmin`` also every point's squared distance
+    to the chosen set (N doubles; its maximum is the squared fill distance).  ``m`` has no cap: ``m >= N`` orders all points.
+
+    ``device``: ``None`` selects on the host, O(N m) NumPy on one thread; an integer runs ``gh_inducing_select`` on that
+    device (one streaming kernel per pick; the first point still comes from the host, one pass over ``x``): the same
+    sequence and the same ``dmin`` bit for bit for up to 7 input dimensions, and from 8 on the greedy sequence under the
+    device's left-to-right sum of squares, where NumPy adds pairwise.  The device route raises ``ValueError`` for ``x`` that
+    is not finite and ``RuntimeError`` without a device."""
     x = np.asarray(x, dtype=np.float64)
     if x.ndim == 1:
         x = x[:, None]
@@ -49,30 +59,41 @@ def inducing_points(x, m):
     k = min(m, n)
     idx = np.empty(k, dtype=np.int64)
     if n == 0:
-        return idx
+        return (idx, np.empty(0)) if return_dmin else idx
+    if device is not None and not np.isfinite(x).all():
+        raise ValueError("inducing_points: the device selection needs finite x")
     d2 = ((x - x.mean(axis=0)) ** 2).sum(axis=1)
+    if device is not None:
+        x = np.ascontiguousarray(x)
+        dmin = np.empty(n) if return_dmin else None
+        N.check(N.lib.gh_inducing_select(int(device), N.ptr(x), n, x.shape[1], int(np.argmin(d2)), m, N.ptr(idx), N.ptr(dmin)))
+        return (idx, dmin) if return_dmin else idx
     idx[0] = np.argmin(d2)                                  # (argmin / argmax return the first of equals: the lower index)
     dmin = ((x - x[idx[0]]) ** 2).sum(axis=1)
     for j in range(1, k):
         idx[j] = np.argmax(dmin)
         np.minimum(dmin, ((x - x[idx[j]]) ** 2).sum(axis=1), out=dmin)
-    return idx
+    return (idx, dmin) if return_dmin else idx
 
 
 class InducingSolver(NativeSolver):
-    """``InducingSolver(kernel, inducing=512, method="fitc", jitter=1e-10, device=0, strip_points=0)``.
+    """``InducingSolver(kernel, inducing=512, method="fitc", jitter=1e-10, device=0, strip_points=0, select="host")``.
 
     ``inducing``: an (m, ndim) array of inducing inputs, or an int ``m``: ``min(m, N)`` of the data points chosen by
     :func:`inducing_points` (kept per data set, so an optimiser pays for the selection once); 1 <= m <= 8192.  ``method``:
     ``"dtc"`` or ``"fitc"``.  ``jitter``: relative to the mean of ``k(u_j, u_j)``.  ``strip_points``: data points per
-    strip on the device, 0 for a choice by memory budget (results do not depend on it beyond rounding).
+    strip on the device, 0 for a choice by memory budget (results do not depend on it beyond rounding).  ``select``: where
+    an int ``inducing`` is turned into points, ``"host"`` (NumPy) or ``"device"`` (``gh_inducing_select`` on the solver's
+    device: the same points for up to 7 input dimensions).
 
     A factorisation that fails raises ``numpy.linalg.LinAlgError`` like the other solvers, naming the factor;
     ``failed_factor`` is then ``"K_uu"`` or ``"A"`` and ``failed_pivot`` its 0-based pivot."""
 
-    def __init__(self, kernel, inducing=512, method="fitc", jitter=1e-10, device=0, strip_points=0):
+    def __init__(self, kernel, inducing=512, method="fitc", jitter=1e-10, device=0, strip_points=0, select="host"):
         if method not in METHODS:
             raise ValueError("InducingSolver: method is 'dtc' or 'fitc'")
+        if select not in ("host", "device"):
+            raise ValueError("InducingSolver: select is 'host' or 'device'")
         jitter = float(jitter)
         if not jitter >= 0.0:
             raise ValueError("InducingSolver: jitter must not be negative")
@@ -92,23 +113,25 @@ class InducingSolver(NativeSolver):
         self.inducing = inducing
         self.method = method
         self.jitter = jitter
+        self.select = select
         self.failed_factor = None
         self.failed_pivot = None
         self.u = None                                       # the inducing inputs of the last compute()
         self._iopts = dict(device=int(device), method=METHODS[method], strip_points=strip_points)
         super(InducingSolver, self).__init__(kernel)
 
-    # The default inducing set depends on the inputs and m only, and GP makes a new solver for every compute (one per iterate
-    # of an optimiser): the last selections are kept, keyed by a digest of the inputs.
+    # The default inducing set depends on the inputs, m and the route only (from 8 dimensions on the two routes may differ), and
+    # GP makes a new solver for every compute (one per iterate of an optimiser): the last selections are kept, keyed by a digest
+    # of the inputs.
     _TABLES = []
     _TABLES_MAX = 2
 
     def _default_points(self, x):
-        key = (x.shape, self.inducing, hashlib.blake2b(memoryview(x).cast("B"), digest_size=16).digest())
+        key = (x.shape, self.inducing, self.select, hashlib.blake2b(memoryview(x).cast("B"), digest_size=16).digest())
         for k, idx in InducingSolver._TABLES:
             if k == key:
                 return idx
-        idx = inducing_points(x, self.inducing)
+        idx = inducing_points(x, self.inducing, device=self._iopts["device"] if self.select == "device" else None)
         InducingSolver._TABLES.append((key, idx))
         del InducingSolver._TABLES[:-InducingSolver._TABLES_MAX]
         return idx

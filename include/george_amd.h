@@ -580,6 +580,22 @@ int  gh_inducing_grad(gh_inducing* h, gh_kernel* k, const uint32_t* which, const
  * may differ from the kernel of compute(). */
 int  gh_inducing_predict(gh_inducing* h, gh_kernel* k, const double* r /* n: y - mean */, const double* xs, int64_t M,
                          double* mu /* M */, double* var /* M or NULL */, double* cov /* M*M or NULL */);
+/* The greedy max-min selection of inducing points on the device (george_amd/csrc/gh_inducing_select.hip); it needs no solver
+ * handle.  idx[0] = first and dmin_i = +inf; for j = 1, 2, ..., min(m, n) - 1: dmin_i = min(dmin_i, d2(x_i, x_idx[j-1])), then
+ * idx[j] = the index of the largest dmin, ties going to the LOWER index; data with fewer distinct points than picks is no special
+ * case (every dmin is 0 and index 0 wins).  After the last pick dmin is updated once more: dmin_out (n doubles, host or device
+ * memory, or NULL) is every point's squared distance to the chosen set and its maximum the squared fill distance.  That is the
+ * rule of inducing_points() in george_amd/solvers/inducing.py, whose choice of `first` (the point nearest the centroid) stays
+ * with the caller.  d2 = sum_k (x_ik - c_k)^2 from k = 0 on without fused multiply-adds: for ndim <= 7 the double NumPy's
+ * ((x - c)**2).sum(-1) gives, so the sequence is the host routine's; for more dimensions NumPy adds in another order and the
+ * result is the greedy sequence under THIS distance.  A d2 that is not a number never lowers a dmin.  m is not capped: m >= n
+ * gives a max-min ordering of all n points.  One kernel launch per pick on one stream, no host synchronisation between them;
+ * O(n m) work, n (8 ndim + 8) bytes on the device beside x.  x may be host or device memory; idx_out (min(m, n) int64) is host
+ * memory.  Host checks before any device call: GH_ERR_BAD_ARG for m < 1, n < 0, n > 0x7ffffff0, a null idx_out, a null x with
+ * n > 0, or first outside [0, n) when n > 0; GH_ERR_DIM for ndim outside 1 .. GH_MAX_NDIM; n == 0 writes nothing and touches no
+ * device.  Two calls give the same bits. */
+int  gh_inducing_select(int32_t device, const double* x, int64_t n, int32_t ndim, int64_t first, int64_t m,
+                        int64_t* idx_out /* min(m, n) */, double* dmin_out /* n or NULL */);
 
 /* --------------------------------------------------- dense solver on several GPUs
  * The BasicSolver protocol of /root/reference/src/george/solvers/basic.py:51-102 (compute, log-determinant,
