@@ -9,20 +9,31 @@ keep the GP glue of ``gp.py:482-545`` / ``:429-466`` device-resident;
 :class:`george_amd.GP` uses them when present, the reference GP simply ignores
 them.
 """
-import atexit
 import ctypes as C
 
 import numpy as np
 
 from .. import _native as N
 from ..program import DeviceKernel
-from .protocol import NativeSolver, rhs_vector
+from .protocol import HandlePool, NativeSolver, rhs_vector
 
 __all__ = ["BasicSolver"]
 
 
+def _fits_the_byte_budget(h):
+    """The admission rule of BasicSolver's pool: a handle is parked as it is while the pool stays under _POOL_MAX_BYTES (read
+    now: it may have been rebound), else trimmed to its factor-sized buffers, and refused when even that does not fit."""
+    size = lambda hh: int(N.lib.gh_chol_device_bytes(hh))
+    room = BasicSolver._POOL_MAX_BYTES - sum(size(p) for free in BasicSolver._POOL.values() for p in free)
+    if size(h) <= room:
+        return True                        # as it is: the next iterate re-uses the work arrays too
+    N.lib.gh_chol_trim(h)                  # keep the factor-sized buffers, drop the work arrays
+    return size(h) <= room
+
+
 class BasicSolver(NativeSolver):
 
+    _CREATE, _DESTROY = "gh_chol_create", "gh_chol_destroy"
     _SOLVE, _DOT_SOLVE, _GET_INVERSE, _APPLY_SQRT = "gh_chol_solve", "gh_chol_dot_solve", "gh_chol_get_inverse", "gh_chol_apply_sqrt"
 
     def __init__(self, kernel, device=0, nb=0, profile=False, lookahead=True):
@@ -41,90 +52,32 @@ class BasicSolver(NativeSolver):
     # the separate calls in round 2's driver run); above that budget it is trimmed to its factor,
     # and above it still it is destroyed.  At most _POOL_MAX handles are parked per option set;
     # ``BasicSolver.release_pool()`` empties the pool, and it is emptied at interpreter exit.
-    _POOL = {}
     _POOL_MAX = 2
     _POOL_MAX_BYTES = 112 << 30
+    _HPOOL = _POOL = HandlePool(_DESTROY, _POOL_MAX, admit=_fits_the_byte_budget)
+    _HANDLES = ("_handle", "_bhandle")
+    # out of memory: the pool (up to _POOL_MAX_BYTES, work arrays included) and the native block cache (up to 48 GB) go; the
+    # solver's own handle stays, it may hold a factor that ``append`` and the rest still need
+    _GIVES_BACK_OWN_HANDLE, _GIVES_BACK_POOLS = False, (_POOL,)
     # ``pickle`` of a computed solver carries the factor (reference behaviour, tests/test_pickle.py:21-36)
     # up to this many points (8 GB of packed lower triangle at 46340); beyond it the state drops the
     # factor and the solver comes back un-computed, like the reference's own native solver does
     # (solvers/hodlr.py:69-76).  Set to 0 to always drop, to None to always keep.
     PICKLE_FACTOR_MAX_N = 32768
 
-    def _pool_key(self):
+    def _options_key(self):
         return tuple(sorted(self._opts.items()))
 
-    def _new_handle(self, key):
-        """a handle parked under ``key``, or a new one"""
-        free = BasicSolver._POOL.get(key)
-        if free:
-            return free.pop()
+    def _native_opts(self):
         o = N.gh_chol_opts()
         o.device, o.nb = self._opts["device"], self._opts["nb"]
         o.profile, o.lookahead = int(self._opts["profile"]), int(self._opts["lookahead"])
-        h = N._vp()
-        N.check(N.lib.gh_chol_create(C.byref(o), C.byref(h)))
-        return h
-
-    def _ensure_handle(self):
-        if self._handle is None:
-            self._handle = self._new_handle(self._pool_key())
-        return self._handle
-
-    @staticmethod
-    def _pooled_bytes():
-        return sum(int(N.lib.gh_chol_device_bytes(h)) for free in BasicSolver._POOL.values() for h in free)
+        return o
 
     # the batched objective's handle (objective_batch): pooled under a key of its own, so that the factor of a GP's solver
     # handle and the bordered batch buffers never share (or evict) one another
-    def _batch_pool_key(self):
-        return self._pool_key() + (("batch", True),)
-
     def _ensure_batch_handle(self):
-        if getattr(self, "_bhandle", None) is None:
-            self._bhandle = self._new_handle(self._batch_pool_key())
-        return self._bhandle
-
-    @staticmethod
-    def _park(h, key):
-        free = BasicSolver._POOL.setdefault(key, [])
-        room = BasicSolver._POOL_MAX_BYTES - BasicSolver._pooled_bytes()
-        if len(free) < BasicSolver._POOL_MAX and int(N.lib.gh_chol_device_bytes(h)) <= room:
-            free.append(h)                     # as it is: the next iterate re-uses the work arrays too
-        elif len(free) < BasicSolver._POOL_MAX:
-            N.lib.gh_chol_trim(h)              # keep the factor-sized buffers, drop the work arrays
-            if int(N.lib.gh_chol_device_bytes(h)) <= room:
-                free.append(h)
-            else:
-                N.lib.gh_chol_destroy(h)
-        else:
-            N.lib.gh_chol_destroy(h)
-
-    def __del__(self):
-        for attr, key in (("_handle", self._pool_key), ("_bhandle", self._batch_pool_key)):
-            h = getattr(self, attr, None)
-            if h is not None and h.value:
-                try:
-                    BasicSolver._park(h, key())
-                except Exception:
-                    pass
-                setattr(self, attr, None)
-
-    def _release_parked_memory(self):
-        """what ``_retry_without_parked_memory`` gives back: the handle pool (up to _POOL_MAX_BYTES, work arrays included) and
-        the native block cache (up to 48 GB)"""
-        BasicSolver.release_pool()
-        N.lib.gh_release_caches(int(self._opts["device"]))
-
-    @classmethod
-    def release_pool(cls):
-        """Destroy every parked native handle (frees their device memory)."""
-        for free in cls._POOL.values():
-            while free:
-                try:
-                    N.lib.gh_chol_destroy(free.pop())
-                except Exception:
-                    pass
-        cls._POOL.clear()
+        return self._take_handle("_bhandle", self._options_key() + (("batch", True),))
 
     # Pickling.  The reference's BasicSolver pickles computed (its factor is a NumPy array,
     # basic.py:68; tests/test_pickle.py:21-36); here the factor is downloaded (packed lower triangle +
@@ -483,7 +436,7 @@ class BasicSolver(NativeSolver):
         returns ``K* K^-1 r`` and (optionally) ``diag`` or full ``K** - K* K^-1 K*^T``."""
         h = self._need()
         dk = self._kernel_for(kernel)
-        r, xs = N.as_f64(r).reshape(-1), N.as_f64(xs)
+        r, xs = rhs_vector(r, self._n), N.as_f64(xs)
         m = len(xs)
         mu = np.empty(m)
         var = np.empty(m) if return_var else None
@@ -540,13 +493,7 @@ class BasicSolver(NativeSolver):
     def grad(self, r, which):
         """kernel part of gp.py:429-466: returns (grad over ALL kernel params (masked ones 0),
         alpha = K^-1 r, diag(alpha alpha^T - K^-1))."""
-        h = self._need()
-        r = N.as_f64(r).reshape(-1)
-        which = np.ascontiguousarray(which, dtype=np.uint32)
-        g = np.zeros(max(self._dk.size, 1))
-        alpha, diagA = np.empty(self._n), np.empty(self._n)
-        N.check(N.lib.gh_chol_grad(h, self._dk.handle, N.ptr(which), N.ptr(r), N.ptr(g), N.ptr(alpha), N.ptr(diagA)))
-        return g[:self._dk.size], alpha, diagA
+        return self._grad("gh_chol_grad", r, which)
 
     # -- leave-one-out cross-validation (no reference counterpart; GPML 5.4.2)
     def _cv_grad_outputs(self, which):
@@ -690,6 +637,3 @@ class BasicSolver(NativeSolver):
         return dict(ms_total=p.ms_total, ms_build=p.ms_build, ms_panel=p.ms_panel, ms_trailing=p.ms_trailing,
                     trailing_flops=p.trailing_flops, n_trailing=p.n_trailing, ms_solve=p.ms_solve,
                     ms_append_relayout=p.ms_append_relayout, ms_remove_gather=p.reserved[0])
-
-
-atexit.register(BasicSolver.release_pool)

@@ -5,21 +5,19 @@ over ``_hodlr.cpp`` / ``include/george/hodlr.h``): same constructor keywords
 (``min_size=100, tol=0.1, seed=42``), same methods, ``apply_sqrt`` raises
 ``NotImplementedError`` (hodlr.py:62-64), pickling drops the factor (:69-76).
 """
-import atexit
 import ctypes as C
 import warnings
 
-import numpy as np
-
 from .. import _native as N
 from .basic import BasicSolver
-from .protocol import NativeSolver, rhs_vector
+from .protocol import HandlePool, NativeSolver
 
 __all__ = ["HODLRSolver"]
 
 
 class HODLRSolver(NativeSolver):
 
+    _CREATE, _DESTROY = "gh_hodlr_create", "gh_hodlr_destroy"
     _SOLVE, _DOT_SOLVE, _GET_INVERSE = "gh_hodlr_solve", "gh_hodlr_dot_solve", "gh_hodlr_get_inverse"
 
     # hodlr.h:147 lets a block's rank grow to min(rows, cols); the level-batched ACA here stops at 1024
@@ -38,89 +36,31 @@ class HODLRSolver(NativeSolver):
         self.min_size = min_size
         self.tol = tol
         self.seed = seed
-        self._hopts = dict(device=int(device), max_rank=int(max_rank))
+        self._opts = dict(device=int(device), max_rank=int(max_rank))
         super(HODLRSolver, self).__init__(kernel)
 
     # A native handle keeps its tree, its per-level job tables on the device and the measured schedule of its
     # last compute(): inside an optimiser loop (GP makes a NEW solver object per compute, gp.py:327) a fresh handle
     # per iterate cost 3 of the 8.4 ms of a C4 step through this class.  Handles of dropped solvers are parked per
     # option set (at most _HPOOL_MAX each) and picked up by the next solver with the same options.
-    _HPOOL = {}
     _HPOOL_MAX = 2
     _HPOOL_TOTAL = 4           # over all option sets: a scan over tolerances must not leave a trail of parked handles
+    _HPOOL = HandlePool(_DESTROY, _HPOOL_MAX, _HPOOL_TOTAL)
+    # out of memory: this solver's own handle first, then what dead solvers left parked: both handle pools and the native
+    # block cache
+    _GIVES_BACK_POOLS = (_HPOOL, BasicSolver._POOL)
 
-    def _hkey(self):
-        return (self._hopts["device"], int(self.min_size), int(self.seed), self._hopts["max_rank"], float(self.tol))
+    def _options_key(self):
+        return (self._opts["device"], int(self.min_size), int(self.seed), self._opts["max_rank"], float(self.tol))
 
-    def _ensure_handle(self):
-        if self._handle is None:
-            self._handle_key = self._hkey()
-            free = HODLRSolver._HPOOL.get(self._handle_key)
-            if free:
-                self._handle = free.pop()
-                if not free:
-                    del HODLRSolver._HPOOL[self._handle_key]
-                return self._handle
-            o = N.gh_hodlr_opts()
-            o.device, o.min_size, o.seed = self._hopts["device"], int(self.min_size), int(self.seed)
-            o.max_rank, o.tol = self._hopts["max_rank"], float(self.tol)
-            h = N._vp()
-            N.check(N.lib.gh_hodlr_create(C.byref(o), C.byref(h)))
-            self._handle = h
-        return self._handle
-
-    def _park_handle(self):
-        h, self._handle = getattr(self, "_handle", None), None
-        if h is not None and h.value:
-            try:
-                key = getattr(self, "_handle_key", None)
-                pool = HODLRSolver._HPOOL
-                if key is None:
-                    N.lib.gh_hodlr_destroy(h)
-                    return
-                free = pool.pop(key, [])                       # (re-inserted last: the dict keeps the option sets oldest first)
-                if len(free) >= HODLRSolver._HPOOL_MAX:
-                    N.lib.gh_hodlr_destroy(free.pop(0))
-                free.append(h)
-                pool[key] = free
-                while sum(len(v) for v in pool.values()) > HODLRSolver._HPOOL_TOTAL:
-                    oldest = next(iter(pool))
-                    if pool[oldest]:
-                        N.lib.gh_hodlr_destroy(pool[oldest].pop(0))
-                    if not pool[oldest]:
-                        del pool[oldest]
-            except Exception:
-                pass
-
-    def __del__(self):
-        self._park_handle()
-
-    @classmethod
-    def release_pool(cls):
-        """Destroy every parked native handle (frees their device memory)."""
-        for free in cls._HPOOL.values():
-            while free:
-                try:
-                    N.lib.gh_hodlr_destroy(free.pop())
-                except Exception:
-                    pass
-        cls._HPOOL.clear()
-
-    def _destroy_handle(self):
-        h, self._handle = self._handle, None
-        if h is not None:
-            N.lib.gh_hodlr_destroy(h)
-
-    def _release_parked_memory(self):
-        """this solver's own handle first, then what dead solvers left parked: both handle pools and the native block cache"""
-        self._destroy_handle()
-        HODLRSolver.release_pool()
-        BasicSolver.release_pool()
-        N.lib.gh_release_caches(self._hopts["device"])
+    def _native_opts(self):
+        o = N.gh_hodlr_opts()
+        o.device, o.min_size, o.seed, o.max_rank, o.tol = self._options_key()
+        return o
 
     def compute(self, x, yerr):
         x, yerr, _ = self._check_inputs(x, yerr)
-        if self._handle is not None and getattr(self, "_handle_key", None) != self._hkey():
+        if self._handle is not None and self._handle_key != self._options_key():
             self._park_handle()               # options were changed on the instance
         logdet = C.c_double(0.0)
         self.dense_fallback, self._dense = False, None
@@ -132,7 +72,7 @@ class HODLRSolver(NativeSolver):
                 raise
             warnings.warn("HODLRSolver: %s -- answering with the dense device solver (exact)" % (e,), RuntimeWarning)
             self._destroy_handle()                        # (frees the HODLR scratch before the N x N matrix is built)
-            self._dense = BasicSolver(self.kernel, device=self._hopts["device"])
+            self._dense = BasicSolver(self.kernel, device=self._opts["device"])
             self._dense.compute(x, yerr)
             self.dense_fallback = True
         self._n = len(x)
@@ -150,9 +90,6 @@ class HODLRSolver(NativeSolver):
         if self._computed and self._dense is not None:
             return self._dense.dot_solve(y)
         return super(HODLRSolver, self).dot_solve(y)
-
-    def apply_sqrt(self, r):
-        raise NotImplementedError("apply_sqrt is not implemented for the HODLRSolver")
 
     def get_inverse(self):
         if self._computed and self._dense is not None:
@@ -182,31 +119,11 @@ class HODLRSolver(NativeSolver):
         ``MemoryError`` when they do not fit."""
         if self._computed and self._dense is not None:
             return self._dense.predict(kernel, r, xs, return_var=return_var, return_cov=return_cov)
-        h = self._need()
-        dk = self._kernel_for(kernel)
-        r, xs = rhs_vector(r, self._n), N.as_f64(xs)
-        want_var = bool(return_var)
-        want_cov = bool(return_cov) and not want_var
-        m = len(xs)
-        mu = np.empty(m)
-        var = np.empty(m) if want_var else None
-        cov = np.empty((m, m)) if want_cov else None
-        if m > 0:
-            N.check(N.lib.gh_hodlr_predict(h, dk.handle, N.ptr(r), N.ptr(xs), m, N.ptr(mu), N.ptr(var), N.ptr(cov)))
-        return mu, var, cov
+        return self._predict("gh_hodlr_predict", kernel, r, xs, return_var, return_cov)
 
     def grad(self, r, which):
         """``BasicSolver.grad`` on the HODLR factor: (grad over ALL kernel parameters (masked ones 0), alpha = K^-1 r,
         diag(alpha alpha^T - K^-1)) with the solver's own K^-1, a strip of its columns at a time (gp.py:429-466)."""
         if self._computed and self._dense is not None:
             return self._dense.grad(r, which)
-        h = self._need()
-        r = rhs_vector(r, self._n)
-        which = np.ascontiguousarray(which, dtype=np.uint32)
-        g = np.zeros(max(self._dk.size, 1))
-        alpha, diagA = np.empty(self._n), np.empty(self._n)
-        N.check(N.lib.gh_hodlr_grad(h, self._dk.handle, N.ptr(which), N.ptr(r), N.ptr(g), N.ptr(alpha), N.ptr(diagA)))
-        return g[:self._dk.size], alpha, diagA
-
-
-atexit.register(HODLRSolver.release_pool)
+        return self._grad("gh_hodlr_grad", r, which)

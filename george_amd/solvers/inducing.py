@@ -21,14 +21,13 @@ same points for up to 7 input dimensions.
 
 Not built: ``apply_sqrt``, variational (VFE) bounds, optimising the inducing locations, and a multi-device form.
 """
-import atexit
 import ctypes as C
 import hashlib
 
 import numpy as np
 
 from .. import _native as N
-from .protocol import NativeSolver, rhs_matrix, rhs_vector
+from .protocol import HandlePool, NativeSolver
 
 __all__ = ["InducingSolver", "inducing_points"]
 
@@ -89,6 +88,9 @@ class InducingSolver(NativeSolver):
     A factorisation that fails raises ``numpy.linalg.LinAlgError`` like the other solvers, naming the factor;
     ``failed_factor`` is then ``"K_uu"`` or ``"A"`` and ``failed_pivot`` its 0-based pivot."""
 
+    _CREATE, _DESTROY = "gh_inducing_create", "gh_inducing_destroy"
+    _SOLVE, _DOT_SOLVE = "gh_inducing_solve", "gh_inducing_dot_solve"   # C^-1 y and y^T C^-1 y; no get_inverse, no apply_sqrt
+
     def __init__(self, kernel, inducing=512, method="fitc", jitter=1e-10, device=0, strip_points=0, select="host"):
         if method not in METHODS:
             raise ValueError("InducingSolver: method is 'dtc' or 'fitc'")
@@ -117,7 +119,7 @@ class InducingSolver(NativeSolver):
         self.failed_factor = None
         self.failed_pivot = None
         self.u = None                                       # the inducing inputs of the last compute()
-        self._iopts = dict(device=int(device), method=METHODS[method], strip_points=strip_points)
+        self._opts = dict(device=int(device), method=METHODS[method], strip_points=strip_points)
         super(InducingSolver, self).__init__(kernel)
 
     # The default inducing set depends on the inputs, m and the route only (from 8 dimensions on the two routes may differ), and
@@ -131,62 +133,24 @@ class InducingSolver(NativeSolver):
         for k, idx in InducingSolver._TABLES:
             if k == key:
                 return idx
-        idx = inducing_points(x, self.inducing, device=self._iopts["device"] if self.select == "device" else None)
+        idx = inducing_points(x, self.inducing, device=self._opts["device"] if self.select == "device" else None)
         InducingSolver._TABLES.append((key, idx))
         del InducingSolver._TABLES[:-InducingSolver._TABLES_MAX]
         return idx
 
     # -- lifetime.  The handle of a dropped solver (its m x m buffers on the device) is parked, at most _HPOOL_MAX per
     # (device, method, strip_points), and picked up by the next solver with the same options.
-    _HPOOL = {}
     _HPOOL_MAX = 2
+    _HPOOL = HandlePool(_DESTROY, _HPOOL_MAX)
+    _GIVES_BACK_POOLS = (_HPOOL,)                           # out of memory: own handle, own pool and the native caches
 
-    def _ensure_handle(self):
-        if self._handle is None:
-            self._hkey = (self._iopts["device"], self._iopts["method"], self._iopts["strip_points"])
-            free = InducingSolver._HPOOL.get(self._hkey)
-            if free:
-                self._handle = free.pop()
-                return self._handle
-            o = N.gh_inducing_opts()
-            o.device, o.method, o.strip_points = self._hkey
-            h = N._vp()
-            N.check(N.lib.gh_inducing_create(C.byref(o), C.byref(h)))
-            self._handle = h
-        return self._handle
+    def _options_key(self):
+        return (self._opts["device"], self._opts["method"], self._opts["strip_points"])
 
-    def _destroy_handle(self):
-        h, self._handle = getattr(self, "_handle", None), None
-        if h is not None and h.value:
-            N.lib.gh_inducing_destroy(h)
-
-    def __del__(self):
-        try:
-            h, self._handle = getattr(self, "_handle", None), None
-            if h is not None and h.value:
-                free = InducingSolver._HPOOL.setdefault(self._hkey, [])
-                if len(free) < InducingSolver._HPOOL_MAX:
-                    free.append(h)
-                else:
-                    N.lib.gh_inducing_destroy(h)
-        except Exception:
-            pass
-
-    @classmethod
-    def release_pool(cls):
-        """Destroy every parked native handle (frees their device memory)."""
-        for free in cls._HPOOL.values():
-            while free:
-                try:
-                    N.lib.gh_inducing_destroy(free.pop())
-                except Exception:
-                    pass
-        cls._HPOOL.clear()
-
-    def _release_parked_memory(self):
-        self._destroy_handle()
-        InducingSolver.release_pool()
-        N.lib.gh_release_caches(self._iopts["device"])
+    def _native_opts(self):
+        o = N.gh_inducing_opts()
+        o.device, o.method, o.strip_points = self._options_key()
+        return o
 
     def compute(self, x, yerr):
         x, yerr, _ = self._check_inputs(x, yerr)
@@ -220,66 +184,19 @@ class InducingSolver(NativeSolver):
         self.computed = True
 
     # -- the solver protocol
-    def apply_inverse(self, y, in_place=False):
-        """``C^-1 y`` for ``y`` of shape (n,) or (n, nrhs); ``in_place`` writes the values back into a writable array ``y``."""
-        h = self._need()
-        yc, nrhs = rhs_matrix(y, self._n)
-        out = np.empty_like(yc)
-        if nrhs > 0:
-            N.check(N.lib.gh_inducing_solve(h, N.ptr(yc), nrhs, N.ptr(out)))
-        if in_place and isinstance(y, np.ndarray) and y.flags.writeable:
-            try:
-                y[...] = out
-                return y
-            except (ValueError, TypeError):
-                pass
-        return out
-
-    def dot_solve(self, y):
-        """``y^T C^-1 y = sum_i y_i^2 / lambda_i - |t(y)|^2``."""
-        h = self._need()
-        y = rhs_vector(y, self._n)
-        out = C.c_double(0.0)
-        N.check(N.lib.gh_inducing_dot_solve(h, N.ptr(y), C.byref(out)))
-        return out.value
-
-    def apply_sqrt(self, r):
-        raise NotImplementedError("apply_sqrt is not implemented for the InducingSolver")
-
-    def get_inverse(self):
-        """``C^-1`` as a dense matrix: ``apply_inverse`` of the identity.  N^2 memory: meant for small N."""
-        self._need()
-        return self.apply_inverse(np.eye(self._n))
+    def _solve_target(self, y, yc, in_place):
+        """``in_place``: the values are copied back into any writable array ``y``, whatever its dtype"""
+        return np.empty_like(yc), (y if in_place and isinstance(y, np.ndarray) and y.flags.writeable else None)
 
     # -- device-resident GP glue
     def grad(self, r, which):
         """``BasicSolver.grad``'s ``(kgrad_full, alpha, diagA)`` for the DTC / FITC likelihood: the gradient over ALL kernel
         parameters (masked ones 0), ``alpha = C^-1 r`` and ``diagA_i = alpha_i^2 - (C^-1)_ii``.  With ``u = x`` and no jitter
         these are the dense values."""
-        h = self._need()
-        r = rhs_vector(r, self._n)
-        which = np.ascontiguousarray(which, dtype=np.uint32)
-        g = np.zeros(max(self._dk.size, 1))
-        alpha, diagA = np.empty(self._n), np.empty(self._n)
-        N.check(N.lib.gh_inducing_grad(h, self._dk.handle, N.ptr(which), N.ptr(r), N.ptr(g), N.ptr(alpha), N.ptr(diagA)))
-        return g[:self._dk.size], alpha, diagA
+        return self._grad("gh_inducing_grad", r, which)
 
     def predict(self, kernel, r, xs, return_var=False, return_cov=False):
         """The predictive mean and (optionally) variance or covariance at ``xs``, the same for DTC and FITC, in strips of
         test points.  The covariance keeps three M x m blocks and the M x M result on the device and raises ``MemoryError``
         over its budget."""
-        h = self._need()
-        dk = self._kernel_for(kernel)
-        r, xs = rhs_vector(r, self._n), N.as_f64(xs)
-        want_var = bool(return_var)
-        want_cov = bool(return_cov) and not want_var
-        m = len(xs)
-        mu = np.empty(m)
-        var = np.empty(m) if want_var else None
-        cov = np.empty((m, m)) if want_cov else None
-        if m > 0:
-            N.check(N.lib.gh_inducing_predict(h, dk.handle, N.ptr(r), N.ptr(xs), m, N.ptr(mu), N.ptr(var), N.ptr(cov)))
-        return mu, var, cov
-
-
-atexit.register(InducingSolver.release_pool)
+        return self._predict("gh_inducing_predict", kernel, r, xs, return_var, return_cov)

@@ -15,17 +15,17 @@ import ctypes as C
 import numpy as np
 
 from .. import _native as N
-from .protocol import NativeSolver
+from .protocol import NativeSolver, rhs_vector
 
 __all__ = ["MultiGPUSolver", "MultiGPUHODLRSolver"]
 
 
 class _MultiDeviceSolver(NativeSolver):
     """What the two solvers over several devices of one process share: the device list, a handle made on first use
-    from the subclass's ``_native_opts()`` and destroyed with the solver (no pool), ``compute`` around one native call,
+    from the subclass's ``_split_opts()`` and destroyed with the solver (no pool), ``compute`` around one native call,
     an ``in_place`` that copies back, and NativeSolver's pickle without the factor."""
 
-    _CREATE = _DESTROY = _COMPUTE = None
+    _COMPUTE = None
 
     def __init__(self, kernel, devices):
         super(_MultiDeviceSolver, self).__init__(kernel)
@@ -33,27 +33,12 @@ class _MultiDeviceSolver(NativeSolver):
         if not 1 <= len(self.devices) <= 16:
             raise ValueError("devices must list 1..16 device ordinals")
 
-    def _ensure_handle(self):
-        if self._handle is None:
-            o = self._native_opts()
-            o.n_dev = len(self.devices)
-            for i, d in enumerate(self.devices):
-                o.devices[i] = d
-            h = N._vp()
-            N.check(getattr(N.lib, self._CREATE)(C.byref(o), C.byref(h)))
-            self._handle = h
-        return self._handle
-
-    def _destroy_handle(self):
-        h, self._handle = getattr(self, "_handle", None), None
-        if h is not None and h.value:
-            try:
-                getattr(N.lib, self._DESTROY)(h)
-            except Exception:
-                pass
-
-    def __del__(self):
-        self._destroy_handle()
+    def _native_opts(self):
+        o = self._split_opts()
+        o.n_dev = len(self.devices)
+        for i, d in enumerate(self.devices):
+            o.devices[i] = d
+        return o
 
     def _compute(self, x, yerr):
         """``compute`` up to the ``computed`` flag, which the subclass sets; returns the coerced ``x``"""
@@ -88,7 +73,7 @@ class MultiGPUSolver(_MultiDeviceSolver):
         self.flags = ((N.GH_MGPU_PLAIN_CYCLIC if plain_cyclic else 0) | (N.GH_MGPU_CHAIN_ONLY if chain_only else 0) |
                       (N.GH_MGPU_TRACE if trace else 0) | (N.GH_MGPU_ONE_COMM if one_comm else 0))
 
-    def _native_opts(self):
+    def _split_opts(self):
         o = N.gh_mgpu_opts()
         o.pr, o.pc = int(self.grid[0]), int(self.grid[1])
         o.nb = self.nb
@@ -129,7 +114,7 @@ class MultiGPUSolver(_MultiDeviceSolver):
         """mean / variance / covariance terms of gp.py:532-545 on the sharded factor (as ``BasicSolver.predict``)."""
         h = self._need()
         dk = self._kernel_for(kernel)
-        r, xs = N.as_f64(r).reshape(-1), N.as_f64(xs)
+        r, xs = rhs_vector(r, self._n), N.as_f64(xs)
         m = len(xs)
         mu = np.empty(m)
         var = np.empty(m) if return_var else None
@@ -159,7 +144,9 @@ class MultiGPUHODLRSolver(_MultiDeviceSolver):
     defines neither, so ``GP`` takes its generic branch on ``apply_inverse`` / ``get_inverse`` here."""
 
     _CREATE, _DESTROY, _COMPUTE = "gh_hodlr_mgpu_create", "gh_hodlr_mgpu_destroy", "gh_hodlr_mgpu_compute"
+    # (no native get_inverse: hodlr.h / _hodlr.cpp:194-199 solve against the identity, and so does the base)
     _SOLVE, _DOT_SOLVE = "gh_hodlr_mgpu_solve", "gh_hodlr_mgpu_dot_solve"
+    _NAME = "HODLRSolver"
 
     def __init__(self, kernel, min_size=100, tol=0.1, seed=42, devices=None, max_rank=0):
         if devices is None:                                  # all visible devices, cut down to a power of two (3, 6, 7 GPUs: 2, 4, 4)
@@ -171,30 +158,24 @@ class MultiGPUHODLRSolver(_MultiDeviceSolver):
             raise ValueError("the HODLR tree is split over 1, 2, 4, 8 or 16 devices (got %d)" % n)
         self.min_size, self.tol, self.seed, self.max_rank = min_size, tol, seed, int(max_rank)
 
-    def _native_opts(self):
+    def _split_opts(self):
         o = N.gh_hodlr_mgpu_opts()
         o.min_size, o.seed, o.max_rank, o.tol = int(self.min_size), int(self.seed), self.max_rank, float(self.tol)
         return o
+
+    def _options_key(self):
+        """(no pool: what ``compute`` compares to see that the options were changed on the instance)"""
+        return (tuple(self.devices), int(self.min_size), int(self.seed), self.max_rank, float(self.tol))
 
     def grid_shape(self):
         raise NotImplementedError("the HODLR split has no process grid: see rows()")
 
     def compute(self, x, yerr):
         """hodlr.h:75-103 over the split tree.  ``yerr`` already contains the white noise (gp.py:330)."""
-        key = (tuple(self.devices), int(self.min_size), int(self.seed), self.max_rank, float(self.tol))
-        if getattr(self, "_handle_key", None) != key:
+        if self._handle is not None and self._handle_key != self._options_key():
             self._destroy_handle()                             # options were changed on the instance
-        self._handle_key = key
         self._compute(x, yerr)
         self.computed = True
-
-    def apply_sqrt(self, r):
-        raise NotImplementedError("apply_sqrt is not implemented for the HODLRSolver")
-
-    def get_inverse(self):
-        """hodlr.h / _hodlr.cpp:194-199: solve against the identity."""
-        self._need()
-        return self.apply_inverse(np.eye(self._n))
 
     def rows(self):
         """[(first row, number of rows)] of every device's sub-tree (after compute())."""

@@ -23,14 +23,13 @@ device's own distances (the two can differ where two distances agree to rounding
 Not built: ordering strategies beyond the three of ``order=`` (max-min and the like), ``apply_sqrt``, and a joint covariance
 between the test points of local prediction.
 """
-import atexit
 import ctypes as C
 import hashlib
 
 import numpy as np
 
 from .. import _native as N
-from .protocol import NativeSolver, rhs_matrix, rhs_vector
+from .protocol import HandlePool, NativeSolver, rhs_vector
 
 __all__ = ["VecchiaSolver", "vecchia_neighbors", "vecchia_query_neighbors"]
 
@@ -257,6 +256,9 @@ class VecchiaSolver(NativeSolver):
     default tables of ``compute`` and of ``predict_local`` are made, ``"host"`` or ``"device"`` (the same tables for up to 7
     input dimensions; see the module's text)."""
 
+    _CREATE, _DESTROY = "gh_vecchia_create", "gh_vecchia_destroy"
+    _SOLVE, _DOT_SOLVE = "gh_vecchia_solve", "gh_vecchia_dot_solve"     # Q y and y^T Q y = sum_i e_i^2 / f_i; no get_inverse, no apply_sqrt
+
     def __init__(self, kernel, m=32, order=None, neighbors=None, device=0, predict="global", search="host"):
         m = int(m)
         if m < 1 or m > M_MAX:
@@ -274,7 +276,7 @@ class VecchiaSolver(NativeSolver):
         self.search = search
         self.failed_point = None
         self.failed_test_point = None
-        self._vopts = dict(device=int(device))
+        self._opts = dict(device=int(device))
         self._perm = None
         self._xo = None                                     # the ordered host inputs of compute(): what predict_local searches
         super(VecchiaSolver, self).__init__(kernel)
@@ -289,62 +291,24 @@ class VecchiaSolver(NativeSolver):
         for k, tab in VecchiaSolver._TABLES:
             if k == key:
                 return tab
-        tab = vecchia_neighbors(x, self.m, device=self._vopts["device"] if self.search == "device" else None)
+        tab = vecchia_neighbors(x, self.m, device=self._opts["device"] if self.search == "device" else None)
         VecchiaSolver._TABLES.append((key, tab))
         del VecchiaSolver._TABLES[:-VecchiaSolver._TABLES_MAX]
         return tab
 
     # -- lifetime.  GP makes a new solver for every compute: the handle of a dropped solver (its neighbour table checked, indexed
     # and on the device) is parked, at most _HPOOL_MAX per (device, m), and picked up by the next solver with the same options.
-    _HPOOL = {}
     _HPOOL_MAX = 2
+    _HPOOL = HandlePool(_DESTROY, _HPOOL_MAX)
+    _GIVES_BACK_POOLS = (_HPOOL,)                           # out of memory: own handle, own pool and the native caches
 
-    def _ensure_handle(self):
-        if self._handle is None:
-            self._hkey = (self._vopts["device"], self.m)
-            free = VecchiaSolver._HPOOL.get(self._hkey)
-            if free:
-                self._handle = free.pop()
-                return self._handle
-            o = N.gh_vecchia_opts()
-            o.device, o.m = self._hkey
-            h = N._vp()
-            N.check(N.lib.gh_vecchia_create(C.byref(o), C.byref(h)))
-            self._handle = h
-        return self._handle
+    def _options_key(self):
+        return (self._opts["device"], self.m)
 
-    def _destroy_handle(self):
-        h, self._handle = getattr(self, "_handle", None), None
-        if h is not None and h.value:
-            N.lib.gh_vecchia_destroy(h)
-
-    def __del__(self):
-        try:
-            h, self._handle = getattr(self, "_handle", None), None
-            if h is not None and h.value:
-                free = VecchiaSolver._HPOOL.setdefault(self._hkey, [])
-                if len(free) < VecchiaSolver._HPOOL_MAX:
-                    free.append(h)
-                else:
-                    N.lib.gh_vecchia_destroy(h)
-        except Exception:
-            pass
-
-    @classmethod
-    def release_pool(cls):
-        """Destroy every parked native handle (frees their device memory)."""
-        for free in cls._HPOOL.values():
-            while free:
-                try:
-                    N.lib.gh_vecchia_destroy(free.pop())
-                except Exception:
-                    pass
-        cls._HPOOL.clear()
-
-    def _release_parked_memory(self):
-        self._destroy_handle()
-        VecchiaSolver.release_pool()
-        N.lib.gh_release_caches(self._vopts["device"])
+    def _native_opts(self):
+        o = N.gh_vecchia_opts()
+        o.device, o.m = self._options_key()
+        return o
 
     def __getstate__(self):
         state = super(VecchiaSolver, self).__getstate__()
@@ -397,52 +361,16 @@ class VecchiaSolver(NativeSolver):
         b[self._perm] = a
         return b
 
-    def apply_inverse(self, y, in_place=False):
-        """``Q y`` for ``y`` of shape (n,) or (n, nrhs); ``in_place`` writes the values back into a writable array ``y``."""
-        h = self._need()
-        yc, nrhs = rhs_matrix(y, self._n)
-        ys = self._in(yc)
-        out = np.empty_like(ys)
-        if nrhs > 0:
-            N.check(N.lib.gh_vecchia_solve(h, N.ptr(ys), nrhs, N.ptr(out)))
-        out = self._out(out)
-        if in_place and isinstance(y, np.ndarray) and y.flags.writeable:
-            try:
-                y[...] = out
-                return y
-            except (ValueError, TypeError):
-                pass
-        return out
-
-    def dot_solve(self, y):
-        """``y^T Q y = sum_i e_i^2 / f_i``."""
-        h = self._need()
-        y = self._in(rhs_vector(y, self._n))
-        out = C.c_double(0.0)
-        N.check(N.lib.gh_vecchia_dot_solve(h, N.ptr(y), C.byref(out)))
-        return out.value
-
-    def apply_sqrt(self, r):
-        raise NotImplementedError("apply_sqrt is not implemented for the VecchiaSolver")
-
-    def get_inverse(self):
-        """The precision ``Q`` as a dense matrix: ``apply_inverse`` of the identity.  O(N^2 m) time and N^2 memory: meant
-        for small N."""
-        self._need()
-        return self.apply_inverse(np.eye(self._n))
+    def _solve_target(self, y, yc, in_place):
+        """``in_place``: the values are copied back into any writable array ``y``, whatever its dtype"""
+        return np.empty_like(yc), (y if in_place and isinstance(y, np.ndarray) and y.flags.writeable else None)
 
     # -- device-resident GP glue
     def grad(self, r, which):
         """``BasicSolver.grad``'s ``(kgrad_full, alpha, diagA)`` for the Vecchia likelihood: the gradient over ALL kernel
         parameters (masked ones 0), ``alpha = Q r`` and ``diagA_j = 2 sum W_jj`` over the blocks that hold ``j``.  At
         ``m >= N - 1`` these are the dense values."""
-        h = self._need()
-        r = self._in(rhs_vector(r, self._n))
-        which = np.ascontiguousarray(which, dtype=np.uint32)
-        g = np.zeros(max(self._dk.size, 1))
-        alpha, diagA = np.empty(self._n), np.empty(self._n)
-        N.check(N.lib.gh_vecchia_grad(h, self._dk.handle, N.ptr(which), N.ptr(r), N.ptr(g), N.ptr(alpha), N.ptr(diagA)))
-        return g[:self._dk.size], self._out(alpha), self._out(diagA)
+        return self._grad("gh_vecchia_grad", r, which)
 
     def predict(self, kernel, r, xs, return_var=False, return_cov=False):
         """``K* Q r`` and (optionally) the diagonal or the whole of ``K** - K* Q K*^T``, in strips of test points.  The
@@ -456,18 +384,7 @@ class VecchiaSolver(NativeSolver):
                                  "independent given their neighbours; ask for return_var=True or return_cov=False")
             mu, var = self.predict_local(kernel, r, xs, return_var=return_var)
             return mu, var, None
-        h = self._need()
-        dk = self._kernel_for(kernel)
-        r, xs = self._in(rhs_vector(r, self._n)), N.as_f64(xs)
-        want_var = bool(return_var)
-        want_cov = bool(return_cov) and not want_var
-        m = len(xs)
-        mu = np.empty(m)
-        var = np.empty(m) if want_var else None
-        cov = np.empty((m, m)) if want_cov else None
-        if m > 0:
-            N.check(N.lib.gh_vecchia_predict(h, dk.handle, N.ptr(r), N.ptr(xs), m, N.ptr(mu), N.ptr(var), N.ptr(cov)))
-        return mu, var, cov
+        return self._predict("gh_vecchia_predict", kernel, r, xs, return_var, return_cov)
 
     def predict_local(self, kernel, r, xs, return_var=False, neighbors=None, m=None, search=None):
         """Nearest-neighbour prediction: test point ``c`` conditioned on the data points of row ``c`` of ``neighbors`` alone,
@@ -522,5 +439,3 @@ class VecchiaSolver(NativeSolver):
             N.check(rc)
         return mu, var
 
-
-atexit.register(VecchiaSolver.release_pool)

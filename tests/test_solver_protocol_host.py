@@ -7,7 +7,7 @@ import pytest
 
 from george_amd import kernels
 from george_amd.distributed import DistributedBasicSolver
-from george_amd.solvers import BasicSolver, HODLRSolver, MultiGPUHODLRSolver, MultiGPUSolver
+from george_amd.solvers import BasicSolver, HODLRSolver, InducingSolver, MultiGPUHODLRSolver, MultiGPUSolver, VecchiaSolver
 from george_amd.solvers.multigpu import _MultiDeviceSolver
 from george_amd.solvers.protocol import NativeSolver, rhs_matrix, rhs_rows, rhs_vector
 
@@ -20,10 +20,15 @@ OFFERS = {
     MultiGPUSolver: {"predict"},
     MultiGPUHODLRSolver: set(),
     DistributedBasicSolver: set(),
+    VecchiaSolver: {"predict", "grad"},
+    InducingSolver: {"predict", "grad"},
 }
 DENSE_ONLY = ("truncate", "append", "remove", "sample_conditional", "objective", "loo", "loo_objective", "lgo", "fisher",
               "predict_gradient", "_restore", "_ensure_batch_handle") + BATCH
 CLASSES = list(OFFERS)
+# the classes without ``apply_sqrt``, and what its message calls them
+NO_SQRT = {HODLRSolver: "HODLRSolver", MultiGPUHODLRSolver: "HODLRSolver", VecchiaSolver: "VecchiaSolver",
+           InducingSolver: "InducingSolver"}
 
 
 def _kernel():
@@ -41,7 +46,8 @@ def test_capability_table(cls):
     assert {name for name in OPTIONAL if callable(getattr(cls, name, None))} == OFFERS[cls]
 
 
-@pytest.mark.parametrize("cls", [HODLRSolver, MultiGPUSolver, MultiGPUHODLRSolver], ids=lambda c: c.__name__)
+@pytest.mark.parametrize("cls", [HODLRSolver, MultiGPUSolver, MultiGPUHODLRSolver, VecchiaSolver, InducingSolver],
+                         ids=lambda c: c.__name__)
 def test_dense_only_calls_are_not_reachable(cls):
     for name in DENSE_ONLY:
         assert not callable(getattr(cls, name, None)), name
@@ -53,7 +59,9 @@ def test_dense_only_calls_are_not_reachable(cls):
 def test_class_relations():
     assert not issubclass(HODLRSolver, BasicSolver)
     assert not issubclass(MultiGPUHODLRSolver, MultiGPUSolver) and not issubclass(MultiGPUSolver, MultiGPUHODLRSolver)
-    for cls in (BasicSolver, HODLRSolver, MultiGPUSolver, MultiGPUHODLRSolver):
+    for cls in (VecchiaSolver, InducingSolver):
+        assert not any(issubclass(cls, other) or issubclass(other, cls) for other in CLASSES if other is not cls)
+    for cls in (BasicSolver, HODLRSolver, MultiGPUSolver, MultiGPUHODLRSolver, VecchiaSolver, InducingSolver):
         assert issubclass(cls, NativeSolver)
 
 
@@ -106,8 +114,8 @@ def test_before_compute(cls):
     assert {"apply_inverse", "dot_solve", "get_inverse", "apply_sqrt"} <= set(calls)
     assert OFFERS[cls] - {"objective", "loo_objective"} - set(BATCH) <= set(calls)
     for name, call in calls.items():
-        if name == "apply_sqrt" and cls in (HODLRSolver, MultiGPUHODLRSolver):
-            with pytest.raises(NotImplementedError):
+        if name == "apply_sqrt" and cls in NO_SQRT:
+            with pytest.raises(NotImplementedError, match="^apply_sqrt is not implemented for the %s$" % NO_SQRT[cls]):
                 call()
             continue
         with pytest.raises(RuntimeError, match="you must call 'compute' first"):
@@ -175,7 +183,8 @@ def test_rhs_rows():
             rhs_rows(bad, N_PTS)
 
 
-@pytest.mark.parametrize("cls", [BasicSolver, HODLRSolver, MultiGPUSolver, MultiGPUHODLRSolver], ids=lambda c: c.__name__)
+@pytest.mark.parametrize("cls", [BasicSolver, HODLRSolver, MultiGPUSolver, MultiGPUHODLRSolver, VecchiaSolver, InducingSolver],
+                         ids=lambda c: c.__name__)
 def test_in_place_policy(cls):
     # (the policy alone: which array the native solve writes and which one gets the values back)
     s = _make(cls)
@@ -196,6 +205,14 @@ def test_in_place_policy(cls):
     ro.flags.writeable = False
     out, back = s._solve_target(ro, ro, True)
     assert out is not ro and out.flags.writeable
+    if cls in (VecchiaSolver, InducingSolver):
+        # these two copy back into every writable array, whatever its dtype, and never write into the caller's array
+        assert back is None
+        yi = np.zeros((N_PTS, 3), dtype=np.int64)
+        out, back = s._solve_target(yi, np.ascontiguousarray(yi, dtype=np.float64), True)
+        assert back is yi and out.dtype == np.float64 and not np.shares_memory(out, yi)
+        out, back = s._solve_target(yi.tolist(), np.ascontiguousarray(yi, dtype=np.float64), True)
+        assert back is None
 
 
 @pytest.mark.parametrize("cls", CLASSES, ids=lambda c: c.__name__)
