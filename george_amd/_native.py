@@ -55,7 +55,7 @@ class gh_vecchia_opts(C.Structure):
 
 
 class gh_inducing_opts(C.Structure):
-    _fields_ = [("device", C.c_int32), ("method", C.c_int32), ("strip_points", C.c_int32), ("reserved", C.c_int32)]
+    _fields_ = [("device", C.c_int32), ("method", C.c_int32), ("strip_points", C.c_int32), ("variational", C.c_int32)]
 
 
 class gh_mgpu_opts(C.Structure):
@@ -217,6 +217,8 @@ SIGNATURES = {
     "gh_inducing_solve": (C.c_int, [_vp, _dp, _i64, _dp]),
     "gh_inducing_dot_solve": (C.c_int, [_vp, _dp, C.POINTER(C.c_double)]),
     "gh_inducing_grad": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _dp, _dp]),
+    "gh_inducing_trace_term": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "gh_inducing_grad_u": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "gh_inducing_predict": (C.c_int, [_vp, _vp, _dp, _dp, _i64, _dp, _dp, _dp]),
     "gh_inducing_select": (C.c_int, [_i32, _dp, _i64, _i32, _i64, _i64, _dp, _dp]),
     "gh_mgpu_create": (C.c_int, [C.POINTER(gh_mgpu_opts), C.POINTER(_vp)]),

@@ -150,6 +150,12 @@ size_t gh_predgrad_work_doubles(int64_t n, int64_t m, int ndim, bool want_var);
 int gh_launch_predgrad(const gh_kernel* k, const double* x, int64_t n, const double* xs, int64_t m, const double* alpha,
                        const double* W /* or NULL */, int64_t ldw, double* dmu /* m*ndim */, double* dvar /* m*ndim or NULL */,
                        double* partial, hipStream_t st);
+// The weighted input-gradient reduction on the same tile: out[c][d] = (add ? out[c][d] : 0) + scale * sum_i Wt[i * ld + c] G_cid,
+// G the x1-gradient of k at (t_c, x_i), for nt points t and nx points x.  Rows i >= nx and columns c >= nt of Wt are neither
+// evaluated nor read.  partial: gh_wxgrad_work_doubles(nx, nt, ndim) doubles.  Fixed-order sums, no atomics.
+size_t gh_wxgrad_work_doubles(int64_t nx, int64_t nt, int ndim);
+int gh_launch_wxgrad(const gh_kernel* k, const double* t, int64_t nt, const double* x, int64_t nx, const double* Wt, int64_t ld,
+                     double scale, bool add, double* out /* nt*ndim */, double* partial, hipStream_t st);
 
 // The pieces of gh_chol_fisher (gh_fisher.hip).  A "plane" is a dense np x np matrix of pitch np, np a multiple of 128.
 #define GH_FISHER_GROUP 4                   // planes per side of one contraction launch (4 x 4 pairs from registers)

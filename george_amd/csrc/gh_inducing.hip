@@ -1,4 +1,5 @@
-// gh_inducing.hip -- the inducing-point (DTC / FITC) solver behind gh_inducing_* (include/george_amd.h has the definition)
+// gh_inducing.hip -- the inducing-point (DTC / FITC / variational bound) solver behind gh_inducing_* (include/george_amd.h has
+// the definition)
 //
 // Everything heavy is a launch of the fp64 GEMM (gh_launch_gemm) on strips of K_fu = K(x_J, u): `se` data points (rows) by mp
 // columns, row-major with pitch mp (m padded to a multiple of 128; the padding is zero, and the identity in the m x m matrices).
@@ -10,18 +11,22 @@
 //   solve:    c = sum_J F_J^T Lambda_J^-1 b_J;  t = M1 c;  w = M1^T t;  out_J = Lambda_J^-1 (b_J - F_J w)
 //   grad:     H_J^T = F_J M1^T gives |H[:, i]|^2, and Z_J^T = alpha_J w^T - Lambda_J^-1 (H_J^T M1) - phi diag(diagA_J) (V_J^T Lui)
 //             (P alpha = w and P C^-1 = M1^T M1 K_uf Lambda^-1 by the Woodbury identity; P^T = V^T Lui);  ZF = sum_J Z_J F_J;
-//             W = -1/2 (ZF Lui^T) Lui
+//             W = -1/2 (ZF Lui^T) Lui.  The variational bound takes the FITC path with omega = -1 / lambda in place of diagA.
+//   grad_u:   the same pass after one for G2 = H Lambda^-1 P^T and w = P alpha; per strip Z_J^T once more, from P_J^T itself
+//             (ind_grad_body has the reason), ugrad += sum_i Z_J^T[i][j] d1 k(u_j, x_i) (gh_launch_wxgrad on the strip) and
+//             Z P^T += Z_J P_J^T; after the strips ugrad -= sum_b (-(W + W^T))[b][j] d1 k(u_j, u_b)
 //   predict:  V*^T = F* Lui^T,  H*^T = F* M1^T,  mu = F* w
 // Strips go in ascending order on the handle's one stream and every sum has a fixed order (GEMM tiles, wave trees, per-workgroup
-// partials added by gh_launch_kgrad_final): two calls give the same bits.  No kernel here uses scratch memory or atomics.
+// partials added by gh_launch_kgrad_final): two calls give the same bits.  No kernel here uses scratch memory or atomics (the
+// interpreter form of gh_launch_wxgrad, gh_predgrad.hip, keeps its operand stacks in scratch memory).
 #include <string.h>
 #include <algorithm>
 #include "gh_common.h"
 #include "gh_device_util.h"
 #include "gh_chol_impl.h"
 
-#define IND_M_MAX 8192                  // the cap on m: five padded m x m matrices (four kept, one of grad's) are 2.7 GB there
-#define IND_STRIP_BYTES (3L << 29)      // what the three strips of a pass (F, Y and the FITC operand) may take together
+#define IND_M_MAX 8192                  // the cap on m: five padded m x m matrices (four kept, one of grad's; grad_u: one more) are 2.7 GB there
+#define IND_STRIP_BYTES (3L << 29)      // what the three strips of a pass (F, Y and the FITC operand) may take together (grad_u: two more strips)
 #define IND_COV_BYTES (8L << 30)        // what predict's covariance may keep on the device: three M x m strips and the M x M result
 #define IND_GT 64                       // tile edge of the gradient reduction = lanes of its one-wavefront workgroup
 #define IND_GRAD_LDS (128 * 1024)
@@ -35,8 +40,9 @@ struct gh_inducing {
   bool computed = false;
   int64_t info = 0;
   double logdet = 0.0;
+  double tau = 0.0;                     // the trace term of the variational bound, sum_i resid_i / yerr_i^2; 0 without the bound
   gh_kernel kc;                         // the kernel program as of compute(): what solve, dot_solve and t(r) build K_fu from
-  GhPooledBuf x, yerr, u, lam, vals, Lui, M1, wk1, wk2, dinv, scal;
+  GhPooledBuf x, yerr, u, lam, resid, vals, Lui, M1, wk1, wk2, dinv, scal;   // resid_i = max(k_ii - q_i, 0): with the bound only
 };
 
 // ================================================================================ kernels
@@ -51,10 +57,12 @@ __global__ __launch_bounds__(256) void ind_logdiag_kernel(const double* __restri
   if (j < n) out[j] = 2.0 * log(A[j * ld + j]);
 }
 // A wavefront per row of V^T (rows x ld, the padding columns zero): q = |row|^2, lambda = yerr^2 + phi max(kd - q, 0), the row
-// scaled by lambda^-1/2 in place; lam and loglam per row.  The sum: lane-strided, then the wave tree.
+// scaled by lambda^-1/2 in place; lam and loglam per row.  The sum: lane-strided, then the wave tree.  With resid (the
+// variational bound) max(kd - q, 0) stays out of lambda: resid and the term of tau, resid / lambda, per row.
 __global__ __launch_bounds__(256) void ind_lambda_kernel(double* __restrict__ Vt, long ld, long rows, const double* __restrict__ yerr,
                                                          const double* __restrict__ kd, double* __restrict__ lam,
-                                                         double* __restrict__ loglam) {
+                                                         double* __restrict__ loglam, double* __restrict__ resid,
+                                                         double* __restrict__ tauterm) {
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= rows) return;
@@ -64,10 +72,11 @@ __global__ __launch_bounds__(256) void ind_lambda_kernel(double* __restrict__ Vt
   q = __shfl(wave_sum(q), 0, 64);
   const double ye = yerr[row];
   double l = ye * ye;
-  if (kd) l += fmax(kd[row] - q, 0.0);
+  if (kd && !resid) l += fmax(kd[row] - q, 0.0);
   const double w = 1.0 / sqrt(l);
   for (long j = lane; j < ld; j += 64) v[j] *= w;
   if (lane == 0) { lam[row] = l; loglam[row] = log(l); }
+  if (resid && lane == 0) { const double rv = fmax(kd[row] - q, 0.0); resid[row] = rv; tauterm[row] = rv / l; }
 }
 // R (se x rp) = Lambda^-1 b over the strip's rows (b: rows x nrhs), zero in the padding
 __global__ __launch_bounds__(256) void ind_rhs_kernel(const double* __restrict__ b, long nrhs, const double* __restrict__ lam, long rows,
@@ -92,9 +101,11 @@ __global__ __launch_bounds__(256) void ind_quad_kernel(const double* __restrict_
   if (i < n) vals[i] = b[i] * b[i] / lam[i];
   else if (i < n + mp) { const double tj = t[(i - n) * ts]; vals[i] = -tj * tj; }
 }
-// A wavefront per data point of the strip: diagA_i = alpha_i^2 - (1 / lambda_i - |H[:, i]|^2 / lambda_i^2) from row i of H^T
+// A wavefront per data point of the strip: diagA_i = alpha_i^2 - (1 / lambda_i - |H[:, i]|^2 / lambda_i^2) from row i of H^T.
+// With resid (the variational bound): diagA_i += resid_i / lambda_i^2, the part of tau, and omega_i = -1 / lambda_i.
 __global__ __launch_bounds__(256) void ind_diaga_kernel(const double* __restrict__ Ht, long ld, long rows, const double* __restrict__ lam,
-                                                        const double* __restrict__ alpha, double* __restrict__ diagA) {
+                                                        const double* __restrict__ alpha, double* __restrict__ diagA,
+                                                        const double* __restrict__ resid, double* __restrict__ omega) {
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= rows) return;
@@ -102,7 +113,11 @@ __global__ __launch_bounds__(256) void ind_diaga_kernel(const double* __restrict
   for (long j = lane; j < ld; j += 64) { const double v = Ht[row * ld + j]; hh += v * v; }
   hh = wave_sum(hh);
   const double l = lam[row], a = alpha[row];
-  if (lane == 0) diagA[row] = a * a - (1.0 / l - hh / (l * l));
+  if (lane == 0) {
+    const double dA = a * a - (1.0 / l - hh / (l * l));
+    diagA[row] = resid ? dA + resid[row] / (l * l) : dA;
+    if (resid) omega[row] = -1.0 / l;
+  }
 }
 // Y (se x ld; `rows` of them data points) holding H^T M1  <-  alpha_i w_j - Y_ij / lambda_i, the DTC part of Z^T; the rows past
 // the data points stay zero
@@ -112,6 +127,32 @@ __global__ __launch_bounds__(256) void ind_zt_kernel(double* __restrict__ Y, lon
   if (idx >= rows * ld) return;
   const long i = idx / ld, j = idx - i * ld;
   Y[idx] = alpha[i] * w[j * ws] - Y[idx] / lam[i];
+}
+// The same Z^T for the gradient of the inducing inputs, from P itself: Zt (rows x ld) holding H^T G2, G2 = H Lambda^-1 P^T  <-
+// alpha_i w_j - (Pt_ij - Zt_ij) / lambda_i - omega_i Pt_ij (omega == nullptr: DTC); w = P alpha with the stride ws
+__global__ __launch_bounds__(256) void ind_zt_p_kernel(double* __restrict__ Zt, const double* __restrict__ Pt, long ld, long rows,
+                                                       const double* __restrict__ lam, const double* __restrict__ alpha,
+                                                       const double* __restrict__ omega, const double* __restrict__ w, long ws) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= rows * ld) return;
+  const long i = idx / ld, j = idx - i * ld;
+  const double p = Pt[idx];
+  double z = alpha[i] * w[j * ws] - (p - Zt[idx]) / lam[i];
+  if (omega) z -= omega[i] * p;
+  Zt[idx] = z;
+}
+// R (se x rp) = the vector a (rows entries) in column 0, zero elsewhere
+__global__ __launch_bounds__(256) void ind_col_kernel(const double* __restrict__ a, long rows, long se, long rp, double* __restrict__ R) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= se * rp) return;
+  const long i = idx / rp, c = idx - i * rp;
+  R[idx] = (i < rows && c == 0) ? a[i] : 0.0;
+}
+// row i of V (rows x ld) divided by d[i]
+__global__ __launch_bounds__(256) void ind_row_div_kernel(double* __restrict__ V, long ld, long rows, const double* __restrict__ d) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= rows * ld) return;
+  V[idx] /= d[idx / ld];
 }
 // row i of V (rows x ld) scaled by d[i]
 __global__ __launch_bounds__(256) void ind_row_scale_kernel(double* __restrict__ V, long ld, long rows, const double* __restrict__ d) {
@@ -213,6 +254,8 @@ extern "C" int gh_inducing_create(const gh_inducing_opts* opts, gh_inducing** ou
   if (!out || !opts) { gh_set_error("null argument"); return GH_ERR_BAD_ARG; }
   if (opts->method != 0 && opts->method != 1) { gh_set_error("the inducing-point solver takes method 0 (DTC) or 1 (FITC), not %d", (int)opts->method); return GH_ERR_BAD_ARG; }
   if (opts->strip_points < 0) { gh_set_error("strip_points must not be negative"); return GH_ERR_BAD_ARG; }
+  if (opts->variational != 0 && opts->variational != 1) { gh_set_error("variational is 0 or 1, not %d", (int)opts->variational); return GH_ERR_BAD_ARG; }
+  if (opts->variational && opts->method != 0) { gh_set_error("the variational bound goes with method 0 (DTC)"); return GH_ERR_BAD_ARG; }
   if (gh_device_count() <= 0) { gh_set_error("no HIP device available: the george_amd inducing-point solver needs an MI355X"); return GH_ERR_HIP; }
   gh_inducing* h = new gh_inducing();
   h->opts = *opts;
@@ -235,6 +278,12 @@ extern "C" void gh_inducing_destroy(gh_inducing* h) {
   delete h;
 }
 extern "C" int64_t gh_inducing_info(const gh_inducing* h) { return h ? h->info : 0; }
+extern "C" int gh_inducing_trace_term(const gh_inducing* h, double* out) {
+  if (!h || !out) { gh_set_error("null argument"); return GH_ERR_BAD_ARG; }
+  if (!h->computed) { gh_set_error("you must call 'compute' first"); return GH_ERR_NOT_COMPUTED; }
+  *out = h->opts.variational ? h->tau : 0.0;
+  return GH_OK;
+}
 
 static int ind_need(gh_inducing* h) {
   if (!h) { gh_set_error("null solver"); return GH_ERR_BAD_ARG; }
@@ -292,6 +341,8 @@ extern "C" int gh_inducing_compute(gh_inducing* h, gh_kernel* k, const double* x
   GH_CHECK(h->yerr.ensure((size_t)n * sizeof(double)));
   GH_CHECK(h->u.ensure((size_t)m * ndim * sizeof(double)));
   GH_CHECK(h->lam.ensure((size_t)n * sizeof(double)));
+  const bool vfe = h->opts.variational != 0, diag = vfe || h->opts.method != 0;    // diag: the kernel diagonal is needed
+  if (vfe) GH_CHECK(h->resid.ensure((size_t)n * sizeof(double)));
   GH_CHECK(h->vals.ensure((size_t)(n + mp) * sizeof(double)));
   for (GhBuf* b : {(GhBuf*)&h->Lui, (GhBuf*)&h->M1, (GhBuf*)&h->wk1, (GhBuf*)&h->wk2}) GH_CHECK(b->ensure(ind_sq(h)));
   GH_CHECK(h->dinv.ensure((size_t)mp * GH_TILE * sizeof(double)));
@@ -302,7 +353,7 @@ extern "C" int gh_inducing_compute(gh_inducing* h, gh_kernel* k, const double* x
   GH_HIP(hipMemsetAsync(h->scal.p, 0, 4 * sizeof(double), st));
   long long* const word_u = (long long*)(h->scal.d() + 1);  // the failure words of the two factorisations
   long long* const word_a = (long long*)(h->scal.d() + 2);
-  double res[3] = {0.0, 0.0, 0.0};
+  double res[4] = {0.0, 0.0, 0.0, 0.0};
 
   // K_uu + jitter I = L_u L_u^T (the padding: the identity), Lui = L_u^-1
   GH_CHECK(gh_launch_kmat(k, h->u.d(), m, h->u.d(), m, nullptr, h->wk1.d(), mp, mp, mp, 0, 0, true, false, st));
@@ -320,19 +371,21 @@ extern "C" int gh_inducing_compute(gh_inducing* h, gh_kernel* k, const double* x
 
   // G = sum_J (Lambda_J^-1/2 V_J^T)^T (Lambda_J^-1/2 V_J^T) into wk2, strips ascending
   const int64_t s = ind_strip_points(h, n);
-  GhPooledBuf sF, sV, kd;
+  GhPooledBuf sF, sV, kd, tauv;
   GH_CHECK(sF.ensure((size_t)s * mp * sizeof(double)));
   GH_CHECK(sV.ensure((size_t)s * mp * sizeof(double)));
-  if (h->opts.method) GH_CHECK(kd.ensure((size_t)s * sizeof(double)));
+  if (diag) GH_CHECK(kd.ensure((size_t)s * sizeof(double)));
+  if (vfe) GH_CHECK(tauv.ensure((size_t)n * sizeof(double)));
   GH_HIP(hipMemsetAsync(h->wk2.p, 0, ind_sq(h), st));
   for (int64_t j0 = 0; j0 < n; j0 += s) {
     const int64_t cw = std::min<int64_t>(s, n - j0), se = gh_round_up(cw, GH_TILE);
     const double* xj = h->x.d() + j0 * ndim;
     GH_CHECK(ind_build(h, k, xj, cw, se, sF.d()));
     GH_CHECK(ind_mm(st, sV.d(), mp, sF.d(), mp, true, h->Lui.d(), mp, true, se, mp, mp, 1.0, 0.0, /* Lui is lower */ true));
-    if (h->opts.method) GH_CHECK(gh_launch_kdiag(k, xj, xj, cw, kd.d(), st));
+    if (diag) GH_CHECK(gh_launch_kdiag(k, xj, xj, cw, kd.d(), st));
     hipLaunchKernelGGL(ind_lambda_kernel, dim3(ind_row_blocks(cw)), dim3(256), 0, st, sV.d(), (long)mp, (long)cw, (const double*)h->yerr.d() + j0,
-                       (const double*)(h->opts.method ? kd.d() : nullptr), h->lam.d() + j0, h->vals.d() + j0);
+                       (const double*)(diag ? kd.d() : nullptr), h->lam.d() + j0, h->vals.d() + j0,
+                       vfe ? h->resid.d() + j0 : (double*)nullptr, vfe ? tauv.d() + j0 : (double*)nullptr);
     GH_HIP(hipGetLastError());
     GH_CHECK(ind_mm(st, h->wk2.d(), mp, sV.d(), mp, false, sV.d(), mp, false, mp, mp, se, 1.0, 1.0, false, /* lower */ true));
   }
@@ -343,10 +396,11 @@ extern "C" int gh_inducing_compute(gh_inducing* h, gh_kernel* k, const double* x
   hipLaunchKernelGGL(ind_logdiag_kernel, dim3(ind_blocks((size_t)mp)), dim3(256), 0, st, (const double*)h->wk2.d(), (long)mp, (long)mp, h->vals.d() + n);
   GH_HIP(hipGetLastError());
   GH_CHECK(gh_launch_kgrad_final(h->vals.d(), n + mp, 1, h->scal.d(), st));
+  if (vfe) GH_CHECK(gh_launch_kgrad_final(tauv.d(), n, 1, h->scal.d() + 3, st));       // tau = sum_i resid_i / lambda_i, fixed order
   // M1 = L_A^-1 L_u^-1
   GH_CHECK(gh_chol_linv(st, h->wk2.d(), h->dinv.d(), mp, h->wk1.d()));
   GH_CHECK(ind_mm(st, h->M1.d(), mp, h->wk1.d(), mp, true, h->Lui.d(), mp, false, mp, mp, mp, 1.0, 0.0));
-  GH_HIP(hipMemcpyAsync(res, h->scal.d(), 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+  GH_HIP(hipMemcpyAsync(res, h->scal.d(), 4 * sizeof(double), hipMemcpyDeviceToHost, st));
   GH_HIP(hipStreamSynchronize(st));
   if (info_from_bits(res[2]) != 0) {
     h->info = -info_from_bits(res[2]);
@@ -354,6 +408,7 @@ extern "C" int gh_inducing_compute(gh_inducing* h, gh_kernel* k, const double* x
     return GH_ERR_NOT_PD;
   }
   h->logdet = res[0];
+  h->tau = vfe ? res[3] : 0.0;
   if (logdet_out) *logdet_out = res[0];
   h->computed = true;
   return GH_OK;
@@ -434,21 +489,38 @@ extern "C" int gh_inducing_dot_solve(gh_inducing* h, const double* y, double* ou
   return GH_OK;
 }
 
-extern "C" int gh_inducing_grad(gh_inducing* h, gh_kernel* k, const uint32_t* which, const double* r, double* grad, double* alpha,
-                                double* diagA) {
-  GH_CHECK(ind_need(h));
-  if (!k || !which || !r || !grad) { gh_set_error("bad argument to grad"); return GH_ERR_BAD_ARG; }
-  if (k->ndim != h->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
-  if (k->size > GH_MAX_GRAD) { gh_set_error("grad: %d kernel parameters, at most %d", k->size, GH_MAX_GRAD); return GH_ERR_BAD_ARG; }
-  GH_CHECK(k->upload());
+// The body of gh_inducing_grad and gh_inducing_grad_u.  which == nullptr: no kernel gradient; ugrad == nullptr: no gradient of
+// the inducing inputs (and then not one launch more than before).
+// ugrad does not take the kernel gradient's Z_J^T and W: those are products with the explicit inverses M1 and Lui, whose single
+// elements carry a relative error of eps cond(K_uu) -- harmless in sums over j against derivatives that are smooth in u_j, but
+// ugrad is one row of Z and W per inducing input.  It takes them from P itself: a pass over the strips for
+// G2 = H Lambda^-1 P^T = sum_J (Lambda_J^-1 H_J^T)^T P_J^T and w = P alpha = sum_J P_J alpha_J, then per strip
+// Z_J^T = alpha_J w^T - Lambda_J^-1 (P_J^T - H_J^T G2) - diag(omega_J) P_J^T  (C^-1 = Lambda^-1 - Lambda^-1 H^T H Lambda^-1)
+// and Z P^T = sum_J Z_J P_J^T = -2 W.
+static int ind_grad_body(gh_inducing* h, gh_kernel* k, const uint32_t* which, const double* r, double* grad, double* alpha, double* diagA,
+                         double* ugrad) {
   hipStream_t st = h->st;
   const int64_t n = h->n, m = h->m, mp = h->mp, nd = h->ndim, s = ind_strip_points(h, n), nstrips = (n + s - 1) / s;
-  const int P = k->size, Pw = P > 0 ? P : 1;
-  const bool fitc = h->opts.method != 0;
-  GhPooledBuf rd, al, dg, ctw, sF, sY, sB, Xb, zero, part, rows, scratch;
+  const int P = which ? k->size : 0, Pw = P > 0 ? P : 1;
+  const bool vfe = h->opts.variational != 0, fitc = h->opts.method != 0 || vfe;    // fitc: Z has a diagonal part, of weight `wd`
+  GhPooledBuf rd, al, dg, om, ug, upart, sP, sZ, aR, wp, Wa, ctw, sF, sY, sB, Xb, zero, part, rows, scratch;
   GH_CHECK(rd.ensure((size_t)n * sizeof(double)));
   GH_CHECK(al.ensure((size_t)n * sizeof(double)));
   GH_CHECK(dg.ensure((size_t)n * sizeof(double)));
+  if (vfe) GH_CHECK(om.ensure((size_t)n * sizeof(double)));
+  const double* const wd = vfe ? om.d() : dg.d();           // omega: diagA (FITC) or -1 / lambda (the bound)
+  if (ugrad) {
+    GH_CHECK(ug.ensure((size_t)m * nd * sizeof(double)));
+    // (the chunk count is not monotone in the row count: the full strip, the last strip and the K_uu term each have their own)
+    const size_t need = std::max({gh_wxgrad_work_doubles(std::min<int64_t>(s, n), m, (int)nd), gh_wxgrad_work_doubles(n - (nstrips - 1) * s, m, (int)nd),
+                                  gh_wxgrad_work_doubles(m, m, (int)nd)});
+    GH_CHECK(upart.ensure(need * sizeof(double)));
+    GH_CHECK(sP.ensure((size_t)s * mp * sizeof(double)));
+    GH_CHECK(sZ.ensure((size_t)s * mp * sizeof(double)));
+    GH_CHECK(aR.ensure((size_t)s * GH_TILE * sizeof(double)));
+    GH_CHECK(wp.ensure((size_t)mp * GH_TILE * sizeof(double)));
+    GH_CHECK(Wa.ensure(ind_sq(h)));
+  }
   GH_CHECK(gh_to_device(rd.d(), r, (size_t)n, st));
   GH_CHECK(ind_apply(h, rd.d(), 1, al.d(), ctw));           // alpha = C^-1 r, and w = M1^T t(r) = P alpha
   const double* w = ctw.d() + 2 * (size_t)mp * GH_TILE;
@@ -472,6 +544,26 @@ extern "C" int gh_inducing_grad(gh_inducing* h, gh_kernel* k, const uint32_t* wh
     GH_HIP(hipFuncSetAttribute((const void*)ind_grad_tile_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, IND_GRAD_LDS));
     GH_HIP(hipFuncSetAttribute((const void*)ind_grad_tile_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, IND_GRAD_LDS));
   }
+  double* const G2 = Xb.d();                                // (Xb is the kernel gradient's only after the strips)
+  if (ugrad) {                                              // the pass for G2 and w = P alpha
+    GH_HIP(hipMemsetAsync(Xb.p, 0, ind_sq(h), st));
+    GH_HIP(hipMemsetAsync(Wa.p, 0, ind_sq(h), st));
+    GH_HIP(hipMemsetAsync(wp.p, 0, (size_t)mp * GH_TILE * sizeof(double), st));
+    for (int64_t j0 = 0; j0 < n; j0 += s) {
+      const int64_t cw = std::min<int64_t>(s, n - j0), se = gh_round_up(cw, GH_TILE);
+      GH_CHECK(ind_build(h, &h->kc, h->x.d() + j0 * nd, cw, se, sF.d()));
+      GH_CHECK(ind_mm(st, sB.d(), mp, sF.d(), mp, true, h->Lui.d(), mp, true, se, mp, mp, 1.0, 0.0, true));
+      GH_CHECK(ind_mm(st, sP.d(), mp, sB.d(), mp, true, h->Lui.d(), mp, false, se, mp, mp, 1.0, 0.0));                          // P_J^T
+      hipLaunchKernelGGL(ind_col_kernel, dim3(ind_blocks((size_t)se * GH_TILE)), dim3(256), 0, st, (const double*)al.d() + j0, (long)cw, (long)se,
+                         (long)GH_TILE, aR.d());
+      GH_HIP(hipGetLastError());
+      GH_CHECK(ind_mm(st, wp.d(), GH_TILE, sP.d(), mp, false, aR.d(), GH_TILE, false, mp, GH_TILE, se, 1.0, 1.0));
+      GH_CHECK(ind_mm(st, sB.d(), mp, sF.d(), mp, true, h->M1.d(), mp, true, se, mp, mp, 1.0, 0.0, true));                      // H_J^T
+      hipLaunchKernelGGL(ind_row_div_kernel, dim3(ind_blocks((size_t)cw * mp)), dim3(256), 0, st, sB.d(), (long)mp, (long)cw, (const double*)h->lam.d() + j0);
+      GH_HIP(hipGetLastError());
+      GH_CHECK(ind_mm(st, G2, mp, sB.d(), mp, false, sP.d(), mp, false, mp, mp, se, 1.0, 1.0));
+    }
+  }
   // ZF = sum_J Z_J F_J into wk2
   GH_HIP(hipMemsetAsync(h->wk2.p, 0, ind_sq(h), st));
   GH_HIP(hipMemsetAsync(zero.p, 0, (size_t)mp * sizeof(double), st));
@@ -482,19 +574,32 @@ extern "C" int gh_inducing_grad(gh_inducing* h, gh_kernel* k, const uint32_t* wh
     GH_CHECK(ind_build(h, &h->kc, xj, cw, se, sF.d()));
     GH_CHECK(ind_mm(st, sB.d(), mp, sF.d(), mp, true, h->M1.d(), mp, true, se, mp, mp, 1.0, 0.0, /* M1 is lower */ true));      // H_J^T
     hipLaunchKernelGGL(ind_diaga_kernel, dim3(ind_row_blocks(cw)), dim3(256), 0, st, (const double*)sB.d(), (long)mp, (long)cw,
-                       (const double*)h->lam.d() + j0, (const double*)al.d() + j0, dg.d() + j0);
+                       (const double*)h->lam.d() + j0, (const double*)al.d() + j0, dg.d() + j0,
+                       vfe ? (const double*)h->resid.d() + j0 : (const double*)nullptr, vfe ? om.d() + j0 : (double*)nullptr);
     GH_HIP(hipGetLastError());
     GH_CHECK(ind_mm(st, sY.d(), mp, sB.d(), mp, true, h->M1.d(), mp, false, se, mp, mp, 1.0, 0.0));
     hipLaunchKernelGGL(ind_zt_kernel, dim3(ind_blocks((size_t)cw * mp)), dim3(256), 0, st, sY.d(), (long)mp, (long)cw, (const double*)h->lam.d() + j0,
                        (const double*)al.d() + j0, w, (long)GH_TILE);
     GH_HIP(hipGetLastError());
-    if (fitc) {                                             // - diag(diagA_J) P_J^T,  P_J^T = (F_J Lui^T) Lui
+    if (fitc) {                                             // - diag(omega_J) P_J^T,  P_J^T = (F_J Lui^T) Lui
       GH_CHECK(ind_mm(st, sB.d(), mp, sF.d(), mp, true, h->Lui.d(), mp, true, se, mp, mp, 1.0, 0.0, true));
-      hipLaunchKernelGGL(ind_row_scale_kernel, dim3(ind_blocks((size_t)cw * mp)), dim3(256), 0, st, sB.d(), (long)mp, (long)cw, (const double*)dg.d() + j0);
+      hipLaunchKernelGGL(ind_row_scale_kernel, dim3(ind_blocks((size_t)cw * mp)), dim3(256), 0, st, sB.d(), (long)mp, (long)cw, wd + j0);
       GH_HIP(hipGetLastError());
       GH_CHECK(ind_mm(st, sY.d(), mp, sB.d(), mp, true, h->Lui.d(), mp, false, se, mp, mp, -1.0, 1.0));
     }
     GH_CHECK(ind_mm(st, h->wk2.d(), mp, sY.d(), mp, false, sF.d(), mp, false, mp, mp, se, 1.0, 1.0));
+    if (ugrad) {
+      GH_CHECK(ind_mm(st, sB.d(), mp, sF.d(), mp, true, h->Lui.d(), mp, true, se, mp, mp, 1.0, 0.0, true));
+      GH_CHECK(ind_mm(st, sP.d(), mp, sB.d(), mp, true, h->Lui.d(), mp, false, se, mp, mp, 1.0, 0.0));                          // P_J^T
+      GH_CHECK(ind_mm(st, sB.d(), mp, sF.d(), mp, true, h->M1.d(), mp, true, se, mp, mp, 1.0, 0.0, true));                      // H_J^T
+      GH_CHECK(ind_mm(st, sZ.d(), mp, sB.d(), mp, true, G2, mp, false, se, mp, mp, 1.0, 0.0));                                  // H_J^T G2
+      hipLaunchKernelGGL(ind_zt_p_kernel, dim3(ind_blocks((size_t)cw * mp)), dim3(256), 0, st, sZ.d(), (const double*)sP.d(), (long)mp, (long)cw,
+                         (const double*)h->lam.d() + j0, (const double*)al.d() + j0, fitc ? wd + j0 : (const double*)nullptr, (const double*)wp.d(),
+                         (long)GH_TILE);
+      GH_HIP(hipGetLastError());
+      GH_CHECK(gh_launch_wxgrad(k, h->u.d(), m, xj, cw, sZ.d(), mp, 1.0, j0 > 0, ug.d(), upart.d(), st));
+      GH_CHECK(ind_mm(st, Wa.d(), mp, sZ.d(), mp, false, sP.d(), mp, false, mp, mp, se, 1.0, 1.0));                             // Z P^T += Z_J P_J^T
+    }
     if (P > 0) {
       const dim3 grid((unsigned)tiles_c, (unsigned)((cw + IND_GT - 1) / IND_GT));
       hipLaunchKernelGGL(ind_grad_tile_kernel<false>, grid, dim3(IND_GT), lds, st, (const GhNode*)k->d_nodes, (int)k->nodes.size(), (int)nd, P, gp,
@@ -504,7 +609,7 @@ extern "C" int gh_inducing_grad(gh_inducing* h, gh_kernel* k, const uint32_t* wh
       if (fitc) {
         const unsigned nwg = (unsigned)((cw + IND_GT * IND_GT - 1) / (IND_GT * IND_GT));
         hipLaunchKernelGGL(ind_grad_tile_kernel<true>, dim3(nwg), dim3(IND_GT), lds, st, (const GhNode*)k->d_nodes, (int)k->nodes.size(), (int)nd, P, gp,
-                           (const uint32_t*)d_which, xj, (long)cw, (const double*)nullptr, 0L, (const double*)dg.d() + j0, 0L, 0.5, partial);
+                           (const uint32_t*)d_which, xj, (long)cw, (const double*)nullptr, 0L, wd + j0, 0L, 0.5, partial);
         GH_HIP(hipGetLastError());
         GH_CHECK(gh_launch_kgrad_final(partial, nwg, P, rows.d() + nrows++ * P, st));
       }
@@ -520,10 +625,38 @@ extern "C" int gh_inducing_grad(gh_inducing* h, gh_kernel* k, const uint32_t* wh
     GH_CHECK(gh_launch_kgrad_final(rows.d(), nrows, P, rows.d() + nrows * P, st));
     GH_CHECK(gh_from_device(grad, rows.d() + nrows * P, (size_t)P, st));
   }
+  if (ugrad) {                                              // sG = 1/2 (Z P^T + its transpose) = -(W + W^T): ugrad_j += sum_b (W + W^T)_jb d1 k(u_j, u_b)
+    double* const sG = Xb.d();
+    hipLaunchKernelGGL(ind_sym_kernel, dim3(ind_blocks((size_t)mp * mp)), dim3(256), 0, st, (const double*)Wa.d(), (long)mp, sG);
+    GH_HIP(hipGetLastError());
+    GH_CHECK(gh_launch_wxgrad(k, h->u.d(), m, h->u.d(), m, sG, mp, -1.0, true, ug.d(), upart.d(), st));
+    GH_CHECK(gh_from_device(ugrad, ug.d(), (size_t)m * nd, st));
+  }
   if (alpha) GH_CHECK(gh_from_device(alpha, al.d(), (size_t)n, st));
   if (diagA) GH_CHECK(gh_from_device(diagA, dg.d(), (size_t)n, st));
   GH_HIP(hipStreamSynchronize(st));
   return GH_OK;
+}
+
+extern "C" int gh_inducing_grad(gh_inducing* h, gh_kernel* k, const uint32_t* which, const double* r, double* grad, double* alpha,
+                                double* diagA) {
+  GH_CHECK(ind_need(h));
+  if (!k || !which || !r || !grad) { gh_set_error("bad argument to grad"); return GH_ERR_BAD_ARG; }
+  if (k->ndim != h->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
+  if (k->size > GH_MAX_GRAD) { gh_set_error("grad: %d kernel parameters, at most %d", k->size, GH_MAX_GRAD); return GH_ERR_BAD_ARG; }
+  GH_CHECK(k->upload());
+  return ind_grad_body(h, k, which, r, grad, alpha, diagA, nullptr);
+}
+extern "C" int gh_inducing_grad_u(gh_inducing* h, gh_kernel* k, const uint32_t* which, const double* r, double* grad, double* alpha,
+                                  double* diagA, double* ugrad) {
+  if (!h) { gh_set_error("null solver"); return GH_ERR_BAD_ARG; }
+  if (!k || !r || !ugrad || (which && !grad)) { gh_set_error("bad argument to grad_u"); return GH_ERR_BAD_ARG; }
+  if (!h->computed) { gh_set_error("you must call 'compute' first"); return GH_ERR_NOT_COMPUTED; }
+  if (k->ndim != h->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
+  if (which && k->size > GH_MAX_GRAD) { gh_set_error("grad_u: %d kernel parameters, at most %d", k->size, GH_MAX_GRAD); return GH_ERR_BAD_ARG; }
+  GH_HIP(hipSetDevice(h->opts.device));
+  GH_CHECK(k->upload());
+  return ind_grad_body(h, k, which, r, grad, alpha, diagA, ugrad);
 }
 
 extern "C" int gh_inducing_predict(gh_inducing* h, gh_kernel* k, const double* r, const double* xs, int64_t M, double* mu, double* var,

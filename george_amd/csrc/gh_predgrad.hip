@@ -13,6 +13,10 @@
 // A lane keeps ndim (x 2 with the variance) running sums for its test point over all tiles of the chunk; the four
 // wavefronts' sums meet in LDS in wavefront order and one partial row per (chunk, test point, d) is written.
 // Rows >= n and test points >= m of the padded buffers are neither evaluated nor read.
+//
+// gh_launch_wxgrad is the same tile without the alpha operand: out_cd (+)= scale sum_i Wt[i][c] G_cid for a dense weight
+// strip Wt, the chunks added in index order by wxgrad_final_kernel (the inducing-point solver's gradient with respect to
+// its inducing inputs, gh_inducing_grad_u).
 #include <algorithm>
 #include "gh_common.h"
 
@@ -33,11 +37,13 @@ struct PredGradArgs {
 
 // ND > 0: the fast form a + b F(r2) in ND input dimensions, registers only (gh_fast_xgrad); ND == 0: any kernel, through
 // the interpreter (gh_eval_xgrad; its operand stacks and the sums live in scratch memory).  VAR = false: no W operand.
-template <bool VAR, int ND>
+// MU = false (with VAR): no alpha operand and no pmu -- the weighted reduction of gh_launch_wxgrad, the same tile.
+template <bool MU, bool VAR, int ND>
 __global__ __launch_bounds__(256) void predgrad_kernel(PredGradArgs a, const GhNode* __restrict__ prog) {
+  static_assert(MU || VAR, "a reduction without operands");
   constexpr int NA = ND > 0 ? ND : GH_MAX_NDIM;
   __shared__ double xr[PG_ROWS * NA];
-  __shared__ double al[PG_ROWS];
+  __shared__ double al[MU ? PG_ROWS : 1];
   __shared__ double xc[ND > 0 ? 1 : PG_COLS * GH_MAX_NDIM];
   __shared__ double red[VAR ? 2 : 1][3][PG_COLS];
   const int nd = ND > 0 ? ND : a.nd;
@@ -67,11 +73,11 @@ __global__ __launch_bounds__(256) void predgrad_kernel(PredGradArgs a, const GhN
     const int rows = (int)(r_end - r0 < PG_ROWS ? r_end - r0 : PG_ROWS);
     __syncthreads();                                    // the previous tile has been read (and xc is staged)
     for (int e = threadIdx.x; e < rows * nd; e += 256) xr[e] = a.x[r0 * nd + e];
-    if ((int)threadIdx.x < rows) al[threadIdx.x] = a.alpha[r0 + threadIdx.x];
+    if (MU && (int)threadIdx.x < rows) al[threadIdx.x] = a.alpha[r0 + threadIdx.x];
     __syncthreads();
     if (!live) continue;
     for (int rr = wave; rr < rows; rr += 4) {
-      const double ai = al[rr];
+      const double ai = MU ? al[rr] : 0.0;
       double wi = 0.0;
       if (VAR) wi = a.W[(r0 + rr) * a.ldw + c];
       if (ND > 0) {
@@ -79,14 +85,14 @@ __global__ __launch_bounds__(256) void predgrad_kernel(PredGradArgs a, const GhN
         gh_fast_xgrad<NA>(a.fast, t, &xr[rr * ND], g);
 #pragma unroll
         for (int d = 0; d < NA; ++d) {
-          am[d] += g[d] * ai;
+          if (MU) am[d] += g[d] * ai;
           if (VAR) av[d] += g[d] * wi;
         }
       } else {
         double g1[GH_MAX_NDIM], g2[GH_MAX_NDIM];
         gh_eval_xgrad(prog, a.n_nodes, nd, &xc[lane * nd], &xr[rr * nd], g1, g2);
         for (int d = 0; d < nd; ++d) {
-          am[d] += g1[d] * ai;
+          if (MU) am[d] += g1[d] * ai;
           if (VAR) av[d] += g1[d] * wi;
         }
       }
@@ -100,13 +106,13 @@ __global__ __launch_bounds__(256) void predgrad_kernel(PredGradArgs a, const GhN
     for (int e = 0; e < NA; ++e) { vm = (e == d) ? am[e] : vm; vv = (e == d) ? av[e] : vv; }
     __syncthreads();
     if (wave > 0) {
-      red[0][wave - 1][lane] = vm;
+      if (MU) red[0][wave - 1][lane] = vm;
       if (VAR) red[VAR ? 1 : 0][wave - 1][lane] = vv;
     }
     __syncthreads();
     if (wave == 0 && live) {
       const long o = ((long)blockIdx.y * a.m + c) * nd + d;
-      a.pmu[o] = ((vm + red[0][0][lane]) + red[0][1][lane]) + red[0][2][lane];
+      if (MU) a.pmu[o] = ((vm + red[0][0][lane]) + red[0][1][lane]) + red[0][2][lane];
       if (VAR) a.pvar[o] = ((vv + red[VAR ? 1 : 0][0][lane]) + red[VAR ? 1 : 0][1][lane]) + red[VAR ? 1 : 0][2][lane];
     }
   }
@@ -132,6 +138,17 @@ __global__ __launch_bounds__(256) void predgrad_final_kernel(const GhNode* __res
   }
 }
 
+// out[c][d] = (add ? out[c][d] : 0) + scale * (the sum over the chunks, in index order).  One thread per entry.
+__global__ __launch_bounds__(256) void wxgrad_final_kernel(const double* __restrict__ part, long entries, long nchunks, double scale,
+                                                           int add, double* __restrict__ out) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= entries) return;
+  double s = 0.0;
+  for (long q = 0; q < nchunks; ++q) s += part[q * entries + e];
+  s *= scale;
+  out[e] = add ? out[e] + s : s;
+}
+
 static void predgrad_chunks(int64_t n, int64_t* nchunks, int64_t* rows_per) {
   const int64_t tiles = (n + PG_ROWS - 1) / PG_ROWS;
   const int64_t per = (tiles + PG_MAX_CHUNKS - 1) / PG_MAX_CHUNKS;       // tiles of a chunk
@@ -142,6 +159,18 @@ size_t gh_predgrad_work_doubles(int64_t n, int64_t m, int ndim, bool want_var) {
   int64_t nchunks, rows_per;
   predgrad_chunks(n, &nchunks, &rows_per);
   return (size_t)nchunks * m * ndim * (want_var ? 2 : 1);
+}
+
+// the tile kernel for k: the fast form's axes index the ND coordinates the kernel holds in registers (validated < ndim at creation)
+template <bool MU, bool VAR>
+static void predgrad_launch_tile(const gh_kernel* k, const PredGradArgs& a, dim3 grid, hipStream_t st) {
+  const dim3 block(256);
+  const GhNode* prog = k->d_nodes;
+  const int fnd = (k->fast.ok && k->ndim <= 3) ? k->ndim : 0;
+  if (fnd == 1)      hipLaunchKernelGGL((predgrad_kernel<MU, VAR, 1>), grid, block, 0, st, a, prog);
+  else if (fnd == 2) hipLaunchKernelGGL((predgrad_kernel<MU, VAR, 2>), grid, block, 0, st, a, prog);
+  else if (fnd == 3) hipLaunchKernelGGL((predgrad_kernel<MU, VAR, 3>), grid, block, 0, st, a, prog);
+  else               hipLaunchKernelGGL((predgrad_kernel<MU, VAR, 0>), grid, block, 0, st, a, prog);
 }
 
 int gh_launch_predgrad(const gh_kernel* k, const double* x, int64_t n, const double* xs, int64_t m, const double* alpha,
@@ -158,22 +187,35 @@ int gh_launch_predgrad(const gh_kernel* k, const double* x, int64_t n, const dou
   a.nd = k->ndim; a.n_nodes = (int)k->nodes.size(); a.fast = k->fast;
   const int64_t gx = (m + PG_COLS - 1) / PG_COLS;
   if (gx > 0x7fffffffL) { gh_set_error("predict_grad: too many test points"); return GH_ERR_BAD_ARG; }
-  const dim3 grid((unsigned)gx, (unsigned)nchunks), block(256);
-  const GhNode* prog = k->d_nodes;
-  // the fast form's axes index the ND coordinates the kernel holds in registers (validated < ndim at creation)
-  const int fnd = (k->fast.ok && k->ndim <= 3) ? k->ndim : 0;
-#define GH_PG_LAUNCH(V)                                                                                       \
-  do {                                                                                                        \
-    if (fnd == 1)      hipLaunchKernelGGL((predgrad_kernel<V, 1>), grid, block, 0, st, a, prog);              \
-    else if (fnd == 2) hipLaunchKernelGGL((predgrad_kernel<V, 2>), grid, block, 0, st, a, prog);              \
-    else if (fnd == 3) hipLaunchKernelGGL((predgrad_kernel<V, 3>), grid, block, 0, st, a, prog);              \
-    else               hipLaunchKernelGGL((predgrad_kernel<V, 0>), grid, block, 0, st, a, prog);              \
-  } while (0)
-  if (var) GH_PG_LAUNCH(true); else GH_PG_LAUNCH(false);
-#undef GH_PG_LAUNCH
+  const dim3 grid((unsigned)gx, (unsigned)nchunks);
+  if (var) predgrad_launch_tile<true, true>(k, a, grid, st); else predgrad_launch_tile<true, false>(k, a, grid, st);
   GH_HIP(hipGetLastError());
-  hipLaunchKernelGGL(predgrad_final_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, prog, a.n_nodes, k->ndim,
+  hipLaunchKernelGGL(predgrad_final_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const GhNode*)k->d_nodes, a.n_nodes, k->ndim,
                      xs, (long)m, a.pmu, a.pvar, (long)nchunks, dmu, dvar);
+  GH_HIP(hipGetLastError());
+  return GH_OK;
+}
+
+size_t gh_wxgrad_work_doubles(int64_t nx, int64_t nt, int ndim) { return gh_predgrad_work_doubles(nx, nt, ndim, false); }
+
+int gh_launch_wxgrad(const gh_kernel* k, const double* t, int64_t nt, const double* x, int64_t nx, const double* Wt, int64_t ld,
+                     double scale, bool add, double* out, double* partial, hipStream_t st) {
+  if (nx <= 0 || nt <= 0) return GH_OK;
+  if (!Wt || ld < nt) { gh_set_error("wxgrad: the weight strip has fewer columns than there are points t"); return GH_ERR_BAD_ARG; }
+  int64_t nchunks, rows_per;
+  predgrad_chunks(nx, &nchunks, &rows_per);
+  PredGradArgs a;
+  a.x = x; a.n = (long)nx; a.xs = t; a.m = (long)nt; a.alpha = nullptr; a.W = Wt; a.ldw = (long)ld;
+  a.rows_per = (long)rows_per;
+  a.pmu = nullptr; a.pvar = partial;
+  a.nd = k->ndim; a.n_nodes = (int)k->nodes.size(); a.fast = k->fast;
+  const int64_t gx = (nt + PG_COLS - 1) / PG_COLS;
+  if (gx > 0x7fffffffL) { gh_set_error("wxgrad: too many points t"); return GH_ERR_BAD_ARG; }
+  predgrad_launch_tile<false, true>(k, a, dim3((unsigned)gx, (unsigned)nchunks), st);
+  GH_HIP(hipGetLastError());
+  const long entries = (long)(nt * k->ndim);
+  hipLaunchKernelGGL(wxgrad_final_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, st, (const double*)partial, entries, (long)nchunks,
+                     scale, add ? 1 : 0, out);
   GH_HIP(hipGetLastError());
   return GH_OK;
 }

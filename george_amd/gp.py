@@ -443,6 +443,66 @@ class GP(ModelSet):
         self._obj_cache = (np.array(vector, dtype=np.float64), np.array(y, dtype=np.float64), g)
         return -ll, -g
 
+    # -- the inducing inputs of a sparse solver as parameters (no reference counterpart) ------------
+    # With ``InducingSolver(variational=True)`` the objective is Titsias' lower bound of the exact log-likelihood
+    # (``log_determinant`` carries its trace term), so maximising it over the hyper-parameters and the inducing inputs jointly
+    # does not over-fit; under DTC and FITC the same calls work, and over-fit.
+    def _need_inducing(self):
+        if not self._offers("grad_inducing", on_type=True):
+            raise NotImplementedError("{0} has no inducing inputs to differentiate (no grad_inducing)".format(self.solver_type.__name__))
+
+    @property
+    def inducing_inputs(self):
+        """The (m, ndim) inducing inputs the solver used in its last ``compute``."""
+        self._need_inducing()
+        self.recompute()
+        return np.array(self.solver.u)
+
+    def grad_log_likelihood_inducing(self, y, quiet=False):
+        """The gradient of :meth:`log_likelihood` with respect to the inducing inputs, (m, ndim).  The relative jitter follows
+        ``mean_j k(u_j, u_j)``, which the gradient treats as a constant: exact for stationary kernels only."""
+        self._need_inducing()
+        r = self._recomputed_residual(y, quiet)
+        if r is None:
+            return np.zeros(np.shape(self.solver.u), dtype=np.float64)
+        return self.solver.grad_inducing(r)[3]
+
+    def nll_and_grad_inducing(self, vector, y, quiet=True):
+        """``(-F, -dF)`` at ``vector`` = the parameter vector followed by ``u.ravel()``, for
+        ``scipy.optimize.minimize(gp.nll_and_grad_inducing, v0, jac=True, args=(y,))``: sets the parameters, puts ``u`` into
+        ``solver_kwargs["inducing"]``, and makes one ``compute``, one ``dot_solve`` and one ``grad_inducing``.  The model must
+        have been computed once (the data are the recorded ones).  ``quiet`` as in :meth:`nll_and_grad`.  The relative jitter
+        follows ``mean_j k(u_j, u_j)``, constant in ``u`` for stationary kernels only: for others the gradient is that of the
+        objective at a fixed absolute jitter."""
+        self._need_inducing()
+        if not (hasattr(self, "_x") and hasattr(self, "_yerr2")):
+            raise RuntimeError("You need to compute the model first")
+        vector = np.asarray(vector, dtype=np.float64)
+        npar, ndim = len(self), self._x.shape[1]
+        if vector.ndim != 1 or len(vector) <= npar or (len(vector) - npar) % ndim:
+            raise ValueError("vector is the parameter vector followed by u.ravel()")
+        bad = (np.inf, np.zeros(len(vector)))
+        self.set_parameter_vector(vector[:npar])
+        if not np.isfinite(self.log_prior()):
+            return bad
+        self.solver_kwargs["inducing"] = np.array(vector[npar:].reshape(-1, ndim))
+        self._obj_cache = None
+        self._computed = False
+        try:
+            self._factorize()
+        except (ValueError, np.linalg.LinAlgError):
+            if quiet:
+                return bad
+            raise
+        r = self._residual_quiet(y, quiet)
+        if r is None:
+            return bad
+        ll = self._const - 0.5 * self.solver.dot_solve(r)
+        kg_full, alpha, diagA, ugrad = self.solver.grad_inducing(r, self.kernel.unfrozen_mask.astype(np.uint32))
+        kgrad = kg_full[self.kernel.unfrozen_mask] if len(self.kernel) else None
+        g = np.concatenate([self._assemble_grad(alpha, diagA, kgrad, quiet), ugrad.ravel()])
+        return (-ll, -g) if np.isfinite(ll) else bad
+
     def _cached_grad(self, vector, y):
         c = getattr(self, "_obj_cache", None)
         if c is None or not self.computed:

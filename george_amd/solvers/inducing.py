@@ -1,5 +1,5 @@
-"""``InducingSolver`` -- the inducing-point approximations DTC and FITC on one MI355X, for smooth kernels on data sets no
-N x N factor fits: 10^5 - 10^6 points, a few hundred to a few thousand inducing inputs.
+"""``InducingSolver`` -- the inducing-point approximations DTC and FITC and the variational bound (VFE) on one MI355X, for
+smooth kernels on data sets no N x N factor fits: 10^5 - 10^6 points, a few hundred to a few thousand inducing inputs.
 
 The covariance is replaced by a low-rank term through ``m`` inducing inputs ``u`` plus a diagonal,
 ``C = K_fu (K_uu + jitter I)^-1 K_uf + diag(lambda)``, with ``lambda_i = yerr_i^2`` (DTC) or ``yerr_i^2`` plus the variance the
@@ -12,6 +12,14 @@ the device side in ``george_amd/csrc/gh_inducing.hip``.
 
 Prediction is the same for both methods, O(M m^2) whatever N.
 
+``variational=True`` (with ``method="dtc"``) turns the objective into Titsias' lower bound of the exact log-likelihood,
+``F = log N(r | 0, C) - 1/2 tau`` with ``tau = sum_i max(k(x_i, x_i) - q_i, 0) / yerr_i^2``: ``F`` never exceeds the dense
+log-likelihood and does not decrease when an inducing input is added, which DTC and FITC do not promise.  It is the objective
+under which the inducing inputs may be optimised without over-fitting: :meth:`InducingSolver.grad_inducing` gives the gradient
+with respect to them (for all three objectives), ``GP.nll_and_grad_inducing`` the joint objective for an optimiser.  The
+gradient costs one more pass of N m kernel input-gradient evaluations and one more pass of strip GEMMs beside ``grad``'s work
+(counts, not measurements; ``include/george_amd.h`` has them).
+
 ``jitter`` is relative: the device gets ``jitter * mean_j k(u_j, u_j)`` on the diagonal of ``K_uu``, and the likelihood gradient
 treats that number as a constant.
 
@@ -19,7 +27,7 @@ The default inducing set is greedy max-min distance over the data (:func:`induci
 default, or ``select="device"``: one streaming kernel per pick (``george_amd/csrc/gh_inducing_select.hip``) that returns the
 same points for up to 7 input dimensions.
 
-Not built: ``apply_sqrt``, variational (VFE) bounds, optimising the inducing locations, and a multi-device form.
+Not built: ``apply_sqrt`` and a multi-device form.
 """
 import ctypes as C
 import hashlib
@@ -27,7 +35,7 @@ import hashlib
 import numpy as np
 
 from .. import _native as N
-from .protocol import HandlePool, NativeSolver
+from .protocol import HandlePool, NativeSolver, rhs_vector
 
 __all__ = ["InducingSolver", "inducing_points"]
 
@@ -76,14 +84,19 @@ def inducing_points(x, m, device=None, return_dmin=False):
 
 
 class InducingSolver(NativeSolver):
-    """``InducingSolver(kernel, inducing=512, method="fitc", jitter=1e-10, device=0, strip_points=0, select="host")``.
+    """``InducingSolver(kernel, inducing=512, method="fitc", jitter=1e-10, device=0, strip_points=0, select="host",
+    variational=False)``.
 
     ``inducing``: an (m, ndim) array of inducing inputs, or an int ``m``: ``min(m, N)`` of the data points chosen by
     :func:`inducing_points` (kept per data set, so an optimiser pays for the selection once); 1 <= m <= 8192.  ``method``:
     ``"dtc"`` or ``"fitc"``.  ``jitter``: relative to the mean of ``k(u_j, u_j)``.  ``strip_points``: data points per
     strip on the device, 0 for a choice by memory budget (results do not depend on it beyond rounding).  ``select``: where
     an int ``inducing`` is turned into points, ``"host"`` (NumPy) or ``"device"`` (``gh_inducing_select`` on the solver's
-    device: the same points for up to 7 input dimensions).
+    device: the same points for up to 7 input dimensions).  ``variational``: the variational bound; it needs ``method="dtc"``.
+
+    Under the bound ``log_determinant`` is ``log|C| + tau`` (``trace_term`` is ``tau``, 0.0 when the bound is off): that is what
+    ``GP``'s ``-1/2 (r^T C^-1 r + log_determinant + N log 2 pi)`` needs, so ``GP.log_likelihood``, ``nll_and_grad`` and the rest
+    return the bound ``F`` and its gradient, with no branch in ``GP``.  It is NOT the log-determinant of a covariance then.
 
     A factorisation that fails raises ``numpy.linalg.LinAlgError`` like the other solvers, naming the factor;
     ``failed_factor`` is then ``"K_uu"`` or ``"A"`` and ``failed_pivot`` its 0-based pivot."""
@@ -91,9 +104,12 @@ class InducingSolver(NativeSolver):
     _CREATE, _DESTROY = "gh_inducing_create", "gh_inducing_destroy"
     _SOLVE, _DOT_SOLVE = "gh_inducing_solve", "gh_inducing_dot_solve"   # C^-1 y and y^T C^-1 y; no get_inverse, no apply_sqrt
 
-    def __init__(self, kernel, inducing=512, method="fitc", jitter=1e-10, device=0, strip_points=0, select="host"):
+    def __init__(self, kernel, inducing=512, method="fitc", jitter=1e-10, device=0, strip_points=0, select="host", variational=False):
         if method not in METHODS:
             raise ValueError("InducingSolver: method is 'dtc' or 'fitc'")
+        variational = bool(variational)
+        if variational and method != "dtc":
+            raise ValueError("InducingSolver: variational=True needs method='dtc'")
         if select not in ("host", "device"):
             raise ValueError("InducingSolver: select is 'host' or 'device'")
         jitter = float(jitter)
@@ -116,10 +132,12 @@ class InducingSolver(NativeSolver):
         self.method = method
         self.jitter = jitter
         self.select = select
+        self.variational = variational
+        self.trace_term = 0.0                               # tau of the last compute(); 0.0 when the bound is off
         self.failed_factor = None
         self.failed_pivot = None
         self.u = None                                       # the inducing inputs of the last compute()
-        self._opts = dict(device=int(device), method=METHODS[method], strip_points=strip_points)
+        self._opts = dict(device=int(device), method=METHODS[method], strip_points=strip_points, variational=int(variational))
         super(InducingSolver, self).__init__(kernel)
 
     # The default inducing set depends on the inputs, m and the route only (from 8 dimensions on the two routes may differ), and
@@ -139,17 +157,18 @@ class InducingSolver(NativeSolver):
         return idx
 
     # -- lifetime.  The handle of a dropped solver (its m x m buffers on the device) is parked, at most _HPOOL_MAX per
-    # (device, method, strip_points), and picked up by the next solver with the same options.
+    # (device, method, strip_points, variational), and picked up by the next solver with the same options.
     _HPOOL_MAX = 2
     _HPOOL = HandlePool(_DESTROY, _HPOOL_MAX)
     _GIVES_BACK_POOLS = (_HPOOL,)                           # out of memory: own handle, own pool and the native caches
 
     def _options_key(self):
-        return (self._opts["device"], self._opts["method"], self._opts["strip_points"])
+        key = (self._opts["device"], self._opts["method"], self._opts["strip_points"])
+        return key + (1,) if self._opts["variational"] else key
 
     def _native_opts(self):
         o = N.gh_inducing_opts()
-        o.device, o.method, o.strip_points = self._options_key()
+        o.device, o.method, o.strip_points, o.variational = (self._opts[k] for k in ("device", "method", "strip_points", "variational"))
         return o
 
     def compute(self, x, yerr):
@@ -180,7 +199,10 @@ class InducingSolver(NativeSolver):
             N.check(rc)
 
         self._retry_without_parked_memory(run)
-        self._log_det = logdet.value
+        tau = C.c_double(0.0)
+        N.check(N.lib.gh_inducing_trace_term(self._handle, C.byref(tau)))
+        self.trace_term = tau.value
+        self._log_det = logdet.value + tau.value if self.variational else logdet.value
         self.computed = True
 
     # -- the solver protocol
@@ -194,6 +216,21 @@ class InducingSolver(NativeSolver):
         parameters (masked ones 0), ``alpha = C^-1 r`` and ``diagA_i = alpha_i^2 - (C^-1)_ii``.  With ``u = x`` and no jitter
         these are the dense values."""
         return self._grad("gh_inducing_grad", r, which)
+
+    def grad_inducing(self, r, which=None):
+        """``(kgrad_full | None, alpha, diagA, ugrad)``: :meth:`grad`'s three results (``None`` for the first without ``which``)
+        and the gradient of the objective -- the DTC or FITC log-likelihood, or the bound -- with respect to the inducing
+        inputs, (m, ndim).  The absolute jitter counts as a constant.  One more pass of N m input-gradient evaluations
+        and a second pass of strip GEMMs beside ``grad``'s work; the first three results have ``grad``'s bits."""
+        h = self._need()
+        r = self._in(rhs_vector(r, self._n))
+        g = None
+        if which is not None:
+            which = np.ascontiguousarray(which, dtype=np.uint32)
+            g = np.zeros(max(self._dk.size, 1))
+        alpha, diagA, ugrad = np.empty(self._n), np.empty(self._n), np.empty(self.u.shape)
+        N.check(N.lib.gh_inducing_grad_u(h, self._dk.handle, N.ptr(which), N.ptr(r), N.ptr(g), N.ptr(alpha), N.ptr(diagA), N.ptr(ugrad)))
+        return (None if g is None else g[:self._dk.size]), self._out(alpha), self._out(diagA), ugrad
 
     def predict(self, kernel, r, xs, return_var=False, return_cov=False):
         """The predictive mean and (optionally) variance or covariance at ``xs``, the same for DTC and FITC, in strips of

@@ -537,7 +537,7 @@ int  gh_vecchia_predict_local_search(gh_vecchia* h, gh_kernel* k_data, gh_kernel
                                      double* mu /* M */, double* var /* M or NULL */, int32_t* table_out /* M*mq or NULL */);
 
 /* ------------------------------------------------------------ inducing-point solver
- * The low-rank approximations DTC and FITC through m inducing inputs u, the complement of the Vecchia solver: near-exact for
+ * The low-rank approximations DTC and FITC, and Titsias' variational bound (VFE), through m inducing inputs u, the complement of the Vecchia solver: near-exact for
  * smooth kernels, mediocre for rough ones.  With s_i = yerr_i^2, K_uu the symmetric build over u (the lower index is the first
  * argument) and K_fu = K(x, u) (the data point is the first argument):
  *   K_uu + jitter I = L_u L_u^T,   V = L_u^-1 K_uf (m x n),   q_i = |V[:, i]|^2,
@@ -548,20 +548,27 @@ int  gh_vecchia_predict_local_search(gh_vecchia* h, gh_kernel* k_data, gh_kernel
  * O(n m^2) flops in GEMM shapes; nothing of size n x m is kept: the data points pass in strips, and the handle holds about five
  * m x m matrices (m padded to a multiple of 128; 2.7 GB at the cap m = 8192).  No reference counterpart.  Sums have a fixed
  * order (strips ascending on one stream): two calls give the same bits.  (george_amd/csrc/gh_inducing.hip)
+ * The variational bound (variational = 1; lambda_i = s_i as DTC):
+ *   F = log N(r | 0, C) - 1/2 tau,   tau = sum_i max(k(x_i, x_i) - q_i, 0) / s_i >= 0,
+ * F <= the dense log-likelihood, and F does not decrease when an inducing input is added.  solve, dot_solve and predict are DTC's.
  * x, yerr, u, b, y, r, xs and the array results out, grad, alpha, diagA, mu, var, cov are host or device memory ("Pointer kinds"
- * at the top of this file); *logdet_out, *out of gh_inducing_dot_solve and which are host memory. */
+ * at the top of this file), and so is ugrad; *logdet_out, *out of gh_inducing_dot_solve and of gh_inducing_trace_term and which
+ * are host memory. */
 typedef struct gh_inducing gh_inducing;
 typedef struct gh_inducing_opts {
   int32_t device;
   int32_t method;        /* 0: DTC, 1: FITC */
   int32_t strip_points;  /* data points per strip: 0 = from a byte budget, else rounded up to a multiple of 128 */
-  int32_t reserved;
+  int32_t variational;   /* 0, or 1: the variational bound; with method 0 only */
 } gh_inducing_opts;
-/* GH_ERR_BAD_ARG for a method other than 0 / 1 or a negative strip_points (host check, before any device is touched) */
+/* GH_ERR_BAD_ARG for a method other than 0 / 1, a negative strip_points, a variational other than 0 / 1 or variational = 1 with
+ * method = 1 (host checks, before any device is touched) */
 int  gh_inducing_create(const gh_inducing_opts* opts, gh_inducing** out);
 void gh_inducing_destroy(gh_inducing* h);
 /* After GH_ERR_NOT_PD: +p when pivot p (1-based) of K_uu + jitter I failed, -p when pivot p of A failed; else 0. */
 int64_t gh_inducing_info(const gh_inducing* h);
+/* *out = tau of the last compute(), 0 when the bound is off (*logdet_out of compute() stays log|C| either way) */
+int  gh_inducing_trace_term(const gh_inducing* h, double* out);
 /* u: (m, ndim), 1 <= m <= 8192 (GH_ERR_BAD_ARG otherwise, a host check); jitter >= 0 is absolute.  A pivot of K_uu + jitter I or
  * of A that is not positive: GH_ERR_NOT_PD, gh_inducing_info() says which, and the handle is not computed. */
 int  gh_inducing_compute(gh_inducing* h, gh_kernel* k, const double* x, int64_t n, int32_t ndim, const double* yerr,
@@ -569,12 +576,27 @@ int  gh_inducing_compute(gh_inducing* h, gh_kernel* k, const double* x, int64_t 
 int  gh_inducing_solve(gh_inducing* h, const double* b, int64_t nrhs, double* out);   /* out = C^-1 b; (n, nrhs) row-major */
 int  gh_inducing_dot_solve(gh_inducing* h, const double* y, double* out);             /* y^T C^-1 y */
 /* The likelihood gradient in the layout of gh_chol_grad: alpha = C^-1 r, diagA_i = alpha_i^2 - (C^-1)_ii, and with
- * P = K_uu^-1 K_uf (K_uu with its jitter), T = (P alpha) alpha^T - P C^-1, Z = T - phi P diag(diagA), W = -1/2 Z P^T:
- *   grad[p] = sum_ij Z_ji dk(x_i, u_j)/dtheta_p + sum_jj' W_jj' dk(u_j, u_j')/dtheta_p + 1/2 phi sum_i diagA_i dk(x_i, x_i)/dtheta_p
- * (parameters not selected by `which`: exactly 0; the clamp in lambda counts as inactive).  k: the kernel of compute(). */
+ * P = K_uu^-1 K_uf (K_uu with its jitter), T = (P alpha) alpha^T - P C^-1 and one weight vector omega for the three objectives,
+ * omega_i = 0 (DTC), diagA_i (FITC), -1 / s_i (the bound):  Z = T - P diag(omega), W = -1/2 Z P^T,
+ *   grad[p] = sum_ij Z_ji dk(x_i, u_j)/dtheta_p + sum_jj' W_jj' dk(u_j, u_j')/dtheta_p + 1/2 sum_i omega_i dk(x_i, x_i)/dtheta_p
+ * (parameters not selected by `which`: exactly 0; the clamp counts as inactive).  Under the bound this is the gradient of F, and
+ * diagA_i = alpha_i^2 - (C^-1)_ii + max(k(x_i, x_i) - q_i, 0) / s_i^2, so that 1/2 diagA_i is dF / ds_i.  k: the kernel of compute(). */
 int  gh_inducing_grad(gh_inducing* h, gh_kernel* k, const uint32_t* which, const double* r,
                       double* grad /* size */, double* alpha /* n or NULL */, double* diagA /* n or NULL */);
-/* The same for DTC and FITC: with V* = L_u^-1 K(u, xs), H* = L_A^-1 V*:  mu = H*^T t(r),
+/* The same, and the gradient of the objective with respect to the inducing inputs, for all three objectives (d1: the derivative
+ * in the first argument, d2: in the second; the absolute jitter is a constant, as in grad):
+ *   ugrad[j, :] = sum_i Z_ji d2 k(x_i, u_j) + sum_b (W_jb + W_bj) d1 k(u_j, u_b)          (b = j included)
+ * d2 k(x_i, u_j) is taken as the evaluator's d1 k(u_j, x_i): kernels are symmetric.  which == NULL: no kernel gradient (grad may
+ * then be NULL too).  grad, alpha and diagA have the bits gh_inducing_grad gives.  ugrad takes Z and W from P itself -- a pass
+ * over the strips for H Lambda^-1 P^T and P alpha, then Z_J^T = alpha_J (P alpha)^T - Lambda_J^-1 (P_J^T - H_J^T (H Lambda^-1 P^T))
+ * - diag(omega_J) P_J^T and Z P^T = sum_J Z_J P_J^T -- since grad's own Z, a product with explicit inverse factors, is exact only
+ * in sums over j.  Beside grad's work: one more pass of n m input-gradient evaluations, seven more strip GEMMs and two m x m ones
+ * (counts); two more strips, one m x m matrix, an (m, ndim) buffer and the partial sums of the reduction on the device.  Host checks come before any device call:
+ * GH_ERR_BAD_ARG for a null h, k, r or ugrad, or which without grad; GH_ERR_NOT_COMPUTED; GH_ERR_DIM. */
+int  gh_inducing_grad_u(gh_inducing* h, gh_kernel* k, const uint32_t* which /* or NULL */, const double* r,
+                        double* grad /* size, or NULL */, double* alpha /* n or NULL */, double* diagA /* n or NULL */,
+                        double* ugrad /* m*ndim */);
+/* The same for DTC, FITC and the bound: with V* = L_u^-1 K(u, xs), H* = L_A^-1 V*:  mu = H*^T t(r),
  * var = diag K(xs,xs) - colsumsq(V*) + colsumsq(H*),  cov = K(xs,xs) - V*^T V* + H*^T H*.  O(M m^2) whatever n, in strips of
  * test points; var / cov may be NULL (not both non-NULL); cov keeps its operands whole: GH_ERR_NOMEM over the strip budget.  k
  * may differ from the kernel of compute(). */
