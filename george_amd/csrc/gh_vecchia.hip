@@ -4,6 +4,7 @@
 // is built from the kernel evaluator and factored; with v = L_cc^-1 k_ci:  f_i = k_ii - v^T v (the square of the block factor's last
 // pivot) and b_i = L_cc^-T v.  Q = (I - B)^T F^-1 (I - B).  Local prediction (gh_vecchia_predict_local) puts a test point in the
 // place of point i and its nearest data points in the place of c(i): the same block, mu = v^T L_cc^-1 r_c, var = k** - v^T v.
+// The expected information of the hyper-parameters (gh_vecchia_fisher) is a sum over the same blocks: vecchia_fisher_kernel.
 //
 // Kernels: one point per 64-thread workgroup (one wavefront), lane s owns conditioning point s.  The point's coordinates, the lower
 // triangle of A (packed by rows) and the evaluator's runtime-indexed temporaries sit in LDS: no kernel here uses scratch memory.
@@ -21,6 +22,8 @@
 #define VWS (GH_EVAL_WS + 1)            // the evaluator's work space per lane, an odd pitch in doubles
 #define V_GRAD_WGS 4096                 // workgroups of the gradient kernel (each walks points blockIdx.x, + gridDim.x, ..)
 #define V_GRAD_LDS (96 * 1024)
+#define V_FISHER_PLANES 64              // derivative planes of one call of the information kernel: one lane each
+#define V_FISHER_LDS (128 * 1024)       // the raised limit of its dynamic LDS (119 KB at most)
 #define V_STRIP_COLS 256                // test points per strip of predict (mean / variance) ..
 #define V_STRIP_BYTES (1L << 30)        // .. within this many bytes for K(x, xs_J) and V together
 #define V_COV_BYTES (8L << 30)          // what predict's covariance may keep on the device: K(x, xs), V and the m x m result
@@ -261,6 +264,140 @@ __global__ __launch_bounds__(VM_MAX) void vecchia_grad_kernel(VArgs a, GhFast fa
     }
   }
   if (lane < P) partial[(long)blockIdx.x * P + lane] = which[lane] ? acc : 0.0;
+}
+
+// The expected (Fisher) information of the Vecchia likelihood, block by block (Guinness 2021).  A derivative plane D_a restricted
+// to the block -- diag(s_a) of a diagonal parameter, or dA/dtheta_a of a kernel parameter -- gives, with u = [-b; 1]:
+//   v_a = D_a u,   df_a = u^T v_a,   w_a = L_cc^-1 (v_a)[:c],   F_ab += 1/2 df_a df_b / f^2 + (w_a . w_b) / f.
+// The workgroup's LDS continues behind v_lds_doubles(m, nd, gp) with the plane area V (Q rows of pitch pw, row a = v_a and then
+// w_a), the Q values df_a and the packed pairs a <= b (gh_fisher_pair), which stay there for the whole kernel.
+__host__ __device__ static inline int v_fisher_pitch(int m) { return (m + 1) | 1; }     // odd: lane a walks row a
+__host__ __device__ static inline size_t v_fisher_lds_doubles(int m, int nd, int gp, int Q) {
+  return v_lds_doubles(m, nd, gp) + (size_t)Q * v_fisher_pitch(m) + VM_MAX + (size_t)Q * (Q + 1) / 2;
+}
+// lanes j < c hold t[e]_j for NP planes at once: v_fwd on each, the steps interleaved
+template <int NP>
+__device__ __forceinline__ void v_fwd_n(const double* A, const double* dinv, int c, int lane, double (&t)[NP]) {
+  for (int k = 0; k < c; ++k) {
+    const double dk = dinv[k];
+    const double ajk = (lane > k && lane < c) ? A[v_tri(lane) + k] : 0.0;
+#pragma unroll
+    for (int e = 0; e < NP; ++e) {
+      const double vk = v_bcast(t[e], k) * dk;
+      if (lane == k) t[e] = vk;
+      else if (lane > k && lane < c) t[e] -= ajk * vk;
+    }
+  }
+}
+// One lane, one kernel plane: the nact entries of the packed triangle from (j, k) on, whose gradient rows lie gp apart in g (this
+// lane's parameter first), added into the lane's row of V in their order.  row[j] of the running row j stays in a register.
+__device__ __forceinline__ void v_fisher_sweep(double* __restrict__ row, const double* __restrict__ g, const double* __restrict__ u,
+                                               int gp, int nact, int j, int k) {
+  int q = 0;
+  while (q < nact) {
+    const int run = min(nact - q, j - k + 1), off = min(run, j - k);      // entries left in row j; those below the diagonal
+    const double uj = u[j];
+    double rj = row[j];
+#pragma unroll 4
+    for (int e = 0; e < off; ++e) {
+      const double ge = g[(q + e) * gp];
+      rj += ge * u[k + e];
+      row[k + e] += ge * uj;
+    }
+    if (off < run) rj += g[(q + off) * gp] * uj;                          // (j, j)
+    row[j] = rj;
+    q += run;
+    k += run;
+    if (k > j) { ++j; k = 0; }
+  }
+}
+// Plane a < n_diag is diag(diag_rows[a]) (row a of an (n_diag, n) array), plane a >= n_diag is the kernel parameter
+// kpar[a - n_diag]; Q planes in all, at most 64.  Lane a owns row a of V while the planes are built, lane j owns slot j during
+// the substitution, and lane b owns the pairs (a, b), a <= b, for the whole kernel.  partial[workgroup][pair].
+template <bool FAST>
+__global__ __launch_bounds__(VM_MAX) void vecchia_fisher_kernel(VArgs a, GhFast fast, const GhNode* __restrict__ prog, int P, int gp,
+                                                                int Q, int n_diag, const int* __restrict__ kpar,
+                                                                const double* __restrict__ diag_rows, double* __restrict__ partial) {
+  extern __shared__ __attribute__((aligned(16))) double vsm[];
+  const int lane = threadIdx.x, nd = a.nd, pw = v_fisher_pitch(a.m), npair = Q * (Q + 1) / 2;
+  const VLds l = v_carve(vsm, a.m, nd, gp);
+  double* const g = l.gl + lane * gp;
+  double* const ws = g + P;
+  __builtin_assume(ws != nullptr);
+  double* const V = vsm + v_lds_doubles(a.m, nd, gp);
+  double* const dfv = V + Q * pw;
+  double* const Fp = dfv + VM_MAX;
+  double* const row = V + (lane < Q ? lane : 0) * pw;
+  const int kp = (lane >= n_diag && lane < Q) ? kpar[lane - n_diag] : -1;
+  for (int p = lane; p < npair; p += VM_MAX) Fp[p] = 0.0;
+  __syncthreads();
+  for (long i = blockIdx.x; i < a.n; i += gridDim.x) {
+    int c = 0;
+    double b = 0.0, f = 1.0;
+    if (!v_block<FAST>(a, fast, prog, i, l, ws, lane, c, b, f)) continue;     // (as the gradient: such a point adds nothing)
+    if (lane < c) l.uv[lane] = -b;
+    if (lane == 0) l.uv[c] = 1.0;
+    __syncthreads();
+    if (lane < n_diag)
+      for (int j = 0; j <= c; ++j) row[j] = diag_rows[(long)lane * a.n + l.gi[j]] * l.uv[j];
+    else if (lane < Q)
+      for (int j = 0; j <= c; ++j) row[j] = 0.0;
+    const int T = v_tri(c + 1);
+    for (int t0 = 0; t0 < T && Q > n_diag; t0 += VM_MAX) {
+      const int t = t0 + lane, nact = T - t0 < VM_MAX ? T - t0 : VM_MAX;
+      if (t < T) {
+        int j, k;
+        tri_index(t, j, k);
+        const bool jlow = l.gi[j] <= l.gi[k];
+        gh_eval_grad(prog, a.n_nodes, &l.xs[(jlow ? j : k) * nd], &l.xs[(jlow ? k : j) * nd], g, ws);
+      }
+      __syncthreads();
+      if (kp >= 0) {
+        int j0, k0;
+        tri_index(t0, j0, k0);
+        v_fisher_sweep(row, l.gl + kp, l.uv, gp, nact, j0, k0);
+      }
+      __syncthreads();
+    }
+    __syncthreads();
+    // df_a and w_a, four planes at a time: lane j has slot j
+    for (int a0 = 0; a0 < Q; a0 += 4) {
+      double t[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        t[e] = (a0 + e < Q && lane < c) ? V[(a0 + e) * pw + lane] : 0.0;
+        const double s = wave_sum(lane < c ? -b * t[e] : 0.0);
+        if (lane == 0 && a0 + e < Q) dfv[a0 + e] = s + V[(a0 + e) * pw + c];
+      }
+      v_fwd_n<4>(l.A, l.dinv, c, lane, t);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (a0 + e < Q && lane < c) V[(a0 + e) * pw + lane] = t[e];
+    }
+    __syncthreads();
+    if (lane < Q) {
+      const double h2 = 0.5 / (f * f), h1 = 1.0 / f, dfb = dfv[lane];
+      for (int pa = 0; pa <= lane; ++pa) {
+        const double* ra = V + pa * pw;
+        double s = 0.0;
+        for (int j = 0; j < c; ++j) s += ra[j] * row[j];
+        Fp[gh_fisher_pair(pa, lane, Q)] += h2 * dfv[pa] * dfb + h1 * s;
+      }
+    }
+  }
+  __syncthreads();
+  for (int p = lane; p < npair; p += VM_MAX) partial[(long)blockIdx.x * npair + p] = Fp[p];
+}
+// out (ptot x ptot, zeroed by the caller): the pair (a, b) of the packed sums F to the rows / columns opos[a], opos[b] and mirrored
+__global__ __launch_bounds__(256) void vecchia_fisher_scatter_kernel(const double* __restrict__ F, int Q, const int* __restrict__ opos,
+                                                                     int ptot, double* __restrict__ out) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= Q * Q) return;
+  const int pa = idx / Q, pb = idx - pa * Q;
+  if (pb < pa) return;
+  const double v = F[gh_fisher_pair(pa, pb, Q)];
+  out[(long)opos[pa] * ptot + opos[pb]] = v;
+  out[(long)opos[pb] * ptot + opos[pa]] = v;
 }
 
 // The forward operator as a row gather over the nrhs columns of r (row pitch ldr): with e = r_i - sum_s b_is r_c(i,s)
@@ -540,6 +677,63 @@ extern "C" int gh_vecchia_grad(gh_vecchia* h, gh_kernel* k, const uint32_t* whic
     GH_CHECK(gh_from_device(diagA, dg.d(), (size_t)n, st));
   }
   GH_HIP(hipStreamSynchronize(st));
+  return GH_OK;
+}
+
+extern "C" int gh_vecchia_fisher(gh_vecchia* h, gh_kernel* k, const uint32_t* which, const double* diag_rows, int32_t n_diag,
+                                 double* out) {
+  GH_CHECK(v_need(h));
+  if (!k || !which || !out || n_diag < 0 || (n_diag > 0 && !diag_rows)) { gh_set_error("bad argument to fisher"); return GH_ERR_BAD_ARG; }
+  if (k->ndim != h->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
+  if (k->size > GH_MAX_GRAD) { gh_set_error("fisher: %d kernel parameters, at most %d", k->size, GH_MAX_GRAD); return GH_ERR_BAD_ARG; }
+  const long n = (long)h->n;
+  const int m = h->opts.m, P = k->size, ptot = n_diag + P;
+  // the planes: the diagonal ones, then the kernel parameters `which` selects; kp_op = kpar (Q - n_diag) and opos (Q) behind it
+  std::vector<int> kp_op;
+  for (int p = 0; p < P; ++p)
+    if (which[p]) kp_op.push_back(p);
+  const int nk = (int)kp_op.size(), Q = n_diag + nk;
+  if (Q > V_FISHER_PLANES) {
+    gh_set_error("fisher: %d diagonal and %d selected kernel parameters, at most %d planes in one call", (int)n_diag, nk, V_FISHER_PLANES);
+    return GH_ERR_BAD_ARG;
+  }
+  if (ptot == 0) return GH_OK;
+  for (int a = 0; a < Q; ++a) kp_op.push_back(a < n_diag ? a : n_diag + kp_op[a - n_diag]);
+  GH_CHECK(k->upload());
+  hipStream_t st = h->st;
+  GhPooledBuf od, rows, part;
+  GH_CHECK(od.ensure((size_t)ptot * ptot * sizeof(double)));
+  GH_HIP(hipMemsetAsync(od.p, 0, (size_t)ptot * ptot * sizeof(double), st));
+  if (Q > 0) {
+    const int gp = (P + GH_EVAL_WS) | 1, npair = Q * (Q + 1) / 2;               // (gp: as gh_vecchia_grad)
+    const size_t lds = v_fisher_lds_doubles(m, h->ndim, gp, Q) * sizeof(double);
+    if (lds > V_FISHER_LDS) { gh_set_error("fisher: %zu bytes of LDS, at most %d", lds, V_FISHER_LDS); return GH_ERR_BAD_ARG; }
+    const unsigned nwg = (unsigned)std::min<long>(n, V_GRAD_WGS);
+    const size_t map_bytes = ((sizeof(int) * kp_op.size() + 15) / 16) * 16;
+    GH_CHECK(rows.ensure(std::max<size_t>((size_t)n_diag * n, 1) * sizeof(double)));
+    GH_CHECK(part.ensure(map_bytes + ((size_t)nwg + 1) * npair * sizeof(double)));
+    if (n_diag > 0) GH_CHECK(gh_to_device(rows.d(), diag_rows, (size_t)n_diag * n, st));
+    int* d_kpar = (int*)part.p;
+    double* partial = (double*)((char*)part.p + map_bytes);
+    double* dF = partial + (size_t)nwg * npair;
+    GH_HIP(hipMemcpyAsync(d_kpar, kp_op.data(), sizeof(int) * kp_op.size(), hipMemcpyHostToDevice, st));
+    const VArgs a = v_args(h, k);
+    if (lds > 64 * 1024) {                                  // (m = 64 in 16 dimensions with 64 planes: 119 KB)
+      GH_HIP(hipFuncSetAttribute((const void*)vecchia_fisher_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, V_FISHER_LDS));
+      GH_HIP(hipFuncSetAttribute((const void*)vecchia_fisher_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, V_FISHER_LDS));
+    }
+    if (k->fast.ok) hipLaunchKernelGGL(vecchia_fisher_kernel<true>, dim3(nwg), dim3(VM_MAX), lds, st, a, k->fast, (const GhNode*)k->d_nodes, P, gp,
+                                       Q, (int)n_diag, (const int*)d_kpar, (const double*)rows.d(), partial);
+    else hipLaunchKernelGGL(vecchia_fisher_kernel<false>, dim3(nwg), dim3(VM_MAX), lds, st, a, k->fast, (const GhNode*)k->d_nodes, P, gp,
+                            Q, (int)n_diag, (const int*)d_kpar, (const double*)rows.d(), partial);
+    GH_HIP(hipGetLastError());
+    GH_CHECK(gh_launch_kgrad_final(partial, nwg, npair, dF, st));                // per-workgroup partials, fixed order
+    hipLaunchKernelGGL(vecchia_fisher_scatter_kernel, dim3(v_blocks((size_t)Q * Q)), dim3(256), 0, st, (const double*)dF, Q,
+                       (const int*)(d_kpar + nk), ptot, od.d());
+    GH_HIP(hipGetLastError());
+  }
+  GH_CHECK(gh_from_device(out, od.d(), (size_t)ptot * ptot, st));
+  GH_HIP(hipStreamSynchronize(st));                         // (kp_op ends with this call)
   return GH_OK;
 }
 

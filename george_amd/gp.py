@@ -779,13 +779,16 @@ class GP(ModelSet):
     # (no reference counterpart.)  For the Gaussian likelihood the expected (Fisher) information is
     #   F_ab = 1/2 tr(K^-1 dK/dtheta_a K^-1 dK/dtheta_b)      white-noise and kernel parameters
     #   F_mn = (d mean / d m)^T K^-1 (d mean / d n)           mean parameters; their cross block with the others is exactly 0
-    # It needs no y and is positive semidefinite by construction.  A solver that offers ``fisher`` (the HIP BasicSolver)
-    # keeps the derivative matrices and every N^3 product on the device; any other one with ``get_inverse`` takes the NumPy
-    # branch, formula for formula.
+    # It needs no y and is positive semidefinite by construction.  A solver that offers ``fisher`` (the HIP BasicSolver) computes the
+    # white-noise and kernel block on the device, keeping the derivative matrices and every N^3 product there; one that offers
+    # ``fisher_blocks`` instead (VecchiaSolver) sums one closed form per block -- the information of ITS likelihood, with Q in
+    # the place of K^-1 in the mean block, and no N x N array anywhere.  Any other solver with ``get_inverse`` takes the NumPy branch, formula for formula.
     def fisher_information(self):
         """The expected (Fisher) information of the unfrozen parameters at their current values, ``(len(gp), len(gp))``,
         ordered mean | white_noise | kernel like :meth:`grad_log_likelihood`.  It does not depend on ``y``.  Its inverse is
-        :meth:`parameter_covariance`; small eigenvalues are directions the data cannot separate.  For a kernel with a general
+        :meth:`parameter_covariance`; small eigenvalues are directions the data cannot separate.  With ``VecchiaSolver`` it is
+        the information of the Vecchia likelihood (the dense one when every predecessor is a neighbour), at about the cost of one
+        ``nll_and_grad`` for any N.  For a kernel with a general
         (full-matrix) metric the parameter derivatives are the reference's, not the derivatives of the value (DESIGN.md
         section 9, "Known discrepancy"), and the information inherits that; isotropic and axis-aligned metrics are right."""
         self.recompute()
@@ -802,9 +805,10 @@ class GP(ModelSet):
             wn = self._call_white_noise(self._x)
             wng = np.atleast_2d(self._call_white_noise_gradient(self._x))
             rows = np.ascontiguousarray(np.exp(wn)[None, :] * wng, dtype=np.float64)
-        if self._offers("fisher"):
+        device = next((name for name in ("fisher", "fisher_blocks") if self._offers(name)), None)
+        if device is not None:
             mask = self.kernel.unfrozen_mask
-            full = self.solver.fisher(mask.astype(np.uint32), rows)
+            full = getattr(self.solver, device)(mask.astype(np.uint32), rows)
             keep = np.concatenate([np.arange(n_wn), n_wn + np.flatnonzero(mask)]).astype(int)
             F[n_m:, n_m:] = full[np.ix_(keep, keep)]
             return F

@@ -472,7 +472,7 @@ int  gh_hodlr_grad(gh_hodlr* h, gh_kernel* k, const uint32_t* which, const doubl
  * Q = (I - B)^T F^-1 (I - B), B strictly lower triangular with the b_i as rows, F = diag(f).  Every predecessor in c(i)
  * (m >= n - 1) gives the dense answers up to rounding.  O(n m^3) flops, O(n m) memory; no reference counterpart.  Fixed-order
  * sums throughout: two calls give the same bits.  (george_amd/csrc/gh_vecchia.hip)
- * x, yerr, b, y, r, xs and the array results mu, var, cov, out, grad, alpha, diagA are host or device memory ("Pointer kinds" at
+ * x, yerr, b, y, r, xs, diag_rows and the array results mu, var, cov, out, grad, alpha, diagA are host or device memory ("Pointer kinds" at
  * the top of this file); *logdet_out, *out of gh_vecchia_dot_solve, which, nbr, qnbr and table_out are host memory.  A compute()
  * on device x always drops a kept search grid (the points cannot be compared on the host). */
 typedef struct gh_vecchia gh_vecchia;
@@ -498,6 +498,20 @@ int  gh_vecchia_dot_solve(gh_vecchia* h, const double* y, double* out);         
  * diagA_j = 2 sum over the blocks that hold j of W_jj.  The layout of gh_chol_grad, and its values when m >= n - 1. */
 int  gh_vecchia_grad(gh_vecchia* h, gh_kernel* k, const uint32_t* which, const double* r,
                      double* grad /* size */, double* alpha /* n or NULL */, double* diagA /* n or NULL */);
+/* The expected (Fisher) information of the Vecchia likelihood (Guinness 2021), a sum of one closed form per block: with
+ * u = [-b_i; 1], L the factor of K_cc and D_a a derivative matrix restricted to the block c(i) + {i},
+ *   v_a = D_a u,  df_a = u^T v_a,  w_a = L^-1 (v_a)[:c],   F_ab = sum_i 1/2 df_a df_b / f_i^2 + (w_a . w_b) / f_i.
+ * D_a: first the n_diag diagonal matrices diag(diag_rows[a]) (how a white-noise model enters; (n_diag, n) row-major in the order
+ * of compute()'s points, host or device memory, NULL with n_diag == 0), then dK/dtheta of every kernel parameter (the lower index
+ * is the first argument).  out: (n_diag + size)^2 row-major, host or device memory, exactly symmetric; a kernel parameter not
+ * selected by `which` (host, size entries) has a row and a column of exactly 0.  At m >= n - 1 this is the dense
+ * 1/2 tr(K^-1 D_a K^-1 D_b) of gh_chol_fisher up to rounding; for smaller m it is the information of the approximate likelihood
+ * with each conditioning set's covariance taken as K_cc, a different quantity.  One pass over the blocks, about the cost of
+ * gh_vecchia_grad; nothing of size n x n.  At most 64 planes in one call -- n_diag plus the selected kernel parameters -- else
+ * GH_ERR_BAD_ARG.  A block that is not positive definite (only with another kernel than compute()'s) adds nothing.  Two calls
+ * give the same bits. */
+int  gh_vecchia_fisher(gh_vecchia* h, gh_kernel* k, const uint32_t* which, const double* diag_rows /* n_diag*n or NULL */,
+                       int32_t n_diag, double* out /* (n_diag + size)^2 */);
 /* mu = K(xs,x) Q r; var = diag K(xs,xs) - colsumsq(V), cov = K(xs,xs) - V^T V with V = F^-1/2 (I - B) K(x,xs).  var / cov may be
  * NULL (not both non-NULL); k may differ from the kernel of compute().  Strips of test points sized to a byte budget; cov keeps
  * K(x,xs), V and the m x m result on the device: GH_ERR_NOMEM when the budget does not hold them. */
