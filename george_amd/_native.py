@@ -206,6 +206,7 @@ SIGNATURES = {
     "gh_vecchia_solve": (C.c_int, [_vp, _dp, _i64, _dp]),
     "gh_vecchia_dot_solve": (C.c_int, [_vp, _dp, C.POINTER(C.c_double)]),
     "gh_vecchia_grad": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _dp, _dp]),
+    "gh_vecchia_loo": (C.c_int, [_vp, _vp, _dp, _dp, C.POINTER(C.c_double), _dp, _dp, _dp, _dp, _dp, _dp]),
     "gh_vecchia_fisher": (C.c_int, [_vp, _vp, _dp, _dp, _i32, _dp]),
     "gh_vecchia_predict": (C.c_int, [_vp, _vp, _dp, _dp, _i64, _dp, _dp, _dp]),
     "gh_vecchia_predict_local": (C.c_int, [_vp, _vp, _vp, _dp, _dp, _i64, _dp, _i32, _dp, _dp]),

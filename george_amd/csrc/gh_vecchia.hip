@@ -5,6 +5,7 @@
 // pivot) and b_i = L_cc^-T v.  Q = (I - B)^T F^-1 (I - B).  Local prediction (gh_vecchia_predict_local) puts a test point in the
 // place of point i and its nearest data points in the place of c(i): the same block, mu = v^T L_cc^-1 r_c, var = k** - v^T v.
 // The expected information of the hyper-parameters (gh_vecchia_fisher) is a sum over the same blocks: vecchia_fisher_kernel.
+// So is the gradient of the leave-one-out score of this density (gh_vecchia_loo: c = diag Q, alpha = Q r): vecchia_loo_grad_kernel.
 //
 // Kernels: one point per 64-thread workgroup (one wavefront), lane s owns conditioning point s.  The point's coordinates, the lower
 // triangle of A (packed by rows) and the evaluator's runtime-indexed temporaries sit in LDS: no kernel here uses scratch memory.
@@ -212,11 +213,36 @@ __global__ __launch_bounds__(VM_MAX) void vecchia_local_kernel(VArgs a, GhFast f
   }
 }
 
+// The weighted triangle walk both gradient kernels end a block with:  acc_p += sum_jk W_jk dA_jk/dtheta_p  for the block that
+// v_block left in LDS and  W = ca u u^T + cb (z u^T + u z^T),  u and z in l.uv and l.zv (c + 1 entries each, written before
+// the barrier that precedes the call).  The lower triangle of the block goes through the evaluator 64 entries at a time (lane
+// t: gradient row into its LDS area g, weight into wl); then lane p adds the 64 rows' entry p in order: the sum of a parameter
+// lives in ONE lane, in one register.
+__device__ __forceinline__ double v_walk(const VArgs& a, const GhNode* __restrict__ prog, const VLds& l, int P, int gp, int c, double ca,
+                                         double cb, double* g, double* ws, int lane, double acc) {
+  const int nd = a.nd, T = v_tri(c + 1);
+  for (int t0 = 0; t0 < T && P > 0; t0 += VM_MAX) {
+    const int t = t0 + lane, nact = T - t0 < VM_MAX ? T - t0 : VM_MAX;
+    if (t < T) {
+      int j, k;
+      tri_index(t, j, k);
+      const double uj = l.uv[j], uk = l.uv[k];
+      const double w = ca * uj * uk + cb * (l.zv[j] * uk + uj * l.zv[k]);
+      const bool jlow = l.gi[j] <= l.gi[k];
+      gh_eval_grad(prog, a.n_nodes, &l.xs[(jlow ? j : k) * nd], &l.xs[(jlow ? k : j) * nd], g, ws);
+      l.wl[lane] = j == k ? w : 2.0 * w;
+    }
+    __syncthreads();
+    if (lane < P)
+      for (int q = 0; q < nact; ++q) acc += l.wl[q] * l.gl[q * gp + lane];
+    __syncthreads();
+  }
+  return acc;
+}
+
 // The likelihood gradient, block by block.  With e = r_i - b^T r_c, z = K_cc^-1 r_c, u = [-b; 1], ze = [z; 0]:
-//   W = 1/2 (e^2/f^2 - 1/f) u u^T + 1/2 (e/f) (ze u^T + u ze^T),    d log p(y_i | y_c) / dtheta = sum_jk W_jk dA_jk/dtheta.
-// The lower triangle of the block goes through the evaluator 64 entries at a time (lane t: gradient row into its LDS area,
-// weight into wl); then lane p adds the 64 rows' entry p in order: the sum of a parameter lives in ONE lane, in one register.
-// partial[workgroup][p]; wd[i][s] = 2 W_ss for slot s (slot m: the point itself).
+//   W = 1/2 (e^2/f^2 - 1/f) u u^T + 1/2 (e/f) (ze u^T + u ze^T),    d log p(y_i | y_c) / dtheta = sum_jk W_jk dA_jk/dtheta
+// (v_walk).  partial[workgroup][p]; wd[i][s] = 2 W_ss for slot s (slot m: the point itself).
 template <bool FAST>
 __global__ __launch_bounds__(VM_MAX) void vecchia_grad_kernel(VArgs a, GhFast fast, const GhNode* __restrict__ prog, int P, int gp,
                                                               const uint32_t* __restrict__ which, const double* __restrict__ r,
@@ -245,23 +271,54 @@ __global__ __launch_bounds__(VM_MAX) void vecchia_grad_kernel(VArgs a, GhFast fa
     if (lane < a.m) wd[i * (a.m + 1) + lane] = lane < c ? 2.0 * (ca * b * b - 2.0 * cb * z * b) : 0.0;
     if (lane == 0) wd[i * (a.m + 1) + a.m] = 2.0 * ca;
     __syncthreads();
-    const int T = v_tri(c + 1);
-    for (int t0 = 0; t0 < T && P > 0; t0 += VM_MAX) {
-      const int t = t0 + lane, nact = T - t0 < VM_MAX ? T - t0 : VM_MAX;
-      if (t < T) {
-        int j, k;
-        tri_index(t, j, k);
-        const double uj = l.uv[j], uk = l.uv[k];
-        const double w = ca * uj * uk + cb * (l.zv[j] * uk + uj * l.zv[k]);
-        const bool jlow = l.gi[j] <= l.gi[k];
-        gh_eval_grad(prog, a.n_nodes, &l.xs[(jlow ? j : k) * nd], &l.xs[(jlow ? k : j) * nd], g, ws);
-        l.wl[lane] = j == k ? w : 2.0 * w;
-      }
-      __syncthreads();
-      if (lane < P)
-        for (int q = 0; q < nact; ++q) acc += l.wl[q] * l.gl[q * gp + lane];
-      __syncthreads();
+    acc = v_walk(a, prog, l, P, gp, c, ca, cb, g, ws, lane, acc);
+  }
+  if (lane < P) partial[(long)blockIdx.x * P + lane] = which[lane] ? acc : 0.0;
+}
+
+// The gradient of the leave-one-out score L = sum_j lpd_j of the Vecchia density, block by block.  With Q = sum_i u u^T / f,
+// c = diag Q, alpha = Q r, wv = 1/2 (1 + alpha^2 / c) / c and av = alpha / c:  dL = sum_i d[u^T M u / f] with
+// M = diag(wv) - 1/2 (av r^T + r av^T) restricted to the block.  g = M u takes this lane's wv, av, r, u and the two wave sums
+// u.r and u.av; h = A^-1 g by the partitioned inverse (h_last = u.g / f, h_c = K_cc^-1 g_c - b h_last: only the factor of K_cc
+// that v_block leaves), and
+//   W = (u.g / f^2) u u^T - (1/f) (h u^T + u h^T),    dL/dtheta = sum_i sum_jk W_jk dA_jk/dtheta    (v_walk; z = h, z[c] = h_last).
+// partial[workgroup][p]; wd[i][s] = W_ss for slot s (slot m: the point itself).
+template <bool FAST>
+__global__ __launch_bounds__(VM_MAX) void vecchia_loo_grad_kernel(VArgs a, GhFast fast, const GhNode* __restrict__ prog, int P, int gp,
+                                                                  const uint32_t* __restrict__ which, const double* __restrict__ r,
+                                                                  const double* __restrict__ wv, const double* __restrict__ av,
+                                                                  double* __restrict__ partial, double* __restrict__ wd) {
+  extern __shared__ __attribute__((aligned(16))) double vsm[];
+  const int lane = threadIdx.x;
+  const VLds l = v_carve(vsm, a.m, a.nd, gp);
+  double* const g = l.gl + lane * gp;
+  double* const ws = g + P;
+  __builtin_assume(ws != nullptr);
+  double acc = 0.0;
+  for (long i = blockIdx.x; i < a.n; i += gridDim.x) {
+    int c = 0;
+    double b = 0.0, f = 1.0;
+    const bool ok = v_block<FAST>(a, fast, prog, i, l, ws, lane, c, b, f);
+    if (!ok) {                                              // (as the likelihood gradient: only with another kernel)
+      for (int s = lane; s <= a.m; s += VM_MAX) wd[i * (a.m + 1) + s] = 0.0;
+      continue;
     }
+    const long gj = lane < c ? (long)l.gi[lane] : i;        // (lanes >= c read the point itself and use none of it)
+    const double rj = r[gj], aj = av[gj], wj = wv[gj];
+    const double ri = r[i], ai = av[i];
+    const double ur = ri - v_bcast(wave_sum(lane < c ? b * rj : 0.0), 0);
+    const double ua = ai - v_bcast(wave_sum(lane < c ? b * aj : 0.0), 0);
+    const double gc = lane < c ? -wj * b - 0.5 * (aj * ur + rj * ua) : 0.0;
+    const double ug = (wv[i] - 0.5 * (ai * ur + ri * ua)) - v_bcast(wave_sum(lane < c ? b * gc : 0.0), 0);
+    const double hl = ug / f;
+    const double h = v_bwd(l.A, l.dinv, c, lane, v_fwd(l.A, l.dinv, c, lane, gc)) - b * hl;
+    const double ca = hl / f, cb = -1.0 / f;
+    if (lane < c) { l.uv[lane] = -b; l.zv[lane] = h; }
+    if (lane == 0) { l.uv[c] = 1.0; l.zv[c] = hl; }
+    if (lane < a.m) wd[i * (a.m + 1) + lane] = lane < c ? ca * b * b - 2.0 * cb * h * b : 0.0;
+    if (lane == 0) wd[i * (a.m + 1) + a.m] = ca + 2.0 * cb * hl;
+    __syncthreads();
+    acc = v_walk(a, prog, l, P, gp, c, ca, cb, g, ws, lane, acc);
   }
   if (lane < P) partial[(long)blockIdx.x * P + lane] = which[lane] ? acc : 0.0;
 }
@@ -436,6 +493,40 @@ __global__ __launch_bounds__(256) void vecchia_diag_kernel(const double* __restr
   double s = wd[j * (m + 1) + m];
   for (long long q = tptr[j]; q < tptr[j + 1]; ++q) s += wd[(long)trow[q] * (m + 1) + tslot[q]];
   diagA[j] = s;
+}
+// c_j = Q_jj = 1 / f_j + sum over the entries (row, slot) of column j of B[row, slot]^2 / f_row, rows ascending
+__global__ __launch_bounds__(256) void vecchia_qdiag_kernel(const double* __restrict__ B, const double* __restrict__ f,
+                                                            const long long* __restrict__ tptr, const int* __restrict__ trow,
+                                                            const int* __restrict__ tslot, long n, int m, double* __restrict__ cq) {
+  const long j = (long)blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  double s = 1.0 / f[j];
+  for (long long q = tptr[j]; q < tptr[j + 1]; ++q) {
+    const double bq = B[(long)trow[q] * m + tslot[q]];
+    s += bq * bq / f[trow[q]];
+  }
+  cq[j] = s;
+}
+// The leave-one-out values of point j from c = Q_jj and alpha = (Q r)_j: resid = alpha / c, var = 1 / c,
+// lpd = 1/2 log c - 1/2 alpha^2 / c - 1/2 log 2 pi, and for the gradient wv = 1/2 (1 + alpha^2 / c) / c and av = alpha / c
+// (= resid).  part[workgroup] = the sum of its 256 lpd in a fixed order.
+__global__ __launch_bounds__(256) void vecchia_loo_point_kernel(const double* __restrict__ cq, const double* __restrict__ alpha, long n,
+                                                                double* __restrict__ resid, double* __restrict__ var,
+                                                                double* __restrict__ lpd, double* __restrict__ wv,
+                                                                double* __restrict__ part) {
+  __shared__ double sh[4];
+  const long j = (long)blockIdx.x * 256 + threadIdx.x;
+  double lp = 0.0;
+  if (j < n) {
+    const double c = cq[j], al = alpha[j], u = al / c;
+    lp = 0.5 * log(c) - 0.5 * al * u - 0.9189385332046727418;
+    resid[j] = u;
+    var[j] = 1.0 / c;
+    lpd[j] = lp;
+    wv[j] = 0.5 * (1.0 + al * u) / c;
+  }
+  lp = block_sum_256(lp, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = lp;
 }
 
 // ================================================================================ host side
@@ -626,6 +717,16 @@ extern "C" int gh_vecchia_dot_solve(gh_vecchia* h, const double* y, double* out)
   return GH_OK;
 }
 
+// The dynamic LDS of a gradient kernel (vecchia_grad_kernel, vecchia_loo_grad_kernel: v_lds_doubles at gp) above 64 KB -- m = 64
+// with eight or more input dimensions and ~60 parameters, 70 KB at most: the limit of both instantiations is raised first.
+static int v_grad_lds_limit(const void* k_fast, const void* k_interp, size_t lds) {
+  if (lds > 64 * 1024) {
+    GH_HIP(hipFuncSetAttribute(k_fast, hipFuncAttributeMaxDynamicSharedMemorySize, V_GRAD_LDS));
+    GH_HIP(hipFuncSetAttribute(k_interp, hipFuncAttributeMaxDynamicSharedMemorySize, V_GRAD_LDS));
+  }
+  return GH_OK;
+}
+
 extern "C" int gh_vecchia_grad(gh_vecchia* h, gh_kernel* k, const uint32_t* which, const double* r, double* grad, double* alpha,
                                double* diagA) {
   GH_CHECK(v_need(h));
@@ -657,10 +758,7 @@ extern "C" int gh_vecchia_grad(gh_vecchia* h, gh_kernel* k, const uint32_t* whic
   const VArgs a = v_args(h, k);
   const int gp = (P + GH_EVAL_WS) | 1;                      // doubles per lane: the gradient row, the evaluator's work space; odd
   const size_t lds = v_lds_doubles(m, h->ndim, gp) * sizeof(double);
-  if (lds > 64 * 1024) {                                    // (m = 64 with eight or more input dimensions and ~60 parameters: 70 KB at most)
-    GH_HIP(hipFuncSetAttribute((const void*)vecchia_grad_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, V_GRAD_LDS));
-    GH_HIP(hipFuncSetAttribute((const void*)vecchia_grad_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, V_GRAD_LDS));
-  }
+  GH_CHECK(v_grad_lds_limit((const void*)vecchia_grad_kernel<true>, (const void*)vecchia_grad_kernel<false>, lds));
   if (k->fast.ok) hipLaunchKernelGGL(vecchia_grad_kernel<true>, dim3(nwg), dim3(VM_MAX), lds, st, a, k->fast, (const GhNode*)k->d_nodes, P, gp,
                                      (const uint32_t*)d_which, (const double*)rd.d(), partial, wd.d());
   else hipLaunchKernelGGL(vecchia_grad_kernel<false>, dim3(nwg), dim3(VM_MAX), lds, st, a, k->fast, (const GhNode*)k->d_nodes, P, gp,
@@ -675,6 +773,78 @@ extern "C" int gh_vecchia_grad(gh_vecchia* h, gh_kernel* k, const uint32_t* whic
                        (const int*)h->trow.p, (const int*)h->tslot.p, n, m, dg.d());
     GH_HIP(hipGetLastError());
     GH_CHECK(gh_from_device(diagA, dg.d(), (size_t)n, st));
+  }
+  GH_HIP(hipStreamSynchronize(st));
+  return GH_OK;
+}
+
+extern "C" int gh_vecchia_loo(gh_vecchia* h, gh_kernel* k, const uint32_t* which, const double* r, double* lpd_sum, double* resid,
+                              double* var, double* lpd, double* grad, double* v, double* diagB) {
+  GH_CHECK(v_need(h));
+  if (!k || !r || !lpd_sum || !resid || !var || (which ? !grad : (grad || v || diagB))) { gh_set_error("bad argument to loo"); return GH_ERR_BAD_ARG; }
+  if (k->ndim != h->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
+  if (k->size > GH_MAX_GRAD) { gh_set_error("loo: %d kernel parameters, at most %d", k->size, GH_MAX_GRAD); return GH_ERR_BAD_ARG; }
+  const long n = (long)h->n;
+  const int m = h->opts.m, P = k->size, Pw = P > 0 ? P : 1;
+  hipStream_t st = h->st;
+  // vals: r, alpha, c, resid (= av), var, lpd, wv, one apply's work space -- n doubles each -- and the partial sums of lpd
+  const unsigned nblk = v_blocks((size_t)n);
+  GhPooledBuf vals, part, wd;
+  GH_CHECK(vals.ensure(((size_t)8 * n + nblk + 1) * sizeof(double)));
+  double* const rd = vals.d();
+  double* const al = rd + n;
+  double* const cq = al + n;
+  double* const rs = cq + n;
+  double* const vr = rs + n;
+  double* const lp = vr + n;
+  double* const wv = lp + n;
+  double* const tmp = wv + n;
+  double* const lpart = tmp + n;
+  GH_CHECK(gh_to_device(rd, r, (size_t)n, st));
+  hipLaunchKernelGGL(vecchia_qdiag_kernel, dim3(nblk), dim3(256), 0, st, (const double*)h->B.d(), (const double*)h->f.d(),
+                     (const long long*)h->tptr.p, (const int*)h->trow.p, (const int*)h->tslot.p, n, m, cq);
+  GH_HIP(hipGetLastError());
+  GH_CHECK(v_apply_q(h, rd, 1L, tmp, al));
+  hipLaunchKernelGGL(vecchia_loo_point_kernel, dim3(nblk), dim3(256), 0, st, (const double*)cq, (const double*)al, n, rs, vr, lp, wv, lpart);
+  GH_HIP(hipGetLastError());
+  GH_CHECK(gh_launch_kgrad_final(lpart, nblk, 1, lpart + nblk, st));           // per-workgroup partials, fixed order
+  GH_HIP(hipMemcpyAsync(lpd_sum, lpart + nblk, sizeof(double), hipMemcpyDeviceToHost, st));
+  GH_CHECK(gh_from_device(resid, rs, (size_t)n, st));
+  GH_CHECK(gh_from_device(var, vr, (size_t)n, st));
+  if (lpd) GH_CHECK(gh_from_device(lpd, lp, (size_t)n, st));
+  if (which) {
+    GH_CHECK(k->upload());
+    const unsigned nwg = (unsigned)std::min<long>(n, V_GRAD_WGS);
+    const size_t which_bytes = ((sizeof(uint32_t) * Pw + 15) / 16) * 16;
+    GH_CHECK(part.ensure(which_bytes + ((size_t)nwg + 1) * Pw * sizeof(double)));
+    GH_CHECK(wd.ensure((size_t)n * (m + 1) * sizeof(double)));
+    uint32_t* d_which = (uint32_t*)part.p;
+    double* partial = (double*)((char*)part.p + which_bytes);
+    double* dgrad = partial + (size_t)nwg * Pw;
+    if (P > 0) GH_HIP(hipMemcpyAsync(d_which, which, sizeof(uint32_t) * P, hipMemcpyHostToDevice, st));
+    const VArgs a = v_args(h, k);
+    const int gp = (P + GH_EVAL_WS) | 1;                    // (as gh_vecchia_grad, and its LDS)
+    const size_t lds = v_lds_doubles(m, h->ndim, gp) * sizeof(double);
+    GH_CHECK(v_grad_lds_limit((const void*)vecchia_loo_grad_kernel<true>, (const void*)vecchia_loo_grad_kernel<false>, lds));
+    if (k->fast.ok) hipLaunchKernelGGL(vecchia_loo_grad_kernel<true>, dim3(nwg), dim3(VM_MAX), lds, st, a, k->fast, (const GhNode*)k->d_nodes, P, gp,
+                                       (const uint32_t*)d_which, (const double*)rd, (const double*)wv, (const double*)rs, partial, wd.d());
+    else hipLaunchKernelGGL(vecchia_loo_grad_kernel<false>, dim3(nwg), dim3(VM_MAX), lds, st, a, k->fast, (const GhNode*)k->d_nodes, P, gp,
+                            (const uint32_t*)d_which, (const double*)rd, (const double*)wv, (const double*)rs, partial, wd.d());
+    GH_HIP(hipGetLastError());
+    if (P > 0) {
+      GH_CHECK(gh_launch_kgrad_final(partial, nwg, P, dgrad, st));
+      GH_CHECK(gh_from_device(grad, dgrad, (size_t)P, st));
+    }
+    if (v) {                                                // Q av; al and cq are free by now
+      GH_CHECK(v_apply_q(h, rs, 1L, tmp, al));
+      GH_CHECK(gh_from_device(v, al, (size_t)n, st));
+    }
+    if (diagB) {
+      hipLaunchKernelGGL(vecchia_diag_kernel, dim3(v_blocks((size_t)n)), dim3(256), 0, st, (const double*)wd.d(), (const long long*)h->tptr.p,
+                         (const int*)h->trow.p, (const int*)h->tslot.p, n, m, cq);
+      GH_HIP(hipGetLastError());
+      GH_CHECK(gh_from_device(diagB, cq, (size_t)n, st));
+    }
   }
   GH_HIP(hipStreamSynchronize(st));
   return GH_OK;

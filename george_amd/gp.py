@@ -548,15 +548,17 @@ class GP(ModelSet):
     # variance 1 / c_i, and L = sum_i log p(y_i | y_-i) = sum_i 1/2 log c_i - 1/2 alpha_i^2 / c_i - 1/2 log 2 pi.  Its gradient
     # is sum_ij B_ij dK_ij/dtheta with B = 1/2 (v alpha^T + alpha v^T) - K^-1 diag(w) K^-1, u = alpha / c, v = K^-1 u,
     # w = 1/2 (1 + alpha^2 / c) / c: one N^3 product for any number of parameters.  A solver that offers
-    # ``loo`` (the HIP BasicSolver) keeps all of it on the device; any other one with ``apply_inverse`` and ``get_inverse``
-    # takes the NumPy branch, formula for formula.
+    # ``loo`` (the HIP BasicSolver) keeps all of it on the device; one that offers ``loo_blocks`` instead (VecchiaSolver) sums
+    # one closed form per block -- the leave-one-out of ITS density, with Q in the place of K^-1 and nothing N x N; any other
+    # one with ``apply_inverse`` and ``get_inverse`` takes the NumPy branch, formula for formula.
     def _loo_parts(self, r, want_grad):
         """``(L, resid, var, lpd, kgrad | None, v | None, diagB | None)`` for the residual ``r`` on the computed solver;
         ``kgrad`` over the unfrozen kernel parameters."""
         n_k = len(self.kernel)
-        if self._offers("loo"):
+        device = next((name for name in ("loo", "loo_blocks") if self._offers(name)), None)
+        if device is not None:
             which = self.kernel.unfrozen_mask.astype(np.uint32) if want_grad else None
-            L, resid, var, lpd, kg_full, v, diagB = self.solver.loo(r, which)
+            L, resid, var, lpd, kg_full, v, diagB = getattr(self.solver, device)(r, which)
             kgrad = kg_full[self.kernel.unfrozen_mask] if (want_grad and n_k) else None
             return L, resid, var, lpd, kgrad, v, diagB
         # (vectorised, not _lgo_parts' loop over N one-point groups: that costs N Python iterations and other low bits)

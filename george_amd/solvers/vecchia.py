@@ -25,9 +25,17 @@ The expected (Fisher) information of the hyper-parameters (``fisher_blocks``, be
 per point over the blocks the gradient already builds (Guinness 2021) -- one pass, no N x N array, about the cost of one
 ``grad``.  It is the information of THIS likelihood: the dense one when every predecessor is a neighbour, another quantity when not.
 
+Leave-one-out cross-validation (``loo_blocks``, behind ``GP.loo_predict``, ``loo_log_likelihood``, ``grad_loo_log_likelihood``
+and ``loo_nll_and_grad``): the density has the precision ``Q = sum_i u_i u_i^T / f_i``, so ``c = diag Q`` is a gather over the
+columns of ``B``, ``alpha = Q r`` one application, and the values ``resid = alpha / c``, ``var = 1 / c`` and ``lpd`` cost O(N m);
+the gradient is again a sum of one closed form per block over the blocks the likelihood gradient builds, about the cost of one
+``grad``, with no N x N array.  It is the leave-one-out of THIS density, exact for it: the dense one when every predecessor is a
+neighbour, and as far from the dense one as ``Q`` is from ``K^-1`` when not -- which is what makes the per-point residuals a
+direct check of ``m``.
+
 Not built: ordering strategies beyond the three of ``order=`` (max-min and the like: tried in NumPy, they moved the error of the
-log-likelihood by a factor of about 2 at most), the observed information, ``apply_sqrt``, and a joint covariance between the test
-points of local prediction.
+log-likelihood by a factor of about 2 at most), the observed information, ``apply_sqrt``, a joint covariance between the test
+points of local prediction, and leave-group-out cross-validation (``GP.lgo_*`` takes the generic N x N branch here).
 """
 import ctypes as C
 import hashlib
@@ -411,6 +419,36 @@ class VecchiaSolver(NativeSolver):
         self._retry_without_parked_memory(lambda hh: N.check(N.lib.gh_vecchia_fisher(
             hh, self._dk.handle, N.ptr(wh), N.ptr(rows) if n_diag else None, n_diag, N.ptr(out))))
         return out
+
+    def loo_blocks(self, r, which=None):
+        """Leave-one-out cross-validation of the Vecchia density for residual ``r = y - mean`` (gh_vecchia_loo), the contract of
+        ``BasicSolver.loo``: ``(lpd_sum, resid, var, lpd, grad_full | None, v | None, diagB | None)`` with ``resid = y - mu_loo``,
+        ``var`` the leave-one-out variances, ``lpd`` the N log predictive densities and ``lpd_sum`` their sum, all from
+        ``c = diag Q`` and ``alpha = Q r``.  ``which=None``: values only, O(N m).  With a parameter mask also ``grad_full`` =
+        d lpd_sum / d theta over ALL kernel parameters (masked ones exactly 0), ``v`` = d lpd_sum / d mean_i and ``diagB`` =
+        d lpd_sum / d K_ii: a sum of one closed form per block, about the cost of one :meth:`grad`, with no N x N array anywhere.
+        The N-vectors are in the caller's point order.  It is the leave-one-out of THIS density, exact for it: the dense one at
+        ``m >= N - 1``, and as far from it as ``Q`` is from ``K^-1`` otherwise -- hence a name of its own: ``loo`` stays the
+        dense call, which only ``BasicSolver`` offers, and ``GP`` takes this one where a solver has no ``loo``."""
+        self._need()
+        n, size = self._n, self._dk.size
+        r = self._in(rhs_vector(r, n))
+        wh = g = v = diagB = None
+        if which is not None:
+            which = np.asarray(which)
+            if which.shape != (size,):
+                raise ValueError("which must have shape ({0},)".format(size))
+            wh = np.zeros(max(size, 1), dtype=np.uint32)
+            wh[:size] = which != 0
+            g, v, diagB = np.zeros(max(size, 1)), np.empty(n), np.empty(n)
+        total = C.c_double(0.0)
+        resid, var, lpd = np.empty(n), np.empty(n), np.empty(n)
+        self._retry_without_parked_memory(lambda hh: N.check(N.lib.gh_vecchia_loo(
+            hh, self._dk.handle, N.ptr(wh), N.ptr(r), C.byref(total), N.ptr(resid), N.ptr(var), N.ptr(lpd),
+            N.ptr(g), N.ptr(v), N.ptr(diagB))))
+        if which is None:
+            return total.value, self._out(resid), self._out(var), self._out(lpd), None, None, None
+        return total.value, self._out(resid), self._out(var), self._out(lpd), g[:size], self._out(v), self._out(diagB)
 
     def predict(self, kernel, r, xs, return_var=False, return_cov=False):
         """``K* Q r`` and (optionally) the diagonal or the whole of ``K** - K* Q K*^T``, in strips of test points.  The

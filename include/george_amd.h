@@ -498,6 +498,22 @@ int  gh_vecchia_dot_solve(gh_vecchia* h, const double* y, double* out);         
  * diagA_j = 2 sum over the blocks that hold j of W_jj.  The layout of gh_chol_grad, and its values when m >= n - 1. */
 int  gh_vecchia_grad(gh_vecchia* h, gh_kernel* k, const uint32_t* which, const double* r,
                      double* grad /* size */, double* alpha /* n or NULL */, double* diagA /* n or NULL */);
+/* Leave-one-out cross-validation of the Vecchia density, the Gaussian with precision Q = sum_i u_i u_i^T / f_i (u_i = [-b_i; 1] on
+ * the block c(i) + {i}); exact for that density.  With c_j = Q_jj = 1/f_j + sum over column j of B of b^2 / f_row and alpha = Q r:
+ *   resid[j] = alpha_j / c_j = y_j - mu_j,   var[j] = 1 / c_j,
+ *   lpd[j]   = 1/2 log c_j - 1/2 alpha_j^2 / c_j - 1/2 log 2 pi;      *lpd_sum = sum_j lpd[j]
+ * and, with w = 1/2 (1 + alpha^2 / c) / c, a = alpha / c and M = diag(w) - 1/2 (a r^T + r a^T):  d lpd_sum = sum_i d[u^T M u / f],
+ * one closed form per block: g = M u, h = A^-1 g, W(i) = (u.g / f^2) u u^T - (1/f) (h u^T + u h^T), and
+ *   grad[p]  = sum_i sum_jk W(i)_jk dk(x_j, x_k)/dtheta_p  for the parameters selected by `which` (others exactly 0)
+ *   v (n)    = Q a: d lpd_sum / d mean_j;      diagB_j = sum over the blocks that hold j of W_jj: d lpd_sum / d K_jj.
+ * The layout of gh_chol_loo, and its values when m >= n - 1; for smaller m this is the leave-one-out of the approximate density,
+ * as far from the dense one as Q is from K^-1.  which == NULL: values only (grad, v and diagB must be NULL; O(n m), no block is
+ * rebuilt); otherwise about the cost of gh_vecchia_grad.  Nothing of size n x n.  *lpd_sum and which are host memory, the
+ * vectors host or device memory.  A block that is not positive definite (only with another kernel than compute()'s) adds nothing
+ * to grad and diagB.  Two calls give the same bits. */
+int  gh_vecchia_loo(gh_vecchia* h, gh_kernel* k, const uint32_t* which /* NULL: values only */, const double* r,
+                    double* lpd_sum, double* resid /* n */, double* var /* n */, double* lpd /* n or NULL */,
+                    double* grad /* size, or NULL */, double* v /* n or NULL */, double* diagB /* n or NULL */);
 /* The expected (Fisher) information of the Vecchia likelihood (Guinness 2021), a sum of one closed form per block: with
  * u = [-b_i; 1], L the factor of K_cc and D_a a derivative matrix restricted to the block c(i) + {i},
  *   v_a = D_a u,  df_a = u^T v_a,  w_a = L^-1 (v_a)[:c],   F_ab = sum_i 1/2 df_a df_b / f_i^2 + (w_a . w_b) / f_i.
