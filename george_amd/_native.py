@@ -221,6 +221,7 @@ SIGNATURES = {
     "gh_inducing_grad": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _dp, _dp]),
     "gh_inducing_trace_term": (C.c_int, [_vp, C.POINTER(C.c_double)]),
     "gh_inducing_grad_u": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "gh_inducing_loo": (C.c_int, [_vp, _vp, _dp, _dp, C.POINTER(C.c_double), _dp, _dp, _dp, _dp, _dp, _dp]),
     "gh_inducing_predict": (C.c_int, [_vp, _vp, _dp, _dp, _i64, _dp, _dp, _dp]),
     "gh_inducing_select": (C.c_int, [_i32, _dp, _i64, _i32, _i64, _i64, _dp, _dp]),
     "gh_mgpu_create": (C.c_int, [C.POINTER(gh_mgpu_opts), C.POINTER(_vp)]),

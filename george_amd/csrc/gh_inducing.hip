@@ -15,6 +15,8 @@
 //   grad_u:   the same pass after one for G2 = H Lambda^-1 P^T and w = P alpha; per strip Z_J^T once more, from P_J^T itself
 //             (ind_grad_body has the reason), ugrad += sum_i Z_J^T[i][j] d1 k(u_j, x_i) (gh_launch_wxgrad on the strip) and
 //             Z P^T += Z_J P_J^T; after the strips ugrad -= sum_b (-(W + W^T))[b][j] d1 k(u_j, u_b)
+//   loo:      c_i = (C^-1)_ii from the rows of H_J^T, and the values; with a mask two passes for B = 1/2 (v alpha^T + alpha v^T) -
+//             C^-1 diag(w) C^-1 in low-rank form, and grad's reduction with 2 B in the place of alpha alpha^T - C^-1 (gh_inducing_loo)
 //   predict:  V*^T = F* Lui^T,  H*^T = F* M1^T,  mu = F* w
 // Strips go in ascending order on the handle's one stream and every sum has a fixed order (GEMM tiles, wave trees, per-workgroup
 // partials added by gh_launch_kgrad_final): two calls give the same bits.  No kernel here uses scratch memory or atomics (the
@@ -140,6 +142,61 @@ __global__ __launch_bounds__(256) void ind_zt_p_kernel(double* __restrict__ Zt, 
   double z = alpha[i] * w[j * ws] - (p - Zt[idx]) / lam[i];
   if (omega) z -= omega[i] * p;
   Zt[idx] = z;
+}
+// Leave-one-out, a wavefront per data point of the strip: c_i = (C^-1)_ii = 1 / lambda_i - |H[:, i]|^2 / lambda_i^2 from row i of
+// H^T; resid = alpha / c, var = 1 / c, lpd = 1/2 log c - 1/2 alpha resid - 1/2 log 2 pi and, with w (the gradient path),
+// w = 1/2 (1 + alpha resid) / c
+__global__ __launch_bounds__(256) void ind_loo_point_kernel(const double* __restrict__ Ht, long ld, long rows, const double* __restrict__ lam,
+                                                            const double* __restrict__ alpha, double* __restrict__ resid,
+                                                            double* __restrict__ var, double* __restrict__ lpd, double* __restrict__ w) {
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  double hh = 0.0;
+  for (long j = lane; j < ld; j += 64) { const double v = Ht[row * ld + j]; hh += v * v; }
+  hh = wave_sum(hh);
+  if (lane == 0) {
+    const double l = lam[row], a = alpha[row];
+    const double c = 1.0 / l - hh / (l * l), rs = a / c;
+    resid[row] = rs;
+    var[row] = 1.0 / c;
+    lpd[row] = 0.5 * log(c) - 0.5 * a * rs - 0.918938533204672741780329736406;     // 1/2 log 2 pi
+    if (w) w[row] = 0.5 * (1.0 + a * rs) / c;
+  }
+}
+// A wavefront per data point of the strip: d2_i = (C^-1 diag(w) C^-1)_ii = w_i / lambda_i^2 - 2 w_i / lambda_i |R[:, i]|^2 +
+// R[:, i] . (S R)[:, i] from rows i of R^T and R^T S (R = H Lambda^-1, S = R diag(w) R^T); diagB_i = alpha_i v_i - d2_i
+__global__ __launch_bounds__(256) void ind_loo_diagb_kernel(const double* __restrict__ Rt, const double* __restrict__ RS, long ld, long rows,
+                                                            const double* __restrict__ lam, const double* __restrict__ w,
+                                                            const double* __restrict__ alpha, const double* __restrict__ v,
+                                                            double* __restrict__ diagB) {
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  double rr = 0.0, rs = 0.0;
+  for (long j = lane; j < ld; j += 64) { const double t = Rt[row * ld + j]; rr += t * t; rs += t * RS[row * ld + j]; }
+  rr = wave_sum(rr);
+  rs = wave_sum(rs);
+  if (lane == 0) {
+    const double wl = w[row] / lam[row];
+    diagB[row] = alpha[row] * v[row] - ((wl / lam[row] - 2.0 * wl * rr) + rs);
+  }
+}
+// Y (se x ld; `rows` of them data points) holding R^T (S G1 - G3), with RG = R^T G1 and Pt = P_J^T  <-  the leave-one-out Z^T:
+// alpha_i pv_j + v_i pa_j - 2 (w_i / lambda_i^2 Pt_ij - w_i / lambda_i RG_ij + Y_ij) - 2 diagB_i Pt_ij (diagB == nullptr: DTC);
+// pa = P alpha and pv = P v with the stride ws; the rows past the data points stay zero
+__global__ __launch_bounds__(256) void ind_loo_zt_kernel(double* __restrict__ Y, const double* __restrict__ RG, const double* __restrict__ Pt, long ld,
+                                                         long rows, const double* __restrict__ lam, const double* __restrict__ w,
+                                                         const double* __restrict__ alpha, const double* __restrict__ v,
+                                                         const double* __restrict__ diagB, const double* __restrict__ pa,
+                                                         const double* __restrict__ pv, long ws) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= rows * ld) return;
+  const long i = idx / ld, j = idx - i * ld;
+  const double wl = w[i] / lam[i], p = Pt[idx];
+  double z = (alpha[i] * pv[j * ws] + v[i] * pa[j * ws]) - 2.0 * ((wl / lam[i] * p - wl * RG[idx]) + Y[idx]);
+  if (diagB) z -= 2.0 * diagB[i] * p;
+  Y[idx] = z;
 }
 // R (se x rp) = the vector a (rows entries) in column 0, zero elsewhere
 __global__ __launch_bounds__(256) void ind_col_kernel(const double* __restrict__ a, long rows, long se, long rp, double* __restrict__ R) {
@@ -489,6 +546,76 @@ extern "C" int gh_inducing_dot_solve(gh_inducing* h, const double* y, double* ou
   return GH_OK;
 }
 
+// The reduction of the kernel gradient, for ind_grad_body and gh_inducing_loo: grad[p] = sum_J (sum_ij Z_J^T[i][j] dk(x_i, u_j) +
+// scale sum_i wd_i dk(x_i, x_i)) + sum_jj' W_jj' dk(u_j, u_j') with W = -1/2 (ZF Lui^T) Lui, ZF = sum_J Z_J F_J in wk2.  The
+// partial sums: one row per workgroup of a launch (part, reused launch after launch in stream order), then one row per launch
+// (rows): the strips' rectangles and diagonals, and the K_uu term last.
+struct IndRed {
+  GhPooledBuf part, rows, zero, scratch;
+  uint32_t* d_which = nullptr;
+  double* partial = nullptr;
+  int P = 0, gp = 0;
+  size_t lds = 0;
+  int64_t tiles_c = 0, nrows = 0;
+};
+// P = 0: no kernel gradient, the buffers at their smallest
+static int ind_red_begin(gh_inducing* h, const uint32_t* which, int P, int64_t s, int64_t nstrips, IndRed& q) {
+  const int64_t nd = h->ndim;
+  const int Pw = P > 0 ? P : 1;
+  q.P = P;
+  GH_CHECK(q.zero.ensure((size_t)h->mp * sizeof(double)));
+  q.tiles_c = (h->m + IND_GT - 1) / IND_GT;
+  const int64_t tiles_r = (s + IND_GT - 1) / IND_GT;
+  const size_t which_bytes = ((sizeof(uint32_t) * Pw + 15) / 16) * 16;
+  GH_CHECK(q.part.ensure(which_bytes + (size_t)q.tiles_c * tiles_r * Pw * sizeof(double)));
+  GH_CHECK(q.rows.ensure((size_t)(2 * nstrips + 2) * Pw * sizeof(double)));
+  q.d_which = (uint32_t*)q.part.p;
+  q.partial = (double*)((char*)q.part.p + which_bytes);
+  if (P > 0) GH_HIP(hipMemcpyAsync(q.d_which, which, sizeof(uint32_t) * P, hipMemcpyHostToDevice, h->st));
+  q.gp = (2 * P + GH_EVAL_WS) | 1;                          // doubles per lane: the gradient row, the sums, the evaluator's work space; odd
+  q.lds = ((size_t)2 * IND_GT * nd + (size_t)IND_GT * q.gp) * sizeof(double);      // (at most 91 KB: 64 parameters, 16 dimensions)
+  if (q.lds > 64 * 1024) {
+    GH_HIP(hipFuncSetAttribute((const void*)ind_grad_tile_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, IND_GRAD_LDS));
+    GH_HIP(hipFuncSetAttribute((const void*)ind_grad_tile_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, IND_GRAD_LDS));
+  }
+  GH_HIP(hipMemsetAsync(q.zero.p, 0, (size_t)h->mp * sizeof(double), h->st));
+  return GH_OK;
+}
+// the strip's rectangle with the weights Zt (cw x mp) and, with wd, its diagonal term with the weights wd_scale * wd
+static int ind_red_strip(gh_inducing* h, const gh_kernel* k, IndRed& q, const double* xj, int64_t cw, const double* Zt, const double* wd,
+                         double wd_scale) {
+  hipStream_t st = h->st;
+  const int P = q.P;
+  const dim3 grid((unsigned)q.tiles_c, (unsigned)((cw + IND_GT - 1) / IND_GT));
+  hipLaunchKernelGGL(ind_grad_tile_kernel<false>, grid, dim3(IND_GT), q.lds, st, (const GhNode*)k->d_nodes, (int)k->nodes.size(), (int)h->ndim, P, q.gp,
+                     (const uint32_t*)q.d_which, xj, (long)cw, (const double*)h->u.d(), (long)h->m, Zt, (long)h->mp, 1.0, q.partial);
+  GH_HIP(hipGetLastError());
+  GH_CHECK(gh_launch_kgrad_final(q.partial, (int64_t)grid.x * grid.y, P, q.rows.d() + q.nrows++ * P, st));
+  if (wd) {
+    const unsigned nwg = (unsigned)((cw + IND_GT * IND_GT - 1) / (IND_GT * IND_GT));
+    hipLaunchKernelGGL(ind_grad_tile_kernel<true>, dim3(nwg), dim3(IND_GT), q.lds, st, (const GhNode*)k->d_nodes, (int)k->nodes.size(), (int)h->ndim, P,
+                       q.gp, (const uint32_t*)q.d_which, xj, (long)cw, (const double*)nullptr, 0L, wd, 0L, wd_scale, q.partial);
+    GH_HIP(hipGetLastError());
+    GH_CHECK(gh_launch_kgrad_final(q.partial, nwg, P, q.rows.d() + q.nrows++ * P, st));
+  }
+  return GH_OK;
+}
+// the K_uu term from ZF in wk2 (Xb: an mp x mp work matrix), the sum over the launches, grad (host or device memory)
+static int ind_red_end(gh_inducing* h, gh_kernel* k, const uint32_t* which, IndRed& q, double* Xb, double* grad) {
+  hipStream_t st = h->st;
+  const int64_t m = h->m, mp = h->mp;
+  const int P = q.P;
+  // W = -1/2 Z P^T = -1/2 (ZF Lui^T) Lui: the symmetric reduction with alpha = 0 and "K^-1" = -2 sym(W) = sym(ZF K_uu^-1)
+  GH_CHECK(ind_mm(st, Xb, mp, h->wk2.d(), mp, true, h->Lui.d(), mp, true, mp, mp, mp, 1.0, 0.0, true));
+  GH_CHECK(ind_mm(st, h->wk1.d(), mp, Xb, mp, true, h->Lui.d(), mp, false, mp, mp, mp, 1.0, 0.0));
+  hipLaunchKernelGGL(ind_sym_kernel, dim3(ind_blocks((size_t)mp * mp)), dim3(256), 0, st, (const double*)h->wk1.d(), (long)mp, h->wk2.d());
+  GH_HIP(hipGetLastError());
+  GH_CHECK(gh_launch_kgrad_reduce(k, which, h->u.d(), m, q.zero.d(), h->wk2.d(), mp, q.rows.d() + q.nrows++ * P, nullptr, q.scratch, st));
+  GH_CHECK(gh_launch_kgrad_final(q.rows.d(), q.nrows, P, q.rows.d() + q.nrows * P, st));
+  GH_CHECK(gh_from_device(grad, q.rows.d() + q.nrows * P, (size_t)P, st));
+  return GH_OK;
+}
+
 // The body of gh_inducing_grad and gh_inducing_grad_u.  which == nullptr: no kernel gradient; ugrad == nullptr: no gradient of
 // the inducing inputs (and then not one launch more than before).
 // ugrad does not take the kernel gradient's Z_J^T and W: those are products with the explicit inverses M1 and Lui, whose single
@@ -501,9 +628,9 @@ static int ind_grad_body(gh_inducing* h, gh_kernel* k, const uint32_t* which, co
                          double* ugrad) {
   hipStream_t st = h->st;
   const int64_t n = h->n, m = h->m, mp = h->mp, nd = h->ndim, s = ind_strip_points(h, n), nstrips = (n + s - 1) / s;
-  const int P = which ? k->size : 0, Pw = P > 0 ? P : 1;
+  const int P = which ? k->size : 0;
   const bool vfe = h->opts.variational != 0, fitc = h->opts.method != 0 || vfe;    // fitc: Z has a diagonal part, of weight `wd`
-  GhPooledBuf rd, al, dg, om, ug, upart, sP, sZ, aR, wp, Wa, ctw, sF, sY, sB, Xb, zero, part, rows, scratch;
+  GhPooledBuf rd, al, dg, om, ug, upart, sP, sZ, aR, wp, Wa, ctw, sF, sY, sB, Xb;
   GH_CHECK(rd.ensure((size_t)n * sizeof(double)));
   GH_CHECK(al.ensure((size_t)n * sizeof(double)));
   GH_CHECK(dg.ensure((size_t)n * sizeof(double)));
@@ -528,22 +655,8 @@ static int ind_grad_body(gh_inducing* h, gh_kernel* k, const uint32_t* which, co
   GH_CHECK(sY.ensure((size_t)s * mp * sizeof(double)));
   GH_CHECK(sB.ensure((size_t)s * mp * sizeof(double)));
   GH_CHECK(Xb.ensure(ind_sq(h)));
-  GH_CHECK(zero.ensure((size_t)mp * sizeof(double)));
-  // the partial sums: one row per workgroup of a launch (part, reused launch after launch in stream order), then one row per
-  // launch (rows): the strips' rectangles and FITC diagonals, and the K_uu term last
-  const int64_t tiles_c = (m + IND_GT - 1) / IND_GT, tiles_r = (s + IND_GT - 1) / IND_GT;
-  const size_t which_bytes = ((sizeof(uint32_t) * Pw + 15) / 16) * 16;
-  GH_CHECK(part.ensure(which_bytes + (size_t)tiles_c * tiles_r * Pw * sizeof(double)));
-  GH_CHECK(rows.ensure((size_t)(2 * nstrips + 2) * Pw * sizeof(double)));
-  uint32_t* d_which = (uint32_t*)part.p;
-  double* partial = (double*)((char*)part.p + which_bytes);
-  if (P > 0) GH_HIP(hipMemcpyAsync(d_which, which, sizeof(uint32_t) * P, hipMemcpyHostToDevice, st));
-  const int gp = (2 * P + GH_EVAL_WS) | 1;                  // doubles per lane: the gradient row, the sums, the evaluator's work space; odd
-  const size_t lds = ((size_t)2 * IND_GT * nd + (size_t)IND_GT * gp) * sizeof(double);      // (at most 91 KB: 64 parameters, 16 dimensions)
-  if (lds > 64 * 1024) {
-    GH_HIP(hipFuncSetAttribute((const void*)ind_grad_tile_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, IND_GRAD_LDS));
-    GH_HIP(hipFuncSetAttribute((const void*)ind_grad_tile_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, IND_GRAD_LDS));
-  }
+  IndRed q;
+  GH_CHECK(ind_red_begin(h, which, P, s, nstrips, q));
   double* const G2 = Xb.d();                                // (Xb is the kernel gradient's only after the strips)
   if (ugrad) {                                              // the pass for G2 and w = P alpha
     GH_HIP(hipMemsetAsync(Xb.p, 0, ind_sq(h), st));
@@ -566,8 +679,6 @@ static int ind_grad_body(gh_inducing* h, gh_kernel* k, const uint32_t* which, co
   }
   // ZF = sum_J Z_J F_J into wk2
   GH_HIP(hipMemsetAsync(h->wk2.p, 0, ind_sq(h), st));
-  GH_HIP(hipMemsetAsync(zero.p, 0, (size_t)mp * sizeof(double), st));
-  int64_t nrows = 0;
   for (int64_t j0 = 0; j0 < n; j0 += s) {
     const int64_t cw = std::min<int64_t>(s, n - j0), se = gh_round_up(cw, GH_TILE);
     const double* xj = h->x.d() + j0 * nd;
@@ -600,31 +711,9 @@ static int ind_grad_body(gh_inducing* h, gh_kernel* k, const uint32_t* which, co
       GH_CHECK(gh_launch_wxgrad(k, h->u.d(), m, xj, cw, sZ.d(), mp, 1.0, j0 > 0, ug.d(), upart.d(), st));
       GH_CHECK(ind_mm(st, Wa.d(), mp, sZ.d(), mp, false, sP.d(), mp, false, mp, mp, se, 1.0, 1.0));                             // Z P^T += Z_J P_J^T
     }
-    if (P > 0) {
-      const dim3 grid((unsigned)tiles_c, (unsigned)((cw + IND_GT - 1) / IND_GT));
-      hipLaunchKernelGGL(ind_grad_tile_kernel<false>, grid, dim3(IND_GT), lds, st, (const GhNode*)k->d_nodes, (int)k->nodes.size(), (int)nd, P, gp,
-                         (const uint32_t*)d_which, xj, (long)cw, (const double*)h->u.d(), (long)m, (const double*)sY.d(), (long)mp, 1.0, partial);
-      GH_HIP(hipGetLastError());
-      GH_CHECK(gh_launch_kgrad_final(partial, (int64_t)grid.x * grid.y, P, rows.d() + nrows++ * P, st));
-      if (fitc) {
-        const unsigned nwg = (unsigned)((cw + IND_GT * IND_GT - 1) / (IND_GT * IND_GT));
-        hipLaunchKernelGGL(ind_grad_tile_kernel<true>, dim3(nwg), dim3(IND_GT), lds, st, (const GhNode*)k->d_nodes, (int)k->nodes.size(), (int)nd, P, gp,
-                           (const uint32_t*)d_which, xj, (long)cw, (const double*)nullptr, 0L, wd + j0, 0L, 0.5, partial);
-        GH_HIP(hipGetLastError());
-        GH_CHECK(gh_launch_kgrad_final(partial, nwg, P, rows.d() + nrows++ * P, st));
-      }
-    }
+    if (P > 0) GH_CHECK(ind_red_strip(h, k, q, xj, cw, sY.d(), fitc ? wd + j0 : nullptr, 0.5));
   }
-  if (P > 0) {
-    // W = -1/2 Z P^T = -1/2 (ZF Lui^T) Lui: the symmetric reduction with alpha = 0 and "K^-1" = -2 sym(W) = sym(ZF K_uu^-1)
-    GH_CHECK(ind_mm(st, Xb.d(), mp, h->wk2.d(), mp, true, h->Lui.d(), mp, true, mp, mp, mp, 1.0, 0.0, true));
-    GH_CHECK(ind_mm(st, h->wk1.d(), mp, Xb.d(), mp, true, h->Lui.d(), mp, false, mp, mp, mp, 1.0, 0.0));
-    hipLaunchKernelGGL(ind_sym_kernel, dim3(ind_blocks((size_t)mp * mp)), dim3(256), 0, st, (const double*)h->wk1.d(), (long)mp, h->wk2.d());
-    GH_HIP(hipGetLastError());
-    GH_CHECK(gh_launch_kgrad_reduce(k, which, h->u.d(), m, zero.d(), h->wk2.d(), mp, rows.d() + nrows++ * P, nullptr, scratch, st));
-    GH_CHECK(gh_launch_kgrad_final(rows.d(), nrows, P, rows.d() + nrows * P, st));
-    GH_CHECK(gh_from_device(grad, rows.d() + nrows * P, (size_t)P, st));
-  }
+  if (P > 0) GH_CHECK(ind_red_end(h, k, which, q, Xb.d(), grad));
   if (ugrad) {                                              // sG = 1/2 (Z P^T + its transpose) = -(W + W^T): ugrad_j += sum_b (W + W^T)_jb d1 k(u_j, u_b)
     double* const sG = Xb.d();
     hipLaunchKernelGGL(ind_sym_kernel, dim3(ind_blocks((size_t)mp * mp)), dim3(256), 0, st, (const double*)Wa.d(), (long)mp, sG);
@@ -657,6 +746,117 @@ extern "C" int gh_inducing_grad_u(gh_inducing* h, gh_kernel* k, const uint32_t* 
   GH_HIP(hipSetDevice(h->opts.device));
   GH_CHECK(k->upload());
   return ind_grad_body(h, k, which, r, grad, alpha, diagA, ugrad);
+}
+
+// Leave-one-out of the DTC / FITC density (include/george_amd.h has the formulas).  Per strip J: H_J^T = F_J M1^T, R_J^T =
+// Lambda_J^-1 H_J^T and P_J^T = (F_J Lui^T) Lui.  The first pass gives c and the values from the rows of H_J^T and, with `which`,
+// S = sum_J (diag(w_J) R_J^T)^T R_J^T, G1 = sum_J R_J P_J^T and G3 = sum_J (diag(w_J D_J) R_J^T)^T P_J^T; then v = C^-1 resid and
+// P v by a second apply and Mx = S G1 - G3; the second pass gives diagB from R_J^T and R_J^T S, Z_J^T from P_J^T, R_J^T G1 and
+// R_J^T Mx, and feeds the reduction of ind_grad_body.  With one strip the second pass keeps the first one's F, R^T and P^T.
+extern "C" int gh_inducing_loo(gh_inducing* h, gh_kernel* k, const uint32_t* which, const double* r, double* lpd_sum, double* resid,
+                               double* var, double* lpd, double* grad, double* v, double* diagB) {
+  GH_CHECK(ind_need(h));
+  if (!k || !r || !lpd_sum || !resid || !var || (which ? !grad : (grad || v || diagB))) { gh_set_error("bad argument to loo"); return GH_ERR_BAD_ARG; }
+  if (k->ndim != h->ndim) { gh_set_error("dimension mismatch"); return GH_ERR_DIM; }
+  if (which && k->size > GH_MAX_GRAD) { gh_set_error("loo: %d kernel parameters, at most %d", k->size, GH_MAX_GRAD); return GH_ERR_BAD_ARG; }
+  hipStream_t st = h->st;
+  const int64_t n = h->n, mp = h->mp, nd = h->ndim, s = ind_strip_points(h, n), nstrips = (n + s - 1) / s;
+  const bool fitc = h->opts.method != 0;                    // (the bound's solves and predictions are DTC's)
+  // vals: r, alpha, resid, var, lpd and their sum; with the gradient also w, v and diagB
+  GhPooledBuf vals, ctw, ctv, sF, sH, sP, sT, sY, mats;
+  GH_CHECK(vals.ensure(((size_t)(which ? 8 : 5) * n + 1) * sizeof(double)));
+  double* const rd = vals.d();
+  double* const al = rd + n;
+  double* const rs = al + n;
+  double* const vr = rs + n;
+  double* const lp = vr + n;
+  double* const total = lp + n;
+  double* const wv = which ? total + 1 : nullptr;
+  double* const vv = which ? wv + n : nullptr;
+  double* const db = which ? vv + n : nullptr;
+  GH_CHECK(gh_to_device(rd, r, (size_t)n, st));
+  GH_CHECK(ind_apply(h, rd, 1, al, ctw));                   // alpha = C^-1 r, and P alpha
+  GH_CHECK(sF.ensure((size_t)s * mp * sizeof(double)));
+  GH_CHECK(sH.ensure((size_t)s * mp * sizeof(double)));
+  double *S = nullptr, *G1 = nullptr, *G3 = nullptr;
+  if (which) {
+    GH_CHECK(sP.ensure((size_t)s * mp * sizeof(double)));
+    GH_CHECK(sT.ensure((size_t)s * mp * sizeof(double)));
+    GH_CHECK(sY.ensure((size_t)s * mp * sizeof(double)));
+    GH_CHECK(mats.ensure(3 * ind_sq(h)));
+    S = mats.d();
+    G1 = S + (size_t)mp * mp;
+    G3 = G1 + (size_t)mp * mp;
+    GH_HIP(hipMemsetAsync(mats.p, 0, 3 * ind_sq(h), st));
+  }
+  // F_J, R_J^T and P_J^T of the strip at j0 into sF, sH and sP (sT: work space)
+  auto strip_factors = [&](int64_t j0, int64_t cw, int64_t se) -> int {
+    GH_CHECK(ind_mm(st, sT.d(), mp, sF.d(), mp, true, h->Lui.d(), mp, true, se, mp, mp, 1.0, 0.0, true));
+    GH_CHECK(ind_mm(st, sP.d(), mp, sT.d(), mp, true, h->Lui.d(), mp, false, se, mp, mp, 1.0, 0.0));
+    hipLaunchKernelGGL(ind_row_div_kernel, dim3(ind_blocks((size_t)cw * mp)), dim3(256), 0, st, sH.d(), (long)mp, (long)cw, (const double*)h->lam.d() + j0);
+    GH_HIP(hipGetLastError());
+    return GH_OK;
+  };
+  for (int64_t j0 = 0; j0 < n; j0 += s) {
+    const int64_t cw = std::min<int64_t>(s, n - j0), se = gh_round_up(cw, GH_TILE);
+    GH_CHECK(ind_build(h, &h->kc, h->x.d() + j0 * nd, cw, se, sF.d()));
+    GH_CHECK(ind_mm(st, sH.d(), mp, sF.d(), mp, true, h->M1.d(), mp, true, se, mp, mp, 1.0, 0.0, /* M1 is lower */ true));      // H_J^T
+    hipLaunchKernelGGL(ind_loo_point_kernel, dim3(ind_row_blocks(cw)), dim3(256), 0, st, (const double*)sH.d(), (long)mp, (long)cw,
+                       (const double*)h->lam.d() + j0, (const double*)al + j0, rs + j0, vr + j0, lp + j0, which ? wv + j0 : (double*)nullptr);
+    GH_HIP(hipGetLastError());
+    if (!which) continue;
+    GH_CHECK(strip_factors(j0, cw, se));
+    GH_CHECK(ind_mm(st, G1, mp, sH.d(), mp, false, sP.d(), mp, false, mp, mp, se, 1.0, 1.0));
+    GH_HIP(hipMemcpyAsync(sT.p, sH.p, (size_t)se * mp * sizeof(double), hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(ind_row_scale_kernel, dim3(ind_blocks((size_t)cw * mp)), dim3(256), 0, st, sT.d(), (long)mp, (long)cw, (const double*)wv + j0);
+    GH_HIP(hipGetLastError());
+    GH_CHECK(ind_mm(st, S, mp, sT.d(), mp, false, sH.d(), mp, false, mp, mp, se, 1.0, 1.0));
+    hipLaunchKernelGGL(ind_row_div_kernel, dim3(ind_blocks((size_t)cw * mp)), dim3(256), 0, st, sT.d(), (long)mp, (long)cw, (const double*)h->lam.d() + j0);
+    GH_HIP(hipGetLastError());
+    GH_CHECK(ind_mm(st, G3, mp, sT.d(), mp, false, sP.d(), mp, false, mp, mp, se, 1.0, 1.0));
+  }
+  GH_CHECK(gh_launch_kgrad_final(lp, n, 1, total, st));     // L = sum_i lpd_i, fixed order
+  GH_HIP(hipMemcpyAsync(lpd_sum, total, sizeof(double), hipMemcpyDeviceToHost, st));
+  GH_CHECK(gh_from_device(resid, rs, (size_t)n, st));
+  GH_CHECK(gh_from_device(var, vr, (size_t)n, st));
+  if (lpd) GH_CHECK(gh_from_device(lpd, lp, (size_t)n, st));
+  if (which) {
+    GH_CHECK(k->upload());
+    const int P = k->size;
+    GH_CHECK(ind_apply(h, rs, 1, vv, ctv));                 // v = C^-1 resid, and P v
+    const double* pa = ctw.d() + 2 * (size_t)mp * GH_TILE;
+    const double* pv = ctv.d() + 2 * (size_t)mp * GH_TILE;
+    GH_CHECK(ind_mm(st, G3, mp, S, mp, true, G1, mp, false, mp, mp, mp, 1.0, -1.0));                                             // Mx = S G1 - G3
+    IndRed q;
+    GH_CHECK(ind_red_begin(h, which, P, s, nstrips, q));
+    GH_HIP(hipMemsetAsync(h->wk2.p, 0, ind_sq(h), st));     // ZF = sum_J Z_J F_J into wk2
+    for (int64_t j0 = 0; j0 < n; j0 += s) {
+      const int64_t cw = std::min<int64_t>(s, n - j0), se = gh_round_up(cw, GH_TILE);
+      const double* xj = h->x.d() + j0 * nd;
+      if (s < n) {                                          // (one strip: F, R^T and P^T are still the first pass's)
+        GH_CHECK(ind_build(h, &h->kc, xj, cw, se, sF.d()));
+        GH_CHECK(ind_mm(st, sH.d(), mp, sF.d(), mp, true, h->M1.d(), mp, true, se, mp, mp, 1.0, 0.0, true));
+        GH_CHECK(strip_factors(j0, cw, se));
+      }
+      GH_CHECK(ind_mm(st, sT.d(), mp, sH.d(), mp, true, S, mp, false, se, mp, mp, 1.0, 0.0));                                   // R_J^T S
+      hipLaunchKernelGGL(ind_loo_diagb_kernel, dim3(ind_row_blocks(cw)), dim3(256), 0, st, (const double*)sH.d(), (const double*)sT.d(), (long)mp, (long)cw,
+                         (const double*)h->lam.d() + j0, (const double*)wv + j0, (const double*)al + j0, (const double*)vv + j0, db + j0);
+      GH_HIP(hipGetLastError());
+      GH_CHECK(ind_mm(st, sY.d(), mp, sH.d(), mp, true, G3, mp, false, se, mp, mp, 1.0, 0.0));                                  // R_J^T Mx
+      GH_CHECK(ind_mm(st, sT.d(), mp, sH.d(), mp, true, G1, mp, false, se, mp, mp, 1.0, 0.0));                                  // R_J^T G1
+      hipLaunchKernelGGL(ind_loo_zt_kernel, dim3(ind_blocks((size_t)cw * mp)), dim3(256), 0, st, sY.d(), (const double*)sT.d(), (const double*)sP.d(),
+                         (long)mp, (long)cw, (const double*)h->lam.d() + j0, (const double*)wv + j0, (const double*)al + j0, (const double*)vv + j0,
+                         fitc ? (const double*)db + j0 : (const double*)nullptr, pa, pv, (long)GH_TILE);
+      GH_HIP(hipGetLastError());
+      GH_CHECK(ind_mm(st, h->wk2.d(), mp, sY.d(), mp, false, sF.d(), mp, false, mp, mp, se, 1.0, 1.0));
+      if (P > 0) GH_CHECK(ind_red_strip(h, k, q, xj, cw, sY.d(), fitc ? db + j0 : nullptr, 1.0));
+    }
+    if (P > 0) GH_CHECK(ind_red_end(h, k, which, q, S, grad));                  // (S is free by now)
+    if (v) GH_CHECK(gh_from_device(v, vv, (size_t)n, st));
+    if (diagB) GH_CHECK(gh_from_device(diagB, db, (size_t)n, st));
+  }
+  GH_HIP(hipStreamSynchronize(st));
+  return GH_OK;
 }
 
 extern "C" int gh_inducing_predict(gh_inducing* h, gh_kernel* k, const double* r, const double* xs, int64_t M, double* mu, double* var,

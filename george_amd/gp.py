@@ -549,13 +549,15 @@ class GP(ModelSet):
     # is sum_ij B_ij dK_ij/dtheta with B = 1/2 (v alpha^T + alpha v^T) - K^-1 diag(w) K^-1, u = alpha / c, v = K^-1 u,
     # w = 1/2 (1 + alpha^2 / c) / c: one N^3 product for any number of parameters.  A solver that offers
     # ``loo`` (the HIP BasicSolver) keeps all of it on the device; one that offers ``loo_blocks`` instead (VecchiaSolver) sums
-    # one closed form per block -- the leave-one-out of ITS density, with Q in the place of K^-1 and nothing N x N; any other
-    # one with ``apply_inverse`` and ``get_inverse`` takes the NumPy branch, formula for formula.
+    # one closed form per block -- the leave-one-out of ITS density, with Q in the place of K^-1 and nothing N x N; one that
+    # offers ``loo_lowrank`` (InducingSolver) does the same for the DTC / FITC density from C^-1 = D - R^T R in strips, with the
+    # gradient through dC, not dK; any other one with ``apply_inverse`` and ``get_inverse`` takes the NumPy branch, formula
+    # for formula (its kernel gradient is exact only where the solver inverts K(x, x) + diag itself).
     def _loo_parts(self, r, want_grad):
         """``(L, resid, var, lpd, kgrad | None, v | None, diagB | None)`` for the residual ``r`` on the computed solver;
         ``kgrad`` over the unfrozen kernel parameters."""
         n_k = len(self.kernel)
-        device = next((name for name in ("loo", "loo_blocks") if self._offers(name)), None)
+        device = next((name for name in ("loo", "loo_blocks", "loo_lowrank") if self._offers(name)), None)
         if device is not None:
             which = self.kernel.unfrozen_mask.astype(np.uint32) if want_grad else None
             L, resid, var, lpd, kg_full, v, diagB = getattr(self.solver, device)(r, which)

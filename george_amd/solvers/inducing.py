@@ -27,7 +27,15 @@ The default inducing set is greedy max-min distance over the data (:func:`induci
 default, or ``select="device"``: one streaming kernel per pick (``george_amd/csrc/gh_inducing_select.hip``) that returns the
 same points for up to 7 input dimensions.
 
-Not built: ``apply_sqrt`` and a multi-device form.
+Leave-one-out cross-validation (``loo_lowrank``, behind ``GP.loo_predict``, ``loo_log_likelihood``, ``grad_loo_log_likelihood``
+and ``loo_nll_and_grad``) is that of the DTC / FITC density, exact for it, at any N: ``diag C^-1`` is one row norm per data point
+of a strip the gradient already builds, and the gradient is ``grad``'s reduction with other weights; nothing N x N or N x m is
+kept.  ``(y - mu) / sqrt(var)`` are the standardised residuals of the model that was fitted: the direct check of ``m``.  (Before
+``loo_lowrank`` ``GP`` went through ``get_inverse()``, an N x N array, and the kernel gradient it returned for this solver was
+not the derivative of its value unless ``u = x``.)
+
+Not built: ``apply_sqrt``, a multi-device form, a Fisher information or leave-group-out form, and the gradient of the
+leave-one-out score with respect to the inducing inputs.
 """
 import ctypes as C
 import hashlib
@@ -231,6 +239,39 @@ class InducingSolver(NativeSolver):
         alpha, diagA, ugrad = np.empty(self._n), np.empty(self._n), np.empty(self.u.shape)
         N.check(N.lib.gh_inducing_grad_u(h, self._dk.handle, N.ptr(which), N.ptr(r), N.ptr(g), N.ptr(alpha), N.ptr(diagA), N.ptr(ugrad)))
         return (None if g is None else g[:self._dk.size]), self._out(alpha), self._out(diagA), ugrad
+
+    def loo_lowrank(self, r, which=None):
+        """Leave-one-out cross-validation of the DTC / FITC density for residual ``r = y - mean`` (gh_inducing_loo), the contract of
+        ``BasicSolver.loo`` and ``VecchiaSolver.loo_blocks``: ``(lpd_sum, resid, var, lpd, grad_full | None, v | None, diagB | None)``
+        with ``resid = y - mu_loo``, ``var`` the leave-one-out variances, ``lpd`` the N log predictive densities and ``lpd_sum``
+        their sum, all from ``c = diag C^-1`` (one row norm of a strip of ``H^T`` per point) and ``alpha = C^-1 r``.
+        ``which=None``: values only, about one ``dot_solve`` and one strip pass.  With a parameter mask also ``grad_full`` =
+        d lpd_sum / d theta over ALL kernel parameters (masked ones exactly 0), ``v`` = d lpd_sum / d mean_i and ``diagB`` =
+        d lpd_sum / d C_ii, by two passes over the strips and ``grad``'s reduction; nothing N x m or N x N is kept.  It is the
+        leave-one-out of THIS density, exact for it, and its gradient is the derivative of its value: the dense one with ``u = x``
+        and no jitter, and as far from it as ``C`` is from ``K`` otherwise -- hence a name of its own: ``loo`` stays the dense
+        call, which only ``BasicSolver`` offers, and ``GP`` takes this one where a solver has neither ``loo`` nor
+        ``loo_blocks``.  With ``variational=True`` it is the leave-one-out of the DTC density (the solves and predictions there
+        are DTC's; ``tau`` does not enter), with the bits of a ``method="dtc"`` solver."""
+        self._need()
+        n, size = self._n, self._dk.size
+        r = self._in(rhs_vector(r, n))
+        wh = g = v = diagB = None
+        if which is not None:
+            which = np.asarray(which)
+            if which.shape != (size,):
+                raise ValueError("which must have shape ({0},)".format(size))
+            wh = np.zeros(max(size, 1), dtype=np.uint32)
+            wh[:size] = which != 0
+            g, v, diagB = np.zeros(max(size, 1)), np.empty(n), np.empty(n)
+        total = C.c_double(0.0)
+        resid, var, lpd = np.empty(n), np.empty(n), np.empty(n)
+        self._retry_without_parked_memory(lambda hh: N.check(N.lib.gh_inducing_loo(
+            hh, self._dk.handle, N.ptr(wh), N.ptr(r), C.byref(total), N.ptr(resid), N.ptr(var), N.ptr(lpd),
+            N.ptr(g), N.ptr(v), N.ptr(diagB))))
+        if which is None:
+            return total.value, self._out(resid), self._out(var), self._out(lpd), None, None, None
+        return total.value, self._out(resid), self._out(var), self._out(lpd), g[:size], self._out(v), self._out(diagB)
 
     def predict(self, kernel, r, xs, return_var=False, return_cov=False):
         """The predictive mean and (optionally) variance or covariance at ``xs``, the same for DTC and FITC, in strips of

@@ -626,6 +626,31 @@ int  gh_inducing_grad(gh_inducing* h, gh_kernel* k, const uint32_t* which, const
 int  gh_inducing_grad_u(gh_inducing* h, gh_kernel* k, const uint32_t* which /* or NULL */, const double* r,
                         double* grad /* size, or NULL */, double* alpha /* n or NULL */, double* diagA /* n or NULL */,
                         double* ugrad /* m*ndim */);
+/* Leave-one-out cross-validation of the DTC / FITC density N(r | 0, C), exact for it, from the low-rank form
+ * C^-1 = D - R^T R (D = Lambda^-1, R = H D, m x n); the layout of gh_chol_loo and gh_vecchia_loo, and the dense values when u = x
+ * without jitter:
+ *   c_i = (C^-1)_ii = 1/lambda_i - |H[:, i]|^2 / lambda_i^2,   alpha = C^-1 r,
+ *   resid[i] = alpha_i / c_i = y_i - mu_i,   var[i] = 1 / c_i,
+ *   lpd[i]   = 1/2 log c_i - 1/2 alpha_i resid_i - 1/2 log 2 pi;      *lpd_sum = sum_i lpd[i]   (fixed order)
+ * and, with w = 1/2 (1 + alpha resid) / c:  v = C^-1 resid (d lpd_sum / d mean_i), and with S = R diag(w) R^T, G1 = R P^T and
+ * G3 = R diag(w D) P^T (three m x m sums over the strips)
+ *   diagB_i = alpha_i v_i - (w_i D_i^2 - 2 w_i D_i |R[:, i]|^2 + R[:, i]^T S R[:, i])          (d lpd_sum / d C_ii)
+ *   Z_J^T   = alpha_J (P v)^T + v_J (P alpha)^T - 2 (diag(w D^2)_J P_J^T - diag(w D)_J R_J^T G1 + R_J^T (S G1 - G3))
+ *             - 2 phi diag(diagB)_J P_J^T,        W = -1/2 Z P^T
+ *   grad[p] = sum_ij Z_ji dk(x_i, u_j)/dtheta_p + sum_jj' W_jj' dk(u_j, u_j')/dtheta_p + phi sum_i diagB_i dk(x_i, x_i)/dtheta_p:
+ * gh_inducing_grad's reduction with 2 B, B = 1/2 (v alpha^T + alpha v^T) - C^-1 diag(w) C^-1, in the place of alpha alpha^T - C^-1
+ * (parameters not selected by `which`: exactly 0; the clamp counts as inactive, the absolute jitter as a constant).  Under the
+ * bound (variational = 1) this is the leave-one-out of the DTC density, with the bits of a method 0 handle: tau does not enter.
+ * which == NULL: values only (grad, v and diagB must be NULL): one apply and one pass of one strip GEMM and one row kernel, about
+ * one gh_inducing_dot_solve more.  Otherwise a second apply and a second pass: thirteen strip GEMMs and three m x m ones in all,
+ * five strips and three m x m matrices beside the handle's on the device (counts, not measurements).  Nothing of size n x m or
+ * n x n is kept.  *lpd_sum and which are host memory, the vectors host or device memory.  Host checks as gh_inducing_grad:
+ * GH_ERR_BAD_ARG for a null h, k, r, lpd_sum, resid or var, which without grad, or grad, v or diagB without which, or more than
+ * GH_MAX_GRAD parameters with which; GH_ERR_NOT_COMPUTED; GH_ERR_DIM.  k: the kernel of compute().  Two calls give the same bits,
+ * and gh_inducing_grad and gh_inducing_grad_u return what they did before. */
+int  gh_inducing_loo(gh_inducing* h, gh_kernel* k, const uint32_t* which /* NULL: values only */, const double* r,
+                     double* lpd_sum, double* resid /* n */, double* var /* n */, double* lpd /* n or NULL */,
+                     double* grad /* size, or NULL */, double* v /* n or NULL */, double* diagB /* n or NULL */);
 /* The same for DTC, FITC and the bound: with V* = L_u^-1 K(u, xs), H* = L_A^-1 V*:  mu = H*^T t(r),
  * var = diag K(xs,xs) - colsumsq(V*) + colsumsq(H*),  cov = K(xs,xs) - V*^T V* + H*^T H*.  O(M m^2) whatever n, in strips of
  * test points; var / cov may be NULL (not both non-NULL); cov keeps its operands whole: GH_ERR_NOMEM over the strip budget.  k
